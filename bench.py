@@ -6,7 +6,7 @@ ControlNet forward + UNet forward (batch 2) + CFG combine + Euler update
 (/root/reference/src/ctrlv/pipelines/pipeline_video_control.py:298-343), on synthetic seeded inputs and random-init
 weights of the SVD-XT architecture, inputs resident in HBM before the timed region.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (RANK / WORLD_SIZE
 in the environment), or started plainly -- then this process, WITHOUT touching the GPU, starts the N rank processes
@@ -80,6 +80,10 @@ def parse():
     ap.add_argument("--no-fp16-leg", action="store_true",
                     help="bf16 runs: skip the extra leg that runs the SAME weights / sample through the fp16 build "
                          "(its parity and step time are reported as `fp16_build` beside the bf16 headline)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy in "
+                         "float32: latents (the updated fp32 latents) and noise_pred (the CFG-batch model output); the "
+                         "inputs are seeded, so two builds run with the same arguments can be compared output for output")
     return ap.parse_args()
 
 
@@ -148,10 +152,35 @@ def make_stepper(unet, ctrl, device, args, clip_index):
 
 
 def run_step(st, i):
+    """Step i of the benchmark; returns the step's noise prediction (st.latents holds the updated latents)."""
     k = i % 25
     if k == 0 and i > 0:                       # wrapped around the 25-step schedule: restart the clip
         st.set_latents(st._init_latents, 0)    # (set_latents copies: the initial latents are never overwritten)
-    st.step(k)
+    return st.step(k)
+
+
+DUMP_BYTES = 64 * 2**20
+
+
+def dump_outputs(outdir, arrays, max_bytes=DUMP_BYTES):
+    """Write each tensor of `arrays` as <outdir>/<name>.npy in float32.  The files stay within `max_bytes` in all: an array
+    larger than its even share is replaced by a fixed sample (the elements at sorted flat positions drawn from a generator
+    of seed 0, the same for every run of the same shape).  Returns {name: shape written}."""
+    import numpy as np
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    share = max_bytes // (4 * len(arrays))         # elements per array
+    shapes = {}
+    for name, t in arrays.items():
+        a = t.detach().float().flatten().cpu()
+        if a.numel() > share:
+            g = torch.Generator().manual_seed(0)
+            a = a[torch.randperm(a.numel(), generator=g)[:share].sort().values]
+        else:
+            a = a.reshape(t.shape)
+        np.save(os.path.join(outdir, name + ".npy"), a.numpy())
+        shapes[name] = list(a.shape)
+    return shapes
 
 
 # ---------------------------------------------------------------------------------------------------- CPU baseline
@@ -452,13 +481,17 @@ def main():
     t0 = time.perf_counter()
     timer = None
     for k in range(args.steps):
-        run_step(st, i)
+        noise_pred = run_step(st, i)
         i += 1
     torch.cuda.synchronize()
     D.barrier()
     elapsed = D.max_over_ranks(time.perf_counter() - t0)
     finite = bool(torch.isfinite(st.latents).all())
     log(f"timed region: {args.steps} steps in {elapsed:.3f} s")
+    if args.dump_outputs and rank == 0:
+        # before the profiling step below, which steps the same latents once more
+        shapes = dump_outputs(args.dump_outputs, {"latents": st.latents, "noise_pred": noise_pred})
+        log(f"outputs of the last timed step written to {args.dump_outputs}: {shapes}")
 
     if rank == 0 and not args.no_profile_step:
         # per-kernel HIP-event timing needs eager launches: one extra identical step outside the timed region, through the
