@@ -104,7 +104,9 @@ __device__ __forceinline__ uint4 pack_elx8(const float* f) {
 // carries one rounding.  Round 6: the lo plane is ONE BYTE per element -- e5m2 ("bf8": fp16's sign / exponent and its two top
 // mantissa bits; v_cvt_pk_bf8_f32 / v_cvt_pk_f32_bf8), i.e. hi + lo keeps ~15 significant bits in 3 bytes.  On the oracle
 // (tests/trunk_precision_study.py) that has the model-level error of a 16-bit lo plane (5.84e-4 vs 5.88e-4) at half the extra
-// bytes; |lo| <= ulp(hi) / 2 is far inside e5m2's range, values under 2^-16 flush to zero (absolute error < 2^-17).
+// bytes; |lo| <= ulp(hi) / 2 is far inside e5m2's range.  The conversion rounds to nearest even with e5m2's subnormals (k *
+// 2^-16): |v - hi| up to 2^-17 gives zero, above it 2^-16 (absolute error <= 2^-17) -- the rounding of torch's float8_e5m2
+// (tests/split_planes.py e5m2_rne; tests/test_split_exact_gpu.py checks the hardware byte for byte).
 typedef uint8_t lo_t;
 __device__ __forceinline__ uint2 split_lo8(const float* v, const uint4& hi) {
 #pragma clang fp contract(off)

@@ -803,9 +803,14 @@ int run_tr(Ctx& c, const Transformer& t, const Trk& x, int H, int W, Trk* out_) 
   {
     // norm1 + attn1 over the frames + residual + the one-key cross-attention vector (attn2): at C = 320 ONE launch -- the
     // normalised rows, q|k|v and the attention output never reach HBM (temporal_fused.hip; CTRLV_TEMPORAL_FUSED=0: the four
-    // launches).  With split trunk planes the in-kernel norm reads the hi plane (the element-rounded branch input: one more
-    // rounding on this branch's input, none on the trunk -- the residual operand stays hi + lo; the complete step's rel-L2
-    // against the oracle is unchanged within 1e-5, bench.py's parity leg).
+    // launches).  With split trunk planes the norm input of a block that HAS the fused form (C = 320: t_wf) is the hi plane
+    // (the element-rounded branch input: one more rounding on this branch's input, none on the trunk -- the residual operand
+    // stays hi + lo; the complete step's rel-L2 against the oracle is unchanged within 1e-5, bench.py's parity leg), on
+    // BOTH routes, so that such a block gives the same numbers fused and as the four launches (the routing test of
+    // tests/test_split_exact_gpu.py).  The kernel's prologue reads hi only because its LO + LN instantiation already uses
+    // 248 of 256 VGPRs (tests/test_build_resources.py): there is no room to hold the row's lo bytes through its three passes.
+    // The blocks the fused kernel never serves (C = 640 / 1280: the fallback is their only route) normalise hi + lo like
+    // every other norm of the split trunk (hi-only norms cost 8.0e-4 -> 9.5e-4 on the complete step).
     ctrlv_temporal_fused_desc fd;
     memset(&fd, 0, sizeof(fd));
     fd.x = tt; fd.ldx = C; fd.wf = t.t_wf; fd.bias = t.t_o.b;
@@ -821,7 +826,7 @@ int run_tr(Ctx& c, const Transformer& t, const Trk& x, int H, int W, Trk* out_) 
     const bool fused = fuse && ctrlv_temporal_fused_serves(&fd);
     if (!fused || !ln_in) {
       if (ln_in) { ln_in = false; fd.x = tt; fd.ln_gamma = fd.ln_beta = nullptr; }
-      TRY(layernorm(c, g0, (int)M, C, t.t_ln1, tt));
+      TRY(layernorm(c, t.t_wf ? Trk{g0.hi, nullptr} : g0, (int)M, C, t.t_ln1, tt));   // (C = 320: hi, as the prologue)
     }
     if (fused) {
       if (!c.dry) {

@@ -407,13 +407,14 @@ class TransformerSpatioTemporalModel(nn.Module):
         xt_vec = ctx.xattn[:, self.xattn_off[1]:]
         # diffusers 0.27.2: time_context rows ordered (s, b), tokens ordered (b, s)
         vkw = dict(vmode=2, vdiv=F * S, vS=S, vmod=B) if (ctx.quirk and B > 1) else dict(vmode=1, vdiv=F * S)
-        # (split trunk: the in-kernel LayerNorm normalises the hi plane of g0, as in the plan)
+        # (split trunk: where the fused form exists (C = 320) the LayerNorm normalises the hi plane of g0 on both routes, as
+        #  its in-kernel prologue does; elsewhere hi + lo -- csrc/plan.hip run_tr)
         fkw = _trk_epi(dict(bias=pk["t_o"][1], R1=g0, V=xt_vec, ln=(pk["t_ln1"][0], pk["t_ln1"][1], 1e-5), **vkw), g1)
         if _TEMPORAL_FUSED and ops.temporal_fused_serves(g0, pk["t_wf"], g1, B, F, S, **fkw):
             # norm1 + attn1 over the frames + residual + the cross-attention vector in ONE launch (csrc/plan.hip run_tr)
             ops.temporal_fused(g0, pk["t_wf"], g1, B, F, S, **fkw)
         else:
-            ops.layernorm(g0, pk["t_ln1"][0], pk["t_ln1"][1], 1e-5, t, x_lo=_lo(g0))
+            ops.layernorm(g0, pk["t_ln1"][0], pk["t_ln1"][1], 1e-5, t, x_lo=None if pk["t_wf"] is not None else _lo(g0))
             ops.gemm(t, pk["t_qkv"], qkv, N=3 * C, cin=C)
             ops.attention_temporal(qkv, a, B, F, S, C)
             ops.gemm(a, pk["t_o"][0], g1, N=C, cin=C, bias=pk["t_o"][1], **_trk_epi(dict(R1=g0, V=xt_vec, **vkw), g1))
