@@ -188,12 +188,21 @@ def gemm_grads(A, weight, dY, geom, s_acc, need_dA=True, need_dW=True, need_db=T
         # Linear weights are written in place; conv weights in the packed tap-major order and permuted afterwards
         # (writing [N, cin, taps] directly scatters the atomics at a 36-byte stride: A/B in DESIGN 3.6)
         direct = taps == 1 or _WGRAD_DIRECT
+        # ctrlv_gemm_wgrad takes N % 8 == 0: an output width below that (the UNet's conv_out, N = 4, trainable in the
+        # stage-1 step) runs on dY zero-padded to 8 columns, and the padded rows of dW / dbias are dropped
+        nw, dYw = (N + 7) // 8 * 8, dY
+        if nw != N:
+            dYw = torch.zeros(dY.shape[0], nw, dtype=dY.dtype, device=dY.device)
+            dYw[:, :N] = dY
         # (deterministic form: the ordered slab sum WRITES dW / dbias -- no zero fill; the atomic form accumulates)
         new = torch.empty if ops.DETERMINISTIC else torch.zeros
-        dWp = new(weight.shape if direct else (N, taps * cin), dtype=torch.float32, device=A.device)
-        dbp = new(N, dtype=torch.float32, device=A.device) if need_db else None
-        ops.gemm_wgrad(A, dY, dWp, N=N, cin=cin, taps=taps, mode=mode, conv=geom.get("conv"),
+        dWp = new((nw,) + tuple(weight.shape[1:]) if direct else (nw, taps * cin), dtype=torch.float32, device=A.device)
+        dbp = new(nw, dtype=torch.float32, device=A.device) if need_db else None
+        ops.gemm_wgrad(A, dYw, dWp, N=nw, cin=cin, taps=taps, mode=mode, conv=geom.get("conv"),
                        temporal=geom.get("temporal"), dbias=dbp, scale=s_acc, torch_layout=direct, assign=ops.DETERMINISTIC)
+        if nw != N:
+            dWp = dWp[:N]
+            dbp = dbp[:N] if dbp is not None else None
         if direct:
             dW = dWp
         elif mode == 1:
@@ -684,7 +693,13 @@ def transformer_train_forward(tr, x, ehs, B, F, H, W, time_context_order="sb"):
         return LayerNormFn.apply(h, n.weight, n.bias, V, vdiv, vmod, True)
 
     def qkv_w(attn):
-        return _frozen(attn.to_q.weight, "qkv_cat", lambda: torch.cat([attn.to_q.weight, attn.to_k.weight, attn.to_v.weight], 0))
+        # the fused q|k|v weight is cached only while ALL THREE are frozen (partial freezing is a public mode of the UNet
+        # step), keyed on all three: a trainable or replaced k / v must not be served an old concatenation
+        q, k, v = attn.to_q.weight, attn.to_k.weight, attn.to_v.weight
+        if q.requires_grad or k.requires_grad or v.requires_grad:
+            return torch.cat([q, k, v], 0)
+        kind = ("qkv_cat",) + tuple((id(p), p._version, p.data_ptr(), p.dtype) for p in (k, v))
+        return _frozen(q, kind, lambda: torch.cat([q, k, v], 0))
 
     # Every trunk tensor (x, h0, h1, h2, g0, g1) feeds the norm that opens a branch AND the skip connection around it: the norm
     # hands the skip its alias (skip=True), so both gradients meet in the norm's backward kernel instead of a separate sum.

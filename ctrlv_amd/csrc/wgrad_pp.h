@@ -5,7 +5,8 @@
 struct ctrlv_wgrad_pp_plan_t {
   int ntiles, ktiles, slabs, rows_per_slab;
 };
-// does the kernel serve this layer (mode 0, stride-1 3x3, temporal conv; N, Cin multiples of 64; no concat operand)?
+// does the kernel serve this layer (mode 0, stride-1 3x3 with or without the fused nearest-x2 upsampling, temporal conv;
+// N, Cin multiples of 64; no concat operand)?
 bool ctrlv_wgrad_pp_serves(const ctrlv_gemm_desc& d, const void* dY, int ldy);
 // grid decomposition: (n tile of 320, k tile of 256, row slab); a function of the layer only
 void ctrlv_wgrad_pp_plan(const ctrlv_gemm_desc& d, ctrlv_wgrad_pp_plan_t* p);

@@ -25,8 +25,12 @@
 // chunk apart, two barriers per chunk) is 1.4 % SLOWER than this loop, whose halves already mix 10 MFMAs with 14 reads.
 // Grid: (n tile, k tile, row slab), dealt out XCD-aware like wgrad_kernel (the tiles of one slab share its rows in one L2);
 // slab partials + the ordered sum of wgrad_reduce_kernel (deterministic), or fp32 atomics without scratch.
-// Serves mode 0, stride-1 3x3 without upsampling, the temporal conv; N, Cin multiples of 64; everything else (stride 2,
-// the concat operand, tiny M) stays on wgrad_kernel.
+// Serves mode 0, stride-1 3x3 (also with the nearest-x2 upsampling fused: the UNet's upsampler convs), the temporal conv;
+// N, Cin multiples of 64; everything else (stride 2, the concat operand, tiny M) stays on wgrad_kernel.
+// Upsampling (MODE 3, its own kernel wgrad_pp_up_kernel): dY and the row walk live on the 2H x 2W grid; the A piece of tap
+// (dy, dx) comes from the source pixel ((y + dy) >> 1, (x + dx) >> 1) of the H x W input, zeros outside the 2H x 2W border --
+// the A waves carry the image's first input row along with the (row, pixel) position and form each piece's row from it.
+// (As a runtime branch of the plain 3x3 kernel that row formation cost the cfg5 3x3 shapes 5-8 %: tools/wgrad_bench.py.)
 #include "common.h"
 #include "wgrad_pp.h"
 
@@ -53,6 +57,7 @@ struct WpArgs {
   const el_t* A; const el_t* dY; float* dW; float* dbias; float* part; float scale; int torch_layout;
   int M, N, Cin, taps, lda, ldy, mode, H, Wd, F, S, rows_per_slab, ntiles, ktiles, slabs;
   float inv_w, inv_h, inv_s, inv_f;
+  int Wi, HWi, MA;                 // MODE 3: the input's width and pixels per image (H, Wd are then the 2H x 2W grid); A rows
 };
 
 typedef int i32x2_t __attribute__((ext_vector_type(2)));
@@ -116,7 +121,7 @@ __device__ __forceinline__ float frag_sum(const Frag& f) {
 }
 
 template <int MODE>
-__global__ __launch_bounds__(512) void wgrad_pp_kernel(const WpArgs a) {
+__device__ __forceinline__ void wgrad_pp_main(const WpArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
   extern __shared__ __attribute__((aligned(1024))) char smem[];
   CTRLV_CLOCK_BEGIN();
@@ -132,7 +137,7 @@ __global__ __launch_bounds__(512) void wgrad_pp_kernel(const WpArgs a) {
   const int nh = wid & 1, kh = wid >> 1;
 
   const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc((void*)a.dY, 0, (int)((long)a.M * a.ldy * 2), kFlags);
-  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)a.A, 0, (int)((long)a.M * a.lda * 2), kFlags);
+  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)a.A, 0, (int)((long)(MODE == 3 ? a.MA : a.M) * a.lda * 2), kFlags);
 
   // ---- DMA roles.  Waves 0-3: rows 8w .. 8w+7 of the 5 dY panels; waves 4-7: rows 8(w-4) .. of the 4 A panels.  Lane l
   // writes 16 B at l * 16 of its piece: row l >> 3, PHYSICAL chunk l & 7 = logical chunk (l & 7) ^ swizzle(row).
@@ -142,7 +147,8 @@ __global__ __launch_bounds__(512) void wgrad_pp_kernel(const WpArgs a) {
   const bool is_y = wid < 4;
   int pbase[5];                                                    // per-piece byte offset relative to row m; kOOB = never valid
   int pdu[4], pdv[4];                                              // the piece's tap offsets (A waves)
-  const int dim_u = MODE == 1 ? a.H : a.F, dim_v = a.Wd, dim_s = a.S;
+  constexpr bool up = MODE == 3, kConv = MODE == 1 || up;          // (kConv: 3x3 taps on an (H, Wd) row walk)
+  const int dim_u = kConv ? a.H : a.F, dim_v = a.Wd, dim_s = a.S;
   const float inv_w = a.inv_w, inv_h = a.inv_h, inv_s = a.inv_s, inv_f = a.inv_f;
 #pragma unroll
   for (int p = 0; p < 5; ++p) {
@@ -153,7 +159,7 @@ __global__ __launch_bounds__(512) void wgrad_pp_kernel(const WpArgs a) {
     const int tap = k_ok ? kcol / a.Cin : 0;
     const int c = kcol - tap * a.Cin;
     int delta = 0, du = 0, dv = 0;
-    if (MODE == 1) { du = tap / 3 - 1; dv = tap % 3 - 1; delta = du * a.Wd + dv; }
+    if (kConv) { du = tap / 3 - 1; dv = tap % 3 - 1; delta = up ? 0 : du * a.Wd + dv; }   // (up: row formed per chunk)
     if (MODE == 2) { du = tap - 1; delta = du * a.S; }
     const int ab = k_ok ? (delta * a.lda + c + lchunk * 8) * 2 : (int)kOOB;
     pbase[p] = is_y ? yb : ab;
@@ -165,11 +171,14 @@ __global__ __launch_bounds__(512) void wgrad_pp_kernel(const WpArgs a) {
   // 32 rows further per chunk with a conditional wrap (the serves() conditions make one wrap per axis enough)
   int dm = m_lo + prow, du_ = 0, dv_ = 0;
   int step_u = 0, step_v = 0;
-  if (MODE == 1) {
+  int img_a = 0;                                                   // up: A row of the input image's first pixel
+  if (kConv) {
     const int q1 = fdiv(dm, dim_v, inv_w);
     dv_ = dm - q1 * dim_v;
-    du_ = q1 - fdiv(q1, dim_u, inv_h) * dim_u;
+    const int img = fdiv(q1, dim_u, inv_h);
+    du_ = q1 - img * dim_u;
     step_u = kRows / dim_v; step_v = kRows - step_u * dim_v;
+    if (up) img_a = img * a.HWi;
   }
   if (MODE == 2) {
     const int q1 = fdiv(dm, dim_s, inv_s);
@@ -192,15 +201,19 @@ __global__ __launch_bounds__(512) void wgrad_pp_kernel(const WpArgs a) {
       for (int p = 0; p < 4; ++p) {
         bool ok = row_ok & (pbase[p] != (int)kOOB);
         if (MODE != 0) ok = ok & ((unsigned)(du_ + pdu[p]) < (unsigned)dim_u);
-        if (MODE == 1) ok = ok & ((unsigned)(dv_ + pdv[p]) < (unsigned)dim_v);
-        const unsigned voff = ok ? rbase + (unsigned)pbase[p] : kOOB;
+        if (kConv) ok = ok & ((unsigned)(dv_ + pdv[p]) < (unsigned)dim_v);
+        unsigned src = rbase;
+        if (up) src = (unsigned)(img_a + ((du_ + pdu[p]) >> 1) * a.Wi + ((dv_ + pdv[p]) >> 1)) * ld2;
+        const unsigned voff = ok ? src + (unsigned)pbase[p] : kOOB;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, LDS_PTR(slot + kAOff + p * kPanel), 16, voff, 0, 0, 0);
       }
-      if (MODE == 1) {
+      if (kConv) {
         dv_ += step_v; du_ += step_u;
         const bool wv = dv_ >= dim_v;
         dv_ -= wv ? dim_v : 0; du_ += wv ? 1 : 0;
-        du_ -= du_ >= dim_u ? dim_u : 0;
+        const bool wu = du_ >= dim_u;
+        du_ -= wu ? dim_u : 0;
+        if (up) img_a += wu ? a.HWi : 0;
       }
       if (MODE == 2) {
         dv_ += kRows;
@@ -343,6 +356,10 @@ __global__ __launch_bounds__(512) void wgrad_pp_kernel(const WpArgs a) {
 #endif
 }
 
+template <int MODE>
+__global__ __launch_bounds__(512) void wgrad_pp_kernel(const WpArgs a) { wgrad_pp_main<MODE>(a); }
+__global__ __launch_bounds__(512) void wgrad_pp_up_kernel(const WpArgs a) { wgrad_pp_main<3>(a); }
+
 }  // namespace
 
 CTRLV_CLOCK_READER(wgrad_pp)
@@ -350,14 +367,18 @@ CTRLV_CLOCK_READER(wgrad_pp)
 bool ctrlv_wgrad_pp_serves(const ctrlv_gemm_desc& d, const void* dY, int ldy) {
   if (!ctrlv_debug().wgrad_pp) return false;
   if (d.A2 != nullptr || d.A == nullptr) return false;
-  if (!(d.mode == 0 || d.mode == 2 || (d.mode == 1 && (d.stride == 0 || d.stride == 1) && d.up == 0 && d.Ho == d.H && d.Wo == d.Wd)))
+  const bool up = d.mode == 1 && d.up != 0;
+  if (!(d.mode == 0 || d.mode == 2 ||
+        (d.mode == 1 && (d.stride == 0 || d.stride == 1) &&
+         (up ? (d.Ho == 2 * d.H && d.Wo == 2 * d.Wd) : (d.Ho == d.H && d.Wo == d.Wd)))))
     return false;
   if (d.N % 64 != 0 || d.Cin % 64 != 0 || ldy % 8 != 0 || d.lda % 8 != 0) return false;
   if (((uintptr_t)d.A | (uintptr_t)dY) & 15) return false;
   if (d.M < 1024 || d.M >= (1 << 24)) return false;
   if ((long)d.M * d.lda * 2 >= (1L << 31) || (long)d.M * ldy * 2 >= (1L << 31)) return false;
   // (the kernel advances a row's (image row, pixel) / (frame, position) by 32 rows with ONE conditional wrap per axis)
-  if (d.mode == 1 && (d.H <= 0 || d.Wd <= 0 || d.M % (d.H * d.Wd) != 0 || d.H <= kRows / d.Wd + 1)) return false;
+  // (upsampling: the walk runs on the output grid Ho x Wo = 2H x 2W, whose M / 4 rows of A are the input's)
+  if (d.mode == 1 && (d.Ho <= 0 || d.Wo <= 0 || d.M % (d.Ho * d.Wo) != 0 || d.Ho <= kRows / d.Wo + 1)) return false;
   if (d.mode == 2 && (d.F <= 0 || d.S < kRows || d.M % (d.F * d.S) != 0)) return false;
   return true;
 }
@@ -394,25 +415,31 @@ int ctrlv_wgrad_pp_launch(const ctrlv_gemm_desc& d, const void* dY, int ldy, flo
   a.A = (const el_t*)d.A; a.dY = (const el_t*)dY; a.dW = dW; a.dbias = dbias; a.part = part; a.scale = scale;
   a.torch_layout = torch_layout;
   a.M = d.M; a.N = d.N; a.Cin = d.Cin; a.taps = d.taps; a.lda = d.lda; a.ldy = ldy; a.mode = d.mode;
-  a.H = d.H; a.Wd = d.Wd; a.F = d.F; a.S = d.S;
+  const bool up = d.mode == 1 && d.up != 0;
+  a.H = up ? d.Ho : d.H; a.Wd = up ? d.Wo : d.Wd; a.F = d.F; a.S = d.S;     // (the row walk's grid: dY's)
+  a.Wi = d.Wd; a.HWi = d.H * d.Wd;
+  a.MA = up ? d.M / 4 : d.M;
   a.rows_per_slab = p.rows_per_slab; a.ntiles = p.ntiles; a.ktiles = p.ktiles; a.slabs = p.slabs;
-  a.inv_w = d.mode == 1 ? 1.0f / (float)d.Wd : 0.f;
-  a.inv_h = d.mode == 1 ? 1.0f / (float)d.H : 0.f;
+  a.inv_w = d.mode == 1 ? 1.0f / (float)a.Wd : 0.f;
+  a.inv_h = d.mode == 1 ? 1.0f / (float)a.H : 0.f;
   a.inv_s = d.mode == 2 ? 1.0f / (float)d.S : 0.f;
   a.inv_f = d.mode == 2 ? 1.0f / (float)d.F : 0.f;
   const int dev = ctrlv_current_device();
-  static bool attr_set[3][CTRLV_MAX_DEVICES] = {};
+  static bool attr_set[4][CTRLV_MAX_DEVICES] = {};
   const unsigned grid = (unsigned)(p.ntiles * p.ktiles * p.slabs);
-#define WP_LAUNCH(MODEV)                                                                                             \
+#define WP_LAUNCH(MODEV, KFN)                                                                                        \
   do {                                                                                                               \
-    auto kfn = wgrad_pp_kernel<MODEV>;                                                                               \
+    auto kfn = KFN;                                                                                                  \
     if (!attr_set[MODEV][dev]) {                                                                                     \
       CTRLV_HIP_TRY(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, kSmem));       \
       attr_set[MODEV][dev] = true;                                                                                   \
     }                                                                                                                \
     hipLaunchKernelGGL(kfn, dim3(grid), dim3(512), kSmem, (hipStream_t)stream, a);                                   \
   } while (0)
-  if (d.mode == 0) WP_LAUNCH(0); else if (d.mode == 1) WP_LAUNCH(1); else WP_LAUNCH(2);
+  if (d.mode == 0) WP_LAUNCH(0, wgrad_pp_kernel<0>);
+  else if (up) WP_LAUNCH(3, wgrad_pp_up_kernel);
+  else if (d.mode == 1) WP_LAUNCH(1, wgrad_pp_kernel<1>);
+  else WP_LAUNCH(2, wgrad_pp_kernel<2>);
 #undef WP_LAUNCH
   CTRLV_LAUNCH_CHECK();
   return CTRLV_OK;

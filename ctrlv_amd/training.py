@@ -1,4 +1,6 @@
 """cfg5: one training step of the ControlNet on the HIP kernels (reference: tools/train_video_controlnet.py:366-488).
+Stage 1 of Ctrl-V (fine-tuning the UNet itself, tools/train_video_diffusion.py:459-541) is `unet_train_step` below: the
+same blocks with the UNet's encoder, mid block and tail trainable as well.
 
     ControlNet forward (trainable, fp32 master parameters, bf16 compute)
     -> frozen UNet forward: encoder + mid on the inference executor (no gradients flow there: the residuals join the skip
@@ -190,6 +192,35 @@ def unet_train_forward(unet, sample, timestep, encoder_hidden_states, added_time
                             dict(mode=1, conv=(H, W, H, W, 1, 0)))
 
 
+def unet_full_train_forward(unet, sample, timestep, encoder_hidden_states, added_time_ids):
+    """`UNetSpatioTemporalConditionModel.forward` (no ControlNet residuals) with gradients for every parameter that
+    requires them: the stage-1 forward of tools/train_video_diffusion.py:519-531.  The encoder and mid block run the
+    ControlNet's trainable blocks (the ControlNet is a copy of this encoder), their taps feed the decoder's skip concat --
+    autograd adds the two gradients of each tap.  Returns the prediction as channels-last rows [B*F*h*w, out_channels]."""
+    B, F, Cin, h, w = sample.shape
+    N, dev = B * F, sample.device
+    order = unet.time_context_order
+    emb_s = clip_embeddings(unet, timestep, added_time_ids, B, dev)
+    ehs = encoder_hidden_states.reshape(B, -1).float()
+    cp = (Cin + 7) // 8 * 8
+    kp = (9 * cp + 63) // 64 * 64
+    col = _input_cols([sample.reshape(N, Cin, h, w)], N, h, w, cp, kp, dev)
+    wi, bi = _input_conv_weight([unet.conv_in], cp, kp)
+    x = FusedLinear.apply(col, wi, bi, None, None, None, {})
+    taps, H, W = [(x, h, w)], h, w
+    with gradient_checkpointing(getattr(unet, "gradient_checkpointing", False)):
+        for blk in unet.down_blocks:
+            x, H, W, t = down_block_train(blk, x, emb_s, ehs, B, F, H, W, order)
+            taps += t
+        x = mid_block_train(unet.mid_block, x, emb_s, ehs, B, F, H, W, order)
+        skips = [t[0] for t in taps]
+        for blk in unet.up_blocks:
+            x, H, W = up_block_train(blk, x, emb_s, ehs, B, F, H, W, skips, order)
+    xn = GroupNormSiLU.apply(x, unet.conv_norm_out.weight, unet.conv_norm_out.bias, N, H * W, 1, 1e-5, True)
+    return GatherGemm.apply(xn, unet.conv_out.weight, unet.conv_out.bias, None, None, 1.0,
+                            dict(mode=1, conv=(H, W, H, W, 1, 0)))
+
+
 # ------------------------------------------------------------------------------------------------- loss / step
 def rows_of(x5):
     """(B, F, C, h, w) -> channels-last rows [B*F*h*w, C] (torch permute: tiny latent tensors)."""
@@ -221,6 +252,35 @@ def train_step(controlnet, unet, batch, optimizer=None, conditioning_scale=1.0, 
     Returns the loss as a device tensor; the one host read of the step is the batched mix-factor fetch at its start."""
     from .autograd import prefetch_mix_factors
     prefetch_mix_factors(controlnet, unet)          # the step's only device-to-host read (about 60 scalars, one copy)
+    lat, sig, noisy, timesteps, sample = _noised_inputs(batch)
+    down, mid = controlnet_train_forward(controlnet, sample, timesteps, batch["encoder_hidden_states"],
+                                         batch["added_time_ids"], batch["control_cond"].to(torch.bfloat16),
+                                         conditioning_scale)
+    pred = unet_train_forward(unet, sample, timesteps, batch["encoder_hidden_states"], batch["added_time_ids"], down, mid)
+    loss = edm_loss(pred, noisy, lat, sig)
+    return _backward_and_step(controlnet, loss, optimizer, world_size, buckets, accumulate, loss_scale)
+
+
+def unet_train_step(unet, batch, optimizer=None, world_size=1, buckets=None, accumulate=False, loss_scale=1.0):
+    """One stage-1 optimisation step: the whole UNet fine-tuned (tools/train_video_diffusion.py:515-541; UNet forward,
+    EDM loss, backward, optimizer step).  Which parameters train is the caller's choice through `unet.enable_grad(...)`
+    (all=True: the demo scripts; temporal_transformer_block=True: temporal-only mode) -- frozen parameters get no gradient,
+    and switching modes between steps needs nothing else (packed forms are cached only for frozen parameters, keyed on
+    their version).  batch: `train_step`'s keys without control_cond; image_latents (B,F,4,h,w) per frame (the
+    predict-bbox layout passes unchanged), encoder_hidden_states with the caller's conditioning dropout already applied.
+    Data parallel / gradient accumulation / zero gradients for parameters without a gradient path: as in `train_step`.
+    Returns the detached loss."""
+    from .autograd import prefetch_mix_factors
+    prefetch_mix_factors(unet)
+    lat, sig, noisy, timesteps, sample = _noised_inputs(batch)
+    pred = unet_full_train_forward(unet, sample, timesteps, batch["encoder_hidden_states"], batch["added_time_ids"])
+    loss = edm_loss(pred, noisy, lat, sig)
+    return _backward_and_step(unet, loss, optimizer, world_size, buckets, accumulate, loss_scale)
+
+
+def _noised_inputs(batch):
+    """EDM noising of a batch (train_video_controlnet.py:404-410, train_video_diffusion.py:519-527): (clean latents,
+    sigmas, noisy latents, continuous timesteps 0.25 ln sigma, bf16 model input = [scaled noisy | image latents])."""
     lat, noise, sig = batch["latents"].float(), batch["noise"].float(), batch["sigmas"].float()
     B = lat.shape[0]
     s5 = sig.reshape(B, 1, 1, 1, 1)
@@ -228,11 +288,11 @@ def train_step(controlnet, unet, batch, optimizer=None, conditioning_scale=1.0, 
     inp = noisy / (s5 * s5 + 1) ** 0.5                                          # :410
     timesteps = 0.25 * torch.log(sig)                                           # continuous timestep of sigma
     sample = torch.cat([inp, batch["image_latents"].float()], dim=2).to(torch.bfloat16)
-    down, mid = controlnet_train_forward(controlnet, sample, timesteps, batch["encoder_hidden_states"],
-                                         batch["added_time_ids"], batch["control_cond"].to(torch.bfloat16),
-                                         conditioning_scale)
-    pred = unet_train_forward(unet, sample, timesteps, batch["encoder_hidden_states"], batch["added_time_ids"], down, mid)
-    loss = edm_loss(pred, noisy, lat, sig)
+    return lat, sig, noisy, timesteps, sample
+
+
+def _backward_and_step(model, loss, optimizer, world_size, buckets, accumulate, loss_scale):
+    """backward, gradient reduction and optimizer step of `train_step` / `unet_train_step` (model: the trained one)."""
     if buckets is not None:
         buckets.enabled = not accumulate
     (loss * loss_scale if loss_scale != 1.0 else loss).backward()
@@ -241,10 +301,10 @@ def train_step(controlnet, unet, batch, optimizer=None, conditioning_scale=1.0, 
     if buckets is not None:
         buckets.finish()
     elif world_size > 1:
-        allreduce_gradients([p for p in controlnet.parameters() if p.requires_grad])
+        allreduce_gradients([p for p in model.parameters() if p.requires_grad])
     # parameters without a gradient path get ZERO gradients (what the reference's autograd gives them: weight decay then
     # applies), whatever the world size -- the data-parallel paths write zeros for them, so does the single-GPU one
-    for p in controlnet.parameters():
+    for p in model.parameters():
         if p.requires_grad and p.grad is None:
             p.grad = torch.zeros_like(p)
     if optimizer is not None:

@@ -324,7 +324,11 @@ int ctrlv_cfg_euler_step(float* latents, const void* noise_pred, int pred_dtype,
  * fp32 partial matrices with plain stores and a second kernel adds them to dW / dbias in slab order (a single writer per
  * element): the same gradient bits in every run.  Without it the slabs add with fp32 atomics (arrival order).
  * torch_layout bit 1 (value 2; with scratch only): ASSIGN -- dW / dbias = scale * sum instead of +=, their previous contents
- * are not read (no zero fill in front of the launch). */
+ * are not read (no zero fill in front of the launch).
+ * Kernel choice (a function of the layer's shape; the result layout is the same): the LDS-DMA ring of wgrad_pp.hip serves
+ * Linear / 1x1, the stride-1 3x3 conv with or without the fused nearest-x2 upsampling, and the temporal conv, with N and
+ * Cin multiples of 64 and M >= 1024; the stride-2 conv, the concat operand (A2) and everything else run on the
+ * register-staged kernel of backward.hip. */
 size_t ctrlv_gemm_wgrad_scratch_bytes(const ctrlv_gemm_desc* fwd);
 int ctrlv_gemm_wgrad(const ctrlv_gemm_desc* fwd, const void* dY, int ldy, float* dW, float* dbias, float scale,
                      int torch_layout, void* scratch, size_t scratch_bytes, ctrlv_stream_t stream);

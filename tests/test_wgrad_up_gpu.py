@@ -1,0 +1,44 @@
+"""Weight and bias gradients of the UNet's upsampler convs (nearest x2 fused into a 3x3 conv, csrc/wgrad_pp.hip's MODE 3)
+at their three channel counts with small M, in both libraries (bf16 and fp16 elements): against fp32 torch autograd on
+conv2d(interpolate(x, 2, "nearest")) with the bound of tests/test_backward_gpu.py::test_wgrad_conv3x3, and bit-identical
+across two runs (the ordered slab sum)."""
+import pytest
+import torch
+import torch.nn.functional as Fn
+
+from tests.parity_utils import rel_l2
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+# (channels, input H, W, images): the SVD decoder's upsamplers are 1280 ch at 9x16 and 18x32 and 640 ch at 36x64 (for the
+# 576 x 1024 frame); rows M = images * 2H * 2W of dY, at least 1024 so that the LDS-DMA kernel serves them
+SHAPES = [(1280, 9, 16, 2), (1280, 18, 32, 1), (640, 36, 64, 1)]
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
+@pytest.mark.parametrize("C,H,W,n", SHAPES, ids=[f"{c}ch_{h}x{w}" for c, h, w, _ in SHAPES])
+def test_wgrad_upsample_conv(hip_lib, C, H, W, n, dtype):
+    from ctrlv_amd.autograd import gemm_grads
+    g = torch.Generator().manual_seed(C + H)
+    x = torch.randn(n, C, H, W, generator=g).to(dtype).float()
+    dy = torch.randn(n, C, 2 * H, 2 * W, generator=g).to(dtype).float()
+    w = (torch.randn(C, C, 3, 3, generator=g) / (9 * C) ** 0.5)
+    # reference: fp32 autograd on the GPU
+    wr = w.to(DEV).requires_grad_(True)
+    br = torch.zeros(C, device=DEV, requires_grad=True)
+    Fn.conv2d(Fn.interpolate(x.to(DEV), scale_factor=2, mode="nearest"), wr, br, padding=1).backward(dy.to(DEV))
+    # HIP: channels-last rows, the geometry GatherGemm gives the upsampler conv
+    A = x.permute(0, 2, 3, 1).reshape(-1, C).to(DEV, dtype).contiguous()
+    dY = dy.permute(0, 2, 3, 1).reshape(-1, C).to(DEV, dtype).contiguous()
+    geom = dict(mode=1, conv=(H, W, 2 * H, 2 * W, 1, 1))
+    runs = []
+    for _ in range(2):
+        _, dW, db = gemm_grads(A, w.to(DEV), dY, geom, 1.0, need_dA=False, need_dW=True, need_db=True)
+        torch.cuda.synchronize()
+        runs.append((dW.clone(), db.clone()))
+    (dW, db), (dW2, db2) = runs
+    ew, eb = rel_l2(dW.cpu(), wr.grad.cpu()), rel_l2(db.cpu(), br.grad.cpu())
+    print(f"  C={C} {H}x{W} -> {2 * H}x{2 * W} x{n} {dtype}: dW rel-L2 {ew:.2e}  dbias rel-L2 {eb:.2e}")
+    assert ew < 2e-3 and eb < 2e-3
+    assert torch.equal(dW, dW2) and torch.equal(db, db2)

@@ -1,0 +1,155 @@
+#!/usr/bin/env python
+"""Stage 1 on one MI355X: the UNet fine-tuning step (tools/train_video_diffusion.py:515-541; B = 1, full SVD width) through
+ctrlv_amd.training.unet_train_step.  Prints ONE JSON line: ms per optimisation step, its split (forward / backward /
+optimizer, HIP events), peak device memory, the mode (`all`: every parameter, the demo scripts; `temporal`: the temporal
+transformer blocks only), gradient checkpointing, and the analytic work of the step -- counted from the layer list (torch's
+FLOP counter over the oracle UNet's forward and backward on the meta device: GEMMs, convs and attention; checkpoint
+recomputes are not counted).  Synthetic data, random-init weights (there are no checkpoints in this image).
+Default size: the stage-1 training size 320 x 512 (src/ctrlv/datasets/kitti_abstract.py:86-90); --height 576 --width 1024
+for the full frame.
+usage: python tools/train_unet_bench.py [--steps 3] [--warmup 1] [--frames 25] [--height 320] [--width 512]
+       [--mode all|temporal] [--gradient-checkpointing 0|1] [--gpus N]
+Data parallel: --gpus N as in tools/train_bench.py (one rank process per GPU, its own clip per rank, the fp32 gradients
+all-reduced in 25 MB buckets while the backward runs); the time is the MAX over ranks."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def analytic_tflop(frames, h, w, mode="all", config=None):
+    """(forward, backward) TFLOP of one stage-1 step at B = 1 and an h x w latent, from the layer list of the oracle UNet
+    (SVD configuration unless `config`), counted on the meta device: no memory, no arithmetic."""
+    from torch.utils.flop_counter import FlopCounterMode
+    if os.path.join(ROOT, "oracle") not in sys.path:
+        sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import ctrlv_ref as R
+    cfg = dict(config or R.SVD_CONFIG, num_frames=frames)
+    with torch.device("meta"):
+        ou = R.UNetSpatioTemporalConditionModel(**cfg)
+    ou = ou.to("meta")                 # (a few parameters are built with the legacy constructor, on the CPU)
+    for n, p in ou.named_parameters():
+        p.requires_grad_(mode == "all" or "temporal_transformer_block" in n)
+    dc = cfg["cross_attention_dim"]
+    dc = dc if isinstance(dc, int) else dc[0]
+    x = torch.empty(1, frames, cfg["in_channels"], h, w, device="meta")
+    with FlopCounterMode(display=False) as fwd:
+        out = ou(x, torch.tensor(1.0, device="meta"), torch.empty(1, 1, dc, device="meta"),
+                 torch.empty(1, 3, device="meta"))[0]
+    with FlopCounterMode(display=False) as bwd:
+        out.float().sum().backward()
+    return fwd.get_total_flops() / 1e12, bwd.get_total_flops() / 1e12
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--frames", type=int, default=25)
+    ap.add_argument("--height", type=int, default=320)
+    ap.add_argument("--width", type=int, default=512)
+    ap.add_argument("--mode", choices=("all", "temporal"), default="all",
+                    help="all: unet.enable_grad(all=True) (the demo scripts); temporal: temporal_transformer_block only")
+    ap.add_argument("--lr", type=float, default=1e-5)
+    ap.add_argument("--fused-adamw", type=int, default=1, help="torch.optim.AdamW(fused=...)")
+    ap.add_argument("--gradient-checkpointing", type=int, default=0,
+                    help="1: unet.enable_gradient_checkpointing() (the GEGLU feed-forward intermediates are recomputed in "
+                         "the backward)")
+    ap.add_argument("--gpus", type=int, default=0,
+                    help="N > 1 without a torchrun environment: start N rank processes (one per GPU) from this GPU-free parent")
+    args = ap.parse_args()
+    if args.gpus > 1 and "RANK" not in os.environ:
+        from ctrlv_amd.distributed import launch_local_ranks
+        launch_local_ranks(__file__, sys.argv[1:], args.gpus)
+        return
+    world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", 1), ("RANK", 0), ("LOCAL_RANK", 0)))
+    if args.gpus and args.gpus != world:
+        raise SystemExit(f"train_unet_bench.py: --gpus {args.gpus} but WORLD_SIZE={world}")
+    dev = torch.device(f"cuda:{local}")
+    torch.cuda.set_device(dev)
+    if world > 1:
+        import torch.distributed as dist
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
+    import __graft_entry__ as ge
+    if rank == 0:
+        ge.build()
+    if world > 1:
+        dist.barrier()
+    from ctrlv_amd import training
+    from ctrlv_amd.autograd import prefetch_mix_factors
+    from ctrlv_amd.models import UNetSpatioTemporalConditionModel
+    from ctrlv_amd.utils import build_on_device, random_init_
+    unet = build_on_device(UNetSpatioTemporalConditionModel, dev, dtype=torch.float32, num_frames=args.frames)  # fp32 masters
+    random_init_(unet, seed=0)
+    if args.mode == "all":
+        unet.enable_grad(all=True)
+    else:
+        unet.enable_grad(temporal_transformer_block=True)
+    if args.gradient_checkpointing:
+        unet.enable_gradient_checkpointing()
+    params = unet.get_parameters_with_grad()
+    opt = torch.optim.AdamW(params, lr=args.lr, weight_decay=1e-2, fused=bool(args.fused_adamw))
+    buckets = training.GradientBuckets(params) if world > 1 else None
+    B, F, h, w = 1, args.frames, args.height // 8, args.width // 8
+    g = torch.Generator(device=dev).manual_seed(1234 + rank)             # every rank: its own clip
+    rn = lambda *s: torch.randn(*s, generator=g, device=dev)      # noqa: E731
+    batch = dict(latents=rn(B, F, 4, h, w), noise=rn(B, F, 4, h, w), sigmas=torch.tensor([1.5], device=dev),
+                 image_latents=rn(B, 1, 4, h, w).repeat(1, F, 1, 1, 1), encoder_hidden_states=rn(B, 1, 1024),
+                 added_time_ids=torch.tensor([[6.0, 127.0, 0.02]], device=dev))
+    ev = lambda: torch.cuda.Event(enable_timing=True)             # noqa: E731
+    times, losses = [], []
+    for i in range(args.warmup + args.steps):
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        t0 = time.time()
+        e = [ev() for _ in range(4)]
+        e[0].record()
+        # unet_train_step, cut at its phase boundaries
+        prefetch_mix_factors(unet)
+        lat, sig, noisy, ts, sample = training._noised_inputs(batch)
+        pred = training.unet_full_train_forward(unet, sample, ts, batch["encoder_hidden_states"], batch["added_time_ids"])
+        loss = training.edm_loss(pred, noisy, lat, sig)
+        e[1].record()
+        training._backward_and_step(unet, loss, None, world, buckets, False, 1.0)
+        e[2].record()
+        opt.step()
+        opt.zero_grad(set_to_none=True)
+        e[3].record()
+        torch.cuda.synchronize()
+        wall = (time.time() - t0) * 1e3
+        if world > 1:                                             # slowest rank defines the step
+            wt = torch.tensor([wall], device=dev)
+            dist.all_reduce(wt, op=dist.ReduceOp.MAX)
+            wall = float(wt)
+        if i >= args.warmup:
+            times.append((wall, e[0].elapsed_time(e[1]), e[1].elapsed_time(e[2]), e[2].elapsed_time(e[3])))
+        losses.append(float(loss.detach()))
+        del pred, loss
+    if rank != 0:
+        return
+    n = len(times)
+    avg = [sum(t[k] for t in times) / n for k in range(4)]
+    tf_f, tf_b = analytic_tflop(F, h, w, args.mode)
+    print(json.dumps({"metric": "stage-1 UNet training step (B=1 per GPU, no CFG)", "n_gpus": world, "mode": args.mode,
+                      "samples_per_s": round(world * 1e3 / avg[0], 3), "scaling": "weak", "ms_per_step": round(avg[0], 1),
+                      "forward_ms": round(avg[1], 1), "backward_ms": round(avg[2], 1), "optimizer_ms": round(avg[3], 1),
+                      "steps": n, "warmup": args.warmup, "frames": F, "latent": [h, w],
+                      "analytic_tflop_per_step": round(tf_f + tf_b, 1), "analytic_tflop_forward": round(tf_f, 1),
+                      "analytic_tflop_backward": round(tf_b, 1), "tflops": round((tf_f + tf_b) / avg[0] * 1e3, 1),
+                      "peak_mem_gb": round(torch.cuda.max_memory_allocated() / 2**30, 1),
+                      "trainable_params_m": round(sum(p.numel() for p in params) / 1e6, 1),
+                      "losses": [round(v, 5) for v in losses],
+                      "gradient_checkpointing": bool(args.gradient_checkpointing),
+                      "dtype": "bf16 compute, fp32 master parameters + AdamW", "data": "synthetic, random-init weights"}))
+
+
+if __name__ == "__main__":
+    main()

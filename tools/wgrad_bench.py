@@ -1,5 +1,6 @@
 """Weight-gradient launches of the cfg5 training step (B = 1, 25 frames, 72 x 128 latent), one by one: time per launch and
-TFLOP/s of ctrlv_gemm_wgrad (main kernel + ordered slab sum).  CTRLV_WGRAD_PP=0 runs every layer on the register-staged
+TFLOP/s of ctrlv_gemm_wgrad (main kernel + ordered slab sum).  The last three rows are the UNet decoder's upsampler convs
+(nearest x2 fused into the 3x3 conv), which only the stage-1 step (unet_train_step) trains.  CTRLV_WGRAD_PP=0 runs every layer on the register-staged
 kernel of backward.hip (A/B of csrc/wgrad_pp.hip).   python tools/wgrad_bench.py [--iters 10] [--dtype bf16|fp16]"""
 import argparse
 import json
@@ -22,6 +23,10 @@ def shapes(F=25, h=72, w=128):
         if lvl < 3:
             out += [(f"L{lvl} linear {C}->{C}", M, C, C, 1, None), (f"L{lvl} GEGLU {C}->{8 * C}", M, 8 * C, C, 1, None),
                     (f"L{lvl} ff out {4 * C}->{C}", M, C, 4 * C, 1, None)]
+    # the upsamplers: input (H, W) -> output (2H, 2W); M counts the rows of dY (output pixels)
+    for lvl, C in ((3, 1280), (2, 1280), (1, 640)):
+        H, W = h >> lvl, w >> lvl
+        out.append((f"up{lvl} conv3x3 x2 {C}->{C}", F * 4 * H * W, C, C, 9, (H, W, 2 * H, 2 * W)))
     return out
 
 
@@ -38,12 +43,15 @@ def main():
     for name, M, N, cin, taps, geo in shapes():
         if args.filter not in name:
             continue
-        A = torch.randn(M, cin, device=dev).to(dt)
+        up = geo is not None and len(geo) == 4
+        A = torch.randn(M // 4 if up else M, cin, device=dev).to(dt)
         dY = torch.randn(M, N, device=dev).to(dt)
         dW = torch.zeros(N, taps * cin, dtype=torch.float32, device=dev)
         db = torch.zeros(N, dtype=torch.float32, device=dev)
         kw = dict(N=N, cin=cin, taps=taps)
-        if taps == 9:
+        if up:
+            kw.update(mode=1, conv=(geo[0], geo[1], geo[2], geo[3], 1, 1))
+        elif taps == 9:
             kw.update(mode=1, conv=(geo[0], geo[1], geo[0], geo[1], 1, 0))
         elif taps == 3:
             kw.update(mode=2, temporal=geo)
