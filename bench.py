@@ -6,7 +6,7 @@ ControlNet forward + UNet forward (batch 2) + CFG combine + Euler update
 (/root/reference/src/ctrlv/pipelines/pipeline_video_control.py:298-343), on synthetic seeded inputs and random-init
 weights of the SVD-XT architecture, inputs resident in HBM before the timed region.
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (RANK / WORLD_SIZE
 in the environment), or started plainly -- then this process, WITHOUT touching the GPU, starts the N rank processes
@@ -14,7 +14,9 @@ itself and relays rank 0's JSON line.  Clips shard one-per-rank, weights replica
 scaling); a barrier + torch.cuda.synchronize() brackets the timed region and the elapsed time is the MAX over ranks.
 `n_gpus` in the output is the world size the process group reports.
 
-Rank 0 prints ONE JSON line with the contract fields plus
+A plain run does only what the headline figure needs: it sets up, warms up, times the K steps, writes --dump-outputs, and
+rank 0 prints ONE JSON line with the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step, n_gpus, ...).
+With --full it goes on after the timed steps and the line also carries
   roofline / rooflines   per kernel family (HIP events on the launch stream during one instrumented eager step), incl.
                          the attention-MFMA and GroupNorm-HBM fractions north_star asks for; `traffic` = PMC HBM bytes
                          per launch from the committed rocprofv3 --pmc summary, or null when that summary was not
@@ -23,7 +25,10 @@ Rank 0 prints ONE JSON line with the contract fields plus
                          (B = 1, all 25 frames at the full latent resolution, full SVD widths; x2 for the CFG pair), the
                          thread count swept up to the physical core count; `--cpu-frames N` bounds it to N frames
                          (converted by the frame count: per-frame work is identical; see cpu_baseline());
-  parity                 the HIP models' output on that same sample (same weights, same inputs) against the oracle's.
+  parity                 the HIP models' output on that same sample (same weights, same inputs) against the oracle's;
+  fp16_build, fp16_split_trunk_build, at_tolerance
+                         bf16 runs: the same weights and sample through the fp16 element build (with and without the split
+                         trunk), and the fastest configuration of the run within north_star's tolerance.
 The CPU baseline times one complete no-CFG step (25 frames, ~109 TFLOP, ~2 minutes); `--cpu-frames 2` bounds it to a ~10 s sample.
 """
 import argparse
@@ -44,7 +49,7 @@ PEAK_HBM_GBS = 8000.0               # 8.0 TB/s spec (6.29 TB/s measured float4 c
 ALG_TFLOP_PER_STEP = {"box2video": 218.52, "svd_unet": 159.90}     # SURVEY.md Appendix B (CFG, 25x72x128)
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=4)
@@ -56,7 +61,12 @@ def parse():
                     help="box2video = BASELINE configs[2] (SVD + ControlNet, the metric's config); svd_unet = configs[1]")
     ap.add_argument("--hip-graph", type=int, default=int(os.environ.get("CTRLV_HIP_GRAPH", "1")),
                     help="replay the two model forwards from a captured HIP graph (default on)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline does not need: the per-kernel "
+                         "rooflines (one instrumented eager step), the CPU oracle baseline, parity against it and the fp16 "
+                         "legs (off by default: a plain run prints the headline line only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full runs: skip the CPU oracle baseline and what compares with it (parity, the fp16 legs)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads for the CPU oracle (0 = calibrate)")
     ap.add_argument("--cpu-frames", type=int, default=0,
                     help="frames of the CPU baseline's sample at the full latent size; 0 (default) = ALL frames: the "
@@ -76,15 +86,15 @@ def parse():
                     help="storage of the residual trunk (with --dtype fp16): same = one fp16 element per value; fp16x2 = split "
                          "fp16 hi + one-byte e5m2 lo planes (~15 significant bits in 3 bytes) -- north_star's 1e-3 model-level tolerance")
     ap.add_argument("--no-profile-step", action="store_true",
-                    help="skip the extra instrumented eager step (no `roofline` in the output): for runs under rocprofv3 --pmc")
+                    help="--full runs: skip the extra instrumented eager step (no `roofline` in the output)")
     ap.add_argument("--no-fp16-leg", action="store_true",
-                    help="bf16 runs: skip the extra leg that runs the SAME weights / sample through the fp16 build "
+                    help="--full bf16 runs: skip the extra leg that runs the SAME weights / sample through the fp16 build "
                          "(its parity and step time are reported as `fp16_build` beside the bf16 headline)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy in "
                          "float32: latents (the updated fp32 latents) and noise_pred (the CFG-batch model output); the "
                          "inputs are seeded, so two builds run with the same arguments can be compared output for output")
-    return ap.parse_args()
+    return ap.parse_args(argv)
 
 
 def torch_dtype(name):
@@ -445,7 +455,6 @@ def main():
         launcher_selftest(args, D)
         return
     from ctrlv_amd import _lib
-    from ctrlv_amd import profiler
     rank, world, local = D.init("nccl" if int(os.environ.get("WORLD_SIZE", 1)) > 1 else None)
     world = D.world_size()                       # what the process group reports, not what the command line asked for
     if world != args.gpus:
@@ -479,7 +488,6 @@ def main():
     D.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    timer = None
     for k in range(args.steps):
         noise_pred = run_step(st, i)
         i += 1
@@ -489,11 +497,13 @@ def main():
     finite = bool(torch.isfinite(st.latents).all())
     log(f"timed region: {args.steps} steps in {elapsed:.3f} s")
     if args.dump_outputs and rank == 0:
-        # before the profiling step below, which steps the same latents once more
+        # before the profiling step of --full below, which steps the same latents once more
         shapes = dump_outputs(args.dump_outputs, {"latents": st.latents, "noise_pred": noise_pred})
         log(f"outputs of the last timed step written to {args.dump_outputs}: {shapes}")
 
-    if rank == 0 and not args.no_profile_step:
+    timer = None
+    if args.full and rank == 0 and not args.no_profile_step:
+        from ctrlv_amd import profiler
         # per-kernel HIP-event timing needs eager launches: one extra identical step outside the timed region, through the
         # SAME executor as the timed steps -- the C++ plan brackets its own launches (ctrlv_plan_profile), so every dispatch
         # decision of the plan (tile choice, fused feed-forward, column groups) is what the roofline describes
@@ -505,12 +515,70 @@ def main():
 
     if rank != 0:
         return
-    fams = timer.summary() if timer is not None else {}
+    ms_per_step = elapsed / args.steps * 1e3
+    value = args.steps * world / elapsed
+    default_shape = (args.height, args.width, args.frames) == (576, 1024, 25)
+    alg = ALG_TFLOP_PER_STEP[args.workload] if default_shape else None      # Appendix B table: BASELINE shape only
+    shape = f"{args.frames}f {args.height}x{args.width}"
+    line = {
+        "metric": (f"denoising steps/sec, SVD+ControlNet {shape}" if args.workload == "box2video"
+                   else f"denoising steps/sec, SVD UNet-only {shape}"),
+        "value": round(value, 4), "unit": "steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 2), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": args.dtype, "trunk": args.trunk, "data": "synthetic",
+        "config": {"workload": f"{args.workload}: {'ControlNet + ' if ctrl is not None else ''}UNet forward, CFG batch 2, "
+                               f"{args.frames} frames, latent {args.height // 8}x{args.width // 8}, 25-step Karras Euler "
+                               "schedule, random-init SVD-XT weights", "clips_per_gpu": 1, "parallelism": f"clip-shard x{world}",
+                   "hip_graph": bool(args.hip_graph)},
+        "reference_algorithm_tflop_per_step": alg,
+        "step_mfma_frac_reference_algorithm": (round(alg / (ms_per_step * 1e-3) / PEAK_MFMA_BF16_TFLOPS, 4)
+                                               if alg else None),
+        "finite": finite,
+        "lib_build_id": _lib.build_id(lib),
+    }
+    if not args.full:
+        print(json.dumps(line))
+        return
+    line.update(kernel_figures(args, lib, timer.summary() if timer is not None else {}, ms_per_step))
+    if world == 1 and not args.no_cpu_baseline:
+        del st
+        torch.cuda.empty_cache()
+        log("timing the CPU oracle baseline (same weights; by default the complete no-CFG step, ~2-4 minutes) and checking the HIP output against it ...")
+        line["cpu_baseline"], line["parity"], ref = cpu_baseline(args, unet, ctrl, device)
+        if args.dtype == "bf16" and ref is not None and not args.no_fp16_leg:
+            log("fp16 leg: the same weights / sample through libctrlv_hip_f16.so ...")
+            line["fp16_build"] = fp16_leg(args, unet, ctrl, ref, device)
+            log("fp16 leg with the split (fp16x2) residual trunk ...")
+            line["fp16_split_trunk_build"] = fp16_leg(args, unet, ctrl, ref, device, trunk="fp16x2")
+        # the two numbers side by side (VERDICT r05 item 1): `value` is the bf16 headline BASELINE.json names; `at_tolerance` is
+        # the fastest measured configuration of THIS run whose complete-step rel-L2 against the CPU oracle is below
+        # north_star's 1e-3 (normally the fp16 build with the split trunk; the run's own line if it already meets it)
+        cands = [("this run", line.get("parity"), line["value"], line["ms_per_step"])]
+        for key in ("fp16_build", "fp16_split_trunk_build"):
+            leg = line.get(key)
+            if leg:
+                cands.append((key, leg.get("parity"), leg["value"], leg["ms_per_step"]))
+        ok = [c for c in cands if c[1] and c[1].get("meets_north_star") and c[1].get("ok")]
+        if ok:
+            best = max(ok, key=lambda c: c[2])
+            line["at_tolerance"] = {"value": best[2], "unit": "steps/s", "ms_per_step": best[3], "rel_l2": best[1]["rel_l2"],
+                                    "tolerance": NORTH_STAR_TOL, "configuration": best[0],
+                                    "vs_headline_ms": round(best[3] / line["ms_per_step"], 4)}
+        else:
+            line["at_tolerance"] = None
+    print(json.dumps(line))
+
+
+# ---------------------------------------------------------------------------------------------------- kernel figures (--full)
+def kernel_figures(args, lib, fams, ms_per_step):
+    """--full: the per-kernel figures of the line, from the families `fams` the instrumented eager step timed ({} without
+    one) and the PMC / MFMA-busy summaries committed under profiles/."""
+    import glob
+    from ctrlv_amd import _lib
     # HBM traffic per launch from the separate rocprofv3 --pmc passes (FETCH_SIZE / WRITE_SIZE, gfx950 corrections
     # applied by tools/pmc_summary.py) committed under profiles/.  Only valid for the library it was collected from:
     # the summary carries that library's build id (hash of csrc/ + include/) and is ignored when it differs.
     pmc, pmc_note, pmc_launches = {}, None, {}
-    import glob
     default_shape = args.workload == "box2video" and (args.height, args.width, args.frames) == (576, 1024, 25)
     try:
         cands = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_hbm_traffic_summary.json")))
@@ -601,64 +669,18 @@ def main():
                               "avg_launch_ms": round(d["ms"] / d["calls"], 4)}
     dominant = max(rooflines, key=lambda f: rooflines[f]["ms_per_step"]) if rooflines else None
     roofline = dict(rooflines[dominant], kernel=dominant) if dominant else None
-    ms_per_step = elapsed / args.steps * 1e3
-    value = args.steps * world / elapsed
     executed = round(sum(d["flops"] for d in fams.values()) / 1e12, 2)
-    default_shape = (args.height, args.width, args.frames) == (576, 1024, 25)
-    alg = ALG_TFLOP_PER_STEP[args.workload] if default_shape else None      # Appendix B table: BASELINE shape only
-    shape = f"{args.frames}f {args.height}x{args.width}"
-    line = {
-        "metric": (f"denoising steps/sec, SVD+ControlNet {shape}" if args.workload == "box2video"
-                   else f"denoising steps/sec, SVD UNet-only {shape}"),
-        "value": round(value, 4), "unit": "steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 2), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": args.dtype, "trunk": args.trunk, "data": "synthetic",
-        "config": {"workload": f"{args.workload}: {'ControlNet + ' if ctrl is not None else ''}UNet forward, CFG batch 2, "
-                               f"{args.frames} frames, latent {args.height // 8}x{args.width // 8}, 25-step Karras Euler "
-                               "schedule, random-init SVD-XT weights", "clips_per_gpu": 1, "parallelism": f"clip-shard x{world}",
-                   "hip_graph": bool(args.hip_graph)},
+    return {
         # whole-step MFMA fraction on the FLOPs the kernels execute (the dead 1-key cross-attention work of the
         # reference, 8.4 TFLOP at the default shape, is not executed and not counted); the reference-algorithm figure
         # is reported next to it
         "step_mfma_frac": round(executed / (ms_per_step * 1e-3) / PEAK_MFMA_BF16_TFLOPS, 4),
         "executed_tflop_per_step": executed,
-        "reference_algorithm_tflop_per_step": alg,
-        "step_mfma_frac_reference_algorithm": (round(alg / (ms_per_step * 1e-3) / PEAK_MFMA_BF16_TFLOPS, 4)
-                                               if alg else None),
         "kernel_ms_per_step": round(sum(d["ms"] for d in fams.values()), 2),
-        "finite": finite,
-        "lib_build_id": _lib.build_id(lib),
         "roofline": roofline, "rooflines": rooflines,
         "traffic_source": pmc.get("_source"), "traffic_note": pmc_note,
         "mfma_busy_source": mfma.get("_source"), "mfma_busy_note": mfma_note, "in_kernel_clock": mfma.get("_in_kernel_clock"),
     }
-    if world == 1 and not args.no_cpu_baseline:
-        del st
-        torch.cuda.empty_cache()
-        log("timing the CPU oracle baseline (same weights; by default the complete no-CFG step, ~2-4 minutes) and checking the HIP output against it ...")
-        line["cpu_baseline"], line["parity"], ref = cpu_baseline(args, unet, ctrl, device)
-        if args.dtype == "bf16" and ref is not None and not args.no_fp16_leg:
-            log("fp16 leg: the same weights / sample through libctrlv_hip_f16.so ...")
-            line["fp16_build"] = fp16_leg(args, unet, ctrl, ref, device)
-            log("fp16 leg with the split (fp16x2) residual trunk ...")
-            line["fp16_split_trunk_build"] = fp16_leg(args, unet, ctrl, ref, device, trunk="fp16x2")
-        # the two numbers side by side (VERDICT r05 item 1): `value` is the bf16 headline BASELINE.json names; `at_tolerance` is
-        # the fastest measured configuration of THIS run whose complete-step rel-L2 against the CPU oracle is below
-        # north_star's 1e-3 (normally the fp16 build with the split trunk; the run's own line if it already meets it)
-        cands = [("this run", line.get("parity"), line["value"], line["ms_per_step"])]
-        for key in ("fp16_build", "fp16_split_trunk_build"):
-            leg = line.get(key)
-            if leg:
-                cands.append((key, leg.get("parity"), leg["value"], leg["ms_per_step"]))
-        ok = [c for c in cands if c[1] and c[1].get("meets_north_star") and c[1].get("ok")]
-        if ok:
-            best = max(ok, key=lambda c: c[2])
-            line["at_tolerance"] = {"value": best[2], "unit": "steps/s", "ms_per_step": best[3], "rel_l2": best[1]["rel_l2"],
-                                    "tolerance": NORTH_STAR_TOL, "configuration": best[0],
-                                    "vs_headline_ms": round(best[3] / line["ms_per_step"], 4)}
-        else:
-            line["at_tolerance"] = None
-    print(json.dumps(line))
 
 
 if __name__ == "__main__":

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Diagnostic: idle time on the device during HIP-graph replay of the denoising step.
-usage (GPU box): cd /tmp; rocprofv3 --kernel-trace --output-format csv -d <dir> -o p -- python3 bench.py --steps 3 --warmup 2 --no-cpu-baseline
+usage (on an MI355X): rocprofv3 --kernel-trace --output-format csv -d <dir> -o p -- python3 bench.py --full --steps 3 --warmup 2 --no-cpu-baseline
                  python tools/graph_gaps.py <dir>/p_kernel_trace.csv
 Takes the kernels of one step (between two consecutive cfg_euler kernels; default: the last TIMED step of bench.py), merges their [start, end)
 intervals and reports the busy union, the idle gaps and which kernels follow the large gaps."""
