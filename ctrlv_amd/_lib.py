@@ -69,6 +69,15 @@ class TemporalFusedDesc(ctypes.Structure):
     ]
 
 
+class LoraDesc(ctypes.Structure):
+    """Mirror of `ctrlv_lora_desc`."""
+    _fields_ = [
+        ("X", c_void_p), ("dY", c_void_p), ("A", c_void_p), ("B", c_void_p), ("dA", c_void_p), ("dB", c_void_p),
+        ("M", c_int), ("Cin", c_int), ("N", c_int), ("g", c_int), ("r", c_int), ("ldx", c_int), ("ldy", c_int),
+        ("scale", c_float),
+    ]
+
+
 class TensorDesc(ctypes.Structure):
     """Mirror of `ctrlv_tensor_desc`."""
     _fields_ = [("name", ctypes.c_char_p), ("data", c_void_p), ("dtype", c_int), ("on_device", c_int),
@@ -150,6 +159,9 @@ SIGNATURES = {
     "ctrlv_layernorm_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_void_p, c_int, c_int, c_int,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ctrlv_geglu_bwd": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p]),
+    "ctrlv_lora_grad_scratch_bytes": (c_size_t, [ctypes.POINTER(LoraDesc)]),
+    "ctrlv_lora_grad": (c_int, [ctypes.POINTER(LoraDesc), c_void_p, c_size_t, c_void_p]),
+    "ctrlv_lora_merge": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     "ctrlv_plan_create": (c_int, [ctypes.POINTER(ModelConfig), c_int, ctypes.POINTER(c_void_p)]),
     "ctrlv_plan_load_weights": (c_int, [c_void_p, ctypes.POINTER(TensorDesc), c_size_t]),
     "ctrlv_plan_set_time_context_order": (c_int, [c_void_p, c_int]),
@@ -186,7 +198,7 @@ def _status_recorder(lib, fn):
         return rc
     call.__name__ = getattr(fn, "__name__", "ctrlv_fn")
     return call
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 
 class CtrlvHipError(RuntimeError):

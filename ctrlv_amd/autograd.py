@@ -21,7 +21,7 @@ import weakref
 
 import torch
 
-from . import ops, packing
+from . import lora as lora_mod, ops, packing
 
 
 def _rows(M, C, like):
@@ -562,7 +562,7 @@ class FusedLinear(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dY):
-        A, weight = ctx.saved_tensors
+        A, weight = ctx.saved_tensors[:2]
         s_acc, s1, s2, vdiv, vmod, has_b, has_r1, has_r2, vshape, vmode, vS = ctx.cfg
         need = ctx.needs_input_grad
         dY = dY.contiguous()
@@ -582,6 +582,96 @@ class FusedLinear(torch.autograd.Function):
                 for j in range(vmod):
                     ops.colsum(dY[j::vmod], dV[j:j + 1])
         return dA, dW, db, dR1, dR2, dV, None
+
+
+def _lora_merged(weight, factors, groups, scale):
+    """fp32 W' = W + s . B_i . A_i for the `groups` row blocks of `weight` (ctrlv_lora_merge, one launch per group).  Cached
+    (as a frozen Parameter, so that its packed layouts are cached too) only while W and every factor are frozen, keyed on
+    (id, _version, data_ptr, dtype) of all of them; rebuilt on every use otherwise."""
+    def build():
+        out = torch.empty(weight.shape, dtype=torch.float32, device=weight.device)
+        n = weight.shape[0] // groups
+        for i in range(groups):
+            ops.lora_merge(weight[i * n:(i + 1) * n], factors[2 * i], factors[2 * i + 1], scale, out=out[i * n:(i + 1) * n])
+        return out
+    if any(f.requires_grad for f in factors):
+        return build()
+    kind = ("lora_merged", float(scale)) + tuple((id(p), p._version, p.data_ptr(), p.dtype) for p in factors)
+    return _frozen(weight, kind, build)
+
+
+class LoraLinear(torch.autograd.Function):
+    """FusedLinear (every epilogue operand) on an nn.Linear -- or the g = 3 fused q|k|v projection -- carrying LoRA factors:
+    forward and dgrad run the existing GEMMs on the merged weight W' = W + s . B_i . A_i (built once per forward in fp32
+    and packed to the element type, exactly how a trainable fp32 master is used); dA_i / dB_i come from ctrlv_lora_grad
+    (csrc/lora.hip) without forming dW; dW of the base only if the base itself requires grad.
+    factors: A_0, B_0, A_1, B_1, ... (one pair per group of weight's rows); lora = (groups, s)."""
+
+    @staticmethod
+    def forward(ctx, A, weight, bias, R1, R2, V, cfg, lora, *factors):
+        groups, scale = lora
+        wm = _lora_merged(weight, factors, groups, scale)
+        out = FusedLinear.forward(ctx, A, wm, bias, R1, R2, V, cfg)
+        ctx.save_for_backward(A, wm, *factors)
+        ctx.lora, ctx.wdtype = lora, weight.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, dY):
+        saved = ctx.saved_tensors
+        A, factors = saved[0], saved[2:]
+        groups, scale = ctx.lora
+        dY = dY.contiguous()
+        dA, dW, db, dR1, dR2, dV, _ = FusedLinear.backward(ctx, dY)
+        if dW is not None:
+            dW = dW.to(ctx.wdtype)
+        need = ctx.needs_input_grad[8:]
+        fgrads = [None] * len(factors)
+        if any(need):
+            Acat = torch.cat([f.detach() for f in factors[0::2]], 0)
+            Bcat = torch.cat([f.detach() for f in factors[1::2]], 0)
+            dAc, dBc = ops.lora_grad(A, dY, Acat, Bcat, groups, scale * ctx.cfg[0])
+            r, n = factors[0].shape[0], dY.shape[1] // groups
+            for i in range(groups):
+                fgrads[2 * i] = dAc[i * r:(i + 1) * r].to(factors[2 * i].dtype) if need[2 * i] else None
+                fgrads[2 * i + 1] = dBc[i * n:(i + 1) * n].to(factors[2 * i + 1].dtype) if need[2 * i + 1] else None
+        return (dA, dW, db, dR1, dR2, dV, None, None) + tuple(fgrads)
+
+
+def _lora_operands(linears):
+    """(groups, s) and the factor list of LoraLinear for these nn.Linears (side by side along N), or None when none is
+    adapted.  A member without an adapter takes frozen zero factors of the same rank (W' = W exactly)."""
+    fs = [lora_mod.factors(lin) for lin in linears]
+    live = [f for f in fs if f is not None]
+    if not live:
+        return None
+    r, s = live[0][0].shape[0], live[0][2]
+    out = []
+    for lin, f in zip(linears, fs):
+        if f is None:
+            z = lin.weight.new_zeros((), dtype=torch.float32)
+            f = (z.expand(r, lin.in_features), z.expand(lin.out_features, r), s)
+        if f[0].shape[0] != r or f[2] != s:
+            raise ValueError("the adapted projections of one fused GEMM must share the rank and lora_alpha")
+        out += [f[0], f[1]]
+    return (len(linears), s), out
+
+
+def linear_apply(A, linears, weight, bias, R1, R2, V, cfg):
+    """FusedLinear.apply, or LoraLinear.apply when one of `linears` (the modules whose weights `weight` stacks) is adapted."""
+    lo = _lora_operands(linears)
+    if lo is None:
+        return FusedLinear.apply(A, weight, bias, R1, R2, V, cfg)
+    return LoraLinear.apply(A, weight, bias, R1, R2, V, cfg, lo[0], *lo[1])
+
+
+def lora_weight_f32(linear):
+    """fp32 weight of a small per-clip torch op with torch autograd through the LoRA factors (attn2's to_v / to_out)."""
+    w = f32(linear.weight)
+    f = lora_mod.factors(linear)
+    if f is None:
+        return w
+    return w + f[2] * (f[1].float() @ f[0].float())
 
 
 class BlendLinear(torch.autograd.Function):
@@ -678,7 +768,7 @@ def transformer_train_forward(tr, x, ehs, B, F, H, W, time_context_order="sb"):
     quirk = time_context_order == "sb" and B > 1       # diffusers 0.27.2: time_context rows (s, b), tokens (b, s) -- H1
 
     def xvec(attn):
-        return Fn.linear(Fn.linear(ehs.float(), f32(attn.to_v.weight)), f32(attn.to_out[0].weight),
+        return Fn.linear(Fn.linear(ehs.float(), lora_weight_f32(attn.to_v)), lora_weight_f32(attn.to_out[0]),
                          f32(attn.to_out[0].bias)).contiguous()
 
     tpe = tr.time_pos_embed
@@ -701,6 +791,9 @@ def transformer_train_forward(tr, x, ehs, B, F, H, W, time_context_order="sb"):
         kind = ("qkv_cat",) + tuple((id(p), p._version, p.data_ptr(), p.dtype) for p in (k, v))
         return _frozen(q, kind, lambda: torch.cat([q, k, v], 0))
 
+    def qkvs(attn):
+        return [attn.to_q, attn.to_k, attn.to_v]
+
     # Every trunk tensor (x, h0, h1, h2, g0, g1) feeds the norm that opens a branch AND the skip connection around it: the norm
     # hands the skip its alias (skip=True), so both gradients meet in the norm's backward kernel instead of a separate sum.
     if _SKIP_FUSE:
@@ -710,10 +803,10 @@ def transformer_train_forward(tr, x, ehs, B, F, H, W, time_context_order="sb"):
     h0 = FusedLinear.apply(t, tr.proj_in.weight, tr.proj_in.bias, None, None, None, {})
     # ---- spatial BasicTransformerBlock
     n, h0 = lns(h0, sb.norm1)
-    qkv = FusedLinear.apply(n, qkv_w(sb.attn1), None, None, None, None, {})
+    qkv = linear_apply(n, qkvs(sb.attn1), qkv_w(sb.attn1), None, None, None, None, {})
     a = SpatialAttention.apply(qkv, N, S, C)
-    h1 = FusedLinear.apply(a, sb.attn1.to_out[0].weight, sb.attn1.to_out[0].bias, h0, None, xvec(sb.attn2),
-                           dict(vdiv=F * S))
+    h1 = linear_apply(a, [sb.attn1.to_out[0]], sb.attn1.to_out[0].weight, sb.attn1.to_out[0].bias, h0, None, xvec(sb.attn2),
+                      dict(vdiv=F * S))
     with _ff_region():
         n, h1 = lns(h1, sb.norm3)
         u = GegluProj.apply(n, sb.ff.net[0].proj.weight, sb.ff.net[0].proj.bias)
@@ -726,10 +819,10 @@ def transformer_train_forward(tr, x, ehs, B, F, H, W, time_context_order="sb"):
         g0 = FusedLinear.apply(u, tb.ff_in.net[2].weight, tb.ff_in.net[2].bias, h2, None, emb, dict(vdiv=S, vmod=F))
     del u
     n, g0 = lns(g0, tb.norm1)
-    qkv = FusedLinear.apply(n, qkv_w(tb.attn1), None, None, None, None, {})
+    qkv = linear_apply(n, qkvs(tb.attn1), qkv_w(tb.attn1), None, None, None, None, {})
     a = TemporalAttention.apply(qkv, B, F, S, C)
-    g1 = FusedLinear.apply(a, tb.attn1.to_out[0].weight, tb.attn1.to_out[0].bias, g0, None, xvec(tb.attn2),
-                           dict(vmode=2, vdiv=F * S, vS=S, vmod=B) if quirk else dict(vdiv=F * S))
+    g1 = linear_apply(a, [tb.attn1.to_out[0]], tb.attn1.to_out[0].weight, tb.attn1.to_out[0].bias, g0, None, xvec(tb.attn2),
+                      dict(vmode=2, vdiv=F * S, vS=S, vmod=B) if quirk else dict(vdiv=F * S))
     with _ff_region():
         n, g1 = lns(g1, tb.norm3)
         u = GegluProj.apply(n, tb.ff.net[0].proj.weight, tb.ff.net[0].proj.bias)

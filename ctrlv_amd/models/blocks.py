@@ -21,6 +21,7 @@ import torch
 from torch import nn
 
 from .. import ops, packing
+from ..lora import merged_weight
 
 
 class FwdCtx:
@@ -331,13 +332,13 @@ class TransformerSpatioTemporalModel(nn.Module):
             pin=(packing.pack_linear(self.proj_in.weight), _f32(self.proj_in.bias)),
             pout=(packing.pack_linear(self.proj_out.weight), _f32(self.proj_out.bias)),
             s_ln1=ln(sb.norm1), s_ln3=ln(sb.norm3),
-            s_qkv=packing.pack_qkv(sb.attn1.to_q.weight, sb.attn1.to_k.weight, sb.attn1.to_v.weight),
-            s_o=(packing.pack_linear(sb.attn1.to_out[0].weight), _f32(sb.attn1.to_out[0].bias)),
+            s_qkv=packing.pack_qkv(merged_weight(sb.attn1.to_q), merged_weight(sb.attn1.to_k), merged_weight(sb.attn1.to_v)),
+            s_o=(packing.pack_linear(merged_weight(sb.attn1.to_out[0])), _f32(sb.attn1.to_out[0].bias)),
             s_ff=ff(sb.ff),
             t_lnin=ln(tb.norm_in), t_ln1=ln(tb.norm1), t_ln3=ln(tb.norm3),
             t_ffin=ff(tb.ff_in),
-            t_qkv=packing.pack_qkv(tb.attn1.to_q.weight, tb.attn1.to_k.weight, tb.attn1.to_v.weight),
-            t_o=(packing.pack_linear(tb.attn1.to_out[0].weight), _f32(tb.attn1.to_out[0].bias)),
+            t_qkv=packing.pack_qkv(merged_weight(tb.attn1.to_q), merged_weight(tb.attn1.to_k), merged_weight(tb.attn1.to_v)),
+            t_o=(packing.pack_linear(merged_weight(tb.attn1.to_out[0])), _f32(tb.attn1.to_out[0].bias)),
             t_ff=ff(tb.ff),
             t_wf=None,
             tpe=(packing.pack_linear(self.time_pos_embed.linear_1.weight), _f32(self.time_pos_embed.linear_1.bias),

@@ -90,6 +90,9 @@ class ControlNetModel(SpatioTemporalEncoderBase):
 
     @classmethod
     def from_unet(cls, unet, load_weights_from_unet: bool = True):                              # :197-224
+        if getattr(unet, "_lora", None) is not None:
+            raise ValueError("ControlNetModel.from_unet: the UNet carries a LoRA adapter; call unet.fuse_lora() first (the "
+                             "base weights alone are not the fine-tuned model)")
         c = unet.config
         ctrlnet = cls(
             in_channels=c.in_channels, down_block_types=c.down_block_types, block_out_channels=c.block_out_channels,

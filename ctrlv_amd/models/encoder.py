@@ -10,6 +10,7 @@ from torch import nn
 
 from .. import _lib, ops, packing
 from .. import profiler as _prof
+from ..lora import has_adapter, merged_state_dict, merged_weight
 from ..plan import Plan
 from ..workspace import Workspace
 from .blocks import (CrossAttnDownBlockSpatioTemporal, DownBlockSpatioTemporal, Downsample2D, FwdCtx,
@@ -137,7 +138,7 @@ class SpatioTemporalEncoderBase(HipModelMixin):
             object.__setattr__(self, "_plan", None)
         if self._plan is None:
             plan = Plan(self._plan_kind, self.config, sample.device, self.time_context_order, dtype=el)
-            plan.load_state_dict(self.state_dict())
+            plan.load_state_dict(merged_state_dict(self) if has_adapter(self) else self.state_dict())
             object.__setattr__(self, "_plan", plan)
             self._plan_order = self.time_context_order
         if self._plan_order != self.time_context_order:
@@ -218,8 +219,8 @@ class SpatioTemporalEncoderBase(HipModelMixin):
         for tr in transformers:
             offs = []
             for attn in tr.cross_attentions():
-                vs_.append(attn.to_v.weight.detach())
-                xo.append((off, attn.to_v.weight.shape[0], packing.pack_linear(attn.to_out[0].weight),
+                vs_.append(merged_weight(attn.to_v).detach())
+                xo.append((off, attn.to_v.weight.shape[0], packing.pack_linear(merged_weight(attn.to_out[0])),
                            _f32(attn.to_out[0].bias)))
                 offs.append(off); off += attn.to_v.weight.shape[0]
             tr.xattn_off = tuple(offs)

@@ -11,7 +11,7 @@ from typing import Optional, Tuple, Union
 import torch
 from torch import nn
 
-from .. import ops, packing
+from .. import lora, ops, packing
 from .blocks import CrossAttnUpBlockSpatioTemporal, UpBlockSpatioTemporal, _f32, _gn_scratch, _lo
 from .encoder import SpatioTemporalEncoderBase, _tup
 
@@ -106,6 +106,16 @@ class UNetSpatioTemporalConditionModel(SpatioTemporalEncoderBase):
             else:
                 param.requires_grad = False
         return parameters_list
+
+    # ---- LoRA (the reference's --enable_lora, tools/train_video_diffusion.py:126-136; ctrlv_amd/lora.py) ---------------
+    def add_adapter(self, adapter_config, adapter_name="default"):
+        """peft-style `unet.add_adapter(LoraConfig(...))`: config is a peft LoraConfig or any object / dict with r, lora_alpha,
+        target_modules, init_lora_weights and lora_dropout.  Freezes everything but the factors."""
+        return lora.add_adapter(self, adapter_config, adapter_name)
+
+    def fuse_lora(self, lora_scale=1.0):
+        """W <- W + lora_scale . s . B . A for every adapted projection (on the device), then drops the adapter."""
+        return lora.fuse(self, lora_scale)
 
     def get_parameters_with_grad(self):
         return [param for param in self.parameters() if param.requires_grad]

@@ -100,6 +100,51 @@ def pack_weight(weight, form=0, geglu=False, dtype=torch.bfloat16):
     return dst
 
 
+def lora_grad(X, dY, A, B, groups=1, scale=1.0):
+    """Factor gradients of `groups` LoRA adapters side by side along dY's columns (ctrlv_lora_grad, deterministic):
+    X [M, Cin] and dY [M, N] element rows; A fp32 [groups * r, Cin] (the groups' A factors stacked), B fp32 [N, r] (the
+    groups' B factors stacked).  Returns (dA [groups * r, Cin], dB [N, r]) fp32 = scale * (G^T X, dY^T H) per group."""
+    _need_gpu(X, "X")
+    if X.stride(1) != 1 or dY.stride(1) != 1:
+        raise ValueError("lora_grad: X and dY must be row-major (unit column stride)")
+    A = A.detach().float().contiguous()
+    B = B.detach().float().contiguous()
+    M, cin = X.shape
+    N, r = B.shape
+    dA = torch.empty(A.shape, dtype=torch.float32, device=X.device)
+    dB = torch.empty(N, r, dtype=torch.float32, device=X.device)
+    d = _lib.LoraDesc()
+    d.X, d.dY, d.A, d.B, d.dA, d.dB = _p(X), _p(dY), _p(A), _p(B), _p(dA), _p(dB)
+    d.M, d.Cin, d.N, d.g, d.r = M, cin, N, groups, r
+    d.ldx, d.ldy, d.scale = X.stride(0), dY.stride(0), float(scale)
+    if A.shape[0] != groups * r or A.shape[1] != cin or dY.shape[0] != M or dY.shape[1] != N:
+        raise ValueError(f"lora_grad: shapes X {tuple(X.shape)}, dY {tuple(dY.shape)}, A {tuple(A.shape)}, B {tuple(B.shape)}"
+                         f" do not fit {groups} group(s)")
+    lib = _L(X, dY)
+    nbytes = lib.ctrlv_lora_grad_scratch_bytes(ctypes.byref(d))
+    if nbytes == 0:
+        check(lib.ctrlv_lora_grad(ctypes.byref(d), None, 0, _stream()), "ctrlv_lora_grad")      # (raises: the reason)
+    scratch = _scratch(X.device, nbytes, "lora")
+    check(lib.ctrlv_lora_grad(ctypes.byref(d), _p(scratch), nbytes, _stream()), "ctrlv_lora_grad")
+    return dA, dB
+
+
+def lora_merge(W, A, B, scale, out=None):
+    """W + scale * B @ A in fp32, torch layout [N, Cin] (ctrlv_lora_merge).  W: any float dtype; A [r, Cin], B [N, r]."""
+    _need_gpu(W, "W")
+    W = W.detach().contiguous()
+    A = A.detach().float().contiguous()
+    B = B.detach().float().contiguous()
+    N, cin = W.shape
+    if A.shape[1] != cin or B.shape[0] != N or A.shape[0] != B.shape[1]:
+        raise ValueError(f"lora_merge: W {tuple(W.shape)}, A {tuple(A.shape)}, B {tuple(B.shape)}")
+    if out is None:
+        out = torch.empty(N, cin, dtype=torch.float32, device=W.device)
+    check(_L(W).ctrlv_lora_merge(_p(W), _DT[W.dtype], _p(A), _p(B), N, cin, A.shape[0], float(scale), _p(out), _stream()),
+          "ctrlv_lora_merge")
+    return out
+
+
 def colsum(x, out, vmode=0, vdiv=1, vmod=1, scale=1.0):
     """out[idx(m), :N] += scale * sum_m x[m, :]  (fp32, atomics): bias gradients (vmode 0) / per-clip row-vector gradients."""
     _need_gpu(x, "x")

@@ -41,7 +41,7 @@ enum {
   CTRLV_E_WORKSPACE = -5,  /* caller-supplied workspace smaller than ctrlv_plan_workspace_bytes() */
 };
 
-/* Library ABI version (bumped on any signature change). */
+/* Library ABI version (bumped on any signature change; 21: the LoRA entry points). */
 int ctrlv_abi_version(void);
 /* dtype code (1 fp16 / 2 bf16) of the element type this library was built for (see above). */
 int ctrlv_elem_dtype(void);
@@ -378,6 +378,43 @@ int ctrlv_layernorm_bwd_add(const void* x, const void* dy, const void* add, int 
 /* GEGLU backward.  raw: the projection output [M, 2I] bf16 in the packed (16 value, 16 gate) column-block order, i.e.
  * ctrlv_gemm on the GEGLU-packed weight with geglu = 0; du: [M, I] bf16; draw: [M, 2I] bf16, same layout as raw. */
 int ctrlv_geglu_bwd(const void* raw, const void* du, size_t M, int I, void* draw, ctrlv_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * LoRA adapters (ABI 21; csrc/lora.hip): the reference's --enable_lora of the stage-1 UNet step
+ * (tools/train_video_diffusion.py:126-136, 205-216: rank-r factors on to_q / to_k / to_v / to_out.0, the UNet frozen).
+ * One adapted linear, s = lora_alpha / r:  Y = X . W'^T,  W' = W + s . B . A,  A fp32 [r][Cin], B fp32 [N][r].
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct ctrlv_lora_desc {
+  const void* X;      /* [M][ldx] elements: the layer's input rows (16-byte aligned, ldx % 8 == 0) */
+  const void* dY;     /* [M][ldy] elements: the gradient of the layer's output (16-byte aligned, ldy % 8 == 0) */
+  const float* A;     /* fp32 [g][r][Cin]: the g groups' A factors, contiguous */
+  const float* B;     /* fp32 [g][N/g][r] == [N][r]: the g groups' B factors, contiguous */
+  float* dA;          /* fp32 [g][r][Cin], WRITTEN (not accumulated) */
+  float* dB;          /* fp32 [N][r], WRITTEN */
+  int M, Cin, N;      /* N = all g groups' output columns; Cin and N / g multiples of 64, any M >= 1 */
+  int g, r;           /* g groups side by side along N (the fused q|k|v projection: 3), rank r % 4 == 0, 4 <= r <= 64,
+                         g * r <= 192 */
+  int ldx, ldy;
+  float scale;        /* s = lora_alpha / r (times the forward's s_acc) */
+} ctrlv_lora_desc;
+/* The factor gradients without the [N][Cin] weight gradient, for the g groups of one launch (group i owns dY's columns
+ * [i N/g, (i+1) N/g) and the factors A_i, B_i):  H_i = X . A_i^T, G_i = dY_i . B_i  ([M][r]),  dA_i = s . G_i^T . X,
+ * dB_i = s . dY_i^T . H_i.
+ * ROUNDING POINTS (a reference reproduces them): NONE beyond the element rows X and dY themselves.  A, B and the fp32
+ * intermediates H and G each enter the matrix pipe as an element pair hi = rne(v), lo = rne(v - hi) (~16 significant bits in
+ * bf16; fp16 pairs lose bits for |v| below fp16's normal range) and are multiplied twice: the fp32 reference is
+ * dA = s (dY.float() B)^T X.float(), dB = s dY.float()^T (X.float() A^T).  dA and dB are accumulated in fp32, scaled by s last.
+ * DETERMINISTIC: row-slab partials (plain stores) added in slab order by a second kernel; the slab partition is a function of
+ * (M, Cin, N, g, r) only -- not of the device, its CU count or the environment: the same bits on every MI355X.  No atomics.
+ * scratch: ctrlv_lora_grad_scratch_bytes(d) bytes (16-byte aligned; its contents are not kept).  Returns 0 bytes for a
+ * descriptor the launch would reject.  Register budget of the csrc/lora.hip kernels: <= 256 VGPRs, no scratch (spill). */
+size_t ctrlv_lora_grad_scratch_bytes(const ctrlv_lora_desc* d);
+int ctrlv_lora_grad(const ctrlv_lora_desc* d, void* scratch, size_t scratch_bytes, ctrlv_stream_t stream);
+/* out = W + scale . B . A in fp32, in the TORCH layout [N][Cin] (ctrlv_pack_weight packs it afterwards); W fp32 / fp16 /
+ * bf16 (w_dtype 0 / 1 / 2) [N][Cin]; A fp32 [r][Cin], B fp32 [N][r]; each element is fma(scale, sum_j B[n][j] A[j][c], W)
+ * with the r products added in index order.  out may be W itself when W is fp32. */
+int ctrlv_lora_merge(const void* W, int w_dtype, const float* A, const float* B, int N, int Cin, int r, float scale,
+                     float* out, ctrlv_stream_t stream);
 
 /* ==================================================================================================================
  * Plan-level entry points: one call = one model forward.  (SURVEY.md 8b "what a C-ABI replacement must export".)

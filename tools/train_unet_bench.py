@@ -8,7 +8,7 @@ recomputes are not counted).  Synthetic data, random-init weights (there are no 
 Default size: the stage-1 training size 320 x 512 (src/ctrlv/datasets/kitti_abstract.py:86-90); --height 576 --width 1024
 for the full frame.
 usage: python tools/train_unet_bench.py [--steps 3] [--warmup 1] [--frames 25] [--height 320] [--width 512]
-       [--mode all|temporal] [--gradient-checkpointing 0|1] [--gpus N]
+       [--mode all|temporal|lora] [--rank 4] [--gradient-checkpointing 0|1] [--gpus N]
 Data parallel: --gpus N as in tools/train_bench.py (one rank process per GPU, its own clip per rank, the fp32 gradients
 all-reduced in 25 MB buckets while the backward runs); the time is the MAX over ranks."""
 import argparse
@@ -23,9 +23,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def analytic_tflop(frames, h, w, mode="all", config=None):
+def analytic_tflop(frames, h, w, mode="all", config=None, rank=4):
     """(forward, backward) TFLOP of one stage-1 step at B = 1 and an h x w latent, from the layer list of the oracle UNet
-    (SVD configuration unless `config`), counted on the meta device: no memory, no arithmetic."""
+    (SVD configuration unless `config`), counted on the meta device: no memory, no arithmetic.  mode "lora": the UNet frozen,
+    rank-`rank` factors on every to_q / to_k / to_v / to_out.0 (the branch base(x) + s B(A(x)) around the oracle's
+    nn.Linear): dgrad everywhere plus the LoRA products, no weight gradient of the base."""
     from torch.utils.flop_counter import FlopCounterMode
     if os.path.join(ROOT, "oracle") not in sys.path:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -35,7 +37,14 @@ def analytic_tflop(frames, h, w, mode="all", config=None):
         ou = R.UNetSpatioTemporalConditionModel(**cfg)
     ou = ou.to("meta")                 # (a few parameters are built with the legacy constructor, on the CPU)
     for n, p in ou.named_parameters():
-        p.requires_grad_(mode == "all" or "temporal_transformer_block" in n)
+        p.requires_grad_(mode == "all" or (mode == "temporal" and "temporal_transformer_block" in n))
+    if mode == "lora":
+        import torch.nn.functional as Fn
+        for n, m in ou.named_modules():
+            if isinstance(m, torch.nn.Linear) and (n.rsplit(".", 1)[-1] in ("to_q", "to_k", "to_v") or n.endswith("to_out.0")):
+                a = torch.empty(rank, m.in_features, device="meta", requires_grad=True)
+                b = torch.empty(m.out_features, rank, device="meta", requires_grad=True)
+                m.register_forward_hook(lambda _m, inp, out, a=a, b=b: out + Fn.linear(Fn.linear(inp[0], a), b))
     dc = cfg["cross_attention_dim"]
     dc = dc if isinstance(dc, int) else dc[0]
     x = torch.empty(1, frames, cfg["in_channels"], h, w, device="meta")
@@ -54,8 +63,10 @@ def main():
     ap.add_argument("--frames", type=int, default=25)
     ap.add_argument("--height", type=int, default=320)
     ap.add_argument("--width", type=int, default=512)
-    ap.add_argument("--mode", choices=("all", "temporal"), default="all",
-                    help="all: unet.enable_grad(all=True) (the demo scripts); temporal: temporal_transformer_block only")
+    ap.add_argument("--mode", choices=("all", "temporal", "lora"), default="all",
+                    help="all: unet.enable_grad(all=True) (the demo scripts); temporal: temporal_transformer_block only; "
+                         "lora: unet.add_adapter(rank --rank on to_q / to_k / to_v / to_out.0), the UNet frozen")
+    ap.add_argument("--rank", type=int, default=4, help="LoRA rank of --mode lora (lora_alpha = rank, as the reference)")
     ap.add_argument("--lr", type=float, default=1e-5)
     ap.add_argument("--fused-adamw", type=int, default=1, help="torch.optim.AdamW(fused=...)")
     ap.add_argument("--gradient-checkpointing", type=int, default=0,
@@ -90,6 +101,9 @@ def main():
     random_init_(unet, seed=0)
     if args.mode == "all":
         unet.enable_grad(all=True)
+    elif args.mode == "lora":                                    # tools/train_video_diffusion.py:126-136
+        unet.add_adapter(dict(r=args.rank, lora_alpha=args.rank, init_lora_weights="gaussian", lora_dropout=0.0,
+                              target_modules=["to_k", "to_q", "to_v", "to_out.0"]))
     else:
         unet.enable_grad(temporal_transformer_block=True)
     if args.gradient_checkpointing:
@@ -137,7 +151,7 @@ def main():
         return
     n = len(times)
     avg = [sum(t[k] for t in times) / n for k in range(4)]
-    tf_f, tf_b = analytic_tflop(F, h, w, args.mode)
+    tf_f, tf_b = analytic_tflop(F, h, w, args.mode, rank=args.rank)
     print(json.dumps({"metric": "stage-1 UNet training step (B=1 per GPU, no CFG)", "n_gpus": world, "mode": args.mode,
                       "samples_per_s": round(world * 1e3 / avg[0], 3), "scaling": "weak", "ms_per_step": round(avg[0], 1),
                       "forward_ms": round(avg[1], 1), "backward_ms": round(avg[2], 1), "optimizer_ms": round(avg[3], 1),
@@ -148,6 +162,7 @@ def main():
                       "trainable_params_m": round(sum(p.numel() for p in params) / 1e6, 1),
                       "losses": [round(v, 5) for v in losses],
                       "gradient_checkpointing": bool(args.gradient_checkpointing),
+                      **({"rank": args.rank} if args.mode == "lora" else {}),
                       "dtype": "bf16 compute, fp32 master parameters + AdamW", "data": "synthetic, random-init weights"}))
 
 
