@@ -10,68 +10,46 @@ per-clip row vector V, s_acc}, GroupNorm(+SiLU) in its 4-D and 5-D forms, and th
   wgrad  = ctrlv_gemm_wgrad (transposed-LDS-read MFMA kernel), bias / row-vector gradients = ctrlv_colsum
   norms  = ctrlv_groupnorm_bwd on the statistics the forward saved
 Activations and activation gradients are bf16 rows; parameter gradients are fp32 in the PyTorch layouts.
-Second slice: LayerNorm, GEGLU, the attention cores (flash-style backward, csrc/attention_bwd.hip), nn.Linear with the
-whole fused epilogue (FusedLinear / BlendLinear) => a complete `TransformerSpatioTemporalModel`; stride-2 and
-upsample-fused convs.  The model-level training step built from these lives in ctrlv_amd/training.py.
+Second slice: LayerNorm, GEGLU, the attention cores (flash-style backward, csrc/attention_bwd.hip), the second residual
+and the indexed row vector of the epilogue => a complete `TransformerSpatioTemporalModel`; stride-2 and upsample-fused
+convs; LoRA factors.  The model-level training step built from these lives in ctrlv_amd/training.py.
+
+Every GEMM of the step is one of two Functions over one forward launcher (`_gemm_forward`) and one backward
+(`gemm_grads`, `_epilogue_grads`): `Gemm` (every mode, every epilogue operand, optional trailing LoRA factors; geometry
+and scalars in a `GemmSpec`) and `BlendGemm` (the two AlphaBlender foldings, which add the mix-factor gradient).  Forms
+derived from frozen parameters are cached in ctrlv_amd/frozen.py.
 """
 import contextlib
 import math
-import os
-import weakref
+from typing import NamedTuple
 
 import torch
 
-from . import lora as lora_mod, ops, packing
+from . import frozen as frozen_cache, lora as lora_mod, ops, packing
+from .frozen import frozen
 
 
 def _rows(M, C, like):
     return torch.empty(M, C, dtype=torch.bfloat16, device=like.device)
 
 
-# Packed (bf16, kernel-layout) forms of FROZEN parameters are built once: the UNet of the training step never changes,
-# and re-packing its decoder (forward form + role-swapped dgrad form) every step is ~10 ms of small torch kernels.
-# Trainable parameters are packed from the fp32 masters on every use.  (Writes through `.data` do not bump _version:
-# call clear_pack_cache() after editing a frozen model that way.)
-_PACK_CACHE = {}
-_WGRAD_DIRECT = os.environ.get("CTRLV_WGRAD_DIRECT", "0") == "1"     # conv dW straight in [N, cin, taps] (A/B handle)
-_SKIP_FUSE = os.environ.get("CTRLV_SKIP_FUSE", "1") != "0"           # 0: autograd sums the skip gradients itself (A/B handle)
-
-
 def clear_pack_cache():
-    _PACK_CACHE.clear()
+    """Drops every cached form of the frozen parameters (frozen.py).  Writes through `.data` do not bump _version: call this
+    after editing a frozen model that way."""
+    frozen_cache.clear()
 
 
 def _packed(weight, kind, fn):
-    if weight.requires_grad or not isinstance(weight, torch.nn.Parameter):     # (temporaries may recycle an address)
-        return fn(weight)
-    key = (id(weight), kind)
-    hit = _PACK_CACHE.get(key)
-    # the entry is valid only for THIS parameter object (ids are recycled after garbage collection) at THIS version and
-    # storage (in-place updates bump _version; .to() / load_state_dict may swap the storage)
-    if hit is not None and hit[0]() is weight and hit[1] == (weight._version, weight.data_ptr(), weight.dtype):
-        return hit[2]
-    if len(_PACK_CACHE) > 4096:
-        _PACK_CACHE.clear()
-    out = fn(weight)
-    _PACK_CACHE[key] = (weakref.ref(weight), (weight._version, weight.data_ptr(), weight.dtype), out)
-    return out
+    return frozen((weight,), kind, lambda: fn(weight))
 
 
 def f32(p):
     """fp32 form of a parameter for the per-clip torch ops and the norm kernels: trainable / fp32 parameters as they are
-    (autograd sees them), FROZEN 16-bit ones converted once (the UNet of the training step: ~500 small conversion kernels
-    per step otherwise)."""
-    if p.dtype == torch.float32 or p.requires_grad or not isinstance(p, torch.nn.Parameter):
+    (autograd sees them; an fp32 parameter IS its fp32 form, and a value must never be its own source), FROZEN 16-bit ones
+    converted once (the UNet of the training step: ~500 small conversion kernels per step otherwise)."""
+    if p.dtype == torch.float32:
         return p.float()
-    return _packed(p, "f32", lambda w: w.detach().float().contiguous())
-
-
-def _frozen(key_param, kind, fn):
-    """A tensor derived from FROZEN parameters (fused q|k|v weight, GEGLU row interleave): built once and kept as a frozen
-    Parameter, so that the packed kernel layouts derived from IT are cached as well.  Trainable: rebuilt on every use."""
-    if key_param.requires_grad or not isinstance(key_param, torch.nn.Parameter):
-        return fn()
-    return _packed(key_param, kind, lambda _w: torch.nn.Parameter(fn().detach(), requires_grad=False))
+    return frozen((p,), "f32", lambda: p.float().contiguous())
 
 
 def _geglu_bias32(bias):
@@ -93,71 +71,147 @@ def _pack_fwd(weight, mode, geglu=False):
     return (packing.pack_linear if mode == 0 else (packing.pack_conv3x3 if mode == 1 else packing.pack_conv_temporal))(weight)
 
 
-class GatherGemm(torch.autograd.Function):
-    """out = s_acc * (gather-GEMM(A, weight) + bias) + R1 + V[(m // vdiv)]   (what the res block's convs fuse).
+_TAPS = {0: 1, 1: 9, 2: 3}
 
-    weight / bias: parameters in the PyTorch layout ([N, C], [N, C, 3, 3] or [N, C, 3, 1, 1]), any float dtype.
-    geom: dict(mode, conv=(H, W, Ho, Wo, 1, 0) | None, temporal=(F, S) | None, vdiv)."""
+
+class GemmSpec(NamedTuple):
+    """Geometry and epilogue scalars of one gather-GEMM: out = s_acc * (gemm + bias) + s1 * R1 + s2 * R2 + V[idx(m)]."""
+    mode: int = 0                # 0 nn.Linear / 1x1 conv, 1 3x3 Conv2d, 2 (3,1,1) Conv3d
+    conv: tuple = None           # mode 1: (H, W, Ho, Wo, stride, up)
+    temporal: tuple = None       # mode 2: (F, S)
+    s_acc: float = 1.0
+    s1: float = 1.0
+    s2: float = 1.0
+    vmode: int = 1               # 1: idx = (m // vdiv) % vmod;  2: ((m // vdiv) * vS + m % vS) % vmod
+    vdiv: int = 1
+    vmod: int = 1 << 30
+    vS: int = 1
+    lora: tuple = None           # (groups, s) when LoRA factors trail the inputs of Gemm
+
+    @property
+    def geom(self):
+        return dict(mode=self.mode, conv=self.conv, temporal=self.temporal)
+
+
+def _gemm_forward(A, weight, bias, R1, R2, V, spec):
+    """The forward launch of Gemm and BlendGemm.  weight / bias: parameters in the PyTorch layout ([N, C], [N, C, 3, 3] or
+    [N, C, 3, 1, 1]), any float dtype; the output is as wide as the weight, the launch's N is padded to 32."""
+    mode = spec.mode
+    N, cin = weight.shape[0], weight.shape[1]
+    m_out = A.shape[0]
+    if mode == 1:        # stride-2 / upsample-fused convs change the row count
+        H, W, Ho, Wo = spec.conv[:4]
+        m_out = A.shape[0] // (H * W) * Ho * Wo
+    out = _rows(m_out, N, A)
+    ops.gemm(A, _packed(weight, ("fwd", mode), lambda w: _pack_fwd(w, mode)), out, N=(N + 31) // 32 * 32, cin=cin,
+             taps=_TAPS[mode], mode=mode, conv=spec.conv, temporal=spec.temporal,
+             bias=None if bias is None else _bias32(bias), s_acc=float(spec.s_acc), R1=R1, s1=float(spec.s1), R2=R2,
+             s2=float(spec.s2), V=V, vmode=spec.vmode if V is not None else 0, vdiv=spec.vdiv, vmod=spec.vmod, vS=spec.vS)
+    return out
+
+
+def _scaled(dy, s):
+    """s * dy as a new bf16 tensor (dy itself when s == 1)."""
+    if s == 1.0:
+        return dy
+    out = torch.empty_like(dy)
+    ops.axpby(dy, dy, float(s), 0.0, out)
+    return out
+
+
+def _epilogue_grads(dY, spec, need_r1, need_r2, vshape):
+    """(dR1, dR2, dV) of the epilogue operands for the upstream gradient dY; vshape: V's shape, None = not wanted."""
+    dR1 = _scaled(dY, spec.s1) if need_r1 else None
+    dR2 = _scaled(dY, spec.s2) if need_r2 else None
+    dV = None
+    if vshape is not None:
+        dV = torch.zeros(vshape, dtype=torch.float32, device=dY.device)
+        vmod = min(spec.vmod, vshape[0])
+        if spec.vmode == 1:
+            ops.colsum(dY, dV, vmode=1, vdiv=spec.vdiv, vmod=vmod)
+        else:
+            # vidx = ((m // vdiv) * vS + m % vS) % vmod (the diffusers-0.27.2 (s, b) context order): with vS and
+            # vdiv multiples of vmod this is m % vmod -- table row j collects every vmod-th row starting at j
+            if spec.vS % spec.vmod or spec.vdiv % spec.vmod:
+                raise NotImplementedError("row-vector gradient for vmode 2 needs vS and vdiv to be multiples of vmod")
+            for j in range(spec.vmod):
+                ops.colsum(dY[j::spec.vmod], dV[j:j + 1])
+    return dR1, dR2, dV
+
+
+class Gemm(torch.autograd.Function):
+    """out = s_acc * (gather-GEMM(A, weight) + bias) + s1 * R1 + s2 * R2 + V[idx(m)]: nn.Linear / 1x1 conv, 3x3 Conv2d
+    (stride 2 and upsample-fused too) and (3,1,1) Conv3d with every epilogue operand the blocks fuse (residuals, the
+    per-clip time-embedding / cross-attention vector, the frame positional embedding).  spec: GemmSpec.
+
+    LoRA (spec.lora = (groups, s), factors = A_0, B_0, A_1, B_1, ...: one pair per group of weight's rows -- an nn.Linear,
+    or the g = 3 fused q|k|v projection): forward and dgrad run on the merged weight W' = W + s . B_i . A_i (built once per
+    forward in fp32 and packed to the element type, exactly how a trainable fp32 master is used); dA_i / dB_i come from
+    ctrlv_lora_grad (csrc/lora.hip) without forming dW; dW of the base only if the base itself requires grad."""
 
     @staticmethod
-    def _pack(weight, mode):
-        return _packed(weight, ("fwd", mode), lambda w: _pack_fwd(w, mode))
-
-    @staticmethod
-    def forward(ctx, A, weight, bias, R1, V, s_acc, geom):
-        mode = geom["mode"]
-        N, cin = weight.shape[0], weight.shape[1]
-        taps = {0: 1, 1: 9, 2: 3}[mode]
-        m_out = A.shape[0]
-        if mode == 1:        # stride-2 / upsample-fused convs change the row count
-            H, W, Ho, Wo = geom["conv"][:4]
-            m_out = A.shape[0] // (H * W) * Ho * Wo
-        out = _rows(m_out, N, A)
-        ops.gemm(A, GatherGemm._pack(weight, mode), out, N=(N + 31) // 32 * 32, cin=cin, taps=taps, mode=mode,
-                 conv=geom.get("conv"), temporal=geom.get("temporal"),
-                 bias=None if bias is None else _bias32(bias), R1=R1, s_acc=float(s_acc),
-                 V=V, vmode=1 if V is not None else 0, vdiv=geom.get("vdiv", 1))
-        ctx.save_for_backward(A, weight)
-        ctx.geom, ctx.s_acc, ctx.has = geom, float(s_acc), (bias is not None, R1 is not None, V is not None)
-        ctx.vshape = None if V is None else tuple(V.shape)
+    def forward(ctx, A, weight, bias, R1, R2, V, spec, *factors):
+        wm = _lora_merged(weight, factors, *spec.lora) if factors else weight
+        out = _gemm_forward(A, wm, bias, R1, R2, V, spec)
+        ctx.save_for_backward(A, wm, *factors)
+        ctx.spec, ctx.wdtype = spec, weight.dtype
+        ctx.has = (bias is not None, R1 is not None, R2 is not None, None if V is None else tuple(V.shape))
         return out
 
     @staticmethod
     def backward(ctx, dY):
-        A, weight = ctx.saved_tensors
-        has_bias, has_r1, has_v = ctx.has
-        need = ctx.needs_input_grad
+        A, wm, *factors = ctx.saved_tensors
+        spec, need = ctx.spec, ctx.needs_input_grad
+        has_b, has_r1, has_r2, vshape = ctx.has
         dY = dY.contiguous()
-        dA, dW, db = gemm_grads(A, weight, dY, ctx.geom, ctx.s_acc, need[0], need[1], has_bias and need[2])
-        dR1 = dY if (has_r1 and need[3]) else None
-        dV = None
-        if has_v and need[4]:
-            dV = torch.zeros(ctx.vshape, dtype=torch.float32, device=A.device)
-            ops.colsum(dY, dV, vmode=1, vdiv=ctx.geom.get("vdiv", 1), vmod=ctx.vshape[0])
-        return dA, dW, db, dR1, dV, None, None
+        dA, dW, db = gemm_grads(A, wm, dY, spec.geom, spec.s_acc, need[0], need[1], has_b and need[2])
+        if dW is not None:
+            dW = dW.to(ctx.wdtype)             # (the saved weight of an adapted layer is the fp32 W', not the base)
+        dR1, dR2, dV = _epilogue_grads(dY, spec, has_r1 and need[3], has_r2 and need[4], vshape if need[5] else None)
+        fgrads = [None] * len(factors)
+        if any(need[7:]):
+            groups, scale = spec.lora
+            Acat = torch.cat([f.detach() for f in factors[0::2]], 0)
+            Bcat = torch.cat([f.detach() for f in factors[1::2]], 0)
+            dAc, dBc = ops.lora_grad(A, dY, Acat, Bcat, groups, scale * spec.s_acc)
+            r, n = factors[0].shape[0], dY.shape[1] // groups
+            for i, f in enumerate(factors):
+                if need[7 + i]:
+                    g = i // 2
+                    fgrads[i] = (dBc[g * n:(g + 1) * n] if i % 2 else dAc[g * r:(g + 1) * r]).to(f.dtype)
+        return (dA, dW, db, dR1, dR2, dV, None) + tuple(fgrads)
+
+
+def _pad_cols(x, n):
+    """x zero-padded to n columns (x itself when it has them)"""
+    if n == x.shape[1]:
+        return x
+    out = torch.zeros(x.shape[0], n, dtype=x.dtype, device=x.device)
+    out[:, :x.shape[1]] = x
+    return out
 
 
 def gemm_grads(A, weight, dY, geom, s_acc, need_dA=True, need_dW=True, need_db=True):
-    """(dA, dW, dbias) of out = s_acc * (gather-GEMM(A, weight) + bias) for the upstream gradient dY (bf16 rows)."""
+    """(dA, dW, dbias) of out = s_acc * (gather-GEMM(A, weight) + bias) for the upstream gradient dY (bf16 rows).
+    geom: dict(mode, conv=(H, W, Ho, Wo, stride, up) | None, temporal=(F, S) | None) -- GemmSpec.geom."""
     mode = geom["mode"]
     N, cin = weight.shape[0], weight.shape[1]
-    taps = {0: 1, 1: 9, 2: 3}[mode]
+    taps = _TAPS[mode]
     dA = dW = db = None
     if need_dA:
         # dgrad: the forward kernel with the weight's roles swapped.  The contraction runs over the forward's OUTPUT
         # channels: the GEMM needs a multiple of 64 of them (conv_out has 4: zero-padded).
         npad = (N + 63) // 64 * 64
-        wd, dYd = weight.detach(), dY
-        if npad != N:
-            wd = torch.cat([wd, wd.new_zeros((npad - N,) + tuple(wd.shape[1:]))], 0)
-            dYd = torch.zeros(dY.shape[0], npad, dtype=dY.dtype, device=dY.device)
-            dYd[:, :N] = dY
+        dYd = _pad_cols(dY, npad)
         conv = geom.get("conv")
 
         def swapped(_):
             direct = ops.pack_weight(weight, 1) if weight.is_cuda else None     # one kernel incl. the zero padding of N
             if direct is not None:
                 return direct
+            wd = weight.detach()
+            if npad != N:
+                wd = torch.cat([wd, wd.new_zeros((npad - N,) + tuple(wd.shape[1:]))], 0)
             if mode == 0:
                 return packing.pack_linear(wd.reshape(npad, cin).t())
             if mode == 1:
@@ -187,13 +241,11 @@ def gemm_grads(A, weight, dY, geom, s_acc, need_dA=True, need_dW=True, need_db=T
         # one kernel: dW (scaled by s_acc) and, riding along in the workgroups that stream dY anyway, the bias gradient.
         # Linear weights are written in place; conv weights in the packed tap-major order and permuted afterwards
         # (writing [N, cin, taps] directly scatters the atomics at a 36-byte stride: A/B in DESIGN 3.6)
-        direct = taps == 1 or _WGRAD_DIRECT
+        direct = taps == 1
         # ctrlv_gemm_wgrad takes N % 8 == 0: an output width below that (the UNet's conv_out, N = 4, trainable in the
         # stage-1 step) runs on dY zero-padded to 8 columns, and the padded rows of dW / dbias are dropped
-        nw, dYw = (N + 7) // 8 * 8, dY
-        if nw != N:
-            dYw = torch.zeros(dY.shape[0], nw, dtype=dY.dtype, device=dY.device)
-            dYw[:, :N] = dY
+        nw = (N + 7) // 8 * 8
+        dYw = _pad_cols(dY, nw)
         # (deterministic form: the ordered slab sum WRITES dW / dbias -- no zero fill; the atomic form accumulates)
         new = torch.empty if ops.DETERMINISTIC else torch.zeros
         dWp = new((nw,) + tuple(weight.shape[1:]) if direct else (nw, taps * cin), dtype=torch.float32, device=A.device)
@@ -259,8 +311,8 @@ _MIX_CACHE = {}      # id(mix_factor parameter) -> (version, sigmoid value); fil
 
 
 def prefetch_mix_factors(*models):
-    """ONE device-to-host copy for all AlphaBlender mix factors of the given models (about 60 scalars).  BlendGemm /
-    BlendLinear fold sigmoid(mix_factor) into GEMM epilogue scalars, i.e. need it on the host: read one by one, that was a
+    """ONE device-to-host copy for all AlphaBlender mix factors of the given models (about 60 scalars).  BlendGemm
+    folds sigmoid(mix_factor) into GEMM epilogue scalars, i.e. needs it on the host: read one by one, that was a
     blocking sync per res block / transformer (it drained the queue ~60 times per step and serialised the backward /
     all-reduce overlap).  training.train_step calls this once per step."""
     ps = [p for m in models for n, p in m.named_parameters() if n.endswith("mix_factor")]
@@ -281,31 +333,38 @@ def _mix_alpha(mix_factor):
 
 
 class BlendGemm(torch.autograd.Function):
-    """AlphaBlender folded into the last temporal conv: out = xs + (1 - a) * (conv(hn) + bias), a = sigmoid(mix_factor)
-    (a * xs + (1 - a) * (xs + conv) of SURVEY A.3).  Gradients for hn, the conv parameters, xs AND mix_factor."""
+    """An AlphaBlender folded into the GEMM that precedes it, a = sigmoid(mix_factor), in its two forms (distinct arithmetic):
+      R2 is None  res block, last temporal conv:  out = xs + (1 - a) * (conv(hn) + bias)          R1 = xs
+      R2 given    transformer, temporal FF output: out = a * h2 + (1 - a) * (g1 + u @ W^T + b)    R1 = g1, R2 = h2
+    Gradients for A, the GEMM's parameters, R1, R2 AND mix_factor.  spec: the geometry (its scalars are derived here)."""
 
     @staticmethod
-    def forward(ctx, hn, weight, bias, xs, mix_factor, geom):
+    def forward(ctx, A, weight, bias, R1, R2, mix_factor, spec):
         a = _mix_alpha(mix_factor)
-        out = GatherGemm.apply(hn, weight, bias, xs, None, 1.0 - a, geom)        # (no graph: forward runs under no_grad)
-        ctx.save_for_backward(hn, weight, xs, out, mix_factor)
-        ctx.geom, ctx.a = geom, a
+        spec = spec._replace(s_acc=1.0 - a, s1=1.0 if R2 is None else 1.0 - a, s2=a)
+        out = _gemm_forward(A, weight, bias, R1, R2, None, spec)
+        ctx.save_for_backward(A, weight, R1 if R2 is None else R2, out, mix_factor)
+        ctx.spec, ctx.a, ctx.res_form = spec, a, R2 is None
         return out
 
     @staticmethod
     def backward(ctx, dY):
-        hn, weight, xs, out, mix = ctx.saved_tensors
-        a, geom = ctx.a, ctx.geom
+        A, weight, other, out, mix = ctx.saved_tensors
+        a, spec, need = ctx.a, ctx.spec, ctx.needs_input_grad
         dY = dY.contiguous()
-        need = ctx.needs_input_grad
-        dhn, dw, db = gemm_grads(hn, weight, dY, geom, 1.0 - a, need[0], need[1], need[2])
+        dA, dW, db = gemm_grads(A, weight, dY, spec.geom, spec.s_acc, need[0], need[1], need[2])
+        dR1, dR2, _ = _epilogue_grads(dY, spec, need[3], need[4], None)
         dmix = None
-        if need[4]:
-            # dL/da = -sum dY * (conv + bias) = -sum dY * (out - xs) / (1 - a);  da/dmix = a (1 - a)
+        if need[5]:
             acc = torch.zeros(1, dtype=torch.float32, device=dY.device)
-            ops.dot_diff(dY, out, xs, acc, scale=-a)
+            if ctx.res_form:
+                # dL/da = -sum dY * (conv + bias) = -sum dY * (out - xs) / (1 - a);  da/dmix = a (1 - a)
+                ops.dot_diff(dY, out, other, acc, scale=-a)
+            else:
+                # dL/da = sum dY * (h2 - g1 - lin) = sum dY * (h2 - out) / (1 - a);  da/dmix = a (1 - a)
+                ops.dot_diff(dY, other, out, acc, scale=a)
             dmix = acc.to(mix.dtype).reshape(mix.shape)
-        return dhn, dw, db, (dY if need[3] else None), dmix, None
+        return dA, dW, db, dR1, dR2, dmix, None
 
 
 class LayerNormFn(torch.autograd.Function):
@@ -354,7 +413,7 @@ class LayerNormFn(torch.autograd.Function):
 # output projection for its wgrad) and the raw projection (saved for the GEGLU backward) -- are 31 GB of the step's 101 GB
 # at the reference's size.  Checkpointed, NEITHER is kept: the forward does not even write the raw projection, and the
 # backward recomputes both with the forward's own launch (one GEGLU GEMM with raw_out: the same bits).  u is saved by
-# whichever Function consumes it (FusedLinear / BlendLinear), so it is swapped for a recompute cell by a saved-tensor hook
+# whichever Function consumes it (Gemm / BlendGemm), so it is swapped for a recompute cell by a saved-tensor hook
 # that is active around the feed-forward pair only.
 _CKPT = [False]
 
@@ -473,7 +532,8 @@ class GegluProj(torch.autograd.Function):
         x, weight, bias, raw = ctx.saved_tensors
         two_i, cin = weight.shape
         inner = two_i // 2
-        wi = _frozen(weight, "geglu_il", lambda: packing.geglu_interleave(weight.detach()))   # rows in the packed (value, gate) block order
+        # rows in the packed (value, gate) block order
+        wi = frozen((weight,), "geglu_il", lambda: packing.geglu_interleave(weight.detach()), derived=True)
         if ctx.cell is not None:
             raw = ctx.cell.take("raw")                                 # (recomputed together with u: one launch)
             ctx.cell = None
@@ -504,142 +564,45 @@ def res_block_train_forward(block, x, temb_tables, B, F, H, W):
     N, S = B * F, H * W
     g2d = dict(mode=1, conv=(H, W, H, W, 1, 0), vdiv=F * S)
     g3d = dict(mode=2, temporal=(F, S), vdiv=F * S)
+    gn = GroupNormSiLU.apply
     # (x and xs each feed a norm AND the skip connection around the branch it opens: the norm hands the skip its alias, so
     #  that both gradients meet in the norm's backward kernel -- GroupNormSiLU, skip=True)
-    if s.conv_shortcut is None and _SKIP_FUSE:
-        xn, res = GroupNormSiLU.apply(x, s.norm1.weight, s.norm1.bias, N, S, 1, block.eps, True, True)
+    if s.conv_shortcut is None:
+        xn, res = gn(x, s.norm1.weight, s.norm1.bias, N, S, 1, block.eps, True, True)
     else:
-        xn, res = GroupNormSiLU.apply(x, s.norm1.weight, s.norm1.bias, N, S, 1, block.eps, True), x
-    h = GatherGemm.apply(xn, s.conv1.weight, s.conv1.bias, None, temb_tables[0], 1.0, g2d)
-    hn = GroupNormSiLU.apply(h, s.norm2.weight, s.norm2.bias, N, S, 1, block.eps, True)
-    if s.conv_shortcut is not None:
-        res = GatherGemm.apply(x, s.conv_shortcut.weight.reshape(block.cout, block.cin), s.conv_shortcut.bias, None, None,
-                               1.0, dict(mode=0))
-    xs = GatherGemm.apply(hn, s.conv2.weight, s.conv2.bias, res, None, 1.0, g2d)
-    if _SKIP_FUSE:
-        hn, xs = GroupNormSiLU.apply(xs, t.norm1.weight, t.norm1.bias, N, S, F, block.eps, True, True)
-    else:
-        hn = GroupNormSiLU.apply(xs, t.norm1.weight, t.norm1.bias, N, S, F, block.eps, True)
-    h = GatherGemm.apply(hn, t.conv1.weight, t.conv1.bias, None, temb_tables[1], 1.0, g3d)
-    hn = GroupNormSiLU.apply(h, t.norm2.weight, t.norm2.bias, N, S, F, block.eps, True)
-    return BlendGemm.apply(hn, t.conv2.weight, t.conv2.bias, xs, block.time_mixer.mix_factor, g3d)
+        xn = gn(x, s.norm1.weight, s.norm1.bias, N, S, 1, block.eps, True)
+    h = gemm(xn, s.conv1.weight, s.conv1.bias, V=temb_tables[0], **g2d)
+    hn = gn(h, s.norm2.weight, s.norm2.bias, N, S, 1, block.eps, True)
+    if s.conv_shortcut is not None:      # (the shortcut conv reads x itself: autograd sums its gradient and the norm's)
+        res = gemm(x, s.conv_shortcut.weight.reshape(block.cout, block.cin), s.conv_shortcut.bias)
+    xs = gemm(hn, s.conv2.weight, s.conv2.bias, res, **g2d)
+    hn, xs = gn(xs, t.norm1.weight, t.norm1.bias, N, S, F, block.eps, True, True)
+    h = gemm(hn, t.conv1.weight, t.conv1.bias, V=temb_tables[1], **g3d)
+    hn = gn(h, t.norm2.weight, t.norm2.bias, N, S, F, block.eps, True)
+    return BlendGemm.apply(hn, t.conv2.weight, t.conv2.bias, xs, None, block.time_mixer.mix_factor, GemmSpec(**g3d))
 
 
 def zero_conv_train_forward(conv, x, scale=1.0):
     """A ControlNet zero-conv (1x1) times conditioning_scale (controlnet.py:331-344) with gradients."""
     C = conv.weight.shape[0]
-    return GatherGemm.apply(x, conv.weight.reshape(C, -1), conv.bias, None, None, float(scale), dict(mode=0))
+    return gemm(x, conv.weight.reshape(C, -1), conv.bias, s_acc=float(scale))
 
 
 # =============================================================================== transformer (second slice)
-def _scaled(dy, s):
-    """s * dy as a new bf16 tensor (dy itself when s == 1)."""
-    if s == 1.0:
-        return dy
-    out = torch.empty_like(dy)
-    ops.axpby(dy, dy, float(s), 0.0, out)
-    return out
-
-
-class FusedLinear(torch.autograd.Function):
-    """out = s_acc * (A @ W^T + b) + s1 * R1 + s2 * R2 + V[(m // vdiv) % vmod]   (nn.Linear with the epilogue operands the
-    transformer fuses: residuals, the per-clip cross-attention vector, the frame positional embedding)."""
-
-    @staticmethod
-    def forward(ctx, A, weight, bias, R1, R2, V, cfg):
-        s_acc, s1, s2 = float(cfg.get("s_acc", 1.0)), float(cfg.get("s1", 1.0)), float(cfg.get("s2", 1.0))
-        vdiv, vmod = cfg.get("vdiv", 1), cfg.get("vmod", 1 << 30)
-        vmode, vS = (cfg.get("vmode", 1), cfg.get("vS", 1)) if V is not None else (0, 1)
-        N, cin = weight.shape
-        out = _rows(A.shape[0], N, A)
-        ops.gemm(A, _packed(weight, ("fwd", 0), lambda w: _pack_fwd(w, 0)), out, N=(N + 31) // 32 * 32, cin=cin,
-                 bias=None if bias is None else _bias32(bias), s_acc=s_acc, R1=R1, s1=s1, R2=R2, s2=s2,
-                 V=V, vmode=vmode, vdiv=vdiv, vmod=vmod, vS=vS)
-        ctx.save_for_backward(A, weight)
-        ctx.cfg = (s_acc, s1, s2, vdiv, vmod, bias is not None, R1 is not None, R2 is not None,
-                   None if V is None else tuple(V.shape), vmode, vS)
-        return out
-
-    @staticmethod
-    def backward(ctx, dY):
-        A, weight = ctx.saved_tensors[:2]
-        s_acc, s1, s2, vdiv, vmod, has_b, has_r1, has_r2, vshape, vmode, vS = ctx.cfg
-        need = ctx.needs_input_grad
-        dY = dY.contiguous()
-        dA, dW, db = gemm_grads(A, weight, dY, dict(mode=0), s_acc, need[0], need[1], has_b and need[2])
-        dR1 = _scaled(dY, s1) if (has_r1 and need[3]) else None
-        dR2 = _scaled(dY, s2) if (has_r2 and need[4]) else None
-        dV = None
-        if vshape is not None and need[5]:
-            dV = torch.zeros(vshape, dtype=torch.float32, device=A.device)
-            if vmode == 1:
-                ops.colsum(dY, dV, vmode=1, vdiv=vdiv, vmod=min(vmod, vshape[0]))
-            else:
-                # vidx = ((m // vdiv) * vS + m % vS) % vmod (the diffusers-0.27.2 (s, b) context order): with vS and
-                # vdiv multiples of vmod this is m % vmod -- table row j collects every vmod-th row starting at j
-                if vS % vmod or vdiv % vmod:
-                    raise NotImplementedError("row-vector gradient for vmode 2 needs vS and vdiv to be multiples of vmod")
-                for j in range(vmod):
-                    ops.colsum(dY[j::vmod], dV[j:j + 1])
-        return dA, dW, db, dR1, dR2, dV, None
-
-
 def _lora_merged(weight, factors, groups, scale):
-    """fp32 W' = W + s . B_i . A_i for the `groups` row blocks of `weight` (ctrlv_lora_merge, one launch per group).  Cached
-    (as a frozen Parameter, so that its packed layouts are cached too) only while W and every factor are frozen, keyed on
-    (id, _version, data_ptr, dtype) of all of them; rebuilt on every use otherwise."""
+    """fp32 W' = W + s . B_i . A_i for the `groups` row blocks of `weight` (ctrlv_lora_merge, one launch per group).  Kept
+    (as a frozen Parameter, so that its packed layouts are kept too) only while W and every factor are frozen parameters."""
     def build():
         out = torch.empty(weight.shape, dtype=torch.float32, device=weight.device)
         n = weight.shape[0] // groups
         for i in range(groups):
             ops.lora_merge(weight[i * n:(i + 1) * n], factors[2 * i], factors[2 * i + 1], scale, out=out[i * n:(i + 1) * n])
         return out
-    if any(f.requires_grad for f in factors):
-        return build()
-    kind = ("lora_merged", float(scale)) + tuple((id(p), p._version, p.data_ptr(), p.dtype) for p in factors)
-    return _frozen(weight, kind, build)
-
-
-class LoraLinear(torch.autograd.Function):
-    """FusedLinear (every epilogue operand) on an nn.Linear -- or the g = 3 fused q|k|v projection -- carrying LoRA factors:
-    forward and dgrad run the existing GEMMs on the merged weight W' = W + s . B_i . A_i (built once per forward in fp32
-    and packed to the element type, exactly how a trainable fp32 master is used); dA_i / dB_i come from ctrlv_lora_grad
-    (csrc/lora.hip) without forming dW; dW of the base only if the base itself requires grad.
-    factors: A_0, B_0, A_1, B_1, ... (one pair per group of weight's rows); lora = (groups, s)."""
-
-    @staticmethod
-    def forward(ctx, A, weight, bias, R1, R2, V, cfg, lora, *factors):
-        groups, scale = lora
-        wm = _lora_merged(weight, factors, groups, scale)
-        out = FusedLinear.forward(ctx, A, wm, bias, R1, R2, V, cfg)
-        ctx.save_for_backward(A, wm, *factors)
-        ctx.lora, ctx.wdtype = lora, weight.dtype
-        return out
-
-    @staticmethod
-    def backward(ctx, dY):
-        saved = ctx.saved_tensors
-        A, factors = saved[0], saved[2:]
-        groups, scale = ctx.lora
-        dY = dY.contiguous()
-        dA, dW, db, dR1, dR2, dV, _ = FusedLinear.backward(ctx, dY)
-        if dW is not None:
-            dW = dW.to(ctx.wdtype)
-        need = ctx.needs_input_grad[8:]
-        fgrads = [None] * len(factors)
-        if any(need):
-            Acat = torch.cat([f.detach() for f in factors[0::2]], 0)
-            Bcat = torch.cat([f.detach() for f in factors[1::2]], 0)
-            dAc, dBc = ops.lora_grad(A, dY, Acat, Bcat, groups, scale * ctx.cfg[0])
-            r, n = factors[0].shape[0], dY.shape[1] // groups
-            for i in range(groups):
-                fgrads[2 * i] = dAc[i * r:(i + 1) * r].to(factors[2 * i].dtype) if need[2 * i] else None
-                fgrads[2 * i + 1] = dBc[i * n:(i + 1) * n].to(factors[2 * i + 1].dtype) if need[2 * i + 1] else None
-        return (dA, dW, db, dR1, dR2, dV, None, None) + tuple(fgrads)
+    return frozen((weight,) + tuple(factors), ("lora_merged", float(scale)), build, derived=True)
 
 
 def _lora_operands(linears):
-    """(groups, s) and the factor list of LoraLinear for these nn.Linears (side by side along N), or None when none is
+    """(groups, s) and the trailing factor inputs of Gemm for these nn.Linears (side by side along N), or None when none is
     adapted.  A member without an adapter takes frozen zero factors of the same rank (W' = W exactly)."""
     fs = [lora_mod.factors(lin) for lin in linears]
     live = [f for f in fs if f is not None]
@@ -657,12 +620,13 @@ def _lora_operands(linears):
     return (len(linears), s), out
 
 
-def linear_apply(A, linears, weight, bias, R1, R2, V, cfg):
-    """FusedLinear.apply, or LoraLinear.apply when one of `linears` (the modules whose weights `weight` stacks) is adapted."""
-    lo = _lora_operands(linears)
+def gemm(A, weight, bias, R1=None, R2=None, V=None, linears=(), **spec):
+    """Gemm.apply with the GemmSpec fields as keywords.  linears: the nn.Linears whose weights `weight` is / stacks (side by
+    side along N) -- when one of them carries a LoRA adapter, the factors of all of them trail the inputs."""
+    lo = _lora_operands(linears) if linears else None
     if lo is None:
-        return FusedLinear.apply(A, weight, bias, R1, R2, V, cfg)
-    return LoraLinear.apply(A, weight, bias, R1, R2, V, cfg, lo[0], *lo[1])
+        return Gemm.apply(A, weight, bias, R1, R2, V, GemmSpec(**spec))
+    return Gemm.apply(A, weight, bias, R1, R2, V, GemmSpec(lora=lo[0], **spec), *lo[1])
 
 
 def lora_weight_f32(linear):
@@ -672,39 +636,6 @@ def lora_weight_f32(linear):
     if f is None:
         return w
     return w + f[2] * (f[1].float() @ f[0].float())
-
-
-class BlendLinear(torch.autograd.Function):
-    """Temporal FF output with the transformer's AlphaBlender folded in:
-        out = a * h2 + (1 - a) * (g1 + u @ W^T + b),   a = sigmoid(mix_factor)."""
-
-    @staticmethod
-    def forward(ctx, u, weight, bias, g1, h2, mix_factor):
-        a = _mix_alpha(mix_factor)
-        N, cin = weight.shape
-        out = _rows(u.shape[0], N, u)
-        ops.gemm(u, _packed(weight, ("fwd", 0), lambda w: _pack_fwd(w, 0)), out, N=N, cin=cin, bias=_bias32(bias), s_acc=1.0 - a,
-                 R1=g1, s1=1.0 - a, R2=h2, s2=a)
-        ctx.save_for_backward(u, weight, h2, out, mix_factor)
-        ctx.a = a
-        return out
-
-    @staticmethod
-    def backward(ctx, dY):
-        u, weight, h2, out, mix = ctx.saved_tensors
-        a = ctx.a
-        need = ctx.needs_input_grad
-        dY = dY.contiguous()
-        du, dW, db = gemm_grads(u, weight, dY, dict(mode=0), 1.0 - a, need[0], need[1], need[2])
-        dg1 = _scaled(dY, 1.0 - a) if need[3] else None
-        dh2 = _scaled(dY, a) if need[4] else None
-        dmix = None
-        if need[5]:
-            # dL/da = sum dY * (h2 - g1 - lin) = sum dY * (h2 - out) / (1 - a);  da/dmix = a (1 - a)
-            acc = torch.zeros(1, dtype=torch.float32, device=dY.device)
-            ops.dot_diff(dY, h2, out, acc, scale=a)
-            dmix = acc.to(mix.dtype).reshape(mix.shape)
-        return du, dW, db, dg1, dh2, dmix
 
 
 class SpatialAttention(torch.autograd.Function):
@@ -778,55 +709,44 @@ def transformer_train_forward(tr, x, ehs, B, F, H, W, time_context_order="sb"):
     big = 1 << 30
 
     def lns(h, n, V=None, vdiv=1, vmod=big):             # (normed rows, the alias of h for the skip connection)
-        if not _SKIP_FUSE:
-            return LayerNormFn.apply(h, n.weight, n.bias, V, vdiv, vmod), h
         return LayerNormFn.apply(h, n.weight, n.bias, V, vdiv, vmod, True)
 
-    def qkv_w(attn):
-        # the fused q|k|v weight is cached only while ALL THREE are frozen (partial freezing is a public mode of the UNet
-        # step), keyed on all three: a trainable or replaced k / v must not be served an old concatenation
-        q, k, v = attn.to_q.weight, attn.to_k.weight, attn.to_v.weight
-        if q.requires_grad or k.requires_grad or v.requires_grad:
-            return torch.cat([q, k, v], 0)
-        kind = ("qkv_cat",) + tuple((id(p), p._version, p.data_ptr(), p.dtype) for p in (k, v))
-        return _frozen(q, kind, lambda: torch.cat([q, k, v], 0))
+    def qkv(n, attn):
+        # the fused q|k|v weight is kept only while ALL THREE are frozen (partial freezing is a public mode of the UNet step)
+        ws = (attn.to_q.weight, attn.to_k.weight, attn.to_v.weight)
+        w = frozen(ws, "qkv_cat", lambda: torch.cat(ws, 0), derived=True)
+        return gemm(n, w, None, linears=[attn.to_q, attn.to_k, attn.to_v])
 
-    def qkvs(attn):
-        return [attn.to_q, attn.to_k, attn.to_v]
+    def out_proj(a, attn, R1, **spec):
+        lin = attn.to_out[0]
+        return gemm(a, lin.weight, lin.bias, R1, linears=[lin], **spec)
 
     # Every trunk tensor (x, h0, h1, h2, g0, g1) feeds the norm that opens a branch AND the skip connection around it: the norm
     # hands the skip its alias (skip=True), so both gradients meet in the norm's backward kernel instead of a separate sum.
-    if _SKIP_FUSE:
-        t, x = GroupNormSiLU.apply(x, tr.norm.weight, tr.norm.bias, N, S, 1, 1e-6, False, True)
-    else:
-        t = GroupNormSiLU.apply(x, tr.norm.weight, tr.norm.bias, N, S, 1, 1e-6, False)
-    h0 = FusedLinear.apply(t, tr.proj_in.weight, tr.proj_in.bias, None, None, None, {})
+    t, x = GroupNormSiLU.apply(x, tr.norm.weight, tr.norm.bias, N, S, 1, 1e-6, False, True)
+    h0 = gemm(t, tr.proj_in.weight, tr.proj_in.bias)
     # ---- spatial BasicTransformerBlock
     n, h0 = lns(h0, sb.norm1)
-    qkv = linear_apply(n, qkvs(sb.attn1), qkv_w(sb.attn1), None, None, None, None, {})
-    a = SpatialAttention.apply(qkv, N, S, C)
-    h1 = linear_apply(a, [sb.attn1.to_out[0]], sb.attn1.to_out[0].weight, sb.attn1.to_out[0].bias, h0, None, xvec(sb.attn2),
-                      dict(vdiv=F * S))
+    a = SpatialAttention.apply(qkv(n, sb.attn1), N, S, C)
+    h1 = out_proj(a, sb.attn1, h0, V=xvec(sb.attn2), vdiv=F * S)
     with _ff_region():
         n, h1 = lns(h1, sb.norm3)
         u = GegluProj.apply(n, sb.ff.net[0].proj.weight, sb.ff.net[0].proj.bias)
-        h2 = FusedLinear.apply(u, sb.ff.net[2].weight, sb.ff.net[2].bias, h1, None, None, {})
+        h2 = gemm(u, sb.ff.net[2].weight, sb.ff.net[2].bias, h1)
     del u
     # ---- temporal block: rows stay ordered (b, f, s); the frame embedding is added inside the consumers
     with _ff_region():
         n, h2 = lns(h2, tb.norm_in, emb, S, F)
         u = GegluProj.apply(n, tb.ff_in.net[0].proj.weight, tb.ff_in.net[0].proj.bias)
-        g0 = FusedLinear.apply(u, tb.ff_in.net[2].weight, tb.ff_in.net[2].bias, h2, None, emb, dict(vdiv=S, vmod=F))
+        g0 = gemm(u, tb.ff_in.net[2].weight, tb.ff_in.net[2].bias, h2, V=emb, vdiv=S, vmod=F)
     del u
     n, g0 = lns(g0, tb.norm1)
-    qkv = linear_apply(n, qkvs(tb.attn1), qkv_w(tb.attn1), None, None, None, None, {})
-    a = TemporalAttention.apply(qkv, B, F, S, C)
-    g1 = linear_apply(a, [tb.attn1.to_out[0]], tb.attn1.to_out[0].weight, tb.attn1.to_out[0].bias, g0, None, xvec(tb.attn2),
-                      dict(vmode=2, vdiv=F * S, vS=S, vmod=B) if quirk else dict(vdiv=F * S))
+    a = TemporalAttention.apply(qkv(n, tb.attn1), B, F, S, C)
+    vspec = dict(vmode=2, vdiv=F * S, vS=S, vmod=B) if quirk else dict(vdiv=F * S)
+    g1 = out_proj(a, tb.attn1, g0, V=xvec(tb.attn2), **vspec)
     with _ff_region():
         n, g1 = lns(g1, tb.norm3)
         u = GegluProj.apply(n, tb.ff.net[0].proj.weight, tb.ff.net[0].proj.bias)
-        h3 = BlendLinear.apply(u, tb.ff.net[2].weight, tb.ff.net[2].bias, g1, h2, tr.time_mixer.mix_factor)
+        h3 = BlendGemm.apply(u, tb.ff.net[2].weight, tb.ff.net[2].bias, g1, h2, tr.time_mixer.mix_factor, GemmSpec())
     del u, n
-    return FusedLinear.apply(h3, tr.proj_out.weight, tr.proj_out.bias, x, None, None, {})
-
+    return gemm(h3, tr.proj_out.weight, tr.proj_out.bias, x)

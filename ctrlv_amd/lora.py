@@ -7,7 +7,7 @@ names, so the state dict reads `...to_q.lora_A.default.weight` ([r, Cin]) and `.
 The layers are parameter containers here (both executors read the tensors directly), so the adapter never runs as a
 branch: every consumer reads the MERGED weight W' = W + (lora_alpha / r) . B . A, built by ctrlv_lora_merge
 (csrc/lora.hip) -- the C++ plan through `merged_state_dict`, the per-op executor through `merged_weight`, the training step
-through ctrlv_amd.autograd.LoraLinear (whose backward forms dA / dB with ctrlv_lora_grad).
+through the trailing factor inputs of ctrlv_amd.autograd.Gemm (whose backward forms dA / dB with ctrlv_lora_grad).
 """
 import math
 

@@ -8,7 +8,6 @@ from . import _lib, profiler as _prof
 from ._lib import GemmDesc, check
 
 _DT = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
-_NO_PACK_KERNEL = __import__("os").environ.get("CTRLV_PACK_KERNEL", "1") == "0"      # A/B handle: torch packers only
 
 
 def _stream():
@@ -38,12 +37,13 @@ DETERMINISTIC = __import__("os").environ.get("CTRLV_DETERMINISTIC", "1") != "0"
 _SCRATCH = {}
 
 
-def _scratch(device, nbytes, tag):
-    """Reduction scratch, one buffer per (device, stream, purpose), grown on demand (launches of a stream are ordered)."""
+def _scratch(device, nbytes, tag, floor=1 << 20):
+    """Kernel scratch, one buffer per (device, stream, purpose) of at least `floor` bytes, grown on demand: the launches of
+    one stream are ordered, two streams (the ControlNet beside the UNet encoder) must not share it."""
     key = (device, torch.cuda.current_stream(device).cuda_stream, tag)
     buf = _SCRATCH.get(key)
     if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=device)
+        buf = torch.empty(max(int(nbytes), floor), dtype=torch.uint8, device=device)
         _SCRATCH[key] = buf
     return buf
 
@@ -82,7 +82,7 @@ def pack_weight(weight, form=0, geglu=False, dtype=torch.bfloat16):
     [N32, taps*C], form 1 = role-swapped dgrad [C32, taps*N64].  Returns None when the shape needs the torch packer
     (K not a multiple of 64 for Linear, odd channel counts)."""
     w = weight.detach()
-    if _NO_PACK_KERNEL or not (w.is_cuda and w.is_contiguous() and w.dtype in _DT):
+    if not (w.is_cuda and w.is_contiguous() and w.dtype in _DT):
         return None
     N, C = w.shape[0], w.shape[1]
     taps = w.numel() // (N * C)
@@ -236,20 +236,6 @@ def _gemm_desc(A, W, out, *, N, cin, taps=1, mode=0, bias=None, A2=None, c_split
     return d
 
 
-_SPLITK_WS = {}
-
-
-def _splitk_scratch(device, nbytes):
-    """fp32 scratch of the split contractions, one per (device, stream), grown on demand: the launches of one stream are
-    ordered, two streams (ControlNet beside the UNet encoder) must not share it."""
-    key = (device, torch.cuda.current_stream(device).cuda_stream)
-    buf = _SPLITK_WS.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(nbytes, 64 << 20), dtype=torch.uint8, device=device)
-        _SPLITK_WS[key] = buf
-    return buf
-
-
 def gemm_splitk_slices(A, W, out, **kw):
     """K slices `gemm(A, W, out, **kw)` runs this launch in (1 = not split): scratch bytes / (M * N * 4)."""
     d = _gemm_desc(A, W, out, **kw)
@@ -274,7 +260,7 @@ def gemm(A, W, out, **kw):
         # and in a batch
         need = lib.ctrlv_gemm_splitk_ws_bytes(ctypes.byref(d))
         if need:
-            d.splitk_ws = _p(_splitk_scratch(A.device, need))
+            d.splitk_ws = _p(_scratch(A.device, need, "splitk", floor=64 << 20))      # (fp32 partials of the K slices)
     cin, taps, mode, geglu = d.Cin, d.taps, d.mode, d.geglu
     R1, R2, raw_out, act = kw.get("R1"), kw.get("R2"), kw.get("raw_out"), kw.get("act", 0)
     out_f32 = kw.get("out_f32", False)

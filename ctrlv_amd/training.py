@@ -16,11 +16,12 @@ reference's DDP default) over torch.distributed WHILE the backward pass runs (ho
 import math
 
 import torch
+import torch.distributed as dist
 import torch.nn.functional as Fn
 
 from . import ops
-from .autograd import (FusedLinear, GatherGemm, GroupNormSiLU, f32, gradient_checkpointing, res_block_train_forward, sinusoid,
-                       transformer_train_forward, zero_conv_train_forward)
+from .autograd import (GroupNormSiLU, f32, gemm, gradient_checkpointing, prefetch_mix_factors, res_block_train_forward,
+                       sinusoid, transformer_train_forward, zero_conv_train_forward)
 from .models.blocks import TransformerSpatioTemporalModel  # noqa: F401  (documentation anchor)
 
 
@@ -55,7 +56,7 @@ def _res(block, x, emb_s, B, F, H, W):
 
 
 def _conv(conv, x, H, W, Ho, Wo, stride, up):
-    return GatherGemm.apply(x, conv.weight, conv.bias, None, None, 1.0, dict(mode=1, conv=(H, W, Ho, Wo, stride, up)))
+    return gemm(x, conv.weight, conv.bias, mode=1, conv=(H, W, Ho, Wo, stride, up))
 
 
 def down_block_train(blk, x, emb_s, ehs, B, F, H, W, order):
@@ -119,30 +120,43 @@ def _input_conv_weight(convs, cp, kp):
     return w, b
 
 
-def controlnet_train_forward(model, sample, timestep, encoder_hidden_states, added_time_ids, control_cond,
-                             conditioning_scale=1.0):
-    """`ControlNetModel.forward` (controlnet.py:226-351) with gradients.  Returns (down, mid): lists of
-    (rows [N*H*W, C] bf16, H, W) in the order of `down_block_res_samples`, and the mid tuple."""
-    B, F, Cin, h, w = sample.shape
-    N, dev = B * F, sample.device
+def _encoder_train(model, planes, timestep, encoder_hidden_states, added_time_ids, B, F):
+    """The encoder side the ControlNet and the trainable UNet share: NCHW input planes -> im2col -> the input conv(s) as ONE
+    GEMM -> down blocks -> mid block, GEGLU feed-forwards checkpointed if the model asks for it
+    (`enable_gradient_checkpointing()`, tools/train_video_controlnet.py:185-186).  Returns (mid rows, H, W, taps, emb_s,
+    ehs); taps: (rows [N*H*W, C] bf16, H, W) in the order of `down_block_res_samples`."""
+    N, (h, w), dev = B * F, planes[0].shape[2:], planes[0].device
     order = model.time_context_order
     emb_s = clip_embeddings(model, timestep, added_time_ids, B, dev)
     ehs = encoder_hidden_states.reshape(B, -1).float()
     convs = [model.conv_in] + model._extra_input_convs()
-    cin_tot = sum(c.weight.shape[1] for c in convs)
-    cp = (cin_tot + 7) // 8 * 8
+    cp = (sum(c.weight.shape[1] for c in convs) + 7) // 8 * 8
     kp = (9 * cp + 63) // 64 * 64
-    col = _input_cols([sample.reshape(N, Cin, h, w), control_cond.reshape(N, -1, h, w).to(dev)], N, h, w, cp, kp, dev)
+    col = _input_cols(planes, N, h, w, cp, kp, dev)
     wi, bi = _input_conv_weight(convs, cp, kp)
-    x = FusedLinear.apply(col, wi, bi, None, None, None, {})
+    x = gemm(col, wi, bi)
     taps, H, W = [(x, h, w)], h, w
-    # `model.enable_gradient_checkpointing()` (the reference's trainer calls it: tools/train_video_controlnet.py:185-186):
-    # the GEGLU feed-forward intermediates are recomputed in the backward instead of kept (autograd.py)
     with gradient_checkpointing(getattr(model, "gradient_checkpointing", False)):
         for blk in model.down_blocks:
             x, H, W, t = down_block_train(blk, x, emb_s, ehs, B, F, H, W, order)
             taps += t
         x = mid_block_train(model.mid_block, x, emb_s, ehs, B, F, H, W, order)
+    return x, H, W, taps, emb_s, ehs
+
+
+def _unet_tail(unet, x, N, H, W):
+    """conv_norm_out + SiLU + conv_out -> the prediction as channels-last rows [N*H*W, out_channels] (bf16)."""
+    xn = GroupNormSiLU.apply(x, unet.conv_norm_out.weight, unet.conv_norm_out.bias, N, H * W, 1, 1e-5, True)
+    return gemm(xn, unet.conv_out.weight, unet.conv_out.bias, mode=1, conv=(H, W, H, W, 1, 0))
+
+
+def controlnet_train_forward(model, sample, timestep, encoder_hidden_states, added_time_ids, control_cond,
+                             conditioning_scale=1.0):
+    """`ControlNetModel.forward` (controlnet.py:226-351) with gradients.  Returns (down, mid): lists of
+    (rows [N*H*W, C] bf16, H, W) in the order of `down_block_res_samples`, and the mid tuple."""
+    B, F, Cin, h, w = sample.shape
+    planes = [sample.reshape(B * F, Cin, h, w), control_cond.reshape(B * F, -1, h, w).to(sample.device)]
+    x, H, W, taps, _, _ = _encoder_train(model, planes, timestep, encoder_hidden_states, added_time_ids, B, F)
     down = [(zero_conv_train_forward(zc, r, conditioning_scale), hh, ww)
             for (r, hh, ww), zc in zip(taps, model.controlnet_down_blocks)]
     mid = (zero_conv_train_forward(model.controlnet_mid_block, x, conditioning_scale), H, W)
@@ -186,10 +200,7 @@ def unet_train_forward(unet, sample, timestep, encoder_hidden_states, added_time
     with gradient_checkpointing(getattr(unet, "gradient_checkpointing", False)):
         for blk in unet.up_blocks:
             x, H, W = up_block_train(blk, x, emb_s, ehs, B, F, H, W, skips, order)
-    c0 = x.shape[1]
-    xn = GroupNormSiLU.apply(x, unet.conv_norm_out.weight, unet.conv_norm_out.bias, N, H * W, 1, 1e-5, True)
-    return GatherGemm.apply(xn, unet.conv_out.weight, unet.conv_out.bias, None, None, 1.0,
-                            dict(mode=1, conv=(H, W, H, W, 1, 0)))
+    return _unet_tail(unet, x, N, H, W)
 
 
 def unet_full_train_forward(unet, sample, timestep, encoder_hidden_states, added_time_ids):
@@ -198,27 +209,13 @@ def unet_full_train_forward(unet, sample, timestep, encoder_hidden_states, added
     ControlNet's trainable blocks (the ControlNet is a copy of this encoder), their taps feed the decoder's skip concat --
     autograd adds the two gradients of each tap.  Returns the prediction as channels-last rows [B*F*h*w, out_channels]."""
     B, F, Cin, h, w = sample.shape
-    N, dev = B * F, sample.device
-    order = unet.time_context_order
-    emb_s = clip_embeddings(unet, timestep, added_time_ids, B, dev)
-    ehs = encoder_hidden_states.reshape(B, -1).float()
-    cp = (Cin + 7) // 8 * 8
-    kp = (9 * cp + 63) // 64 * 64
-    col = _input_cols([sample.reshape(N, Cin, h, w)], N, h, w, cp, kp, dev)
-    wi, bi = _input_conv_weight([unet.conv_in], cp, kp)
-    x = FusedLinear.apply(col, wi, bi, None, None, None, {})
-    taps, H, W = [(x, h, w)], h, w
+    x, H, W, taps, emb_s, ehs = _encoder_train(unet, [sample.reshape(B * F, Cin, h, w)], timestep, encoder_hidden_states,
+                                               added_time_ids, B, F)
+    skips = [t[0] for t in taps]
     with gradient_checkpointing(getattr(unet, "gradient_checkpointing", False)):
-        for blk in unet.down_blocks:
-            x, H, W, t = down_block_train(blk, x, emb_s, ehs, B, F, H, W, order)
-            taps += t
-        x = mid_block_train(unet.mid_block, x, emb_s, ehs, B, F, H, W, order)
-        skips = [t[0] for t in taps]
         for blk in unet.up_blocks:
-            x, H, W = up_block_train(blk, x, emb_s, ehs, B, F, H, W, skips, order)
-    xn = GroupNormSiLU.apply(x, unet.conv_norm_out.weight, unet.conv_norm_out.bias, N, H * W, 1, 1e-5, True)
-    return GatherGemm.apply(xn, unet.conv_out.weight, unet.conv_out.bias, None, None, 1.0,
-                            dict(mode=1, conv=(H, W, H, W, 1, 0)))
+            x, H, W = up_block_train(blk, x, emb_s, ehs, B, F, H, W, skips, unet.time_context_order)
+    return _unet_tail(unet, x, B * F, H, W)
 
 
 # ------------------------------------------------------------------------------------------------- loss / step
@@ -250,7 +247,6 @@ def train_step(controlnet, unet, batch, optimizer=None, conditioning_scale=1.0, 
     all-reduced and the optimizer does not step; the last micro-batch (accumulate=False) reduces the sums and steps.  batch: dict(latents (B,F,4,h,w) clean, noise, sigmas [B], image_latents (B,F,4,h,w)
     (conditioning frame repeated), control_cond (B,F,4,h,w), encoder_hidden_states (B,1,D), added_time_ids (B,3)).
     Returns the loss as a device tensor; the one host read of the step is the batched mix-factor fetch at its start."""
-    from .autograd import prefetch_mix_factors
     prefetch_mix_factors(controlnet, unet)          # the step's only device-to-host read (about 60 scalars, one copy)
     lat, sig, noisy, timesteps, sample = _noised_inputs(batch)
     down, mid = controlnet_train_forward(controlnet, sample, timesteps, batch["encoder_hidden_states"],
@@ -270,7 +266,6 @@ def unet_train_step(unet, batch, optimizer=None, world_size=1, buckets=None, acc
     predict-bbox layout passes unchanged), encoder_hidden_states with the caller's conditioning dropout already applied.
     Data parallel / gradient accumulation / zero gradients for parameters without a gradient path: as in `train_step`.
     Returns the detached loss."""
-    from .autograd import prefetch_mix_factors
     prefetch_mix_factors(unet)
     lat, sig, noisy, timesteps, sample = _noised_inputs(batch)
     pred = unet_full_train_forward(unet, sample, timesteps, batch["encoder_hidden_states"], batch["added_time_ids"])
@@ -330,20 +325,10 @@ class GradientBuckets:
     byte mask) and reduces those buckets again with the gradient in place, so no gradient is ever dropped."""
 
     def __init__(self, params, bucket_bytes=25 * 1024 * 1024, group=None):
-        import torch.distributed as dist
-        self.dist, self.group = dist, group
+        self.group = group
         self.active = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
         self.world = dist.get_world_size(group) if self.active else 1
-        self.buckets, cur, size = [], [], 0
-        for p in reversed([p for p in params if p.requires_grad]):
-            nbytes = p.numel() * 4
-            if cur and size + nbytes > bucket_bytes:
-                self.buckets.append(cur)
-                cur, size = [], 0
-            cur.append(p)
-            size += nbytes
-        if cur:
-            self.buckets.append(cur)
+        self.buckets = _bucketed(reversed([p for p in params if p.requires_grad]), bucket_bytes)
         self.bucket_of = {id(p): i for i, b in enumerate(self.buckets) for p in b}
         self.enabled = True               # False = accumulate locally (accelerate's no_sync micro-batches): no collective
         self.launch_order = []
@@ -363,8 +348,7 @@ class GradientBuckets:
         self.dirty = set()                # buckets that went out before a (formerly unused) parameter's gradient arrived
 
     def _launch(self, i):
-        flat = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).float().reshape(-1) for p in self.buckets[i]])
-        self.inflight[i] = (flat, self.dist.all_reduce(flat, op=self.dist.ReduceOp.SUM, group=self.group, async_op=True))
+        self.inflight[i] = _launch_bucket(self.buckets[i], self.group)
         self.launch_order.append(i)
 
     def _hook(self, p):
@@ -392,24 +376,13 @@ class GradientBuckets:
         mask = torch.zeros(len(self.buckets), dtype=torch.uint8, device=self.inflight[0][0].device)
         for i in self.dirty:
             mask[i] = 1
-        self.dist.all_reduce(mask, op=self.dist.ReduceOp.MAX, group=self.group)
+        dist.all_reduce(mask, op=dist.ReduceOp.MAX, group=self.group)
         redo = [i for i, v in enumerate(mask.tolist()) if v]
         for i in redo:
             self.inflight[i][1].wait()
             self._launch(i)
-        for i, b in enumerate(self.buckets):
-            flat, work = self.inflight[i]
-            work.wait()
-            flat.div_(self.world)
-            off = 0
-            for p in b:
-                n = p.numel()
-                g = flat[off:off + n].reshape(p.shape).to(p.dtype)
-                if p.grad is None:
-                    p.grad = g
-                else:
-                    p.grad.copy_(g)
-                off += n
+        for b, inflight in zip(self.buckets, self.inflight):
+            _write_back(b, *inflight, self.world)
         n = len(self.buckets)
         self.unused = {id(p) for b in self.buckets for p in b if id(p) not in self.fired}
         self._arm()
@@ -421,15 +394,8 @@ class GradientBuckets:
         self.handles = []
 
 
-def allreduce_gradients(params, bucket_bytes=25 * 1024 * 1024, group=None):
-    """Average the gradients over the process group in flat fp32 buckets (reference: DDP's 25 MB default under
-    `accelerate`, train_video_controlnet.py:225,485).  All buckets are launched asynchronously before the first wait, so
-    the transfers queue back to back on the collective stream; parameters without a gradient contribute zeros (every
-    rank must issue identical collectives)."""
-    import torch.distributed as dist
-    if not dist.is_available() or not dist.is_initialized() or dist.get_world_size(group) == 1:
-        return 0
-    world = dist.get_world_size(group)
+def _bucketed(params, bucket_bytes):
+    """params in order, grouped into buckets of at most `bucket_bytes` of fp32 (a larger parameter gets its own)"""
     buckets, cur, size = [], [], 0
     for p in params:
         nbytes = p.numel() * 4
@@ -440,20 +406,39 @@ def allreduce_gradients(params, bucket_bytes=25 * 1024 * 1024, group=None):
         size += nbytes
     if cur:
         buckets.append(cur)
-    pending = []
-    for b in buckets:
-        flat = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).float().reshape(-1) for p in b])
-        pending.append((b, flat, dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group, async_op=True)))
-    for b, flat, work in pending:
-        work.wait()
-        flat.div_(world)
-        off = 0
-        for p in b:
-            n = p.numel()
-            g = flat[off:off + n].reshape(p.shape).to(p.dtype)
-            if p.grad is None:
-                p.grad = g
-            else:
-                p.grad.copy_(g)
-            off += n
+    return buckets
+
+
+def _launch_bucket(bucket, group):
+    """(flat fp32 gradients of the bucket -- zeros where there is none: every rank must issue identical collectives --,
+    the handle of their asynchronous SUM all-reduce)"""
+    flat = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).float().reshape(-1) for p in bucket])
+    return flat, dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group, async_op=True)
+
+
+def _write_back(bucket, flat, work, world):
+    """waits for the bucket's all-reduce and writes the average into the parameters' .grad"""
+    work.wait()
+    flat.div_(world)
+    off = 0
+    for p in bucket:
+        n = p.numel()
+        g = flat[off:off + n].reshape(p.shape).to(p.dtype)
+        if p.grad is None:
+            p.grad = g
+        else:
+            p.grad.copy_(g)
+        off += n
+
+
+def allreduce_gradients(params, bucket_bytes=25 * 1024 * 1024, group=None):
+    """Average the gradients over the process group in flat fp32 buckets (reference: DDP's 25 MB default under
+    `accelerate`, train_video_controlnet.py:225,485).  All buckets are launched asynchronously before the first wait, so
+    the transfers queue back to back on the collective stream; parameters without a gradient contribute zeros."""
+    if not dist.is_available() or not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return 0
+    buckets = _bucketed(params, bucket_bytes)
+    pending = [_launch_bucket(b, group) for b in buckets]
+    for b, inflight in zip(buckets, pending):
+        _write_back(b, *inflight, dist.get_world_size(group))
     return len(buckets)

@@ -340,8 +340,8 @@ def test_norm_backward_adds_the_skip_gradient(ops, C, with_v):
 
 @pytest.mark.parametrize("C", [64, 320])
 def test_geglu_feedforward_backward(ops, C):
-    """GEGLU projection + output Linear (diffusers FeedForward) through GegluProj / GatherGemm vs torch.autograd."""
-    from ctrlv_amd.autograd import GatherGemm, GegluProj
+    """GEGLU projection + output Linear (diffusers FeedForward) through GegluProj / Gemm vs torch.autograd."""
+    from ctrlv_amd.autograd import GegluProj, Gemm, GemmSpec
     M = 777
     x = bf(torch.randn(M, C, generator=g(1)))
     w1 = (bf(torch.randn(8 * C, C, generator=g(2)) / math.sqrt(C))).float().requires_grad_(True)
@@ -356,7 +356,7 @@ def test_geglu_feedforward_backward(ops, C):
     xd = x.to(DEV).requires_grad_(True)
     pd = [t.detach().to(DEV).requires_grad_(True) for t in (w1, b1, w2, b2)]
     u = GegluProj.apply(xd, pd[0], pd[1])
-    y = GatherGemm.apply(u, pd[2], pd[3], xd, None, 1.0, dict(mode=0))
+    y = Gemm.apply(u, pd[2], pd[3], xd, None, None, GemmSpec())
     assert parity_err(y.detach(), yr.detach(), "FF forward") < 4e-3
     y.backward(dy.to(DEV))
     errs = {"x": rel_l2(xd.grad, xr.grad)}

@@ -1,4 +1,4 @@
-"""LoRA adapters on the GPU (csrc/lora.hip, ctrlv_amd/lora.py, autograd.LoraLinear): the factor-gradient kernel against fp32
+"""LoRA adapters on the GPU (csrc/lora.hip, ctrlv_amd/lora.py, autograd.Gemm): the factor-gradient kernel against fp32
 torch and against the naive merged-weight chain, the merge kernel, B = 0 leaving every forward and the training loss
 bit-identical, the stage-1 step with an adapter against the oracle's fp32 autograd (the oracle's nn.Linears wrapped as
 base(x) + s B(A(x)), test-side), inference after optimizer steps through both executors and after fuse_lora(), the

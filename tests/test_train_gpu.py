@@ -239,7 +239,7 @@ def test_geglu_checkpointing_is_bit_identical_at_c1280_and_quiet_without_grad(hi
         with A.gradient_checkpointing(ck):
             with A._ff_region():
                 u = A.GegluProj.apply(x, ps[0], ps[1])
-                y = A.FusedLinear.apply(u, ps[2], ps[3], None, None, None, {})
+                y = A.Gemm.apply(u, ps[2], ps[3], None, None, None, A.GemmSpec())
         y.backward(dy)
         return [y.detach()] + [t.grad for t in [x] + ps]
     plain, ckpt = run(False), run(True)
@@ -248,5 +248,5 @@ def test_geglu_checkpointing_is_bit_identical_at_c1280_and_quiet_without_grad(hi
     with A.gradient_checkpointing(True), torch.no_grad():
         with A._ff_region():
             u = A.GegluProj.apply(x0, w1, b1)
-            y = A.FusedLinear.apply(u, w2, b2, None, None, None, {})
+            y = A.Gemm.apply(u, w2, b2, None, None, None, A.GemmSpec())
     assert torch.equal(y, plain[0]) and not A._CELLS

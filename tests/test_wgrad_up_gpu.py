@@ -28,7 +28,7 @@ def test_wgrad_upsample_conv(hip_lib, C, H, W, n, dtype):
     wr = w.to(DEV).requires_grad_(True)
     br = torch.zeros(C, device=DEV, requires_grad=True)
     Fn.conv2d(Fn.interpolate(x.to(DEV), scale_factor=2, mode="nearest"), wr, br, padding=1).backward(dy.to(DEV))
-    # HIP: channels-last rows, the geometry GatherGemm gives the upsampler conv
+    # HIP: channels-last rows, the geometry Gemm gives the upsampler conv
     A = x.permute(0, 2, 3, 1).reshape(-1, C).to(DEV, dtype).contiguous()
     dY = dy.permute(0, 2, 3, 1).reshape(-1, C).to(DEV, dtype).contiguous()
     geom = dict(mode=1, conv=(H, W, 2 * H, 2 * W, 1, 1))
