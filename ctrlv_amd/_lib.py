@@ -113,6 +113,8 @@ SIGNATURES = {
     "ctrlv_layernorm": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_int,
                                 c_void_p, c_void_p]),
     "ctrlv_softmax_rows": (c_int, [c_void_p, c_int, c_int, ctypes.c_long, c_void_p, ctypes.c_long, c_void_p]),
+    "ctrlv_softmax_rows_bwd": (c_int, [c_void_p, ctypes.c_long, c_void_p, ctypes.c_long, c_int, c_int, c_float, c_void_p,
+                                       ctypes.c_long, c_void_p]),
     "ctrlv_ff_fused_w1f_bytes": (c_int, []),
     "ctrlv_ff_fused_pack": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ctrlv_ff_fused_serves": (c_int, [ctypes.POINTER(GemmDesc), c_int]),
@@ -135,6 +137,8 @@ SIGNATURES = {
     "ctrlv_rows_to_nchw": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "ctrlv_time_conv_rows_to_nchw": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                              c_void_p]),
+    "ctrlv_time_conv_rows_to_nchw_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                                 c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ctrlv_im2col3x3": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "ctrlv_axpby": (c_int, [c_void_p, c_void_p, c_float, c_float, c_void_p, c_size_t, c_void_p]),
     "ctrlv_timestep_embedding": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
@@ -198,7 +202,7 @@ def _status_recorder(lib, fn):
         return rc
     call.__name__ = getattr(fn, "__name__", "ctrlv_fn")
     return call
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 
 class CtrlvHipError(RuntimeError):

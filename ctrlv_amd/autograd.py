@@ -310,15 +310,22 @@ class GroupNormSiLU(torch.autograd.Function):
 _MIX_CACHE = {}      # id(mix_factor parameter) -> (version, sigmoid value); filled by prefetch_mix_factors()
 
 
-def prefetch_mix_factors(*models):
+def prefetch_mix_factors(*models, host_sigmoid=False):
     """ONE device-to-host copy for all AlphaBlender mix factors of the given models (about 60 scalars).  BlendGemm
     folds sigmoid(mix_factor) into GEMM epilogue scalars, i.e. needs it on the host: read one by one, that was a
     blocking sync per res block / transformer (it drained the queue ~60 times per step and serialised the backward /
-    all-reduce overlap).  training.train_step calls this once per step."""
+    all-reduce overlap).  training.train_step calls this once per step.
+    host_sigmoid: copy the raw factors and take the sigmoid on the host in double precision -- the value `_mix_alpha` reads
+    one by one and the inference executor of the VAE decoder packs (vae_decoder_hip._sig), so that a training forward and
+    that executor hand the kernels the same scalar (the device's fp32 sigmoid may differ from it in the last bit)."""
     ps = [p for m in models for n, p in m.named_parameters() if n.endswith("mix_factor")]
     if not ps:
         return
-    vals = torch.sigmoid(torch.stack([p.detach().float().reshape(()) for p in ps])).cpu().tolist()
+    if host_sigmoid:
+        raw = torch.stack([p.detach().float().reshape(()) for p in ps]).cpu().tolist()
+        vals = [1.0 / (1.0 + math.exp(-v)) for v in raw]
+    else:
+        vals = torch.sigmoid(torch.stack([p.detach().float().reshape(()) for p in ps])).cpu().tolist()
     _MIX_CACHE.clear()
     for p, v in zip(ps, vals):
         _MIX_CACHE[id(p)] = (p._version, p.data_ptr(), float(v))
@@ -336,12 +343,20 @@ class BlendGemm(torch.autograd.Function):
     """An AlphaBlender folded into the GEMM that precedes it, a = sigmoid(mix_factor), in its two forms (distinct arithmetic):
       R2 is None  res block, last temporal conv:  out = xs + (1 - a) * (conv(hn) + bias)          R1 = xs
       R2 given    transformer, temporal FF output: out = a * h2 + (1 - a) * (g1 + u @ W^T + b)    R1 = g1, R2 = h2
-    Gradients for A, the GEMM's parameters, R1, R2 AND mix_factor.  spec: the geometry (its scalars are derived here)."""
+    Gradients for A, the GEMM's parameters, R1, R2 AND mix_factor.  spec: the geometry (its scalars are derived here).
+    Opt-in (a trailing True, res block form only): switch_spatial_to_temporal_mix of the VAE decoder's blender, i.e. the
+    first form with mix -> -mix:  out = xs + a * (conv(hn) + bias)."""
 
     @staticmethod
-    def forward(ctx, A, weight, bias, R1, R2, mix_factor, spec):
+    def forward(ctx, A, weight, bias, R1, R2, mix_factor, spec, *opt):
         a = _mix_alpha(mix_factor)
-        spec = spec._replace(s_acc=1.0 - a, s1=1.0 if R2 is None else 1.0 - a, s2=a)
+        ctx.switched, ctx.n_opt = bool(opt[0]) if opt else False, len(opt)
+        if ctx.switched:
+            if R2 is not None:
+                raise ValueError("BlendGemm: the switched mix exists for the res block form only")
+            spec = spec._replace(s_acc=a, s1=1.0, s2=1.0)
+        else:
+            spec = spec._replace(s_acc=1.0 - a, s1=1.0 if R2 is None else 1.0 - a, s2=a)
         out = _gemm_forward(A, weight, bias, R1, R2, None, spec)
         ctx.save_for_backward(A, weight, R1 if R2 is None else R2, out, mix_factor)
         ctx.spec, ctx.a, ctx.res_form = spec, a, R2 is None
@@ -357,14 +372,17 @@ class BlendGemm(torch.autograd.Function):
         dmix = None
         if need[5]:
             acc = torch.zeros(1, dtype=torch.float32, device=dY.device)
-            if ctx.res_form:
+            if ctx.switched:
+                # dL/da = sum dY * (conv + bias) = sum dY * (out - xs) / a;  da/dmix = a (1 - a)
+                ops.dot_diff(dY, out, other, acc, scale=1.0 - a)
+            elif ctx.res_form:
                 # dL/da = -sum dY * (conv + bias) = -sum dY * (out - xs) / (1 - a);  da/dmix = a (1 - a)
                 ops.dot_diff(dY, out, other, acc, scale=-a)
             else:
                 # dL/da = sum dY * (h2 - g1 - lin) = sum dY * (h2 - out) / (1 - a);  da/dmix = a (1 - a)
                 ops.dot_diff(dY, other, out, acc, scale=a)
             dmix = acc.to(mix.dtype).reshape(mix.shape)
-        return dA, dW, db, dR1, dR2, dmix, None
+        return (dA, dW, db, dR1, dR2, dmix, None) + (None,) * ctx.n_opt
 
 
 class LayerNormFn(torch.autograd.Function):
@@ -750,3 +768,160 @@ def transformer_train_forward(tr, x, ehs, B, F, H, W, time_context_order="sb"):
         h3 = BlendGemm.apply(u, tb.ff.net[2].weight, tb.ff.net[2].bias, g1, h2, tr.time_mixer.mix_factor, GemmSpec())
     del u, n
     return gemm(h3, tr.proj_out.weight, tr.proj_out.bias, x)
+
+
+# =============================================================================== VAE temporal decoder (fine-tuning)
+# tools/train_vae_finetuning.py:303-320 trains every `decoder.*` parameter of AutoencoderKLTemporalDecoder.  The blocks below
+# run the launches of ctrlv_amd/models/vae_decoder_hip.py (`_res`, `_attn`, the tail) -- the same bits forward -- with every
+# op recording its backward.  Rows are ordered (clip, frame, pixel); n_clips clips of F frames run in one walk.
+def vae_res_block_train_forward(block, x, n_clips, F, H, W):
+    """Training-mode forward of the VAE decoder's `SpatioTemporalResBlock` (no time embedding; eps 1e-6 in the spatial half,
+    1e-5 in the temporal one; a 1x1 `conv_shortcut` where cin != cout; blender with switch_spatial_to_temporal_mix:
+    out = xs + sigmoid(mix) * h).  x: bf16 rows [n_clips*F*H*W, cin]."""
+    s, t = block.spatial_res_block, block.temporal_res_block
+    N, S = n_clips * F, H * W
+    cout, cin = s.conv1.weight.shape[:2]
+    g2d = dict(mode=1, conv=(H, W, H, W, 1, 0))
+    g3d = dict(mode=2, temporal=(F, S))
+    eps_s, eps_t = s.norm1.eps, t.norm1.eps
+    gn = GroupNormSiLU.apply
+    if s.conv_shortcut is None:
+        xn, res = gn(x, s.norm1.weight, s.norm1.bias, N, S, 1, eps_s, True, True)
+    else:
+        xn = gn(x, s.norm1.weight, s.norm1.bias, N, S, 1, eps_s, True)
+    h = gemm(xn, s.conv1.weight, s.conv1.bias, **g2d)
+    hn = gn(h, s.norm2.weight, s.norm2.bias, N, S, 1, eps_s, True)
+    if s.conv_shortcut is not None:
+        res = gemm(x, s.conv_shortcut.weight.reshape(cout, cin), s.conv_shortcut.bias)
+    xs = gemm(hn, s.conv2.weight, s.conv2.bias, res, **g2d)
+    hn, xs = gn(xs, t.norm1.weight, t.norm1.bias, N, S, F, eps_t, True, True)
+    h = gemm(hn, t.conv1.weight, t.conv1.bias, **g3d)
+    hn = gn(h, t.norm2.weight, t.norm2.bias, N, S, F, eps_t, True)
+    return BlendGemm.apply(hn, t.conv2.weight, t.conv2.bias, xs, None, block.time_mixer.mix_factor, GemmSpec(**g3d), True)
+
+
+def _rows16(weight):
+    """element-type copy of a [N, K] parameter in its own layout (the A operand of a role-swapped GEMM)"""
+    return _packed(weight, "rows16", lambda w: w.detach().to(torch.bfloat16).contiguous())
+
+
+class VaeAttentionCore(torch.autograd.Function):
+    """softmax(q k^T / sqrt(C)) v per frame for ONE head of dim C (the VAE mid block: C = 512, which the 64-wide attention
+    cores do not serve), v = t @ Wv^T without its bias (the caller folds b_v into the output projection's bias: rows of P
+    sum to one).  Forward = the launches of vae_decoder_hip._attn: scores GEMM with fp32 output and the scale folded in,
+    ctrlv_softmax_rows, V^T = Wv t^T by a role-swapped GEMM, P.V with K = S.  Nothing S x S is kept: the backward runs the
+    first two launches again per frame, then
+        dP = dO V^T (fp32)   dS = ctrlv_softmax_rows_bwd(P, dP)   dQ = dS K        forward GEMMs (weight operand V / K^T)
+        dV = P^T dO          dK = dS^T Q                                           ctrlv_gemm_wgrad (dY = P / dS, A = dO / Q)
+    and the Linear backward of the v projection on dV.  Gradients for q, k, t and Wv."""
+
+    @staticmethod
+    def forward(ctx, q, k, t, wv, n, S):
+        C, dev = q.shape[1], q.device
+        o = _rows(n * S, C, q)
+        scores = torch.empty(S, S, dtype=torch.float32, device=dev)
+        probs = torch.empty(S, S, dtype=torch.bfloat16, device=dev)
+        vt = torch.empty(C, S, dtype=torch.bfloat16, device=dev)
+        wv_rows = _rows16(wv)
+        for f in range(n):
+            r0, r1 = f * S, (f + 1) * S
+            ops.gemm(q[r0:r1], k[r0:r1], scores, N=S, cin=C, s_acc=C ** -0.5, out_f32=True)
+            ops.softmax_rows(scores, probs)
+            ops.gemm(wv_rows, t[r0:r1], vt, N=S, cin=C)
+            ops.gemm(probs, vt, o[r0:r1], N=C, cin=S)
+        ctx.save_for_backward(q, k, t, wv)
+        ctx.cfg = (n, S)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        q, k, t, wv = ctx.saved_tensors
+        n, S = ctx.cfg
+        C, dev, M = q.shape[1], q.device, q.shape[0]
+        scale = C ** -0.5
+        do = do.contiguous()
+        v = _rows(M, C, q)                                                          # V rows of every frame: one GEMM
+        ops.gemm(t, _packed(wv, ("fwd", 0), lambda w: _pack_fwd(w, 0)), v, N=C, cin=C)
+        new = torch.empty if ops.DETERMINISTIC else torch.zeros
+        dq = _rows(M, C, q)
+        dk32 = new(M, C, dtype=torch.float32, device=dev)
+        dv32 = new(M, C, dtype=torch.float32, device=dev)
+        scores = torch.empty(S, S, dtype=torch.float32, device=dev)
+        dp = torch.empty(S, S, dtype=torch.float32, device=dev)
+        probs = torch.empty(S, S, dtype=torch.bfloat16, device=dev)
+        ds = torch.empty(S, S, dtype=torch.bfloat16, device=dev)
+        flat = dict(N=S, cin=C, torch_layout=True, assign=ops.DETERMINISTIC)
+        for f in range(n):
+            r0, r1 = f * S, (f + 1) * S
+            ops.gemm(q[r0:r1], k[r0:r1], scores, N=S, cin=C, s_acc=scale, out_f32=True)
+            ops.softmax_rows(scores, probs)
+            ops.gemm(do[r0:r1], v[r0:r1], dp, N=S, cin=C, out_f32=True)             # dP = dO V^T
+            ops.softmax_rows_bwd(probs, dp, scale, ds)
+            ops.gemm(ds, k[r0:r1].t().contiguous(), dq[r0:r1], N=C, cin=S)          # dQ = dS K  (weight operand K^T [C, S])
+            ops.gemm_wgrad(q[r0:r1], ds, dk32[r0:r1], **flat)                       # dK = dS^T Q
+            ops.gemm_wgrad(do[r0:r1], probs, dv32[r0:r1], **flat)                   # dV = P^T dO
+        need = ctx.needs_input_grad
+        dt, dwv, _ = gemm_grads(t, wv, dv32.to(torch.bfloat16), dict(mode=0), 1.0, need[2], need[3], False)
+        return dq, dk32.to(torch.bfloat16), dt, dwv, None, None
+
+
+class _ExactZeroGrad(torch.autograd.Function):
+    """Identity on a parameter whose gradient is identically zero by the structure of the graph: the backward hands back
+    exact zeros instead of the rounding noise a computed path would leave."""
+
+    @staticmethod
+    def forward(ctx, p):
+        return p.detach().clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        return torch.zeros_like(g)
+
+
+def vae_attention_train_forward(attn, x, n, H, W):
+    """Training-mode forward of the VAE mid block's `Attention` (one head of dim C): GroupNorm (no SiLU) -> q, k -> the core
+    above -> to_out + x, with vae_decoder_hip._attn's launches and its folding of b_v into b_o (P (V + 1 b_v^T) W_o^T =
+    P V W_o^T + W_o b_v; the fold is a differentiable torch op on [C]-sized tensors, so b_v and W_o get its gradient).
+    x: bf16 rows [n*H*W, C].  to_k.bias shifts every score of a row by the same q . b_k, which the softmax removes: its
+    gradient is identically zero, and it is returned as exact zeros (the computed path, the column sum of dK, would leave
+    the rounding noise of the bf16 dS rows, which sum to zero only in exact arithmetic)."""
+    if attn.heads != 1:
+        raise ValueError("the HIP VAE attention is specialised for the SVD VAE's single head")
+    S, C = H * W, x.shape[1]
+    if S % 64 or S > 16384:
+        raise ValueError(f"HIP VAE attention: {H}x{W} latent pixels per frame must be a multiple of 64 and <= 16384")
+    gnm, lin_o = attn.group_norm, attn.to_out[0]
+    t, x = GroupNormSiLU.apply(x, gnm.weight, gnm.bias, n, S, 1, gnm.eps, False, True)
+    q = gemm(t, attn.to_q.weight, attn.to_q.bias)
+    k = gemm(t, attn.to_k.weight, _ExactZeroGrad.apply(attn.to_k.bias))
+    o = VaeAttentionCore.apply(q, k, t, attn.to_v.weight, n, S)
+    bo = lin_o.bias.float() + lin_o.weight.float() @ attn.to_v.bias.float()
+    return gemm(o, lin_o.weight, bo.contiguous(), x)
+
+
+class TimeConvOut(torch.autograd.Function):
+    """`time_conv_out` of the VAE decoder -- Conv3d(C, C, (3,1,1)) over the frames of each clip, C <= 4 -- fused with rows ->
+    NCHW: rows [n_clips*F*HW, ldc] bf16 (conv_out's output) -> (n_clips*F, C, H, W) fp32, one ctrlv_time_conv_rows_to_nchw
+    launch per clip; backward = ctrlv_time_conv_rows_to_nchw_bwd (ordered parameter sums)."""
+
+    @staticmethod
+    def forward(ctx, rows, weight, bias, n_clips, F, H, W):
+        C, HW = weight.shape[0], H * W
+        w32 = weight.detach().float()[:, :, :, 0, 0].contiguous()                  # [o, c, t]
+        b32 = bias.detach().float().contiguous()
+        out = torch.empty(n_clips * F, C, H, W, dtype=torch.float32, device=rows.device)
+        for c in range(n_clips):
+            ops.time_conv_rows_to_nchw(rows[c * F * HW:(c + 1) * F * HW], F, C, HW, w32, b32, out[c * F:(c + 1) * F])
+        ctx.save_for_backward(rows, w32)
+        ctx.cfg = (n_clips, F, C, HW, weight.dtype, bias.dtype, tuple(weight.shape))
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        rows, w32 = ctx.saved_tensors
+        n_clips, F, C, HW, wdt, bdt, wshape = ctx.cfg
+        drows = torch.empty_like(rows)
+        dw = torch.empty(C, C, 3, dtype=torch.float32, device=rows.device)
+        db = torch.empty(C, dtype=torch.float32, device=rows.device)
+        ops.time_conv_rows_to_nchw_bwd(dout.float().contiguous(), rows, n_clips * F, F, C, HW, w32, drows, dw, db)
+        return drows, dw.reshape(wshape).to(wdt), db.to(bdt), None, None, None, None

@@ -64,6 +64,95 @@ __global__ void time_conv_rows_to_nchw_kernel(const el_t* __restrict__ src, int 
   for (int o = 0; o < C; ++o) store_any(dst, dtype, ((long)f * C + o) * HW + p, acc[o]);
 }
 
+// Backward of time_conv_rows_to_nchw_kernel.  One thread per (frame, pixel), grid-stride over at most kTcbBlocks blocks:
+//   drows[f, p, c]  = sum_{t, o} w[o, c, t] * dout[f - t + 1, o, p]      (frames of the SAME clip only: the forward's zero padding)
+//   dw[o, c, t]    += dout[f, o, p] * src[f + t - 1, p, c],   db[o] += dout[f, o, p]
+// The parameter sums stay in registers over the thread's pixels, are reduced over the block (wave shuffles, then a fixed
+// 4-term sum) and written as ONE row of `partials` per block; time_conv_bwd_finish_kernel adds the rows in block order.
+// Grid and order are functions of the shape only: the same bits in every run.  Slots: (o * 4 + c) * 3 + t, 48 + o = db[o].
+constexpr int kTcbBlocks = 256, kTcbSlots = 52, kTcbPitch = 64;
+__global__ __launch_bounds__(256) void time_conv_bwd_kernel(const float* __restrict__ dout, const el_t* __restrict__ src, int lds,
+                                                            int n_frames, int clip, int C, int HW, const float* __restrict__ w,
+                                                            el_t* __restrict__ drows, int ldd, float* __restrict__ partials) {
+  __shared__ float red[4][kTcbSlots];
+  float acc[kTcbSlots];
+#pragma unroll
+  for (int j = 0; j < kTcbSlots; ++j) acc[j] = 0.f;
+  float wr[48];
+#pragma unroll
+  for (int o = 0; o < 4; ++o)
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+      for (int t = 0; t < 3; ++t) wr[(o * 4 + c) * 3 + t] = (o < C && c < C) ? w[(o * C + c) * 3 + t] : 0.f;
+  const long total = (long)n_frames * HW;
+  for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+    const int f = (int)(idx / HW);
+    const long p = idx % HW;
+    const int f0 = f - f % clip, f1 = f0 + clip;             // this frame's clip: [f0, f1)
+    float g[3][4];                                           // dout of frames f + 1, f, f - 1 (tap t reads frame f - t + 1)
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+      const int fo = f - t + 1;
+      const bool in = fo >= f0 && fo < f1;
+#pragma unroll
+      for (int o = 0; o < 4; ++o) g[t][o] = (in && o < C) ? dout[((long)fo * C + o) * HW + p] : 0.f;
+    }
+    float dr[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int t = 0; t < 3; ++t)
+#pragma unroll
+      for (int o = 0; o < 4; ++o)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) dr[c] = __builtin_fmaf(wr[(o * 4 + c) * 3 + t], g[t][o], dr[c]);
+    el_t* d = drows + idx * ldd;
+    if (ldd == 4) {
+      *(uint2*)d = make_uint2(pack_elx2(dr[0], dr[1]), pack_elx2(dr[2], dr[3]));      // (channels >= C: wr is zero there)
+    } else {
+      for (int c = 0; c < ldd; ++c) d[c] = f32_to_el(c < 4 ? dr[c] : 0.f);
+    }
+#pragma unroll
+    for (int o = 0; o < 4; ++o) acc[48 + o] += g[1][o];
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+      const int ff = f + t - 1;
+      if (ff < f0 || ff >= f1) continue;
+      const el_t* s = src + ((long)ff * HW + p) * lds;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        if (c >= C) break;
+        const float x = el_to_f32(s[c]);
+#pragma unroll
+        for (int o = 0; o < 4; ++o) acc[(o * 4 + c) * 3 + t] = __builtin_fmaf(g[1][o], x, acc[(o * 4 + c) * 3 + t]);
+      }
+    }
+  }
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+  for (int j = 0; j < kTcbSlots; ++j) {
+    const float v = wave_sum(acc[j]);
+    if (lane == 0) red[wid][j] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < kTcbSlots)
+    partials[(long)blockIdx.x * kTcbPitch + threadIdx.x] =
+        (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
+
+__global__ void time_conv_bwd_finish_kernel(const float* __restrict__ partials, int nblocks, int C, float* __restrict__ dw,
+                                            float* __restrict__ db) {
+  const int j = threadIdx.x;
+  if (j >= kTcbSlots) return;
+  float s = 0.f;
+  for (int b = 0; b < nblocks; ++b) s += partials[(long)b * kTcbPitch + j];
+  if (j >= 48) {
+    if (j - 48 < C) db[j - 48] = s;
+    return;
+  }
+  const int o = j / 12, c = (j / 3) % 4, t = j % 3;
+  if (o < C && c < C) dw[(o * C + c) * 3 + t] = s;
+}
+
 // tiled transpose for wide tensors (foreign NCHW ControlNet residuals): 64 pixels x 64 channels per block
 __global__ __launch_bounds__(256) void nchw_to_rows_tiled_kernel(const void* __restrict__ src, int dtype, int C,
                                                                  int HW, el_t* __restrict__ dst, int ldc,
@@ -240,6 +329,26 @@ extern "C" int ctrlv_time_conv_rows_to_nchw(const void* src, int ldc, int n_fram
   const long total = (long)n_frames * HW;
   hipLaunchKernelGGL(time_conv_rows_to_nchw_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const el_t*)src, ldc, n_frames, C, HW, weight, bias, dst, dst_dtype);
+  CTRLV_LAUNCH_CHECK();
+  return CTRLV_OK;
+}
+
+extern "C" int ctrlv_time_conv_rows_to_nchw_bwd(const float* dout, const void* src, int ldc_src, int n_frames, int clip_frames,
+                                                int C, int HW, const float* weight, void* drows, int ldc, float* dweight,
+                                                float* dbias, float* scratch, ctrlv_stream_t stream) {
+  CTRLV_CHECK_ARG(dout && src && weight && drows && dweight && dbias && scratch, "time_conv_rows_to_nchw_bwd: null pointer");
+  CTRLV_CHECK_SHAPE(n_frames > 0 && HW > 0 && C > 0 && C <= 4 && C <= ldc_src && C <= ldc && ldc <= 64,
+                    "time_conv_rows_to_nchw_bwd: 1 <= C <= 4 channels, C <= ldc <= 64");
+  CTRLV_CHECK_SHAPE(clip_frames > 0 && n_frames % clip_frames == 0,
+                    "time_conv_rows_to_nchw_bwd: n_frames=%d must be whole clips of clip_frames=%d", n_frames, clip_frames);
+  static_assert(kTcbBlocks * kTcbPitch == CTRLV_TIME_CONV_BWD_SCRATCH_FLOATS, "scratch size of the header");
+  const long total = (long)n_frames * HW;
+  const long want = (total + 255) / 256;
+  const int blocks = (int)(want < kTcbBlocks ? want : kTcbBlocks);
+  hipLaunchKernelGGL(time_conv_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dout, (const el_t*)src, ldc_src,
+                     n_frames, clip_frames, C, HW, weight, (el_t*)drows, ldc, scratch);
+  CTRLV_LAUNCH_CHECK();
+  hipLaunchKernelGGL(time_conv_bwd_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, scratch, blocks, C, dweight, dbias);
   CTRLV_LAUNCH_CHECK();
   return CTRLV_OK;
 }

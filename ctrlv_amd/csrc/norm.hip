@@ -367,6 +367,44 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
   }
 }
 
+// Backward of softmax_rows_kernel for one frame's tile: ds[r, :] = scale * p[r, :] o (dp[r, :] - sum_c p[r, c] dp[r, c]) with the
+// element-type P the forward wrote, fp32 dP (= dO . V^T, a GEMM with fp32 output) and `scale` the factor the scores GEMM
+// folded in (1 / sqrt(C)), so that ds is the gradient of the UNSCALED q k^T.  Same shape as the forward: one workgroup per
+// row, the row in registers between the sum and the write, fp32 row sum (wave shuffles + a fixed 4-term sum: no atomics).
+__global__ __launch_bounds__(256) void softmax_rows_bwd_kernel(const el_t* __restrict__ p, long ldp, const float* __restrict__ dp,
+                                                               long lddp, int cols, float scale, el_t* __restrict__ ds,
+                                                               long ldds) {
+  __shared__ float red[4];
+  const el_t* prow = p + (long)blockIdx.x * ldp;
+  const float* grow = dp + (long)blockIdx.x * lddp;
+  el_t* out = ds + (long)blockIdx.x * ldds;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  float pv[kSmxPer], g[kSmxPer];
+  float sum = 0.f;
+#pragma unroll
+  for (int k = 0; k < kSmxPer; k += 4) {
+    const int c = (k / 4 * 256 + tid) * 4;
+    uint2 q = make_uint2(0, 0);
+    float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (c < cols) { q = *(const uint2*)(prow + c); d = *(const float4*)(grow + c); }
+    pv[k] = el_lo_f32(q.x); pv[k + 1] = el_hi_f32(q.x); pv[k + 2] = el_lo_f32(q.y); pv[k + 3] = el_hi_f32(q.y);
+    g[k] = d.x; g[k + 1] = d.y; g[k + 2] = d.z; g[k + 3] = d.w;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) sum = __builtin_fmaf(pv[k + e], g[k + e], sum);
+  }
+  sum = wave_sum(sum);
+  if (lane == 0) red[wid] = sum;
+  __syncthreads();
+  const float delta = (red[0] + red[1]) + (red[2] + red[3]);
+#pragma unroll
+  for (int k = 0; k < kSmxPer; k += 4) {
+    const int c = (k / 4 * 256 + tid) * 4;
+    if (c < cols)
+      *(uint2*)(out + c) = make_uint2(pack_elx2(scale * pv[k] * (g[k] - delta), scale * pv[k + 1] * (g[k + 1] - delta)),
+                                      pack_elx2(scale * pv[k + 2] * (g[k + 2] - delta), scale * pv[k + 3] * (g[k + 3] - delta)));
+  }
+}
+
 // ---- LayerNorm, several rows per wave (round 4).  ln_kernel above gives one row to a wave: at C = 320 only 40 of its 64
 // lanes hold data and every row pays two 6-step wave reductions -- 76 wave-instructions per row, 4.67 TB/s where the
 // device copies at 5.3 (tools/stream_bench.py).  Here LPR = 8 / 16 / 32 lanes share a row (C = 320 / 640 / 1280: NCH = 5
@@ -458,6 +496,19 @@ extern "C" int ctrlv_softmax_rows(const float* scores, int rows, int cols, long 
                     "softmax_rows: cols=%d must be a multiple of 4, <= %d", cols, kSmxPer * 256);
   hipLaunchKernelGGL(softmax_rows_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, scores, cols, ld_scores,
                      (el_t*)probs, ld_probs);
+  CTRLV_LAUNCH_CHECK();
+  return CTRLV_OK;
+}
+
+extern "C" int ctrlv_softmax_rows_bwd(const void* probs, long ld_probs, const float* dprobs, long ld_dprobs, int rows, int cols,
+                                      float scale, void* dscores, long ld_dscores, ctrlv_stream_t stream) {
+  CTRLV_CHECK_ARG(probs && dprobs && dscores, "softmax_rows_bwd: null pointer");
+  CTRLV_CHECK_SHAPE(rows > 0 && cols > 0 && cols % 4 == 0 && cols <= kSmxPer * 256 && ld_probs % 4 == 0 && ld_dprobs % 4 == 0 &&
+                        ld_dscores % 4 == 0 && ld_probs >= cols && ld_dprobs >= cols && ld_dscores >= cols,
+                    "softmax_rows_bwd: cols=%d must be a multiple of 4, <= %d, pitches multiples of 4 and >= cols", cols,
+                    kSmxPer * 256);
+  hipLaunchKernelGGL(softmax_rows_bwd_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, (const el_t*)probs, ld_probs,
+                     dprobs, ld_dprobs, cols, scale, (el_t*)dscores, ld_dscores);
   CTRLV_LAUNCH_CHECK();
   return CTRLV_OK;
 }

@@ -573,3 +573,32 @@ def softmax_rows(scores, probs):
     check(_L(probs).ctrlv_softmax_rows(_p(scores), scores.shape[0], scores.shape[1], scores.stride(0), _p(probs),
                                          probs.stride(0), _stream()), "ctrlv_softmax_rows")
     return probs
+
+
+def softmax_rows_bwd(probs, dprobs, scale, dscores):
+    """dscores (element type) = scale * probs o (dprobs - rowsum(probs o dprobs)): the backward of `softmax_rows` for scores
+    that carry `scale` (probs: what the forward wrote; dprobs fp32; all 2-D with unit inner stride)."""
+    _need_gpu(probs, "probs")
+    if dprobs.dtype != torch.float32 or probs.shape != dprobs.shape or probs.shape != dscores.shape:
+        raise ValueError("softmax_rows_bwd: probs / dscores in the element type and fp32 dprobs of one shape")
+    check(_L(probs, dscores).ctrlv_softmax_rows_bwd(_p(probs), probs.stride(0), _p(dprobs), dprobs.stride(0), probs.shape[0],
+                                                    probs.shape[1], float(scale), _p(dscores), dscores.stride(0), _stream()),
+          "ctrlv_softmax_rows_bwd")
+    return dscores
+
+
+TIME_CONV_BWD_SCRATCH_FLOATS = 16384       # CTRLV_TIME_CONV_BWD_SCRATCH_FLOATS of include/ctrlv_hip.h
+
+
+def time_conv_rows_to_nchw_bwd(dout, rows, n_frames, clip_frames, C, HW, weight, drows, dweight, dbias):
+    """Backward of `time_conv_rows_to_nchw` over whole clips of `clip_frames`: dout fp32 (n_frames, C, H, W), rows / weight the
+    forward's operands -> drows [n_frames * HW, ldc] (element type, every column written), dweight fp32 [C, C, 3], dbias
+    fp32 [C]; ordered sums (bit-reproducible)."""
+    _need_gpu(rows, "rows")
+    if dout.dtype != torch.float32 or not dout.is_contiguous():
+        raise ValueError("time_conv_rows_to_nchw_bwd: dout must be contiguous fp32 NCHW")
+    scratch = _scratch(rows.device, TIME_CONV_BWD_SCRATCH_FLOATS * 4, "time_conv_bwd", floor=TIME_CONV_BWD_SCRATCH_FLOATS * 4)
+    check(_L(rows, drows).ctrlv_time_conv_rows_to_nchw_bwd(_p(dout), _p(rows), rows.stride(0), n_frames, clip_frames, C, HW,
+                                                           _p(weight), _p(drows), drows.stride(0), _p(dweight), _p(dbias),
+                                                           _p(scratch), _stream()), "ctrlv_time_conv_rows_to_nchw_bwd")
+    return drows

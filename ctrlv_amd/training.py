@@ -1,6 +1,7 @@
 """cfg5: one training step of the ControlNet on the HIP kernels (reference: tools/train_video_controlnet.py:366-488).
 Stage 1 of Ctrl-V (fine-tuning the UNet itself, tools/train_video_diffusion.py:459-541) is `unet_train_step` below: the
-same blocks with the UNet's encoder, mid block and tail trainable as well.
+same blocks with the UNet's encoder, mid block and tail trainable as well.  The third script, the VAE decoder fine-tuning
+(tools/train_vae_finetuning.py:303-320), is `vae_train_step` at the end of this file.
 
     ControlNet forward (trainable, fp32 master parameters, bf16 compute)
     -> frozen UNet forward: encoder + mid on the inference executor (no gradients flow there: the residuals join the skip
@@ -20,8 +21,9 @@ import torch.distributed as dist
 import torch.nn.functional as Fn
 
 from . import ops
-from .autograd import (GroupNormSiLU, f32, gemm, gradient_checkpointing, prefetch_mix_factors, res_block_train_forward,
-                       sinusoid, transformer_train_forward, zero_conv_train_forward)
+from .autograd import (GroupNormSiLU, TimeConvOut, f32, gemm, gradient_checkpointing, prefetch_mix_factors,
+                       res_block_train_forward, sinusoid, transformer_train_forward, vae_attention_train_forward,
+                       vae_res_block_train_forward, zero_conv_train_forward)
 from .models.blocks import TransformerSpatioTemporalModel  # noqa: F401  (documentation anchor)
 
 
@@ -442,3 +444,83 @@ def allreduce_gradients(params, bucket_bytes=25 * 1024 * 1024, group=None):
     for b, inflight in zip(buckets, pending):
         _write_back(b, *inflight, dist.get_world_size(group))
     return len(buckets)
+
+
+# ------------------------------------------------------------------------------------------------- VAE decoder fine-tuning
+def _vae_train_supported(decoder, z, num_frames):
+    """Shapes the training walk takes: what the inference executor takes (vae_decoder_hip.supports) and, since all clips run
+    in ONE walk, every activation of the whole batch below the kernels' 32-bit byte-offset limit."""
+    from .models import vae_decoder_hip as vh
+    if z.dim() != 4 or z.shape[0] % num_frames or not vh.supports(z, num_frames, decoder):
+        return False
+    n, _, h, w = z.shape
+    wide = [max(blk.resnets[0].spatial_res_block.conv1.weight.shape[:2]) for blk in decoder.up_blocks]
+    return all(n * h * w * 4 ** i * c * 2 < vh._LIMIT for i, c in enumerate(wide))
+
+
+def vae_decoder_train_forward(decoder, z, num_frames):
+    """`TemporalDecoder.forward` of the SVD VAE with gradients for every decoder parameter that requires them (the decoder of
+    tools/train_vae_finetuning.py:303-320): conv_in as the im2col GEMM, the mid block (res block, head-dim-512 attention, res
+    block), the up blocks with nearest-x2 fused into the upsampler convs, conv_norm_out + SiLU, conv_out and time_conv_out.
+    The launches are those of models/vae_decoder_hip.decode (same bits forward; all clips of the batch in one walk).
+    z: (n, 4, h, w) latents, n a multiple of num_frames (frames per clip).  Returns (n, 3, 8h, 8w) fp32."""
+    if z.dim() != 4 or z.shape[0] % num_frames:
+        raise ValueError(f"vae_decoder_train_forward: latents {tuple(z.shape)} are not whole clips of num_frames={num_frames}")
+    if not _vae_train_supported(decoder, z, num_frames):
+        raise ValueError(f"vae_decoder_train_forward: {tuple(z.shape)} latents in clips of {num_frames} are not served by the HIP "
+                         "decoder (CUDA latents, h*w a multiple of 64 and <= 16384, every activation below 4 GiB)")
+    n, cz, H, W = z.shape
+    n_clips, F = n // num_frames, num_frames
+    cp = (cz + 7) // 8 * 8
+    kp = (9 * cp + 63) // 64 * 64
+    col = _input_cols([z.detach()], n, H, W, cp, kp, z.device)
+    wi, bi = _input_conv_weight([decoder.conv_in], cp, kp)
+    x = gemm(col, wi, bi)
+    mid = decoder.mid_block
+    x = vae_res_block_train_forward(mid.resnets[0], x, n_clips, F, H, W)
+    for attn, resnet in zip(mid.attentions, mid.resnets[1:]):
+        x = vae_attention_train_forward(attn, x, n, H, W)
+        x = vae_res_block_train_forward(resnet, x, n_clips, F, H, W)
+    for blk in decoder.up_blocks:
+        for resnet in blk.resnets:
+            x = vae_res_block_train_forward(resnet, x, n_clips, F, H, W)
+        if blk.upsamplers is not None:
+            x = _conv(blk.upsamplers[0].conv, x, H, W, 2 * H, 2 * W, 1, 1)
+            H, W = 2 * H, 2 * W
+    gno = decoder.conv_norm_out
+    xn = GroupNormSiLU.apply(x, gno.weight, gno.bias, n, H * W, 1, gno.eps, True)
+    # conv_out has 3 output channels: its rows are stored 4 wide (zero weight row and bias: differentiable torch pads on the
+    # [3, 128, 3, 3] parameter), the width time_conv_out's kernel reads; the GEMM backward pads N further as for the UNet's 4
+    co = decoder.conv_out.weight.shape[0]
+    pad = (co + 3) // 4 * 4 - co
+    y = gemm(xn, Fn.pad(decoder.conv_out.weight, (0, 0, 0, 0, 0, 0, 0, pad)), Fn.pad(decoder.conv_out.bias, (0, pad)),
+             mode=1, conv=(H, W, H, W, 1, 0))
+    return TimeConvOut.apply(y, decoder.time_conv_out.weight, decoder.time_conv_out.bias, n_clips, F, H, W)
+
+
+def vae_train_step(vae, batch, optimizer=None, num_frames=1, sample_posterior=True, generator=None, world_size=1, buckets=None,
+                   accumulate=False, loss_scale=1.0):
+    """One step of the VAE decoder fine-tuning (tools/train_vae_finetuning.py:303-320: `vae(images, sample_posterior=True)`
+    with num_frames=1, clamp(-1, 1), MSE, AdamW on the `decoder.*` parameters).  batch["pixel_values"]: (B, 3, H, W) in
+    [-1, 1], B whole clips of num_frames.  The frozen side -- encoder, quant_conv, the posterior sample -- runs under
+    no_grad on the HIP encoder path; the decoder runs `vae_decoder_train_forward`; clamp and MSE are plain torch on the
+    image-sized fp32 prediction.  Which decoder parameters train is the caller's choice through requires_grad (the
+    reference: all of them); encoder and quant_conv are never touched.  Data parallel / gradient accumulation: as in
+    `train_step` (the reduced model is the decoder).  Returns the detached loss."""
+    px = batch["pixel_values"]
+    if px.dim() != 4 or px.shape[1] != vae.config.in_channels:
+        raise ValueError(f"vae_train_step: pixel_values must be (B, {vae.config.in_channels}, H, W), got {tuple(px.shape)}")
+    B, _, Hp, Wp = px.shape
+    if B % num_frames:
+        raise ValueError(f"vae_train_step: a batch of {B} images is not whole clips of num_frames={num_frames}")
+    probe = torch.empty(B, vae.config.latent_channels, Hp // 8, Wp // 8, dtype=torch.bfloat16, device=px.device)
+    if Hp % 8 or Wp % 8 or not _vae_train_supported(vae.decoder, probe, num_frames):
+        raise ValueError(f"vae_train_step: {B} images of {Hp}x{Wp} in clips of {num_frames} are not served by the HIP decoder "
+                         "(CUDA tensors, H and W multiples of 8, H*W/64 a multiple of 64 and <= 16384, activations below 4 GiB)")
+    with torch.no_grad():
+        dist = vae.encode(px).latent_dist
+        z = dist.sample(generator) if sample_posterior else dist.mode()
+    prefetch_mix_factors(vae.decoder, host_sigmoid=True)       # the step's only device-to-host read
+    pred = vae_decoder_train_forward(vae.decoder, z, num_frames)
+    loss = Fn.mse_loss(pred.clamp(-1.0, 1.0), px.float())
+    return _backward_and_step(vae.decoder, loss, optimizer, world_size, buckets, accumulate, loss_scale)

@@ -41,7 +41,8 @@ enum {
   CTRLV_E_WORKSPACE = -5,  /* caller-supplied workspace smaller than ctrlv_plan_workspace_bytes() */
 };
 
-/* Library ABI version (bumped on any signature change; 21: the LoRA entry points). */
+/* Library ABI version (bumped on any signature change; 21: the LoRA entry points; 22: the two backward kernels of the VAE
+ * decoder's training walk, ctrlv_softmax_rows_bwd and ctrlv_time_conv_rows_to_nchw_bwd). */
 int ctrlv_abi_version(void);
 /* dtype code (1 fp16 / 2 bf16) of the element type this library was built for (see above). */
 int ctrlv_elem_dtype(void);
@@ -244,6 +245,14 @@ int ctrlv_temporal_fused_serves(const ctrlv_temporal_fused_desc* d);
  * pipeline_video_control.py:235,278,346) runs as scores GEMM -> this -> P.V GEMM. */
 int ctrlv_softmax_rows(const float* scores, int rows, int cols, long ld_scores, void* probs, long ld_probs,
                        ctrlv_stream_t stream);
+/* Backward of ctrlv_softmax_rows for one frame's tile (ABI 22; the VAE decoder fine-tuning of
+ * tools/train_vae_finetuning.py:303-320 -- the mid block's attention core trains through GEMMs around this kernel):
+ * dscores[r, :cols] = scale * probs[r, :] o (dprobs[r, :] - sum_c probs[r, c] * dprobs[r, c]).  probs: the element-type P the
+ * forward wrote; dprobs: fp32 (dO . V^T from a GEMM with fp32 output); scale: the factor the scores GEMM folded in
+ * (1 / sqrt(C)), so dscores is the gradient of the unscaled q k^T, in the element type.  The row sum is fp32, one
+ * workgroup per row; cols as in the forward (a multiple of 4, <= 16384), pitches multiples of 4.  No atomics. */
+int ctrlv_softmax_rows_bwd(const void* probs, long ld_probs, const float* dprobs, long ld_dprobs, int rows, int cols,
+                           float scale, void* dscores, long ld_dscores, ctrlv_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Self-attention cores (diffusers AttnProcessor2_0 = F.scaled_dot_product_attention, head_dim 64, no mask).
@@ -288,6 +297,17 @@ int ctrlv_rows_to_nchw(const void* src, int ldc, int n_img, int C, int HW, void*
  * fp32 [C]; dst (n_frames, C, H, W) in dst_dtype. */
 int ctrlv_time_conv_rows_to_nchw(const void* src, int ldc, int n_frames, int C, int HW, const float* weight,
                                  const float* bias, void* dst, int dst_dtype, ctrlv_stream_t stream);
+/* Backward of ctrlv_time_conv_rows_to_nchw (ABI 22; the last op of the decoder in tools/train_vae_finetuning.py:303-320).
+ * dout: fp32 (n_frames, C, H, W) gradient of the forward's output; src / ldc_src / weight: the forward's operands.  The
+ * n_frames frames are whole clips of clip_frames (one forward call each): taps never cross a clip, exactly the forward's
+ * zero padding -- with clip_frames = 1 the outer taps of dweight are exactly zero.  Writes drows [n_frames*HW, ldc] in the
+ * element type (EVERY one of the ldc columns: the padding columns >= C are zero; C <= ldc <= 64), dweight fp32 [C][C][3]
+ * and dbias fp32 [C].  The parameter sums are per-block partials in `scratch` (CTRLV_TIME_CONV_BWD_SCRATCH_FLOATS fp32)
+ * added in block order: no atomics, the same bits in every run. */
+#define CTRLV_TIME_CONV_BWD_SCRATCH_FLOATS 16384
+int ctrlv_time_conv_rows_to_nchw_bwd(const float* dout, const void* src, int ldc_src, int n_frames, int clip_frames, int C,
+                                     int HW, const float* weight, void* drows, int ldc, float* dweight, float* dbias,
+                                     float* scratch, ctrlv_stream_t stream);
 /* im2col for the tiny-channel 3x3 input convs (conv_in, control_conv_in): rows [n_img*H*W, Cp] -> [.., 9*Cp (+pad to Kp)] */
 int ctrlv_im2col3x3(const void* x, int n_img, int H, int W, int Cp, void* col, int Kp, ctrlv_stream_t stream);
 /* y = a*x + b*r  (bf16 rows, n elements) -- the ControlNet residual add of
