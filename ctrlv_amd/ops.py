@@ -447,6 +447,68 @@ def attention_temporal(qkv, out, B, F, S, C):
     return out
 
 
+def attention_tokens(qkv, out, n_img, S, C, head_dim):
+    """Self-attention over the S tokens of each image at any 1 <= S <= 4096 and head_dim 16..128 (a multiple of 16): the CLIP
+    vision tower's core (ctrlv_attention_tokens; qkv [n_img*S, 3C] with q | k | v column blocks, out [n_img*S, C])."""
+    _need_gpu(qkv, "qkv")
+    if qkv.stride(0) != 3 * C or out.stride(0) != C or qkv.stride(1) != 1 or out.stride(1) != 1:
+        raise ValueError("attention_tokens: qkv [rows, 3C] and out [rows, C] must be dense row-major")
+    if qkv.shape[0] < n_img * S or out.shape[0] < n_img * S:
+        raise ValueError(f"attention_tokens: {n_img} x {S} rows do not fit qkv {tuple(qkv.shape)} / out {tuple(out.shape)}")
+    ev = _prof.begin()
+    check(_L(qkv, out).ctrlv_attention_tokens(_p(qkv), _p(out), n_img, S, C, head_dim, _stream()), "ctrlv_attention_tokens")
+    _prof.end(ev, "attention_tokens", 4.0 * n_img * S * S * C, 2.0 * 4 * n_img * S * C)
+    return out
+
+
+def clip_patch_rows(pixels, patch, rows):
+    """pixels: contiguous (n, 3, H, W) fp32 / fp16 / bf16 -> rows [n * (H/patch) * (W/patch), ld] in the element type, columns in
+    (c, dy, dx) order, columns >= 3 patch^2 zero (ctrlv_clip_patch_rows)."""
+    _need_gpu(pixels, "pixels")
+    if pixels.dim() != 4 or pixels.shape[1] != 3 or not pixels.is_contiguous() or pixels.dtype not in _DT:
+        raise ValueError("clip_patch_rows: pixels must be contiguous (n, 3, H, W) in fp32 / fp16 / bf16")
+    n, _, H, W = pixels.shape
+    if patch <= 0 or H % patch or W % patch or rows.shape[0] != n * (H // patch) * (W // patch) or rows.stride(1) != 1:
+        raise ValueError(f"clip_patch_rows: image {H}x{W}, patch {patch}, rows {tuple(rows.shape)}")
+    ev = _prof.begin()
+    check(_L(rows).ctrlv_clip_patch_rows(_p(pixels), _DT[pixels.dtype], n, H, W, patch, _p(rows), rows.stride(0), _stream()),
+          "ctrlv_clip_patch_rows")
+    _prof.end(ev, "clip_patch_rows", 0.0, float(pixels.numel() * pixels.element_size() + rows.numel() * 2))
+    return rows
+
+
+def clip_tokens(patch_out, class_emb, pos_emb, n, out):
+    """out [n * (P + 1), C] = (class_emb + pos_emb[0] | patch_out[p] + pos_emb[p + 1]) per image: fp32 sum, one rounding
+    (ctrlv_clip_tokens).  patch_out [n * P, C] elements; class_emb fp32 [C]; pos_emb fp32 [P + 1, C]."""
+    _need_gpu(patch_out, "patch_out")
+    P, C = pos_emb.shape[0] - 1, pos_emb.shape[1]
+    if (class_emb.dtype != torch.float32 or pos_emb.dtype != torch.float32 or not class_emb.is_contiguous()
+            or not pos_emb.is_contiguous() or not patch_out.is_contiguous() or not out.is_contiguous()
+            or tuple(patch_out.shape) != (n * P, C) or tuple(out.shape) != (n * (P + 1), C) or class_emb.numel() != C):
+        raise ValueError("clip_tokens: dense patch_out [n*P, C], out [n*(P+1), C]; fp32 class_emb [C], pos_emb [P+1, C]")
+    ev = _prof.begin()
+    check(_L(patch_out, out).ctrlv_clip_tokens(_p(patch_out), _p(class_emb), _p(pos_emb), n, P, C, _p(out), _stream()),
+          "ctrlv_clip_tokens")
+    _prof.end(ev, "clip_tokens", 0.0, 2.0 * (patch_out.numel() + out.numel()))
+    return out
+
+
+ACT_KINDS = {"gelu": 0, "quick_gelu": 1}
+
+
+def act_rows(x, kind):
+    """In place on the element rows x [M, N] (any row pitch that is a multiple of 8): "gelu" (erf form) or "quick_gelu"
+    (x sigmoid(1.702 x)); fp32 arithmetic, one rounding (ctrlv_act_rows)."""
+    _need_gpu(x, "x")
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError("act_rows: x must be 2-D with unit column stride")
+    ev = _prof.begin()
+    check(_L(x).ctrlv_act_rows(_p(x), x.shape[0], x.shape[1], x.stride(0), ACT_KINDS[kind] if isinstance(kind, str) else kind,
+                               _stream()), "ctrlv_act_rows")
+    _prof.end(ev, "act_rows", 0.0, 2.0 * 2 * x.shape[0] * x.shape[1])
+    return x
+
+
 def temporal_fused_pack(wqkv_packed, wo_packed):
     """Fragment-major weights of `temporal_fused` from the packed [960, >= 320] q|k|v projection and [320, >= 320] to_out."""
     _need_gpu(wqkv_packed, "wqkv_packed")

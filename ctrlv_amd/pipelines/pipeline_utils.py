@@ -166,12 +166,59 @@ def _load_vae(path, **kw):
 
 
 def _load_image_encoder(path, **kw):
-    from transformers import CLIPVisionModelWithProjection
+    """transformers' CLIPVisionModelWithProjection when transformers is installed, else ctrlv_amd's own module of the same
+    architecture and state-dict layout (models/clip_vision.py).  Either one runs on the HIP kernels where
+    models/clip_vision_hip.supports() holds (`_encode_image`)."""
+    try:
+        from transformers import CLIPVisionModelWithProjection
+    except ImportError:
+        from ..models.clip_vision import CLIPVisionModelWithProjection
     return CLIPVisionModelWithProjection.from_pretrained(path, **kw)
 
 
+class MinimalCLIPImageProcessor:
+    """What the pipelines ask of CLIPImageProcessor, for machines without transformers: `image_mean` / `image_std` of
+    `preprocessor_config.json` and the ONE call `_encode_image` makes -- normalisation of a float tensor batch, every other step
+    off, `return_tensors="pt"`.  Any other request raises (resizing / cropping / rescaling are not implemented here)."""
+
+    def __init__(self, image_mean=(0.48145466, 0.4578275, 0.40821073), image_std=(0.26862954, 0.26130258, 0.27577711), **_):
+        self.image_mean, self.image_std = [float(v) for v in image_mean], [float(v) for v in image_std]
+
+    @classmethod
+    def from_pretrained(cls, path, **_):
+        import json
+        with open(os.path.join(str(path), "preprocessor_config.json")) as f:
+            cfg = json.load(f)
+        return cls(image_mean=cfg["image_mean"], image_std=cfg["image_std"])
+
+    def save_pretrained(self, save_directory, **_):
+        import json
+        os.makedirs(save_directory, exist_ok=True)
+        with open(os.path.join(save_directory, "preprocessor_config.json"), "w") as f:
+            json.dump({"image_processor_type": "CLIPImageProcessor", "image_mean": self.image_mean, "image_std": self.image_std,
+                       "do_normalize": True}, f, indent=2)
+
+    def __call__(self, images=None, do_normalize=None, do_center_crop=None, do_resize=None, do_rescale=None,
+                 return_tensors=None, **other):
+        import types
+        if (other or do_normalize is not True or do_center_crop is not False or do_resize is not False
+                or do_rescale is not False or return_tensors != "pt" or not isinstance(images, torch.Tensor) or images.dim() != 4
+                or images.shape[1] != len(self.image_mean)):
+            raise NotImplementedError(
+                "MinimalCLIPImageProcessor serves only feature_extractor(images=<(n, 3, H, W) tensor>, do_normalize=True, "
+                "do_center_crop=False, do_resize=False, do_rescale=False, return_tensors='pt'); install transformers for the "
+                "full CLIPImageProcessor")
+        x = images.to(torch.float32)
+        mean = torch.tensor(self.image_mean, dtype=torch.float32, device=x.device).view(1, -1, 1, 1)
+        std = torch.tensor(self.image_std, dtype=torch.float32, device=x.device).view(1, -1, 1, 1)
+        return types.SimpleNamespace(pixel_values=(x - mean) / std)
+
+
 def _load_feature_extractor(path, **kw):
-    from transformers import CLIPImageProcessor
+    try:
+        from transformers import CLIPImageProcessor
+    except ImportError:
+        return MinimalCLIPImageProcessor.from_pretrained(path)
     return CLIPImageProcessor.from_pretrained(path)
 
 
@@ -351,7 +398,11 @@ class SVDPipelineBase:
         image = self.feature_extractor(images=image, do_normalize=True, do_center_crop=False, do_resize=False,
                                        do_rescale=False, return_tensors="pt").pixel_values
         image = image.to(device=device, dtype=dtype)
-        image_embeddings = self.image_encoder(image).image_embeds
+        from ..models import clip_vision_hip
+        if clip_vision_hip.enabled() and clip_vision_hip.supports(self.image_encoder, image):
+            image_embeddings = clip_vision_hip.encode(self.image_encoder, image)       # the HIP kernels
+        else:
+            image_embeddings = self.image_encoder(image).image_embeds
         image_embeddings = image_embeddings.unsqueeze(1)
         bs_embed, seq_len, _ = image_embeddings.shape
         image_embeddings = image_embeddings.repeat(1, num_videos_per_prompt, 1)

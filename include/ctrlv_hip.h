@@ -42,7 +42,10 @@ enum {
 };
 
 /* Library ABI version (bumped on any signature change; 21: the LoRA entry points; 22: the two backward kernels of the VAE
- * decoder's training walk, ctrlv_softmax_rows_bwd and ctrlv_time_conv_rows_to_nchw_bwd). */
+ * decoder's training walk, ctrlv_softmax_rows_bwd and ctrlv_time_conv_rows_to_nchw_bwd).  Purely ADDITIVE entry points do not
+ * bump the number: a host built against 22 runs unchanged on a library that also exports the CLIP vision kernels
+ * (ctrlv_attention_tokens, ctrlv_clip_patch_rows, ctrlv_clip_tokens, ctrlv_act_rows), and a host that needs them fails at symbol
+ * lookup on a library without them. */
 int ctrlv_abi_version(void);
 /* dtype code (1 fp16 / 2 bf16) of the element type this library was built for (see above). */
 int ctrlv_elem_dtype(void);
@@ -280,6 +283,30 @@ int ctrlv_attention_spatial_bwd(const void* qkv, const void* out, const void* do
                                 float* delta, int n_img, int S, int C, ctrlv_stream_t stream);
 int ctrlv_attention_temporal_bwd(const void* qkv, const void* out, const void* dout, void* dqkv, int B, int F, int S, int C,
                                  ctrlv_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * CLIP vision tower (csrc/clip.hip): transformers' CLIPVisionModelWithProjection -- the `image_encoder(pixel_values)
+ * .image_embeds` of pipeline_video_control.py:220 and src/ctrlv/utils/util.py:97-125 (ViT-H/14: 257 tokens, 16 heads of 80).
+ * Projections, MLP and patch embedding run on ctrlv_gemm, the norms on ctrlv_layernorm; these four are the rest.
+ * ------------------------------------------------------------------------------------------------------------------ */
+/* Self-attention over the S tokens of each image for ANY 1 <= S <= 4096: qkv [n_img*S, 3C] with q | k | v column blocks (as
+ * ctrlv_attention_spatial), heads = C / head_dim, head_dim a multiple of 16 in [16, 128]; out [n_img*S, C].  softmax(q k^T
+ * head_dim^-0.5) v with the scale applied in fp32, scores and P.V on MFMA with fp32 accumulation, fp32 softmax; the key tail of
+ * the last tile is masked in the kernel, no S x S tensor reaches memory, no atomics.  An image's result does not depend on
+ * n_img.  qkv / out 16-byte aligned. */
+int ctrlv_attention_tokens(const void* qkv, void* out, int n_img, int S, int C, int head_dim, ctrlv_stream_t stream);
+/* NCHW pixels (n, 3, Hpx, Wpx), dtype_code 0 fp32 / 1 fp16 / 2 bf16 -> element rows [n*P, ld], P = (Hpx/patch) (Wpx/patch), one
+ * row per patch in row-major patch order, columns in (c, dy, dx) order (= patch_embedding.weight.flatten(1)); columns
+ * [3 patch^2, ld) are written as zeros (the GEMM wants Cin % 64 == 0: 588 -> 640).  ld a multiple of 8. */
+int ctrlv_clip_patch_rows(const void* pixels, int dtype_code, int n, int Hpx, int Wpx, int patch, void* rows, int ld,
+                          ctrlv_stream_t stream);
+/* Token rows out [n*(P+1), C]: row 0 of an image = class_emb + pos_emb[0], row p + 1 = patch_out[p] + pos_emb[p + 1]; patch_out
+ * [n*P, C] elements, class_emb fp32 [C], pos_emb fp32 [P+1, C]; the sum in fp32, one rounding.  C a multiple of 8. */
+int ctrlv_clip_tokens(const void* patch_out, const float* class_emb, const float* pos_emb, int n, int P, int C, void* out,
+                      ctrlv_stream_t stream);
+/* In place on element rows x [M, ld] (first N columns; N, ld multiples of 8): kind 0 = GELU in the erf form
+ * 0.5 x (1 + erf(x / sqrt 2)), kind 1 = quick-GELU x sigmoid(1.702 x); fp32 arithmetic, one rounding. */
+int ctrlv_act_rows(void* x, int M, int N, int ld, int kind, ctrlv_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Element-wise / layout kernels.

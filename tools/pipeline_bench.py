@@ -3,7 +3,8 @@
 evaluation settings (576x1024, 25 frames, 25 steps, decode_chunk_size 8, tools/eval_video_controlnet.py:79-89): encode the
 conditioning image and the 25 bbox frames (VAE encoder, PyTorch-ROCm), 25 denoising steps (HIP graph), decode (VAE temporal
 decoder on the HIP kernels).  Random-init full-size UNet / ControlNet / VAE, a stand-in CLIP (tests/fakes.py) -- the CLIP
-image encoder is one 224x224 ViT-H forward per clip.  Prints one JSON line."""
+image encoder is one 224x224 ViT-H forward per clip; --real-clip puts a random-init ViT-H/14 (ctrlv_amd's own class, on the HIP
+kernels where CTRLV_CLIP_HIP routes it there) in its place and feeds it a 224x224 tensor.  Prints one JSON line."""
 import json
 import os
 import sys
@@ -25,11 +26,22 @@ def main():
     from tests.fakes import FakeCLIP, fake_feature_extractor
     unet, ctrl = bench.build_models(torch.device(dev), "box2video", 25, torch.bfloat16)
     vae = AutoencoderKLTemporalDecoder().to(dev, torch.bfloat16).eval()
-    clip = FakeCLIP(1024).to(dev, torch.bfloat16)
+    real_clip = "--real-clip" in sys.argv
+    if real_clip:
+        from tools.clip_bench import build_vit_h
+        clip = build_vit_h(torch.bfloat16)
+    else:
+        clip = FakeCLIP(1024).to(dev, torch.bfloat16)
     pipe = StableVideoControlPipeline(vae, clip, unet, ctrl, EulerDiscreteScheduler(), fake_feature_extractor)
     pipe.set_progress_bar_config(disable=True)
     g = torch.Generator().manual_seed(1)
     image = (torch.rand(1, 3, 576, 1024, generator=g) * 2 - 1).to(dev, torch.bfloat16)
+    if real_clip:
+        # the stand-in feature extractor passes tensors through: CLIP sees the conditioning image resized to its 224 x 224, the
+        # VAE the full-size one (what the pipeline's PIL path does with _resize_with_antialiasing)
+        small = torch.nn.functional.interpolate(image.float(), size=(224, 224), mode="bilinear", antialias=True).to(image.dtype)
+        enc = pipe._encode_image
+        pipe._encode_image = lambda im, *a, **k: enc(small, *a, **k)
     cond = (torch.rand(1, 25, 3, 576, 1024, generator=g) * 2 - 1).to(dev)
     times = []
     for rep in range(3):
@@ -44,7 +56,7 @@ def main():
     print(json.dumps({"metric": "clip latency, StableVideoControlPipeline.__call__ 576x1024 x 25 frames x 25 steps",
                       "seconds_per_clip": round(min(times[1:]), 3), "all_runs_s": [round(t, 3) for t in times],
                       "first_call_includes": "HIP-graph capture, MIOpen find (fast mode), weight packing",
-                      "frames": list(fr.shape), "finite": ok, "vae_decode": os.environ.get("CTRLV_VAE_HIP", "1") != "0" and "hip" or "torch"}))
+                      "frames": list(fr.shape), "finite": ok, "clip": "vit_h" if real_clip else "fake", "vae_decode": os.environ.get("CTRLV_VAE_HIP", "1") != "0" and "hip" or "torch"}))
 
 
 if __name__ == "__main__":
