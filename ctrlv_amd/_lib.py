@@ -84,6 +84,25 @@ class TensorDesc(ctypes.Structure):
                 ("numel", ctypes.c_int64)]
 
 
+class GemmTokensDesc(ctypes.Structure):
+    """Mirror of `ctrlv_gemm_tokens_desc`."""
+    _fields_ = [
+        ("A", c_void_p), ("W", c_void_p), ("bias", c_void_p), ("R1", c_void_p), ("out", c_void_p),
+        ("workspace", c_void_p), ("workspace_bytes", c_size_t),
+        ("M", c_int), ("N", c_int), ("K", c_int), ("lda", c_int), ("ldr1", c_int), ("ldo", c_int),
+        ("act", c_int), ("ws_zeroed", c_int),
+    ]
+
+
+class ClipConfig(ctypes.Structure):
+    """Mirror of `ctrlv_clip_config`."""
+    _fields_ = [
+        ("hidden_size", c_int), ("intermediate_size", c_int), ("num_hidden_layers", c_int), ("num_attention_heads", c_int),
+        ("image_size", c_int), ("patch_size", c_int), ("projection_dim", c_int), ("hidden_act", c_int),
+        ("layer_norm_eps", c_float),
+    ]
+
+
 # name -> (restype, argtypes); lists every symbol include/ctrlv_hip.h declares (tests/test_abi.py checks this)
 SIGNATURES = {
     "ctrlv_abi_version": (c_int, []),
@@ -137,6 +156,9 @@ SIGNATURES = {
     "ctrlv_clip_patch_rows": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "ctrlv_clip_tokens": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "ctrlv_act_rows": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "ctrlv_gemm_tokens": (c_int, [ctypes.POINTER(GemmTokensDesc), c_void_p]),
+    "ctrlv_gemm_tokens_plan": (c_int, [c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "ctrlv_gemm_tokens_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "ctrlv_nchw_to_rows": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     "ctrlv_rows_to_nchw": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "ctrlv_time_conv_rows_to_nchw": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
@@ -189,6 +211,11 @@ SIGNATURES = {
     "ctrlv_plan_destroy": (c_int, [c_void_p]),
     "ctrlv_plan_profile": (c_int, [c_void_p, c_int]),
     "ctrlv_plan_profile_read": (c_int, [c_void_p, ctypes.POINTER(ProfileRecord), c_int]),
+    "ctrlv_clip_plan_create": (c_int, [ctypes.POINTER(ClipConfig), c_int, ctypes.POINTER(c_void_p)]),
+    "ctrlv_clip_plan_load_weights": (c_int, [c_void_p, ctypes.POINTER(TensorDesc), c_size_t]),
+    "ctrlv_clip_plan_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "ctrlv_clip_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ctrlv_clip_plan_destroy": (c_int, [c_void_p]),
 }
 
 _libs = {}                # element dtype code (2 bf16 / 1 fp16) -> CDLL
@@ -196,7 +223,9 @@ _tls = threading.local()  # .failed = the library whose call returned a negative
 # c_int-returning entry points whose value is NOT a status code
 _NO_STATUS = {"ctrlv_abi_version", "ctrlv_elem_dtype", "ctrlv_build_id", "ctrlv_last_error", "ctrlv_ff_fused_w1f_bytes",
               "ctrlv_gemm_gn_partials_serves", "ctrlv_ff_fused_serves", "ctrlv_plan_num_down_residuals",
-              "ctrlv_temporal_fused_serves"}
+              "ctrlv_temporal_fused_serves",
+              # size queries (size_t: never wrapped, listed with their kin for the reader)
+              "ctrlv_gemm_tokens_ws_bytes", "ctrlv_clip_plan_workspace_bytes"}
 
 
 def _status_recorder(lib, fn):

@@ -357,6 +357,9 @@ void ctrlv_set_error(const char* fmt, ...);
 #define CTRLV_MAX_DEVICES 64
 int ctrlv_current_device();   // hipGetDevice clamped to [0, CTRLV_MAX_DEVICES)
 int ctrlv_num_cu(int dev);    // cached hipDeviceAttributeMultiprocessorCount
+// bytes of the counter block at the head of a ctrlv_gemm_tokens workspace for (M, N, K); 0 when the shape is not sliced
+// (csrc/gemm_tokens.hip; the CLIP plan clears exactly this much once per forward)
+size_t ctrlv_gemm_tokens_counter_bytes(int M, int N, int K);
 #define CTRLV_CHECK_ARG(cond, ...)                  \
   do {                                              \
     if (!(cond)) {                                  \

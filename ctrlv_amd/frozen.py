@@ -10,6 +10,7 @@ _CACHE = {}          # (ids of the sources, kind) -> (weakrefs of the sources, t
 
 def clear():
     _CACHE.clear()
+    _MODULES.clear()
 
 
 def _stamp(p):
@@ -37,4 +38,21 @@ def frozen(sources, kind, build, derived=False):
     def drop(_ref, key=key):
         _CACHE.pop(key, None)
     _CACHE[key] = (tuple(weakref.ref(p, drop) for p in sources), stamps, value)
+    return value
+
+
+_MODULES = weakref.WeakKeyDictionary()      # module -> {kind: (stamps of its parameters, value)}
+
+
+def frozen_module(module, kind, build):
+    """`build()`, cached per MODULE while every parameter of it keeps its version, storage and dtype -- whether or not the
+    parameters require grad: for values that are used without a gradient path only (an inference plan of the whole module),
+    where an optimizer step, an in-place edit, `.to()` or `load_state_dict` must rebuild and nothing else may."""
+    stamps = tuple(_stamp(p) for p in module.parameters())
+    kinds = _MODULES.setdefault(module, {})
+    hit = kinds.get(kind)
+    if hit is not None and hit[0] == stamps:
+        return hit[1]
+    value = build()
+    kinds[kind] = (stamps, value)
     return value

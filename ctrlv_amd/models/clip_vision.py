@@ -5,7 +5,7 @@ loops (`encode_video_image`, src/ctrlv/utils/util.py:97-125).
 Parameters are registered under transformers' state-dict keys (`vision_model.embeddings.class_embedding`,
 `vision_model.pre_layrnorm.weight` -- transformers' spelling --, `vision_model.encoder.layers.N.self_attn.q_proj.weight`, ...,
 `visual_projection.weight`), in transformers' order, so `image_encoder/model.safetensors` loads by name.  `forward` runs the
-HIP executor (clip_vision_hip.py) where it is switched on (CTRLV_CLIP_HIP=1: opt-in, see there) and serves the call, and the
+HIP executor (clip_vision_hip.py) where it is switched on (CTRLV_CLIP_HIP=1, or =plan for the one-call C plan: opt-in, see there) and serves the call, and the
 plain torch forward below otherwise: that one is the CPU path and the checker."""
 import json
 import os
@@ -129,8 +129,10 @@ class CLIPVisionModelWithProjection(HipModelMixin):
 
     def forward(self, pixel_values):
         from . import clip_vision_hip
-        if clip_vision_hip.enabled() and clip_vision_hip.supports(self, pixel_values):
-            embeds, hidden = clip_vision_hip.encode(self, pixel_values, return_hidden=True)
+        r = clip_vision_hip.route(self, pixel_values)
+        if r != "torch":
+            run = clip_vision_hip.encode_plan if r == "plan" else clip_vision_hip.encode
+            embeds, hidden = run(self, pixel_values, return_hidden=True)
             return types.SimpleNamespace(image_embeds=embeds, last_hidden_state=hidden)
         return self.torch_forward(pixel_values)
 

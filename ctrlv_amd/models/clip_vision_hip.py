@@ -10,24 +10,37 @@ ctrlv_amd's own class alike -- everything is reached by attribute name) are exec
                 layernorm -> gemm (fc1) -> act_rows -> gemm (fc2, +residual)
     class rows -> layernorm (post_layernorm) -> gemm (visual_projection)
 
-8 launches per layer.  The residual trunk stays in the element type (the 16-bit torch module's own storage); out_proj / fc2 add
+8 launches per layer.  `encode_plan` is the same walk as ONE C call (csrc/clip_plan.hip: ctrlv_clip_forward) with fc1 and the
+activation in one launch -- 7 per layer.  The residual trunk stays in the element type (the 16-bit torch module's own storage); out_proj / fc2 add
 the residual in the GEMM epilogue (fp32, one rounding)."""
 import os
 
 import torch
 
 from .. import ops, packing
-from ..frozen import frozen
+from ..frozen import frozen, frozen_module
 
 # The HIP route is the default only where it was measured no slower than the module's torch forward at batch 1 in both
 # element types (tools/clip_bench.py).  It was not (profiles/clip_encode_bench.jsonl, one MI355X: 8.1 ms against 6.2 ms in bf16,
 # 8.1 against 6.1 in fp16; DESIGN.md 3.12), so the route is OPT-IN: CTRLV_CLIP_HIP=1 selects it, unset / 0 = torch forward.
+# The one-call plan (CTRLV_CLIP_HIP=plan, encode_plan) meets that rule in bf16 (6.50 against 6.70 ms) and misses it in fp16 (6.35
+# against 6.24), and is the slowest route at 8 images (13.2 ms): opt-in as well.
 DEFAULT_ON = False
 
 
 def enabled():
     v = os.environ.get("CTRLV_CLIP_HIP")
     return DEFAULT_ON if v is None else v != "0"
+
+
+def route(model=None, pixel_values=None):
+    """Which forward serves a call: "torch", "ops" (the per-op executor `encode`: CTRLV_CLIP_HIP=1) or "plan" (`encode_plan`,
+    one C call: CTRLV_CLIP_HIP=plan).  With a module and an input, a HIP route is named only where `supports()` holds."""
+    if not enabled():
+        return "torch"
+    if model is not None and not supports(model, pixel_values):
+        return "torch"
+    return "plan" if os.environ.get("CTRLV_CLIP_HIP") == "plan" else "ops"
 
 
 def _parts(model):
@@ -182,3 +195,44 @@ def encode(model, pixel_values, return_hidden=False):
     embeds = rows(n, wp.shape[0])
     ops.gemm(pn, _lin(wp), embeds, N=wp.shape[0], cin=C)
     return (embeds, hidden) if return_hidden else embeds
+
+
+def plan_launches(num_layers):
+    """Kernels of one `encode_plan` call (plus one memset node and one strided copy node)."""
+    return 4 + 7 * num_layers + 2
+
+
+def _plan(model):
+    """The module's ClipPlan, kept while every parameter keeps its version, storage and dtype (frozen.frozen_module: the plan
+    has no gradient path, so a module whose parameters require grad is cached as well -- rebuilding it is 1.3 GB of packing)."""
+    from ..plan import ClipPlan
+
+    def build():
+        vm, emb, layers = _parts(model)
+        w = emb.patch_embedding.weight
+        ln = vm.pre_layrnorm
+        cfg = dict(hidden_size=w.shape[0], intermediate_size=layers[0].mlp.fc1.weight.shape[0], num_hidden_layers=len(layers),
+                   num_attention_heads=_heads(model, layers[0]), patch_size=w.shape[2],
+                   image_size=int(round((emb.position_embedding.weight.shape[0] - 1) ** 0.5)) * w.shape[2],
+                   projection_dim=model.visual_projection.weight.shape[0], hidden_act=_cfg(model, "hidden_act"),
+                   layer_norm_eps=ln.eps)
+        plan = ClipPlan(cfg, w.device, w.dtype)
+        plan.load_state_dict({k: v for k, v in model.state_dict().items() if not k.endswith("position_ids")})
+        return plan
+    return frozen_module(model, "clip_plan", build)
+
+
+@torch.no_grad()
+def encode_plan(model, pixel_values, return_hidden=False):
+    """`encode` through the C plan: one ctrlv_clip_forward call on the module's cached ClipPlan (same gate, same outputs)."""
+    if not supports(model, pixel_values):
+        raise ValueError("HIP CLIP encode: unsupported module / input (see clip_vision_hip.supports)")
+    eps = {l.eps for l in _norms(model)}
+    if len(eps) != 1:
+        raise ValueError("HIP CLIP encode_plan: the plan takes ONE layer_norm_eps")
+    return _plan(model).forward(pixel_values, return_hidden=return_hidden)
+
+
+def _norms(model):
+    vm, _, layers = _parts(model)
+    return [vm.pre_layrnorm, vm.post_layernorm] + [n for l in layers for n in (l.layer_norm1, l.layer_norm2)]

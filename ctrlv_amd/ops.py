@@ -509,6 +509,50 @@ def act_rows(x, kind):
     return x
 
 
+TOKEN_ACTS = {None: 0, "none": 0, "gelu": 1, "quick_gelu": 2}
+
+
+def gemm_tokens_plan(N, K, dtype=None):
+    """(bn, slices) of ctrlv_gemm_tokens for a weight [N, K]: a function of (N, K) only."""
+    bn, sl = ctypes.c_int32(), ctypes.c_int32()
+    check(_lib.load(dtype).ctrlv_gemm_tokens_plan(N, K, ctypes.byref(bn), ctypes.byref(sl)), "ctrlv_gemm_tokens_plan")
+    return bn.value, sl.value
+
+
+def gemm_tokens(A, W, out, *, N, K, bias=None, R1=None, act=None, M=None, workspace=None, ws_zeroed=False):
+    """out[m, n] = act(sum_k A[m, k] W[n, k] + bias[n]) + R1[m, n] for a few hundred rows (ctrlv_gemm_tokens): W elements
+    [N, K] as packing.pack_linear makes them, bias fp32, act None / "gelu" (erf form) / "quick_gelu" evaluated in fp32 before the
+    one rounding.  K slices are combined inside the launch through `workspace` (a uint8 tensor of at least
+    ctrlv_gemm_tokens_ws_bytes; default: this stream's scratch).  ws_zeroed: the caller vouches that the counter words at the
+    head of `workspace` are zero -- they are after every call of the same (N, K) into it -- and no memset is enqueued."""
+    _need_gpu(A, "A")
+    if W.dim() != 2 or W.stride(1) != 1 or W.stride(0) != K or W.shape[0] < N:
+        raise ValueError(f"gemm_tokens: W must be dense [>= N, K] rows (got {tuple(W.shape)}, strides {tuple(W.stride())}; N={N}, K={K})")
+    if ws_zeroed and workspace is None:
+        raise ValueError("gemm_tokens: ws_zeroed needs the caller's own workspace")
+    lib = _L(A, W, out, R1)
+    d = _lib.GemmTokensDesc()
+    d.A, d.W, d.bias, d.R1, d.out = _p(A), _p(W), _p(bias), _p(R1), _p(out)
+    d.M = out.shape[0] if M is None else M
+    d.N, d.K = N, K
+    d.lda, d.ldo = A.stride(0), out.stride(0)
+    d.ldr1 = R1.stride(0) if R1 is not None else 0
+    d.act = TOKEN_ACTS[act] if (act is None or isinstance(act, str)) else act
+    d.ws_zeroed = 1 if ws_zeroed else 0
+    if workspace is None and d.M >= 1 and N > 0 and K > 0 and N % 32 == 0 and K % 64 == 0:
+        need = lib.ctrlv_gemm_tokens_ws_bytes(d.M, N, K)
+        if need:
+            workspace = _scratch(A.device, need, "gemm_tokens", floor=16 << 20)
+    if workspace is not None:
+        d.workspace, d.workspace_bytes = _p(workspace), workspace.numel() * workspace.element_size()
+    ev = _prof.begin()
+    check(lib.ctrlv_gemm_tokens(ctypes.byref(d), _stream()), "ctrlv_gemm_tokens")
+    if ev is not None:
+        nbytes = 2.0 * (d.M * K + N * K + d.M * N * (2 if R1 is not None else 1))
+        _prof.end(ev, "gemm_linear", 2.0 * d.M * N * K, nbytes, detail=("gemm_tokens", d.M, N, K, 0, int(R1 is not None), 0, d.act))
+    return out
+
+
 def temporal_fused_pack(wqkv_packed, wo_packed):
     """Fragment-major weights of `temporal_fused` from the packed [960, >= 320] q|k|v projection and [320, >= 320] to_out."""
     _need_gpu(wqkv_packed, "wqkv_packed")

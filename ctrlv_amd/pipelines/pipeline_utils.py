@@ -399,7 +399,10 @@ class SVDPipelineBase:
                                        do_rescale=False, return_tensors="pt").pixel_values
         image = image.to(device=device, dtype=dtype)
         from ..models import clip_vision_hip
-        if clip_vision_hip.enabled() and clip_vision_hip.supports(self.image_encoder, image):
+        r = clip_vision_hip.route(self.image_encoder, image)
+        if r == "plan":
+            image_embeddings = clip_vision_hip.encode_plan(self.image_encoder, image)  # one C call
+        elif r == "ops":
             image_embeddings = clip_vision_hip.encode(self.image_encoder, image)       # the HIP kernels
         else:
             image_embeddings = self.image_encoder(image).image_embeds

@@ -183,3 +183,94 @@ class Plan:
             self._h, sample.data_ptr(), control.data_ptr(), _DT[sample.dtype], t32.data_ptr(), t32.numel(),
             ehs.data_ptr(), ids32.data_ptr(), ids32.shape[1], float(scale), outs, out_mid.data_ptr(), B, F, H, W,
             ws.data_ptr(), ws.numel(), self._stream()), "ctrlv_controlnet_forward")
+
+
+CLIP_ACTS = {"gelu": 0, "quick_gelu": 1}
+
+
+class ClipPlan:
+    """Owns one `ctrlv_clip_plan`: the CLIP vision tower (transformers' CLIPVisionModelWithProjection) as one C call --
+    create, `load_state_dict` (transformers' keys), workspace, `forward` (include/ctrlv_hip.h)."""
+
+    def __init__(self, config, device, dtype=torch.bfloat16):
+        """config: transformers' CLIPVisionConfig fields (a dict); dtype: the element type, as for `Plan`."""
+        self.device = torch.device(device)
+        self.dtype = dtype
+        self._lib = _lib.load(dtype)
+        self._h = ctypes.c_void_p()
+        act = config["hidden_act"]
+        if act not in CLIP_ACTS:
+            raise ValueError(f"ClipPlan: hidden_act {act!r} (gelu or quick_gelu)")
+        c = self._cfg = _lib.ClipConfig()
+        for k in ("hidden_size", "intermediate_size", "num_hidden_layers", "num_attention_heads", "image_size", "patch_size",
+                  "projection_dim"):
+            setattr(c, k, int(config[k]))
+        c.hidden_act = CLIP_ACTS[act]
+        c.layer_norm_eps = float(config.get("layer_norm_eps", 1e-5))
+        check(self._lib.ctrlv_clip_plan_create(ctypes.byref(c), self.device.index or 0, ctypes.byref(self._h)),
+              "ctrlv_clip_plan_create")
+        self.tokens = (c.image_size // c.patch_size) ** 2 + 1
+        self._ws = {}            # stream -> uint8 workspace tensor
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                self._lib.ctrlv_clip_plan_destroy(h)
+            except Exception:       # noqa: BLE001  (interpreter shutdown)
+                pass
+
+    def load_state_dict(self, state_dict):
+        """Hand every parameter to the library by its transformers key; packing happens on the device in C++."""
+        items = [(k, v.detach()) for k, v in state_dict.items() if torch.is_tensor(v) and v.is_floating_point()]
+        keep = []
+        arr = (TensorDesc * len(items))()
+        for i, (k, v) in enumerate(items):
+            if v.dtype not in _DT:
+                v = v.float()
+            v = v.contiguous()
+            keep.append(v)
+            arr[i].name = k.encode()
+            arr[i].data = v.data_ptr()
+            arr[i].dtype = _DT[v.dtype]
+            arr[i].on_device = 1 if v.is_cuda else 0
+            arr[i].numel = v.numel()
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        check(self._lib.ctrlv_clip_plan_load_weights(self._h, arr, len(items)), "ctrlv_clip_plan_load_weights")
+        del keep
+
+    def workspace_bytes(self, n_img):
+        n = self._lib.ctrlv_clip_plan_workspace_bytes(self._h, n_img)
+        if n == 0:
+            check(-2, "ctrlv_clip_plan_workspace_bytes", lib=self._lib)
+        return n
+
+    def workspace(self, n_img):
+        need = self.workspace_bytes(n_img)
+        key = torch.cuda.current_stream(self.device).cuda_stream
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < need:
+            ws = self._ws[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return ws
+
+    def forward(self, pixel_values, return_hidden=False, workspace=None):
+        """image_embeds [n, projection_dim] (and last_hidden_state [n, tokens, hidden]) in the plan's element type, enqueued on
+        torch's current stream."""
+        if pixel_values.dim() != 4 or pixel_values.dtype not in _DT or not pixel_values.is_cuda:
+            raise ValueError("ClipPlan.forward: pixel_values must be a (n, 3, H, W) fp32 / fp16 / bf16 tensor on the HIP device")
+        if pixel_values.device != self.device and (pixel_values.device.index or 0) != (self.device.index or 0):
+            raise ValueError(f"ClipPlan.forward: pixel_values on {pixel_values.device}, the plan's weights on {self.device}")
+        c = self._cfg
+        if tuple(pixel_values.shape[1:]) != (3, c.image_size, c.image_size):
+            raise ValueError(f"ClipPlan.forward: pixel_values {tuple(pixel_values.shape)}, the plan is for 3 x {c.image_size}^2")
+        px = pixel_values.contiguous()
+        n = px.shape[0]
+        ws = self.workspace(n) if workspace is None else workspace
+        embeds = torch.empty(n, c.projection_dim, dtype=self.dtype, device=self.device)
+        hidden = torch.empty(n, self.tokens, c.hidden_size, dtype=self.dtype, device=self.device) if return_hidden else None
+        st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        check(self._lib.ctrlv_clip_forward(self._h, px.data_ptr(), _DT[px.dtype], n, embeds.data_ptr(),
+                                           hidden.data_ptr() if return_hidden else None, ws.data_ptr(), ws.numel(), st),
+              "ctrlv_clip_forward")
+        return (embeds, hidden) if return_hidden else embeds

@@ -44,8 +44,8 @@ enum {
 /* Library ABI version (bumped on any signature change; 21: the LoRA entry points; 22: the two backward kernels of the VAE
  * decoder's training walk, ctrlv_softmax_rows_bwd and ctrlv_time_conv_rows_to_nchw_bwd).  Purely ADDITIVE entry points do not
  * bump the number: a host built against 22 runs unchanged on a library that also exports the CLIP vision kernels
- * (ctrlv_attention_tokens, ctrlv_clip_patch_rows, ctrlv_clip_tokens, ctrlv_act_rows), and a host that needs them fails at symbol
- * lookup on a library without them. */
+ * (ctrlv_attention_tokens, ctrlv_clip_patch_rows, ctrlv_clip_tokens, ctrlv_act_rows) or ctrlv_gemm_tokens and the CLIP plan
+ * (ctrlv_clip_*), and a host that needs them fails at symbol lookup on a library without them. */
 int ctrlv_abi_version(void);
 /* dtype code (1 fp16 / 2 bf16) of the element type this library was built for (see above). */
 int ctrlv_elem_dtype(void);
@@ -307,6 +307,43 @@ int ctrlv_clip_tokens(const void* patch_out, const float* class_emb, const float
 /* In place on element rows x [M, ld] (first N columns; N, ld multiples of 8): kind 0 = GELU in the erf form
  * 0.5 x (1 + erf(x / sqrt 2)), kind 1 = quick-GELU x sigmoid(1.702 x); fp32 arithmetic, one rounding. */
 int ctrlv_act_rows(void* x, int M, int N, int ld, int kind, ctrlv_stream_t stream);
+
+/* GEMM for a few hundred rows (csrc/gemm_tokens.hip): the tower's projections at batch 1 -- 257 token rows against 1280 -> 3840,
+ * 1280 -> 1280, 1280 -> 5120, 5120 -> 1280 -- are weight streaming, and ctrlv_gemm's 256-row tiles put 8-40 workgroups on 256 CUs.
+ *     out[m, n] = act( sum_k A[m, k] W[n, k] + bias[n] ) + R1[m, n]
+ * A, R1, out: element rows (lda / ldr1 / ldo multiples of 8, 16-byte aligned bases); W: elements [N][K], K contiguous -- what
+ * packing.pack_linear / pack_qkv and ctrlv_pack_weight produce; bias fp32 [N] (16-byte aligned) or NULL; R1 optional.
+ * act: 0 none, 1 erf-GELU, 2 quick-GELU -- ctrlv_act_rows' formulas (erff, not the GEGLU polynomial) in fp32 on accumulator +
+ * bias; the output is rounded ONCE (fc1 + ctrlv_act_rows as one launch).  K % 64 == 0, N % 32 == 0, any M >= 1.  fp32 accumulation
+ * on MFMA; rows >= M and columns >= N are never written.
+ * DECOMPOSITION: a workgroup owns a column tile of bn weight rows for a block of 288 activation rows and one of `slices` K
+ * slices; (bn, slices) are a function of (N, K) only (ctrlv_gemm_tokens_plan) -- never of M, the device or the environment: a
+ * row has the same bits alone and in any batch.  With slices > 1 the fp32 partial sums go to `workspace`
+ * (ctrlv_gemm_tokens_ws_bytes(M, N, K) bytes, 16-byte aligned; 0 when slices == 1) and are combined INSIDE the launch by the
+ * workgroup of each tile that arrives last (agent-scope release / counter / acquire, slabs read past the L1): summed in
+ * slice-index order, no float atomics, no second launch, no waiting.  The workspace starts with one counter word per tile;
+ * the call clears them on the stream (a captured memset node) unless ws_zeroed, and leaves them zero. */
+typedef struct ctrlv_gemm_tokens_desc {
+  const void* A;            /* elements [M][lda] */
+  const void* W;            /* elements [N][K] */
+  const float* bias;        /* fp32 [N] or NULL */
+  const void* R1;           /* elements [M][ldr1] or NULL */
+  void* out;                /* elements [M][ldo] */
+  void* workspace;          /* ctrlv_gemm_tokens_ws_bytes(M, N, K) bytes; may be NULL when that is 0 */
+  size_t workspace_bytes;
+  int32_t M, N, K;
+  int32_t lda, ldr1, ldo;
+  int32_t act;              /* 0 none, 1 erf-GELU, 2 quick-GELU */
+  int32_t ws_zeroed;        /* 1: the caller vouches that the workspace's counter words are zero (they are after every call):
+                               no memset is enqueued.  Only for a workspace that serves ONE (N, K): the counter block is sized
+                               by the shape, and another shape's slabs would overwrite it */
+} ctrlv_gemm_tokens_desc;
+int ctrlv_gemm_tokens(const ctrlv_gemm_tokens_desc* d, ctrlv_stream_t stream);
+/* The launch plan of (N, K): bn = weight rows per column tile (64 or 32), slices = K slices (1 whenever K / 64 < 8). */
+int ctrlv_gemm_tokens_plan(int N, int K, int* bn, int* slices);
+/* counter words (one per row block x column tile, rounded up to 256 bytes) + slices x row blocks x 288 x N fp32; 0 when the
+ * shape is not sliced (or invalid: see ctrlv_last_error). */
+size_t ctrlv_gemm_tokens_ws_bytes(int M, int N, int K);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Element-wise / layout kernels.
@@ -575,6 +612,43 @@ typedef struct ctrlv_profile_record {
 } ctrlv_profile_record;
 int ctrlv_plan_profile(ctrlv_plan* plan, int enable);
 int ctrlv_plan_profile_read(ctrlv_plan* plan, ctrlv_profile_record* out, int max_records);
+
+/* ==================================================================================================================
+ * CLIP vision tower as ONE call (csrc/clip_plan.hip): transformers' CLIPVisionModelWithProjection.forward -- the
+ * `image_encoder(pixel_values).image_embeds` of pipeline_video_control.py:220 -- for a host in any language:
+ *     ctrlv_clip_plan_create -> ctrlv_clip_plan_load_weights -> ctrlv_clip_plan_workspace_bytes -> ctrlv_clip_forward.
+ * Same contract as the plan above: create validates on the host and needs no GPU; packed weights are library-owned; a forward
+ * allocates nothing, never synchronises the host and enqueues only on the caller's stream, as ONE chain (HIP-graph capturable,
+ * no parallel branch).
+ * The walk:  clip_patch_rows -> GEMM -> clip_tokens -> layernorm (pre_layrnorm);  per layer: layernorm -> q|k|v GEMM ->
+ * attention_tokens -> out_proj GEMM + residual -> layernorm -> fc1 GEMM with the activation in its epilogue -> fc2 GEMM +
+ * residual;  class rows -> layernorm (post_layernorm) -> projection GEMM:  4 + 7 L + 2 kernels (230 for ViT-H), plus one memset
+ * node per sliced weight shape (the K-slice counters of ctrlv_gemm_tokens; 2 for ViT-H) and one strided copy node (the class rows).  Which GEMM serves a layer is a
+ * table keyed on (N, K) only (csrc/clip_plan.hip): an image has the same bits alone and in any batch.
+ * ================================================================================================================== */
+typedef struct ctrlv_clip_config {
+  int32_t hidden_size, intermediate_size, num_hidden_layers, num_attention_heads;
+  int32_t image_size, patch_size, projection_dim;
+  int32_t hidden_act;           /* 0 gelu (erf form), 1 quick_gelu */
+  float layer_norm_eps;
+} ctrlv_clip_config;
+typedef struct ctrlv_clip_plan ctrlv_clip_plan;
+/* Size rules (clip_vision_hip.supports): hidden and intermediate sizes multiples of 64, hidden <= 2048, projection a multiple
+ * of 32, head_dim = hidden / heads a multiple of 16 in [16, 128], image a whole number of patches, at most 4096 tokens. */
+int ctrlv_clip_plan_create(const ctrlv_clip_config* cfg, int device, ctrlv_clip_plan** out);
+/* transformers' state-dict keys: vision_model.embeddings.{class_embedding, patch_embedding.weight, position_embedding.weight},
+ * vision_model.pre_layrnorm.*, vision_model.encoder.layers.N.{layer_norm1, layer_norm2, self_attn.{q,k,v,out}_proj, mlp.fc1,
+ * mlp.fc2}.{weight, bias}, vision_model.post_layernorm.*, visual_projection.weight.  Host or device tensors, fp32 or 16-bit;
+ * extra names are ignored, a missing one is an error.  q|k|v become one weight.  May be called again; synchronises the device. */
+int ctrlv_clip_plan_load_weights(ctrlv_clip_plan* plan, const ctrlv_tensor_desc* tensors, size_t n);
+/* Bytes of workspace a forward of n_img images needs; 0 on error ("not loaded" before load_weights: ctrlv_last_error). */
+size_t ctrlv_clip_plan_workspace_bytes(ctrlv_clip_plan* plan, int n_img);
+/* pixel_values (n_img, 3, image_size, image_size) contiguous, dtype 0 / 1 / 2; image_embeds [n_img, projection_dim] and
+ * last_hidden_state [n_img, tokens, hidden_size] (the encoder output before post_layernorm; or NULL) in the element type.
+ * workspace 256-byte aligned. */
+int ctrlv_clip_forward(ctrlv_clip_plan* plan, const void* pixel_values, int dtype, int n_img, void* image_embeds,
+                       void* last_hidden_state, void* workspace, size_t workspace_bytes, ctrlv_stream_t stream);
+int ctrlv_clip_plan_destroy(ctrlv_clip_plan* plan);
 
 #ifdef __cplusplus
 }

@@ -1,12 +1,12 @@
 #!/usr/bin/env python
 """Time of one CLIP ViT-H/14 image encode -- `image_encoder(pixel_values).image_embeds`, the call that opens every pipeline call
-and every step of the reference's video training loops -- on the HIP kernels (models/clip_vision_hip.encode) against the SAME
-module's torch forward.  Random-init weights on the device (1280 / 5120 / 32 layers / 16 heads / 224 / projection 1024),
+and every step of the reference's video training loops -- on the HIP kernels, per op (models/clip_vision_hip.encode) and as one C
+call (encode_plan: ctrlv_clip_forward), against the SAME module's torch forward.  Random-init weights on the device (1280 / 5120 / 32 layers / 16 heads / 224 / projection 1024),
 batches 1 and 8, bf16 and fp16 elements.
 
-The two paths ALTERNATE in one process after a warm-up (weights packed, code objects loaded, torch's GEMM choices made); every
+The three paths ALTERNATE in one process after a warm-up (weights packed, code objects loaded, torch's GEMM choices made); every
 call ends in a device synchronise and the iteration count gives each path a window of at least `--seconds`.  Reported per
-case: ms per call of both (mean and median), the launch count and per-family kernel times of the HIP path (one profiled call,
+case: ms per call of each (mean and median), the launch count and per-family kernel times of the HIP path (one profiled call,
 HIP events around every launch, outside the timed window), the agreement of the two results, and the algorithmic FLOPs and
 weight bytes.  One JSON line per case is printed and appended to profiles/clip_encode_bench.jsonl (--out)."""
 import argparse
@@ -50,31 +50,39 @@ def run_case(m, n, seconds, warmup):
     assert H.supports(m, px)
     hip = lambda: H.encode(m, px)                          # noqa: E731
     tor = lambda: m.torch_forward(px).image_embeds         # noqa: E731
+    pln = lambda: H.encode_plan(m, px)                     # noqa: E731
     with torch.no_grad():
         for _ in range(warmup):
-            hip(), tor()
+            hip(), tor(), pln()
         torch.cuda.synchronize()
-        probe = max(timed(hip), timed(tor))
-        iters = max(10, int(seconds * 1e3 / max(min(timed(hip), timed(tor)), 1e-3)) + 1)
-        t_hip, t_tor = [], []
-        for _ in range(iters):                              # alternate: both see the same clock / machine state
+        probe = max(timed(hip), timed(tor), timed(pln))
+        iters = max(10, int(seconds * 1e3 / max(min(timed(hip), timed(tor), timed(pln)), 1e-3)) + 1)
+        t_hip, t_tor, t_pln = [], [], []
+        for _ in range(iters):                              # alternate: all see the same clock / machine state
             t_hip.append(timed(hip))
             t_tor.append(timed(tor))
+            t_pln.append(timed(pln))
         with profiler.KernelTimer() as kt:
             a = hip()
         torch.cuda.synchronize()
         b = tor()
+        c = pln()
     fam = {k: dict(calls=v["calls"], ms=round(v["ms"], 4)) for k, v in kt.summary().items()}
     rel = ((a.float() - b.float()).norm() / b.float().norm()).item()
+    rel_plan = ((c.float() - b.float()).norm() / b.float().norm()).item()
     flops, wbytes = algorithmic(VIT_H, n)
     return {"metric": "CLIP ViT-H/14 image encode, ms per call", "batch": n, "dtype": str(m.dtype)[6:], "iters": iters,
             "hip_ms_mean": round(statistics.mean(t_hip), 4), "hip_ms_median": round(statistics.median(t_hip), 4),
             "torch_ms_mean": round(statistics.mean(t_tor), 4), "torch_ms_median": round(statistics.median(t_tor), 4),
-            "window_s": {"hip": round(sum(t_hip) / 1e3, 3), "torch": round(sum(t_tor) / 1e3, 3)}, "first_probe_ms": round(probe, 3),
+            "plan_ms_mean": round(statistics.mean(t_pln), 4), "plan_ms_median": round(statistics.median(t_pln), 4),
+            "window_s": {"hip": round(sum(t_hip) / 1e3, 3), "torch": round(sum(t_tor) / 1e3, 3), "plan": round(sum(t_pln) / 1e3, 3)},
+            "first_probe_ms": round(probe, 3), "plan_launches": H.plan_launches(VIT_H["num_hidden_layers"]),
+            "plan_vs_torch_rel_l2": float(f"{rel_plan:.3e}"),
             "hip_launches": len(kt.records), "hip_launches_expected": H.launches(VIT_H["num_hidden_layers"]),
             "hip_family_ms_profiled_call": fam, "hip_vs_torch_rel_l2": float(f"{rel:.3e}"),
             "algorithmic_gflop": round(flops / 1e9, 2), "weight_mbytes": round(wbytes / 1e6, 1),
-            "hip_tflops": round(flops / statistics.median(t_hip) / 1e9, 2), "device": torch.cuda.get_device_name(0)}
+            "hip_tflops": round(flops / statistics.median(t_hip) / 1e9, 2),
+            "plan_tflops": round(flops / statistics.median(t_pln) / 1e9, 2), "device": torch.cuda.get_device_name(0)}
 
 
 def build_vit_h(dtype, device="cuda:0"):
