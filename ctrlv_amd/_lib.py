@@ -25,7 +25,8 @@ class GemmDesc(ctypes.Structure):
         ("s_acc", c_float), ("s1", c_float), ("s2", c_float),
         ("vmode", c_int), ("vdiv", c_int), ("vmod", c_int), ("vS", c_int), ("ldv", c_int),
         ("act", c_int), ("geglu", c_int), ("out_f32", c_int), ("tile", c_int),
-        ("ld_raw", c_int), ("raw_out", c_void_p),
+        ("ld_raw", c_int), ("pad_br", c_int),          # pad_br: in what was alignment padding in front of raw_out
+        ("raw_out", c_void_p),
         ("n_scale2", c_int), ("s_acc2", c_float),
         ("gn_partials", c_void_p), ("splitk_ws", c_void_p), ("ksplit", c_int), ("w_cin", c_int),
         ("R1_lo", c_void_p), ("R2_lo", c_void_p), ("out_lo", c_void_p),      # split trunk planes (fp16 library)
@@ -103,6 +104,15 @@ class ClipConfig(ctypes.Structure):
     ]
 
 
+class VaeConfig(ctypes.Structure):
+    """Mirror of `ctrlv_vae_config`."""
+    _fields_ = [
+        ("in_channels", c_int), ("out_channels", c_int), ("latent_channels", c_int), ("layers_per_block", c_int),
+        ("n_blocks", c_int), ("block_out_channels", c_int * CTRLV_MAX_BLOCKS), ("scaling_factor", c_float),
+        ("offset_limit_bytes", ctypes.c_int64),
+    ]
+
+
 # name -> (restype, argtypes); lists every symbol include/ctrlv_hip.h declares (tests/test_abi.py checks this)
 SIGNATURES = {
     "ctrlv_abi_version": (c_int, []),
@@ -163,6 +173,8 @@ SIGNATURES = {
     "ctrlv_rows_to_nchw": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "ctrlv_time_conv_rows_to_nchw": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                              c_void_p]),
+    "ctrlv_vae_posterior": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p,
+                                    c_void_p, c_int, c_void_p]),
     "ctrlv_time_conv_rows_to_nchw_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                                  c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ctrlv_im2col3x3": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
@@ -216,6 +228,14 @@ SIGNATURES = {
     "ctrlv_clip_plan_workspace_bytes": (c_size_t, [c_void_p, c_int]),
     "ctrlv_clip_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ctrlv_clip_plan_destroy": (c_int, [c_void_p]),
+    "ctrlv_vae_plan_create": (c_int, [ctypes.POINTER(VaeConfig), c_int, ctypes.POINTER(c_void_p)]),
+    "ctrlv_vae_plan_load_weights": (c_int, [c_void_p, ctypes.POINTER(TensorDesc), c_size_t]),
+    "ctrlv_vae_plan_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int, c_int]),
+    "ctrlv_vae_encode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_int,
+                                 c_void_p, c_size_t, c_void_p]),
+    "ctrlv_vae_decode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_size_t,
+                                 c_void_p]),
+    "ctrlv_vae_plan_destroy": (c_int, [c_void_p]),
 }
 
 _libs = {}                # element dtype code (2 bf16 / 1 fp16) -> CDLL
@@ -225,7 +245,7 @@ _NO_STATUS = {"ctrlv_abi_version", "ctrlv_elem_dtype", "ctrlv_build_id", "ctrlv_
               "ctrlv_gemm_gn_partials_serves", "ctrlv_ff_fused_serves", "ctrlv_plan_num_down_residuals",
               "ctrlv_temporal_fused_serves",
               # size queries (size_t: never wrapped, listed with their kin for the reader)
-              "ctrlv_gemm_tokens_ws_bytes", "ctrlv_clip_plan_workspace_bytes"}
+              "ctrlv_gemm_tokens_ws_bytes", "ctrlv_clip_plan_workspace_bytes", "ctrlv_vae_plan_workspace_bytes"}
 
 
 def _status_recorder(lib, fn):

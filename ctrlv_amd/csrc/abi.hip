@@ -72,6 +72,10 @@ extern "C" int ctrlv_last_error(char* buf, size_t n) {
 }
 
 extern "C" int ctrlv_abi_version(void) { return 22; }
+// pad_br sits in what was alignment padding: the descriptor's size and the offsets around it are those of ABI 22
+static_assert(sizeof(ctrlv_gemm_desc) == 264 && offsetof(ctrlv_gemm_desc, ld_raw) == 192 && offsetof(ctrlv_gemm_desc, pad_br) == 196 &&
+                  offsetof(ctrlv_gemm_desc, raw_out) == 200,
+              "ctrlv_gemm_desc layout changed: that is an ABI bump");
 extern "C" int ctrlv_elem_dtype(void) { return CTRLV_ELEM_DTYPE; }
 
 // sha256 prefix of ctrlv_amd/csrc/* + include/*.h at build time (stamped by __graft_entry__.build()): the host layer

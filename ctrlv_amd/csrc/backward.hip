@@ -769,6 +769,7 @@ extern "C" int ctrlv_gemm_wgrad(const ctrlv_gemm_desc* dp, const void* dY, int l
   CTRLV_CHECK_ARG(!assign || scratch, "gemm_wgrad: assign (torch_layout bit 1) needs the deterministic form (scratch)");
   const ctrlv_gemm_desc& d = *dp;
   CTRLV_CHECK_ARG(d.A != nullptr, "gemm_wgrad: A must be non-null");
+  CTRLV_CHECK_ARG(d.pad_br == 0, "gemm_wgrad: pad_br (bottom / right padded stride-2 conv) is inference only");
   CTRLV_CHECK_SHAPE(d.M > 0 && d.N > 0 && d.Cin > 0 && d.Cin % 64 == 0, "gemm_wgrad: Cin=%d must be a positive multiple of 64", d.Cin);
   CTRLV_CHECK_SHAPE(d.N % 8 == 0 && ldy % 8 == 0 && d.lda % 8 == 0, "gemm_wgrad: N, ldy, lda must be multiples of 8");
   CTRLV_CHECK_SHAPE((d.mode == 0 && d.taps == 1) || (d.mode == 1 && d.taps == 9) || (d.mode == 2 && d.taps == 3),

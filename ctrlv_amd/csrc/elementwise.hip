@@ -64,6 +64,56 @@ __global__ void time_conv_rows_to_nchw_kernel(const el_t* __restrict__ src, int 
   for (int o = 0; o < C; ++o) store_any(dst, dtype, ((long)f * C + o) * HW + p, acc[o]);
 }
 
+// quant_conv (1x1, 2L -> 2L) + DiagonalGaussianDistribution of AutoencoderKL.encode on the rows the encoder's conv_out GEMM
+// wrote: one thread per (image, pixel), L <= 8 latent channels.  fp32 throughout: q[o] = b[o] + sum_c w[o][c] x[c] with c
+// ascending (fmaf), mean = q[:L], logvar = clamp(q[L:], -30, 20), latent = scale * (mean + exp(0.5 logvar) * noise).  No
+// atomics, fixed channel order: the same bits in every run.  Either output may be absent; each value is rounded once.
+__global__ void vae_posterior_kernel(const el_t* __restrict__ rows, int ld, int n_img, int L, int HW, const float* __restrict__ qw,
+                                     const float* __restrict__ qb, const float* __restrict__ noise, float scale,
+                                     void* __restrict__ moments, void* __restrict__ latents, int dtype) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long)n_img * HW) return;
+  const long n = idx / HW, p = idx % HW;
+  const int C = 2 * L;
+  const el_t* s = rows + idx * ld;
+  float x[16], q[16];
+#pragma unroll
+  for (int c = 0; c < 16; ++c) x[c] = c < C ? el_to_f32(s[c]) : 0.f;
+#pragma unroll
+  for (int o = 0; o < 16; ++o) {
+    float a = 0.f;
+    if (o < C) {
+      a = qb[o];
+#pragma unroll
+      for (int c = 0; c < 16; ++c)
+        if (c < C) a = __builtin_fmaf(qw[o * C + c], x[c], a);
+    }
+    q[o] = a;
+  }
+  if (moments != nullptr) {
+#pragma unroll
+    for (int o = 0; o < 16; ++o)
+      if (o < C) store_any(moments, dtype, (n * C + o) * HW + p, q[o]);
+  }
+  if (latents != nullptr) {
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      if (c >= L) break;
+      float v = q[c];
+      if (noise != nullptr) {
+        // (q[] is indexed by unrolled constants only: L + c is a runtime index, so the log-variance is picked by a select chain)
+        float lv = 0.f;
+#pragma unroll
+        for (int o = 0; o < 16; ++o)
+          if (o == L + c) lv = q[o];
+        lv = fminf(fmaxf(lv, -30.f), 20.f);
+        v = __builtin_fmaf(expf(0.5f * lv), noise[(n * L + c) * HW + p], v);
+      }
+      store_any(latents, dtype, (n * L + c) * HW + p, scale * v);
+    }
+  }
+}
+
 // Backward of time_conv_rows_to_nchw_kernel.  One thread per (frame, pixel), grid-stride over at most kTcbBlocks blocks:
 //   drows[f, p, c]  = sum_{t, o} w[o, c, t] * dout[f - t + 1, o, p]      (frames of the SAME clip only: the forward's zero padding)
 //   dw[o, c, t]    += dout[f, o, p] * src[f + t - 1, p, c],   db[o] += dout[f, o, p]
@@ -329,6 +379,23 @@ extern "C" int ctrlv_time_conv_rows_to_nchw(const void* src, int ldc, int n_fram
   const long total = (long)n_frames * HW;
   hipLaunchKernelGGL(time_conv_rows_to_nchw_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const el_t*)src, ldc, n_frames, C, HW, weight, bias, dst, dst_dtype);
+  CTRLV_LAUNCH_CHECK();
+  return CTRLV_OK;
+}
+
+extern "C" int ctrlv_vae_posterior(const void* rows, int ld, int n_img, int L, int HW, const float* quant_weight,
+                                   const float* quant_bias, const float* noise, float scale, void* moments_out,
+                                   void* latents_out, int out_dtype, ctrlv_stream_t stream) {
+  CTRLV_CHECK_ARG(rows && quant_weight && quant_bias, "vae_posterior: null pointer");
+  CTRLV_CHECK_ARG(moments_out || latents_out, "vae_posterior: moments_out and latents_out are both NULL");
+  CTRLV_CHECK_ARG(out_dtype >= 0 && out_dtype <= 2, "vae_posterior: out_dtype=%d (0 fp32, 1 fp16, 2 bf16)", out_dtype);
+  CTRLV_CHECK_SHAPE(L > 0 && L <= 8, "vae_posterior: latent_channels=%d must be in [1, 8]", L);
+  CTRLV_CHECK_SHAPE(n_img > 0 && HW > 0 && ld >= 2 * L, "vae_posterior: bad shape (n=%d, pixels=%d, ld=%d < 2 L=%d)", n_img, HW, ld,
+                    2 * L);
+  const long total = (long)n_img * HW;
+  hipLaunchKernelGGL(vae_posterior_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const el_t*)rows, ld, n_img, L, HW, quant_weight, quant_bias, noise, scale, moments_out, latents_out,
+                     out_dtype);
   CTRLV_LAUNCH_CHECK();
   return CTRLV_OK;
 }

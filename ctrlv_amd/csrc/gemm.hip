@@ -73,8 +73,8 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(const ctrlv_gemm_desc
       const int hw = d.Ho * d.Wo;
       const int n_img = m / hw, rem = m - n_img * hw;
       const int yo = rem / d.Wo, xo = rem - yo * d.Wo;
-      a_y0[q] = yo * d.stride - 1;
-      a_x0[q] = xo * d.stride - 1;
+      a_y0[q] = yo * d.stride - 1 + d.pad_br;      // (pad_br: the padding is on the bottom / right only)
+      a_x0[q] = xo * d.stride - 1 + d.pad_br;
       a_base[q] = (long)n_img * d.H * d.Wd;
     } else if (d.mode == 2) {
       a_y0[q] = (m / d.S) % d.F;
@@ -328,7 +328,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ctrlv_gemm_des
 // only (pixels per image, N, Cin, taps) -- priced for the 50 frame-images of a CFG'd 25-frame clip, never the actual batch:
 // a clip takes the same path, with the same summation order, alone and in any batch.
 static int splitk_plan(const ctrlv_gemm_desc& d, int* tile_out) {
-  if (!ctrlv_debug().splitk || (d.mode == 0 && d.S <= 0) || d.geglu || d.A2 || d.act || d.out_f32 || d.raw_out || d.gn_partials || d.n_scale2 || d.tile) return 1;
+  if (!ctrlv_debug().splitk || (d.mode == 0 && d.S <= 0) || d.geglu || d.A2 || d.act || d.out_f32 || d.raw_out || d.gn_partials || d.n_scale2 || d.tile || d.pad_br) return 1;
   if (d.N % 32 || d.N < 256 || d.n_store != d.N || d.ldo % 8 || (d.R1 && d.ldr1 % 8) || (d.R2 && d.ldr2 % 8) ||
       (d.vmode && d.ldv % 8) || d.Cin % 64)
     return 1;
@@ -411,6 +411,9 @@ extern "C" int ctrlv_gemm(const ctrlv_gemm_desc* dp, ctrlv_stream_t stream_) {
   CTRLV_CHECK_SHAPE(d.lda % 8 == 0 && (d.A2 == nullptr || (d.lda2 % 8 == 0 && d.c_split % 64 == 0)),
                     "ctrlv_gemm: lda/lda2 must be multiples of 8 and c_split a multiple of 64");
   CTRLV_CHECK_SHAPE(d.ldo % 4 == 0 && d.n_store % 4 == 0, "ctrlv_gemm: ldo and n_store must be multiples of 4");
+  CTRLV_CHECK_ARG(d.pad_br == 0 || (d.pad_br == 1 && d.mode == 1 && d.stride == 2 && d.up == 0),
+                  "ctrlv_gemm: pad_br=%d is the 3x3 conv of stride 2 without upsampling (mode %d, stride %d, up %d)", d.pad_br,
+                  d.mode, d.stride, d.up);
   if (d.mode == 0) {
     CTRLV_CHECK_SHAPE(d.taps == 1, "ctrlv_gemm: mode 0 needs taps == 1");
   } else if (d.mode == 1) {
@@ -418,6 +421,10 @@ extern "C" int ctrlv_gemm(const ctrlv_gemm_desc* dp, ctrlv_stream_t stream_) {
                           (d.up == 0 || d.up == 1),
                       "ctrlv_gemm: bad conv2d geometry");
     CTRLV_CHECK_SHAPE(d.M % (d.Ho * d.Wo) == 0, "ctrlv_gemm: M must be a multiple of Ho*Wo in conv2d mode");
+    if (d.pad_br) {       // bottom / right padding only: F.pad(x, (0, 1, 0, 1)) + stride 2 + no padding
+      CTRLV_CHECK_SHAPE(d.H % 2 == 0 && d.Wd % 2 == 0 && d.Ho == d.H / 2 && d.Wo == d.Wd / 2,
+                        "ctrlv_gemm: pad_br needs an even input %dx%d and an output of half its size (%dx%d)", d.H, d.Wd, d.Ho, d.Wo);
+    } else
     CTRLV_CHECK_SHAPE(((d.H << d.up) + 2 - 3) / d.stride + 1 == d.Ho && ((d.Wd << d.up) + 2 - 3) / d.stride + 1 == d.Wo,
                       "ctrlv_gemm: conv2d output size %dx%d inconsistent with input %dx%d stride %d up %d", d.Ho, d.Wo,
                       d.H, d.Wd, d.stride, d.up);
@@ -442,6 +449,7 @@ extern "C" int ctrlv_gemm(const ctrlv_gemm_desc* dp, ctrlv_stream_t stream_) {
     CTRLV_CHECK_ARG((!d.R1_lo || d.R1) && (!d.R2_lo || d.R2), "ctrlv_gemm: R1_lo / R2_lo need R1 / R2");
     CTRLV_CHECK_ARG(!d.geglu && !d.act && !d.out_f32 && !d.raw_out && !d.n_scale2,
                     "ctrlv_gemm: split planes do not combine with GEGLU / SiLU / fp32 output / raw_out / n_scale2");
+    CTRLV_CHECK_ARG(!d.pad_br, "ctrlv_gemm: split planes do not combine with pad_br");
   }
   if (d.splitk_ws) {      // split contraction where the layer's shape calls for it (splitk_plan)
     int tile_s = 0;

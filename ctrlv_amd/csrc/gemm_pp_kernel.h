@@ -786,7 +786,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const ctrlv_gemm_desc d, c
         const int yo = rem / d.Wo, xo = rem - yo * d.Wo;
         int cy, cx;
         if (d.up) { cy = yo >> 1; cx = xo >> 1; mask = ((unsigned)(yo & 1) << 16) | ((unsigned)(xo & 1) << 17); }
-        else { cy = yo * d.stride; cx = xo * d.stride; }
+        else { cy = yo * d.stride + d.pad_br; cx = xo * d.stride + d.pad_br; }    // (pad_br: tap centre (2 yo + 1, 2 xo + 1))
         row = (n_img * d.H + cy) * d.Wd + cx;
         const int hl = d.H << d.up, wl = d.Wd << d.up;
         const int y0 = d.up ? yo : cy, x0 = d.up ? xo : cx;   // coordinates in the (upsampled) conv input grid

@@ -51,7 +51,7 @@ extern "C" int ctrlv_gemm_gn_partials_serves(const ctrlv_gemm_desc* dp) {
   if (!ctrlv_debug().gn_fused) return 0;
   const int cpg = d.N / 32;
   if (d.N <= 0 || d.N % 320 != 0 || !(cpg == 10 || cpg == 20 || cpg == 40)) return 0;      // 160-column wave tiles hold whole groups
-  if (d.n_store != d.N || d.ldo % 8 != 0 || d.geglu || d.A2 || d.raw_out || d.n_scale2) return 0;
+  if (d.n_store != d.N || d.ldo % 8 != 0 || d.geglu || d.A2 || d.raw_out || d.n_scale2 || d.pad_br) return 0;
   if (pp_split_io(d) && pp_epi_of(d) != 2) return 0;        // split planes: the {R1} writers only (launch_epi_split)
   if ((d.R1 && d.ldr1 % 8 != 0) || (d.vmode && d.ldv % 8 != 0) || d.Cin % 64 != 0) return 0;
   const int e = pp_epi_of(d);

@@ -243,10 +243,14 @@ class AutoencoderKLTemporalDecoder(HipModelMixin):
         self.quant_conv = nn.Conv2d(2 * latent_channels, 2 * latent_channels, 1)
 
     def encode(self, x, return_dict=True):
-        import os
+        from . import vae_decoder_hip as vh
         from . import vae_encoder_hip as ve
-        if (os.environ.get("CTRLV_VAE_HIP", "1") != "0" and x.is_cuda and not torch.is_grad_enabled()
+        route = vh.route()
+        if (route != "torch" and x.is_cuda and not torch.is_grad_enabled()
                 and x.dtype in (torch.bfloat16, torch.float16, torch.float32) and ve.supports(x, self.encoder)):
+            if route == "plan":                            # one C call; quant_conv in the posterior kernel (csrc/vae_plan.hip)
+                dist = DiagonalGaussianDistribution(ve.encode_plan(self, x)[1])
+                return types.SimpleNamespace(latent_dist=dist) if return_dict else (dist,)
             moments = ve.encode(self.encoder, x)           # HIP kernels (vae_encoder_hip.py)
         else:
             moments = self.encoder(x)
@@ -259,10 +263,12 @@ class AutoencoderKLTemporalDecoder(HipModelMixin):
         # the decoder runs on the HIP kernels when it can (vae_decoder_hip.py: ~30x the MIOpen path at 576x1024);
         # CTRLV_VAE_HIP=0, CPU tensors, autograd or > 4 GiB intermediates use the torch modules below
         from . import vae_decoder_hip as vh
-        import os
-        if (os.environ.get("CTRLV_VAE_HIP", "1") != "0" and z.is_cuda and not torch.is_grad_enabled()
+        route = vh.route()
+        if (route != "torch" and z.is_cuda and not torch.is_grad_enabled()
                 and vh.supports(z, num_frames, self.decoder)):
-            sample = vh.decode(self.decoder, z, num_frames)
+            sample = (vh.decode_plan(self, z, num_frames) if route == "plan" and z.dtype in (torch.bfloat16, torch.float16,
+                                                                                              torch.float32)
+                      else vh.decode(self.decoder, z, num_frames))
         else:
             sample = self.decoder(z, num_frames)
         return types.SimpleNamespace(sample=sample) if return_dict else (sample,)

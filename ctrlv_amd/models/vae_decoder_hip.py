@@ -215,6 +215,27 @@ def decode(dec, z, num_frames):
     return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
 
 
+def route():
+    """Which VAE walk `AutoencoderKLTemporalDecoder.encode / decode` take where `supports` holds: CTRLV_VAE_HIP unset or 1 =
+    "ops" (the per-op executors of this file and vae_encoder_hip.py), plan = "plan" (one C call each: decode_plan /
+    encode_plan), 0 = "torch"."""
+    import os
+    v = os.environ.get("CTRLV_VAE_HIP", "1")
+    return "torch" if v == "0" else ("plan" if v == "plan" else "ops")
+
+
+@torch.no_grad()
+def decode_plan(vae, z, num_frames, offset_limit_bytes=0):
+    """`decode` through the C plan (csrc/vae_plan.hip): one ctrlv_vae_decode call on the VAE module's cached VaePlan.  Same
+    gate, same walk; bit-identical where `to_v.bias` is zero (the plan folds it into the output bias in fp64 on the host)."""
+    from ..plan import vae_plan
+    if z.shape[0] % num_frames:
+        raise ValueError(f"decode: {z.shape[0]} latent frames are not a multiple of num_frames={num_frames}")
+    if not supports(z, num_frames, vae.decoder):
+        raise ValueError("HIP VAE decode_plan: unsupported shape (see vae_decoder_hip.supports)")
+    return vae_plan(vae, offset_limit_bytes).decode(z, num_frames)
+
+
 def _decode_clip(dec, z):
     pk = _pack(dec)
     n, cz, H, W = z.shape

@@ -7,7 +7,9 @@ GEMM.  Two things are not native: the mid block's single-head attention core (he
 projections) and the down-samplers' ASYMMETRIC padding (`F.pad(x, (0, 1, 0, 1))` + stride-2 conv without padding, i.e.
 out[yo, xo] = sum x[2 yo + ky, 2 xo + kx]): the gather-GEMM's stride-2 mode is the symmetric form, so the three
 down-samplers run as a stride-1 convolution whose odd rows / columns are kept (out1[2 yo + 1, 2 xo + 1] is exactly that
-sum, the zero padding included) -- 4x the arithmetic on 3 of 25 convolutions.
+sum, the zero padding included) -- 4x the arithmetic on 3 of 25 convolutions.  `encode(..., native_down=True)` runs them
+as ONE launch each through the gather-GEMM's bottom / right padded stride-2 mode (`pad_br`) instead: no stride-1
+convolution, no strided copy; the default route is unchanged.  It is the per-op twin of the C plan (`encode_plan`).
 Limit: 32-bit byte offsets, n * H * W * 128 channels * 2 B < 4 GiB (28 frames at 576x1024; the pipeline encodes 25)."""
 import torch
 import torch.nn.functional as F
@@ -92,9 +94,23 @@ def supports(x, enc=None):
 
 
 @torch.no_grad()
-def encode(enc, x):
+def encode_plan(vae, x, noise=None, scale=1.0, moments=True):
+    """`vae.encode(x).latent_dist` through the C plan (csrc/vae_plan.hip): one ctrlv_vae_encode call on the VAE module's cached
+    VaePlan -- the walk of `encode(native_down=True)`, then quant_conv and the posterior in ctrlv_vae_posterior.  noise: None
+    for `mode()`, else fp32 (n, L, H/8, W/8) for `mean + std * noise`.  Returns (latents * scale, moments after quant_conv or
+    None) in x.dtype."""
+    from ..plan import vae_plan
+    if not supports(x, vae.encoder):
+        raise ValueError("HIP VAE encode_plan: unsupported shape (see vae_encoder_hip.supports)")
+    return vae_plan(vae).encode(x, noise=noise, scale=scale, moments=moments)
+
+
+@torch.no_grad()
+def encode(enc, x, native_down=False, rows=False):
     """enc: `Encoder` module; x: (n, 3, H, W) images in [-1, 1].  Returns the moments (n, 2 * latent_channels, H/8, W/8)
-    BEFORE quant_conv, in x.dtype."""
+    BEFORE quant_conv, in x.dtype.  native_down: the three down-samplers as one `pad_br` launch each (see above).
+    rows: return conv_out's channels-last rows [n * H/8 * W/8, 2 * latent_channels padded to 4] instead -- what
+    `ops.vae_posterior` consumes (the tests compare the plan with this twin through it)."""
     from .vae_decoder_hip import _attn
     if not supports(x, enc):
         raise ValueError("HIP VAE encode: unsupported shape (CUDA (n, 3, H, W) with H, W multiples of 8, < 4 GiB per tensor)")
@@ -116,6 +132,13 @@ def encode(enc, x):
             h = _res(rp, h, n, H, W, sc)
         if ds is not None:
             C = h.shape[1]
+            if native_down:
+                half = _rows(n * (H // 2) * (W // 2), C, dev)
+                ops.gemm(h, ds[0], half, N=C, cin=C, taps=9, mode=1, conv=(H, W, H // 2, W // 2, 2, 0), bias=ds[1],
+                         pad_br=True)
+                h = half
+                H, W = H // 2, W // 2
+                continue
             full = _rows(n * H * W, C, dev)
             ops.gemm(h, ds[0], full, N=C, cin=C, taps=9, mode=1, conv=(H, W, H, W, 1, 0), bias=ds[1])
             h = full.view(n, H, W, C)[:, 1::2, 1::2].contiguous().view(n * (H // 2) * (W // 2), C)
@@ -132,6 +155,8 @@ def encode(enc, x):
     co_p = (co + 3) // 4 * 4
     y = _rows(M, co_p, dev)
     ops.gemm(hn, wco, y, N=wco.shape[0], cin=C, taps=9, mode=1, conv=(H, W, H, W, 1, 0), bias=bco, n_store=co_p)
+    if rows:
+        return y
     out = torch.empty(n, co, H, W, dtype=x.dtype, device=dev)
     ops.rows_to_nchw(y, out)
     return out

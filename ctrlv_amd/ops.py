@@ -202,7 +202,7 @@ def geglu_bwd(raw, du, draw):
 def _gemm_desc(A, W, out, *, N, cin, taps=1, mode=0, bias=None, A2=None, c_split=0, conv=None, temporal=None,
                R1=None, s1=1.0, R2=None, s2=1.0, s_acc=1.0, V=None, vmode=0, vdiv=1, vmod=1 << 30, vS=1,
                act=0, geglu=0, out_f32=False, n_store=None, M=None, tile=0, raw_out=None, n_scale2=0, s_acc2=1.0, _dbg=0,
-               gn_partials=None, splitk=True, rows_per_image=0, R1_lo=None, R2_lo=None, out_lo=None):
+               gn_partials=None, splitk=True, rows_per_image=0, R1_lo=None, R2_lo=None, out_lo=None, pad_br=False):
     d = GemmDesc()
     d.A, d.A2, d.W, d.out = _p(A), _p(A2), _p(W), _p(out)
     d.bias, d.R1, d.R2, d.V = _p(bias), _p(R1), _p(R2), _p(V)
@@ -233,6 +233,7 @@ def _gemm_desc(A, W, out, *, N, cin, taps=1, mode=0, bias=None, A2=None, c_split
     d.gn_partials = _p(gn_partials)
     # split residual-trunk planes (fp16 library; include/ctrlv_hip.h): same shapes / pitches as R1 / R2 / out
     d.R1_lo, d.R2_lo, d.out_lo = _p(R1_lo), _p(R2_lo), _p(out_lo)
+    d.pad_br = int(pad_br)            # mode 1, stride 2: padding on the bottom / right only (the VAE encoder's down-samplers)
     return d
 
 
@@ -614,6 +615,20 @@ def rows_to_nchw(src, dst, C=None):
     check(_L(src).ctrlv_rows_to_nchw(_p(src), src.stride(0), n_img, Cd if C is None else C, HW, _p(dst),
                                          _DT[dst.dtype], _stream()), "ctrlv_rows_to_nchw")
     return dst
+
+
+def vae_posterior(rows, n_img, L, HW, quant_weight, quant_bias, noise=None, scale=1.0, moments=None, latents=None):
+    """quant_conv + posterior on the encoder's conv_out rows [n_img * HW, ld >= 2 L] (ctrlv_vae_posterior): `moments`
+    (n_img, 2 L, H, W) and / or `latents` (n_img, L, H, W), contiguous, of one dtype; `noise` fp32 (n_img, L, H, W) or None
+    for the distribution's mode.  quant_weight [2 L, 2 L] / quant_bias [2 L] fp32."""
+    _need_gpu(rows, "rows")
+    outs = [t for t in (moments, latents) if t is not None]
+    if len({t.dtype for t in outs}) > 1:
+        raise ValueError("vae_posterior: moments and latents must have one dtype")
+    dt = _DT[outs[0].dtype] if outs else 0
+    check(_L(rows).ctrlv_vae_posterior(_p(rows), rows.stride(0), n_img, L, HW, _p(quant_weight), _p(quant_bias), _p(noise),
+                                       float(scale), _p(moments), _p(latents), dt, _stream()), "ctrlv_vae_posterior")
+    return moments, latents
 
 
 def im2col3x3(x, n_img, H, W, col):

@@ -274,3 +274,134 @@ class ClipPlan:
                                            hidden.data_ptr() if return_hidden else None, ws.data_ptr(), ws.numel(), st),
               "ctrlv_clip_forward")
         return (embeds, hidden) if return_hidden else embeds
+
+
+class VaePlan:
+    """Owns one `ctrlv_vae_plan`: the SVD VAE (AutoencoderKLTemporalDecoder) as one C call each way -- create,
+    `load_state_dict` (diffusers keys: encoder.*, decoder.*, quant_conv.*), workspace, `encode` / `decode`
+    (include/ctrlv_hip.h).  The plan runs in bf16 elements: the Python layer routes the VAE to libctrlv_hip.so."""
+
+    def __init__(self, config, device, offset_limit_bytes=0):
+        """config: the fields of AutoencoderKLTemporalDecoder's config (a dict or its config object)."""
+        get = config.get if isinstance(config, dict) else (lambda k, d=None: getattr(config, k, d))
+        self.device = torch.device(device)
+        self._lib = _lib.load(torch.bfloat16)
+        self._h = ctypes.c_void_p()
+        c = self._cfg = _lib.VaeConfig()
+        boc = tuple(get("block_out_channels"))
+        if len(boc) > _lib.CTRLV_MAX_BLOCKS:
+            raise ValueError(f"VaePlan: {len(boc)} blocks, at most {_lib.CTRLV_MAX_BLOCKS}")
+        c.in_channels, c.out_channels = int(get("in_channels")), int(get("out_channels"))
+        c.latent_channels, c.layers_per_block, c.n_blocks = int(get("latent_channels")), int(get("layers_per_block")), len(boc)
+        for i, ch in enumerate(boc):
+            c.block_out_channels[i] = int(ch)
+        c.scaling_factor = float(get("scaling_factor", 0.18215))
+        c.offset_limit_bytes = int(offset_limit_bytes)
+        check(self._lib.ctrlv_vae_plan_create(ctypes.byref(c), self.device.index or 0, ctypes.byref(self._h)),
+              "ctrlv_vae_plan_create")
+        self._ws = {}            # stream -> uint8 workspace tensor
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                self._lib.ctrlv_vae_plan_destroy(h)
+            except Exception:       # noqa: BLE001  (interpreter shutdown)
+                pass
+
+    def load_state_dict(self, state_dict):
+        """Hand every parameter to the library by its diffusers key; packing happens on the device in C++."""
+        items = [(k, v.detach()) for k, v in state_dict.items() if torch.is_tensor(v) and v.is_floating_point()]
+        keep = []
+        arr = (TensorDesc * len(items))()
+        for i, (k, v) in enumerate(items):
+            if v.dtype not in _DT:
+                v = v.float()
+            v = v.contiguous()
+            keep.append(v)
+            arr[i].name = k.encode()
+            arr[i].data = v.data_ptr()
+            arr[i].dtype = _DT[v.dtype]
+            arr[i].on_device = 1 if v.is_cuda else 0
+            arr[i].numel = v.numel()
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        check(self._lib.ctrlv_vae_plan_load_weights(self._h, arr, len(items)), "ctrlv_vae_plan_load_weights")
+        del keep
+
+    def workspace_bytes(self, what, n, num_frames, H, W):
+        """what: "encode" (n images of H x W pixels) or "decode" (n latent frames of H x W latent pixels, clips of num_frames)."""
+        nb = self._lib.ctrlv_vae_plan_workspace_bytes(self._h, {"encode": 0, "decode": 1}[what], n, num_frames, H, W)
+        if nb == 0:
+            check(-2, "ctrlv_vae_plan_workspace_bytes", lib=self._lib)
+        return nb
+
+    def workspace(self, what, n, num_frames, H, W):
+        need = self.workspace_bytes(what, n, num_frames, H, W)
+        key = torch.cuda.current_stream(self.device).cuda_stream
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < need:
+            ws = self._ws[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return ws
+
+    def _check(self, t, what):
+        if t.dim() != 4 or t.dtype not in _DT or not t.is_cuda:
+            raise ValueError(f"VaePlan.{what}: a 4-D fp32 / fp16 / bf16 tensor on the HIP device")
+        if (t.device.index or 0) != (self.device.index or 0):
+            raise ValueError(f"VaePlan.{what}: input on {t.device}, the plan's weights on {self.device}")
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def encode(self, x, noise=None, scale=1.0, moments=True, workspace=None):
+        """x (n, 3, H, W) in [-1, 1] -> (latents, moments): latents (n, L, H/8, W/8) = scale * (mean + std * noise) -- noise
+        fp32 (n, L, H/8, W/8), None = the distribution's mode --, moments (n, 2 L, H/8, W/8) after quant_conv (or None).  Both
+        in x.dtype, enqueued on torch's current stream."""
+        self._check(x, "encode")
+        x = x.contiguous()
+        n, _, H, W = x.shape
+        L = self._cfg.latent_channels
+        ws = self.workspace("encode", n, 1, H, W) if workspace is None else workspace
+        lat = torch.empty(n, L, H // 8, W // 8, dtype=x.dtype, device=x.device)
+        mom = torch.empty(n, 2 * L, H // 8, W // 8, dtype=x.dtype, device=x.device) if moments else None
+        if noise is not None:
+            noise = noise.to(device=x.device, dtype=torch.float32).contiguous()
+            if noise.shape != lat.shape:
+                raise ValueError(f"VaePlan.encode: noise {tuple(noise.shape)} must be {tuple(lat.shape)}")
+        check(self._lib.ctrlv_vae_encode(self._h, x.data_ptr(), _DT[x.dtype], n, H, W,
+                                         noise.data_ptr() if noise is not None else None, float(scale), lat.data_ptr(),
+                                         mom.data_ptr() if moments else None, _DT[x.dtype], ws.data_ptr(), ws.numel(),
+                                         self._stream()), "ctrlv_vae_encode")
+        return lat, mom
+
+    def decode(self, z, num_frames, workspace=None, out=None):
+        """z (n, L, h, w) latents already divided by the scaling factor -> frames (n, 3, 8 h, 8 w) in z.dtype."""
+        self._check(z, "decode")
+        z = z.contiguous()
+        n, _, h, w = z.shape
+        ws = self.workspace("decode", n, num_frames, h, w) if workspace is None else workspace
+        if out is None:
+            out = torch.empty(n, self._cfg.out_channels, 8 * h, 8 * w, dtype=z.dtype, device=z.device)
+        check(self._lib.ctrlv_vae_decode(self._h, z.data_ptr(), _DT[z.dtype], n, num_frames, h, w, out.data_ptr(),
+                                         _DT[out.dtype], ws.data_ptr(), ws.numel(), self._stream()), "ctrlv_vae_decode")
+        return out
+
+
+_VAE_PLANS = {}
+
+
+def vae_plan(vae, offset_limit_bytes=0):
+    """The `VaePlan` of an AutoencoderKLTemporalDecoder module, cached per object and keyed on the parameters' versions and
+    storage (as the per-op executors' `_pack`): an in-place parameter update reloads the weights."""
+    import weakref
+    key = (id(vae), int(offset_limit_bytes))
+    params = list(vae.parameters())
+    ver = tuple(p._version for p in params) + (params[0].data_ptr(),)
+    hit = _VAE_PLANS.get(key)
+    if hit is not None and hit[0] == ver and hit[1]() is vae:
+        return hit[2]
+    plan = hit[2] if hit is not None and hit[1]() is vae and hit[2].device == params[0].device else \
+        VaePlan(vae.config, params[0].device, offset_limit_bytes)
+    plan.load_state_dict(vae.state_dict())
+    _VAE_PLANS[key] = (ver, weakref.ref(vae), plan)
+    return plan

@@ -45,7 +45,9 @@ enum {
  * decoder's training walk, ctrlv_softmax_rows_bwd and ctrlv_time_conv_rows_to_nchw_bwd).  Purely ADDITIVE entry points do not
  * bump the number: a host built against 22 runs unchanged on a library that also exports the CLIP vision kernels
  * (ctrlv_attention_tokens, ctrlv_clip_patch_rows, ctrlv_clip_tokens, ctrlv_act_rows) or ctrlv_gemm_tokens and the CLIP plan
- * (ctrlv_clip_*), and a host that needs them fails at symbol lookup on a library without them. */
+ * (ctrlv_clip_*) ctrlv_vae_posterior or the VAE plan (ctrlv_vae_*), and a host that needs them fails at symbol lookup on a library without them.
+ * NOT neutral, although the number did not move: ctrlv_gemm_desc.pad_br gives meaning to four bytes that were alignment
+ * padding, so descriptors must now be zero-initialised (see the field). */
 int ctrlv_abi_version(void);
 /* dtype code (1 fp16 / 2 bf16) of the element type this library was built for (see above). */
 int ctrlv_elem_dtype(void);
@@ -101,6 +103,22 @@ typedef struct ctrlv_gemm_desc {
   int32_t out_f32;
   int32_t tile;                       /* 0 auto, else forces a tile configuration (testing) */
   int32_t ld_raw;                     /* leading dimension of raw_out (elements) */
+  int32_t pad_br;                     /* 1 (mode 1, taps 9, stride 2, up 0 only): the stride-2 conv with the padding on the
+                                         BOTTOM and RIGHT only -- F.pad(x, (0, 1, 0, 1)) + Conv2d(3, stride 2, padding 0), the
+                                         down-sampler of the VAE encoder: out[yo, xo] = sum_{ky, kx} w[ky, kx] x[2 yo + ky,
+                                         2 xo + kx], row H and column Wd read as zero; H and Wd even, Ho = H / 2, Wo = Wd / 2.
+                                         The tap centre moves from (2 yo, 2 xo) to (2 yo + 1, 2 xo + 1); inference only (the
+                                         backward entry points refuse it), no gn_partials, no K split, no split planes.
+                                         LAYOUT AND A REQUIREMENT.  The field occupies the four bytes that were alignment
+                                         padding in front of raw_out (offset 196): sizeof and every other offset are those
+                                         of ABI 22 and the version number stays 22.  Until this field those bytes had no
+                                         meaning and nothing asked a host to initialise them; from now on a descriptor MUST
+                                         be zero-initialised (memset / calloc / `= {0}` / ctypes) before its fields are
+                                         set.  A host built against an older header that fills a stack descriptor field by
+                                         field passes whatever the stack held: a non-zero value is CTRLV_E_BAD_ARG on
+                                         launches that worked before, and the value 1 on a stride-2 conv selects THIS
+                                         convolution.  Such a host has to be changed to clear the descriptor; the
+                                         library's own callers and the documented bindings always did */
   void* raw_out;                      /* GEGLU only, optional (training forward): the projection BEFORE the gate,
                                          [M, ld_raw] bf16 in the packed (16 value | 16 gate) column-block order -- what
                                          ctrlv_geglu_bwd consumes -- written by the same launch (ping-pong tiles) */
@@ -361,6 +379,17 @@ int ctrlv_rows_to_nchw(const void* src, int ldc, int n_img, int C, int HW, void*
  * fp32 [C]; dst (n_frames, C, H, W) in dst_dtype. */
 int ctrlv_time_conv_rows_to_nchw(const void* src, int ldc, int n_frames, int C, int HW, const float* weight,
                                  const float* bias, void* dst, int dst_dtype, ctrlv_stream_t stream);
+/* quant_conv + posterior of AutoencoderKLTemporalDecoder.encode (`moments = quant_conv(encoder(x))`,
+ * `DiagonalGaussianDistribution(moments).mode() / .sample()`) on the rows the encoder's conv_out GEMM wrote.
+ *   rows         [n_img * HW, ld >= 2 L] in the element type: the moments BEFORE quant_conv (L = latent_channels <= 8)
+ *   quant_weight [2 L, 2 L] fp32, quant_bias [2 L] fp32 (quant_conv.weight / .bias)
+ *   moments_out  (n_img, 2 L, H, W) NCHW, dtype code out_dtype, or NULL: quant_conv(rows), computed in fp32, rounded once
+ *   latents_out  (n_img, L, H, W) NCHW, same dtype, or NULL: scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * noise);
+ *                noise (n_img, L, H, W) fp32 from the caller, or NULL for mode() -- the library draws no random numbers
+ * At least one output.  One thread per (image, pixel), no atomics, a fixed channel order: the same bits in every run. */
+int ctrlv_vae_posterior(const void* rows, int ld, int n_img, int L, int HW, const float* quant_weight, const float* quant_bias,
+                        const float* noise, float scale, void* moments_out, void* latents_out, int out_dtype,
+                        ctrlv_stream_t stream);
 /* Backward of ctrlv_time_conv_rows_to_nchw (ABI 22; the last op of the decoder in tools/train_vae_finetuning.py:303-320).
  * dout: fp32 (n_frames, C, H, W) gradient of the forward's output; src / ldc_src / weight: the forward's operands.  The
  * n_frames frames are whole clips of clip_frames (one forward call each): taps never cross a clip, exactly the forward's
@@ -649,6 +678,67 @@ size_t ctrlv_clip_plan_workspace_bytes(ctrlv_clip_plan* plan, int n_img);
 int ctrlv_clip_forward(ctrlv_clip_plan* plan, const void* pixel_values, int dtype, int n_img, void* image_embeds,
                        void* last_hidden_state, void* workspace, size_t workspace_bytes, ctrlv_stream_t stream);
 int ctrlv_clip_plan_destroy(ctrlv_clip_plan* plan);
+
+/* ==================================================================================================================
+ * The VAE as ONE call each way (csrc/vae_plan.hip): `vae.encode(x).latent_dist` (the conditioning image and the bbox frames,
+ * pipeline_video_control.py:71-101, 235) and `vae.decode(z, num_frames).sample` (:346) of AutoencoderKLTemporalDecoder, for a
+ * host in any language:
+ *     ctrlv_vae_plan_create -> ctrlv_vae_plan_load_weights -> ctrlv_vae_plan_workspace_bytes -> ctrlv_vae_encode / _decode.
+ * With the CLIP plan, the UNet / ControlNet plan and ctrlv_cfg_euler_step, everything a Box2Video clip computes on the GPU is
+ * reachable from this header.  Same contract as the plans above: create validates on the host and needs no GPU; packed
+ * weights are library-owned; a forward allocates nothing, never synchronises the host and enqueues only on the caller's
+ * stream, as ONE chain (HIP-graph capturable; the only non-kernel nodes are the memsets of the zero-padded input channels).
+ * The walks are the per-op Python executors' (models/vae_encoder_hip.py with native_down, models/vae_decoder_hip.py), launch
+ * for launch and operand for operand:
+ *   encode:  nchw_to_rows -> im2col3x3 -> GEMM (conv_in);  per level: res blocks {GroupNorm+SiLU (stats, apply) -> conv1 ->
+ *            GroupNorm+SiLU -> [1x1 shortcut] -> conv2 + residual: 6 or 7 kernels}, then the down-sampler as ONE pad_br launch
+ *            (3 of the 4 levels);  mid: res, attention, res;  GroupNorm+SiLU -> conv_out -> ctrlv_vae_posterior (quant_conv and
+ *            the posterior).  Attention (one head of dim C): GroupNorm -> q, k GEMMs -> per image {scores GEMM (fp32) ->
+ *            ctrlv_softmax_rows -> V^T GEMM -> P.V GEMM} -> to_out GEMM + residual: 5 + 4 n kernels.
+ *   decode:  per clip of num_frames: conv_in as above;  mid: res, attention, res;  per level: 3 res blocks {the spatial half
+ *            as above, per frame range; GroupNorm+SiLU over the clip -> temporal conv1 -> GroupNorm+SiLU -> temporal conv2 with
+ *            the AlphaBlender in its epilogue: 12 or 13 kernels}, then the up-sampler conv with the nearest-x2 gather fused
+ *            (3 of the 4 levels);  GroupNorm+SiLU -> conv_out -> ctrlv_time_conv_rows_to_nchw.
+ *   A conv whose layer shape asks for the K split (ctrlv_gemm_splitk_ws_bytes) runs as two kernels, as in the executors.
+ * Two operands are computed at load time: sigmoid(mix_factor) as 1 / (1 + exp(-(double) p)) rounded to float, and the
+ * attention's folded output bias b_o + W_o . b_v, in fp64 on the host from the fp32 values, rounded once (the Python
+ * executor forms it with a device matvec: the two routes agree bit for bit where to_v.bias is zero, to rounding elsewhere).
+ * Element type: the plan runs in the library's element type.  It is exported by libctrlv_hip_f16.so too (same sources) but
+ * validated on the bf16 library only: the Python layer routes the VAE there.
+ * ================================================================================================================== */
+typedef struct ctrlv_vae_config {
+  int32_t in_channels, out_channels, latent_channels, layers_per_block, n_blocks;    /* 3, 3, 4, 2, 4 */
+  int32_t block_out_channels[CTRLV_MAX_BLOCKS];                                       /* 128, 256, 512, 512 */
+  float scaling_factor;         /* 0.18215; informative: ctrlv_vae_encode takes the scale of a call as an argument */
+  int64_t offset_limit_bytes;   /* 0 = the kernels' 32-bit limit (2^32 - 2^24); smaller values only shrink the frame
+                                   ranges of the per-frame ops: same bits (tests use it) */
+} ctrlv_vae_config;
+typedef struct ctrlv_vae_plan ctrlv_vae_plan;
+/* Size rules (vae_encoder_hip.supports / vae_decoder_hip.supports): four down / up blocks, channel counts multiples of 64,
+ * latent_channels <= 8, in_channels <= 8, out_channels <= 4; the mid blocks' attention has one head. */
+int ctrlv_vae_plan_create(const ctrlv_vae_config* cfg, int device, ctrlv_vae_plan** out);
+/* The diffusers state-dict keys of vae/diffusion_pytorch_model.safetensors (encoder.*, decoder.*, quant_conv.*).  Host or
+ * device tensors, fp32 or 16-bit; packed on the device; extra names are ignored, a missing one is an error.  May be called
+ * again; synchronises the device. */
+int ctrlv_vae_plan_load_weights(ctrlv_vae_plan* plan, const ctrlv_tensor_desc* tensors, size_t n);
+/* Bytes of workspace of one call; 0 on error ("not loaded" before load_weights, or a shape the call would refuse:
+ * ctrlv_last_error).  what 0: ctrlv_vae_encode of n images of H x W PIXELS (num_frames ignored); what 1: ctrlv_vae_decode of
+ * n latent frames of H x W LATENT pixels in clips of num_frames (the workspace is one clip's: it does not grow with n). */
+size_t ctrlv_vae_plan_workspace_bytes(ctrlv_vae_plan* plan, int what, int n, int num_frames, int H, int W);
+/* pixels (n, in_channels, Hpx, Wpx) in [-1, 1], dtype 0 / 1 / 2.  Outputs, NCHW of out_dtype, either may be NULL:
+ * moments (n, 2 L, Hpx/8, Wpx/8) = quant_conv(encoder(pixels)); latents (n, L, Hpx/8, Wpx/8) = scale * (mean + std * noise),
+ * noise (n, L, Hpx/8, Wpx/8) fp32 or NULL for latent_dist.mode() (ctrlv_vae_posterior).  Shapes: Hpx, Wpx multiples of 8, latent
+ * pixels per image a multiple of 64 and <= 16384, n * Hpx * Wpx * block_out_channels[0] * 2 below the offset limit
+ * (CTRLV_E_BAD_SHAPE).  workspace 256-byte aligned; too small: CTRLV_E_WORKSPACE before anything is launched. */
+int ctrlv_vae_encode(ctrlv_vae_plan* plan, const void* pixels, int dtype, int n, int Hpx, int Wpx, const float* noise,
+                     float scale, void* latents, void* moments, int out_dtype, void* workspace, size_t workspace_bytes,
+                     ctrlv_stream_t stream);
+/* z (n, L, h, w) latents already divided by the scaling factor, dtype 0 / 1 / 2; frames (n, out_channels, 8 h, 8 w) of
+ * out_dtype.  n % num_frames == 0: the clips are decoded one after the other.  Shapes: h * w a multiple of 64 and <= 16384,
+ * every whole-clip tensor (num_frames * pixels * channels * 2 bytes per level) below the offset limit (CTRLV_E_BAD_SHAPE). */
+int ctrlv_vae_decode(ctrlv_vae_plan* plan, const void* z, int dtype, int n, int num_frames, int h, int w, void* frames,
+                     int out_dtype, void* workspace, size_t workspace_bytes, ctrlv_stream_t stream);
+int ctrlv_vae_plan_destroy(ctrlv_vae_plan* plan);
 
 #ifdef __cplusplus
 }
