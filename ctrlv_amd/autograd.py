@@ -127,16 +127,32 @@ def _epilogue_grads(dY, spec, need_r1, need_r2, vshape):
     if vshape is not None:
         dV = torch.zeros(vshape, dtype=torch.float32, device=dY.device)
         vmod = min(spec.vmod, vshape[0])
-        if spec.vmode == 1:
+        if spec.vmode == 1 and (spec.vdiv % 4 == 0 or not ops.DETERMINISTIC):
             ops.colsum(dY, dV, vmode=1, vdiv=spec.vdiv, vmod=vmod)
-        else:
+        elif spec.vmode == 2 and spec.vS % spec.vmod == 0 and spec.vdiv % spec.vmod == 0:
             # vidx = ((m // vdiv) * vS + m % vS) % vmod (the diffusers-0.27.2 (s, b) context order): with vS and
             # vdiv multiples of vmod this is m % vmod -- table row j collects every vmod-th row starting at j
-            if spec.vS % spec.vmod or spec.vdiv % spec.vmod:
-                raise NotImplementedError("row-vector gradient for vmode 2 needs vS and vdiv to be multiples of vmod")
             for j in range(spec.vmod):
                 ops.colsum(dY[j::spec.vmod], dV[j:j + 1])
+        else:
+            _row_vector_grad_by_table_row(dY, dV, spec)
     return dR1, dR2, dV
+
+
+def _row_vector_grad_by_table_row(dY, dV, spec):
+    """dV for the index maps the two fast forms do not serve -- vmode 2 with vS or vdiv no multiple of vmod (B = 3 clips in
+    the (s, b) context order), and vmode 1 with a row group that is no multiple of 4, which ctrlv_colsum serves with fp32
+    atomics only: one ordered column sum per table row over the rows whose index is that row.  The row lists come from the
+    host (no read of the device); shapes of this kind are small or rare, the gather copy is not on the hot path."""
+    m = torch.arange(dY.shape[0])
+    if spec.vmode == 1:
+        idx = (m // spec.vdiv) % spec.vmod
+    else:
+        idx = ((m // spec.vdiv) * spec.vS + m % spec.vS) % spec.vmod
+    for j in range(dV.shape[0]):
+        sel = (idx == j).nonzero().flatten()
+        if sel.numel():
+            ops.colsum(dY.index_select(0, sel.to(dY.device)), dV[j:j + 1])
 
 
 class Gemm(torch.autograd.Function):
