@@ -122,6 +122,8 @@ SIGNATURES = {
     "ctrlv_gemm": (c_int, [ctypes.POINTER(GemmDesc), c_void_p]),
     "ctrlv_gemm_gn_partials_serves": (c_int, [ctypes.POINTER(GemmDesc)]),
     "ctrlv_gemm_splitk_ws_bytes": (c_size_t, [ctypes.POINTER(GemmDesc)]),
+    "ctrlv_gemm_up_phase_serves": (c_int, [ctypes.POINTER(GemmDesc)]),
+    "ctrlv_pack_up_phase_weight": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "ctrlv_groupnorm_from_partials": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
                                               c_int, c_void_p, c_void_p]),
     "ctrlv_groupnorm_from_partials_split": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
@@ -242,7 +244,7 @@ _libs = {}                # element dtype code (2 bf16 / 1 fp16) -> CDLL
 _tls = threading.local()  # .failed = the library whose call returned a negative status last (this thread)
 # c_int-returning entry points whose value is NOT a status code
 _NO_STATUS = {"ctrlv_abi_version", "ctrlv_elem_dtype", "ctrlv_build_id", "ctrlv_last_error", "ctrlv_ff_fused_w1f_bytes",
-              "ctrlv_gemm_gn_partials_serves", "ctrlv_ff_fused_serves", "ctrlv_plan_num_down_residuals",
+              "ctrlv_gemm_gn_partials_serves", "ctrlv_gemm_up_phase_serves", "ctrlv_ff_fused_serves", "ctrlv_plan_num_down_residuals",
               "ctrlv_temporal_fused_serves",
               # size queries (size_t: never wrapped, listed with their kin for the reader)
               "ctrlv_gemm_tokens_ws_bytes", "ctrlv_clip_plan_workspace_bytes", "ctrlv_vae_plan_workspace_bytes"}

@@ -329,6 +329,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ctrlv_gemm_des
 // a clip takes the same path, with the same summation order, alone and in any batch.
 static int splitk_plan(const ctrlv_gemm_desc& d, int* tile_out) {
   if (!ctrlv_debug().splitk || (d.mode == 0 && d.S <= 0) || d.geglu || d.A2 || d.act || d.out_f32 || d.raw_out || d.gn_partials || d.n_scale2 || d.tile || d.pad_br) return 1;
+  if (d.mode == 1 && d.up == 2) return 1;      // phase form of the upsampler conv: one launch on the 256x320 tile
   if (d.N % 32 || d.N < 256 || d.n_store != d.N || d.ldo % 8 || (d.R1 && d.ldr1 % 8) || (d.R2 && d.ldr2 % 8) ||
       (d.vmode && d.ldv % 8) || d.Cin % 64)
     return 1;
@@ -418,14 +419,14 @@ extern "C" int ctrlv_gemm(const ctrlv_gemm_desc* dp, ctrlv_stream_t stream_) {
     CTRLV_CHECK_SHAPE(d.taps == 1, "ctrlv_gemm: mode 0 needs taps == 1");
   } else if (d.mode == 1) {
     CTRLV_CHECK_SHAPE(d.taps == 9 && d.H > 0 && d.Wd > 0 && d.Ho > 0 && d.Wo > 0 && (d.stride == 1 || d.stride == 2) &&
-                          (d.up == 0 || d.up == 1),
+                          (d.up == 0 || d.up == 1 || d.up == 2),
                       "ctrlv_gemm: bad conv2d geometry");
     CTRLV_CHECK_SHAPE(d.M % (d.Ho * d.Wo) == 0, "ctrlv_gemm: M must be a multiple of Ho*Wo in conv2d mode");
     if (d.pad_br) {       // bottom / right padding only: F.pad(x, (0, 1, 0, 1)) + stride 2 + no padding
       CTRLV_CHECK_SHAPE(d.H % 2 == 0 && d.Wd % 2 == 0 && d.Ho == d.H / 2 && d.Wo == d.Wd / 2,
                         "ctrlv_gemm: pad_br needs an even input %dx%d and an output of half its size (%dx%d)", d.H, d.Wd, d.Ho, d.Wo);
     } else
-    CTRLV_CHECK_SHAPE(((d.H << d.up) + 2 - 3) / d.stride + 1 == d.Ho && ((d.Wd << d.up) + 2 - 3) / d.stride + 1 == d.Wo,
+    CTRLV_CHECK_SHAPE(((d.H << (d.up ? 1 : 0)) + 2 - 3) / d.stride + 1 == d.Ho && ((d.Wd << (d.up ? 1 : 0)) + 2 - 3) / d.stride + 1 == d.Wo,
                       "ctrlv_gemm: conv2d output size %dx%d inconsistent with input %dx%d stride %d up %d", d.Ho, d.Wo,
                       d.H, d.Wd, d.stride, d.up);
   } else if (d.mode == 2) {
@@ -450,6 +451,18 @@ extern "C" int ctrlv_gemm(const ctrlv_gemm_desc* dp, ctrlv_stream_t stream_) {
     CTRLV_CHECK_ARG(!d.geglu && !d.act && !d.out_f32 && !d.raw_out && !d.n_scale2,
                     "ctrlv_gemm: split planes do not combine with GEGLU / SiLU / fp32 output / raw_out / n_scale2");
     CTRLV_CHECK_ARG(!d.pad_br, "ctrlv_gemm: split planes do not combine with pad_br");
+  }
+  if (d.mode == 1 && d.up == 2) {
+    // Phase form of the nearest-x2 upsampler conv (gemm_pp_up.hip): W = the four packed 2x2 panels.  The layer decides
+    // (ctrlv_gemm_up_phase_serves); the launch runs on the 256x320 ping-pong tile whatever M is.
+    CTRLV_CHECK_SHAPE(ctrlv_gemm_up_phase_serves(&d), "ctrlv_gemm: up=2 (phase form) is not served for this layer (ask "
+                                                      "ctrlv_gemm_up_phase_serves first)");
+    ctrlv_gemm_desc dd = d;
+    dd.taps = 4;                      // (what the kernel contracts over: the limits below are those of the launch)
+    CTRLV_CHECK_SHAPE(ctrlv_gemm_pp_supports(dd) && (long)4 * d.N * 4 * d.Cin * 2 <= 0xFFFFFFF0L,
+                      "ctrlv_gemm: up=2 operands beyond 32-bit byte offsets (M=%d): split the batch", d.M);
+    d.tile = 0;
+    return ctrlv_gemm_launch_pp(d, 6, stream);
   }
   if (d.splitk_ws) {      // split contraction where the layer's shape calls for it (splitk_plan)
     int tile_s = 0;

@@ -211,11 +211,15 @@ __device__ __forceinline__ void pp_bias_store(char* bias_lds, const u32x4_t& v, 
 // Needs WTN % cpg == 0 and a wave tile inside one image (S % 64 == 0): ctrlv_gemm_gn_partials_serves.
 // LO (round 5): SPLIT residual-trunk planes (include/ctrlv_hip.h R1_lo / R2_lo / out_lo): R1 / R2 are read as hi + lo (one
 // fma per plane, hi first -- gemm_epilogue.h's sequence) and the output goes out as hi = rne(v) plus lo = rne(v - hi).
-template <int TM, int TN, bool GEGLU, int EPI, bool RAW = false, bool GNS = false, bool LO = false>
+// UP2 (phase form of the nearest-x2 upsampler conv, include/ctrlv_hip.h up = 2): the tile's rows are INPUT pixels m = r * Wd + x
+// (r = image * H + y) of phase up_ph = 2 py + px, and row m is stored to output pixel (2 r + py) * 2 Wd + 2 x + px =
+// 4 m - 2 x + (2 py Wd + px) -- with Wd a power of two, a mask, a shift and two adds per lane and row pass.
+template <int TM, int TN, bool GEGLU, int EPI, bool RAW = false, bool GNS = false, bool LO = false, bool UP2 = false>
 __device__ __forceinline__ void gemm_epilogue_lds(const ctrlv_gemm_desc& d, f32x16 (&acc)[TM][TN], int bm, int bn,
                                                   int wr, int wc, int WTM, int WTN, int lane, char* p0, char* p1,
                                                   char* p2, char* p3, const char* bias_lds, const char* gelu_tab,
-                                                  char* gns_strip = nullptr) {
+                                                  char* gns_strip = nullptr, int up_ph = 0) {
+  static_assert(!UP2 || (!GEGLU && EPI == 0 && !RAW && !GNS), "phase form: bias-only epilogue");
   constexpr unsigned kOOB = 0xFFFFFFFFu;
   constexpr int kFlags = 0x00020000;
   const int r32 = lane & 31, hsel = lane >> 5, l4 = lane & 3;
@@ -285,6 +289,8 @@ __device__ __forceinline__ void gemm_epilogue_lds(const ctrlv_gemm_desc& d, f32x
     const unsigned r1_base = (unsigned)m0 * (unsigned)(d.ldr1 * 2) + (unsigned)(ocol0 * 2);
     const unsigned r2_base = (unsigned)m0 * (unsigned)(d.ldr2 * 2) + (unsigned)(ocol0 * 2);
     const unsigned o_base = (unsigned)m0 * (unsigned)(d.ldo * 2) + (unsigned)(ocol0 * 2);
+    const int up_rows = UP2 ? d.M >> 2 : 0;                          // UP2: input pixels (rows of one phase)
+    const int up_c = UP2 ? (up_ph >> 1) * 2 * d.Wd + (up_ph & 1) : 0;
     auto load_res = [&](int s) {
       const int i = GNS ? s % TM : s / TN, j = GNS ? s / TM : s % TN;
 #pragma unroll
@@ -373,7 +379,7 @@ __device__ __forceinline__ void gemm_epilogue_lds(const ctrlv_gemm_desc& d, f32x
         const float4 v0 = img[pass][0], v1 = img[pass][1];
         float o[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
         const int m = m0 + i * 32 + pass * 16;
-        const bool ok = m < d.M && ocol < d.n_store;
+        const bool ok = m < (UP2 ? up_rows : d.M) && ocol < d.n_store;
         // Fixed operation sequence -- t = acc * s_acc (rounded), then ONE fma per residual -- shared with the 2-stage
         // kernel (gemm_epilogue.h).  Left to the contraction heuristics, the SLP vectoriser paired fma(s_acc, acc, s1*R)
         // in one half of a v_pk_fma_f32 with fma(s1, R, s_acc*acc) in the other: legal, but a layer then differed in an
@@ -438,11 +444,13 @@ __device__ __forceinline__ void gemm_epilogue_lds(const ctrlv_gemm_desc& d, f32x
         }
         const uint4 pk = pack_elx8(o);
         const u32x4_t pv = {pk.x, pk.y, pk.z, pk.w};
-        pp_store_out(pv, rsO, ok ? o_base : kOOB, ((i * 32 + pass * 16) * d.ldo + j * 32) * 2);
+        // (UP2: the row's own offset per lane, only the column block in the scalar)
+        const unsigned o_row = UP2 ? (unsigned)(4 * m - 2 * (m & (d.Wd - 1)) + up_c) * (unsigned)(d.ldo * 2) + (unsigned)(ocol0 * 2) : o_base;
+        pp_store_out(pv, rsO, ok ? o_row : kOOB, UP2 ? j * 64 : ((i * 32 + pass * 16) * d.ldo + j * 32) * 2);
         if (LO) {
           const uint2 pl = split_lo8(o, pk);
           const u32x2_t pvl = {pl.x, pl.y};
-          pp_store_out_lo(pvl, rsOL, ok ? (o_base >> 1) : kOOB, (i * 32 + pass * 16) * d.ldo + j * 32);
+          pp_store_out_lo(pvl, rsOL, ok ? (o_row >> 1) : kOOB, UP2 ? j * 32 : (i * 32 + pass * 16) * d.ldo + j * 32);
         }
       }
       if (GNS && i == TM - 1) {
@@ -635,8 +643,12 @@ __device__ __forceinline__ void gemm_epilogue_lds(const ctrlv_gemm_desc& d, f32x
 // HAS_A2: the launch has a second A source for channels >= c_split (skip concat).  Only the plain-GEMM / bias-only
 // combination exists (the 1x1 shortcut convs of the up blocks; every other consumer of a concat reads the GroupNorm
 // output), so all other instantiations carry no source-select instructions in their hot loop (~15 of ~95 per half-step).
+// UP2: the nearest-x2 upsampler conv as four 2x2 convs on the LOW-resolution input, one per output parity (include/ctrlv_hip.h
+// up = 2): 4 Cin of contraction per output pixel instead of 9 Cin.  The four phases are extra ROW BLOCKS of the tile order (as
+// the K slices are): a tile holds 256 input pixels of ONE phase, so the tap displacement and the weight panel are scalars of
+// the tile and the hot loop is the per-tap gather's; only the epilogue's row addresses know the output grid.
 template <int BN, int WM, int WN, int MODE, bool GEGLU, int EPI, bool HAS_A2 = false, bool RAW = false, bool HALO = false,
-          bool GNS = false, bool LO = false>
+          bool GNS = false, bool LO = false, bool UP2 = false>
 __global__ __launch_bounds__(512) void gemm_pp_kernel(const ctrlv_gemm_desc d, const int cgrp) {
 #if defined(__HIP_DEVICE_COMPILE__)   // the body uses device-only types (__amdgpu_buffer_rsrc_t): keep it out of the host pass
   constexpr int BM = 256, NW = 8, NH = 4;
@@ -645,6 +657,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const ctrlv_gemm_desc d, c
   constexpr int A_SLOT = BM * 64, B_SLOT = BN * 64, SLOT = A_SLOT + B_SLOT;
   constexpr int A_TOT = BM / 16, B_TOT = BN / 16;            // 1-KiB DMA pieces (16 rows x 64 B) per half-step
   static_assert(!HALO || (MODE == 1 && !HAS_A2 && !GEGLU), "row-halo staging: 3x3 gather only");
+  static_assert(!UP2 || (MODE == 1 && !HALO && !HAS_A2 && !GEGLU && !RAW && !GNS && EPI == 0), "phase form: 3x3 gather, bias only");
   // HALO: one A piece per wave and half-step (piece POS * 8 + wid of the row-halo slot of the NEXT (dy, channel block)
   // triple, POS = half-step mod 3); pieces beyond the slot's real ones go to the dummy KiB
   constexpr int A_Q = HALO ? 1 : A_TOT / NW;                 // per wave (2)
@@ -689,8 +702,9 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const ctrlv_gemm_desc d, c
   // the tile order (row block mt -> slice mt / tiles_m_real): only the per-tile lane offsets know about them.
   constexpr bool KS = EPI == 8;
   const int tiles_n = (d.N + BN - 1) / BN;
-  const int tiles_m_real = (d.M + BM - 1) / BM;
-  const int tiles_m = KS ? tiles_m_real * d.ksplit : tiles_m_real;
+  const int up_rows = UP2 ? d.M >> 2 : 0;                     // UP2: input pixels = rows of one phase (d.M counts output pixels)
+  const int tiles_m_real = ((UP2 ? up_rows : d.M) + BM - 1) / BM;
+  const int tiles_m = KS ? tiles_m_real * d.ksplit : (UP2 ? tiles_m_real * 4 : tiles_m_real);
   const int ntiles = tiles_m * tiles_n;
   const int G = gridDim.x;
   // Tile order.  Tile numbers run over COLUMN GROUPS of `cgrp` column tiles: all row blocks of group 0 (row-major inside the
@@ -715,9 +729,10 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const ctrlv_gemm_desc d, c
   // tile of round r for this block: XCD-contiguous inside every window of G tiles
   const int my_first = xcd_remap(blockIdx.x, G);
   const int my_ntiles = (ntiles - my_first + G - 1) / G;       // >= 1 (grid <= ntiles)
-  const int J = d.taps * (d.Cin >> 5);                       // half-steps per tile (>= 4: ctrlv_gemm_pp_supports)
+  const int ktaps = UP2 ? 4 : d.taps;                        // taps of the contraction (UP2: the 2x2 taps of a phase)
+  const int J = ktaps * (d.Cin >> 5);                        // half-steps per tile (>= 4: ctrlv_gemm_pp_supports)
   const int wcin = KS ? d.w_cin : d.Cin;                     // channels per tap in W
-  const long ktot = (long)d.taps * wcin;
+  const long ktot = (long)ktaps * wcin;
 
   // ---- DMA addressing.  Sources go through buffer descriptors (buffer_load ... lds): address = base + voffset (per
   // lane) + soffset (scalar), and only the per-lane part is range-checked.  So a lane's offset is computed ONCE per
@@ -741,7 +756,8 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const ctrlv_gemm_desc d, c
   const __amdgpu_buffer_rsrc_t rsA2 = __builtin_amdgcn_make_buffer_rsrc(
       (void*)((const char*)(d.A2 ? d.A2 : d.A) - bias_a2), 0, (int)(d.A2 ? a_rows * d.lda2 * 2 + bias_a2 : 0), 0x00020000);
   const __amdgpu_buffer_rsrc_t rsW =
-      __builtin_amdgcn_make_buffer_rsrc((void*)d.W, 0, (int)((long)d.N * ktot * 2), 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc((void*)d.W, 0, (int)((long)d.N * ktot * 2 * (UP2 ? 4 : 1)), 0x00020000);   // (UP2: four panels)
+  int is_py = 0, is_px = 0;                                  // UP2: parity of the issue stream's tile
   unsigned a_voff[A_Q], a_voff2[A_Q];                        // per-lane row offsets into A / A2 (kOOB if the row is invalid)
   unsigned a_mask[A_Q];                                      // modes 1/2, bits 0..8: tap validity; bits 16,17: y/x parity (upsample)
   unsigned b_voff[B_Q];                                      // byte offset of the weight row (+chunk), kOOB if out of range
@@ -770,17 +786,26 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const ctrlv_gemm_desc d, c
   auto setup = [&](int tile) {
     int mt_, nt_;
     tile_mn(tile, mt_, nt_);
-    const int ksl = KS ? mt_ / tiles_m_real : 0;               // K slice (>= ksplit past the last tile: all rows invalid)
-    const int bm = (KS ? mt_ - ksl * tiles_m_real : mt_) * BM, bn = nt_ * BN;
+    const int ksl = (KS || UP2) ? mt_ / tiles_m_real : 0;      // K slice / UP2: phase (past the last tile: all rows invalid)
+    const int bm = ((KS || UP2) ? mt_ - ksl * tiles_m_real : mt_) * BM, bn = nt_ * BN;
     const unsigned ks_off = KS ? (unsigned)(ksl * d.Cin * 2) : 0u;   // byte offset of the slice's first channel
     (void)bm;
+    if constexpr (UP2) { is_py = (ksl >> 1) & 1; is_px = ksl & 1; }
 #pragma unroll
     for (int q = 0; q < (HALO ? 0 : A_Q); ++q) {
       const int m = bm + (q * NW + wid) * 16 + prow;
-      const bool ok = m < d.M && (!KS || ksl < d.ksplit);
+      const bool ok = UP2 ? (m < up_rows && ksl < 4) : (m < d.M && (!KS || ksl < d.ksplit));
       int row = m;
       unsigned mask = 0;
-      if (MODE == 1) {
+      if constexpr (UP2) {
+        // row = the input pixel itself; tap (a, b) of phase (py, px) reads pixel (y - 1 + py + a, x - 1 + px + b)
+        const int pr = m / d.Wd, x = m - pr * d.Wd, y = pr % d.H;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const int yi = y - 1 + is_py + (t >> 1), xi = x - 1 + is_px + (t & 1);
+          if (ok && (unsigned)yi < (unsigned)d.H && (unsigned)xi < (unsigned)d.Wd) mask |= 1u << t;
+        }
+      } else if (MODE == 1) {
         const int hw = d.Ho * d.Wo;
         const int n_img = m / hw, rem = m - n_img * hw;
         const int yo = rem / d.Wo, xo = rem - yo * d.Wo;
@@ -807,7 +832,8 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const ctrlv_gemm_desc d, c
     for (int q = 0; q < B_Q; ++q) {
       const int ib = q * NW + wid;
       const int n = bn + ib * 16 + prow;
-      b_voff[q] = (ib < B_TOT && n < d.N) ? (unsigned)n * (unsigned)(ktot * 2) + coff + ks_off : kOOB;
+      b_voff[q] = (ib < B_TOT && n < d.N && (!UP2 || ksl < 4))
+                      ? (unsigned)(UP2 ? ksl * d.N + n : n) * (unsigned)(ktot * 2) + coff + ks_off : kOOB;   // (UP2: the phase's panel)
     }
   };
 
@@ -842,7 +868,9 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const ctrlv_gemm_desc d, c
     is_second = HAS_A2 && is_cc >= d.c_split;
     is_ld2 = (is_second ? d.lda2 : d.lda) * 2;               // row pitch in bytes of the active source
     int roff = 0;                                            // tap displacement in rows, biased to be >= 0
-    if (MODE == 1) {
+    if constexpr (UP2) {
+      roff = (is_py + (is_tap >> 1)) * d.Wd + is_px + (is_tap & 1);   // (y - 1 + py + a, x - 1 + px + b), biased by Wd + 1
+    } else if (MODE == 1) {
       is_dyo = is_tap / 3 - 1; is_dxo = is_tap % 3 - 1;
       roff = d.up ? 0 : (is_dyo + 1) * d.Wd + is_dxo + 1;    // upsample: per-lane (parity), see issue_a
     } else if (MODE == 2) {
@@ -856,7 +884,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const ctrlv_gemm_desc d, c
   auto issue_a = [&](int q) {
     unsigned voff = (HAS_A2 && is_second) ? a_voff2[q] : a_voff[q];
     if (MODE != 0) {
-      if (MODE == 1 && d.up) {   // nearest x2: source = ((yo + dy - 1) >> 1, (xo + dx - 1) >> 1), relative to the centre
+      if (MODE == 1 && !UP2 && d.up) {   // nearest x2: source = ((yo + dy - 1) >> 1, (xo + dx - 1) >> 1), relative to the centre
         const int oy = ((int)((a_mask[q] >> 16) & 1) + is_dyo) >> 1, ox = ((int)((a_mask[q] >> 17) & 1) + is_dxo) >> 1;
         voff += (unsigned)((oy * d.Wd + ox + d.Wd + 1) * is_ld2);
       }
@@ -1127,8 +1155,8 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const ctrlv_gemm_desc d, c
     const int tile = my_first + tr * G;
     int mt_, nt_;
     tile_mn(tile, mt_, nt_);
-    const int ksl = KS ? mt_ / tiles_m_real : 0;
-    const int bm = (KS ? mt_ - ksl * tiles_m_real : mt_) * BM, bn = nt_ * BN;
+    const int ksl = (KS || UP2) ? mt_ / tiles_m_real : 0;      // (UP2: the tile's phase)
+    const int bm = ((KS || UP2) ? mt_ - ksl * tiles_m_real : mt_) * BM, bn = nt_ * BN;
     // The issue stream runs three half-steps ahead of the consuming one: it stays in this tile for J-3 half-steps and
     // then moves to the block's next tile (two K loops, so that the per-tile lane state is loop-invariant in each --
     // one loop with a conditional switch costs a dozen register copies per half-step).
@@ -1210,13 +1238,14 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const ctrlv_gemm_desc d, c
             }
         }
       } else
-      gemm_epilogue_lds<TM, TN, GEGLU, EPI, RAW, GNS, LO>(d, acc, bm, bn, wr, wc, WTM, WTN, lane_e, sa0 + wid * 1024, sa0 + (NW + wid) * 1024,
+      gemm_epilogue_lds<TM, TN, GEGLU, EPI, RAW, GNS, LO, UP2>(d, acc, bm, bn, wr, wc, WTM, WTN, lane_e, sa0 + wid * 1024, sa0 + (NW + wid) * 1024,
                                 s0 + A_SLOT + wid * 1024,
                                 OWN_P3 ? smem + P3_OFF + wid * 1024 : s0 + A_SLOT + (NW + wid) * 1024, bias_lds,
                                 smem + TAB_OFF,
                                 // GNS + HALO: the last 6 KiB of a row-halo slot are never written (a slot has <= 18 real
                                 // pieces: conv_halo_geometry; dummies go to the dummy KiB): four waves' strips per slot
-                                (GNS && HALO) ? smem + (wid >> 2) * A_HSLOT + 18 * 1024 + (wid & 3) * (2 * WTN * 4) : nullptr);
+                                (GNS && HALO) ? smem + (wid >> 2) * A_HSLOT + 18 * 1024 + (wid & 3) * (2 * WTN * 4) : nullptr,
+                                UP2 ? ksl : 0);
       if (refill) pp_bias_store<WTN>(bias_lds, nb, lane);
       // The accumulators are dead here -- the next tile's first MFMAs overwrite them from a literal-zero C operand --
       // but that redefinition sits behind a `j == 0` test inside the K loop, so the compiler would keep all 128-160
@@ -1250,7 +1279,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const ctrlv_gemm_desc d, c
 }
 
 template <int BN, int WM, int WN, int MODE, bool GEGLU, int EPI, bool HAS_A2 = false, bool RAW = false, bool HALO = false,
-          bool GNS = false, bool LO = false>
+          bool GNS = false, bool LO = false, bool UP2 = false>
 int launch_one(const ctrlv_gemm_desc& d, bool persistent, hipStream_t stream) {
   // DMA ring + one bias strip (BN / WN floats) per wave + one dummy piece (ragged B piece count / row-halo staging) +
   // private fourth staging pieces (128-wide tile only) + the Phi table (GEGLU only); HALO: three 24-KiB row-halo slots in
@@ -1260,14 +1289,15 @@ int launch_one(const ctrlv_gemm_desc& d, bool persistent, hipStream_t stream) {
   static_assert(smem <= 160 * 1024, "ping-pong tile does not fit the LDS");
   // per-device caches (a process may drive several GPUs; the dynamic-LDS attribute is per device code object)
   static bool attr_set[CTRLV_MAX_DEVICES] = {};
-  auto kfn = gemm_pp_kernel<BN, WM, WN, MODE, GEGLU, EPI, HAS_A2, RAW, HALO, GNS, LO>;
+  auto kfn = gemm_pp_kernel<BN, WM, WN, MODE, GEGLU, EPI, HAS_A2, RAW, HALO, GNS, LO, UP2>;
   const int dev = ctrlv_current_device();
   if (!attr_set[dev]) {
     CTRLV_HIP_TRY(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
     attr_set[dev] = true;
   }
   const int num_cu = ctrlv_num_cu(dev);
-  const int tiles = ((d.M + 255) / 256) * ((d.N + BN - 1) / BN) * (EPI == 8 ? d.ksplit : 1);
+  // (UP2: four phases of ceil(input pixels / 256) row blocks each -- a tile never straddles two phases)
+  const int tiles = (UP2 ? 4 * (((d.M >> 2) + 255) / 256) : (d.M + 255) / 256) * ((d.N + BN - 1) / BN) * (EPI == 8 ? d.ksplit : 1);
   // persistent: one 512-thread workgroup per CU, every workgroup the same number of tiles.  1800 tiles (the N = 320 layers of
   // the 72 x 128 level) are 8 rounds on 256 CUs with 8 workgroups in the last one: 225 workgroups finish at the same time
   // and leave 31 CUs to the other stream's kernels (and their power to the clock) for the whole launch, not for its tail.

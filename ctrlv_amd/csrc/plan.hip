@@ -132,7 +132,10 @@ struct Transformer {
   float* frame_emb = nullptr;     // [cfg.num_frames][C] fp32, prepared at load time
   std::string name;
 };
-struct Resample { int C = 0; Linear conv; bool present = false; };
+struct Resample {
+  int C = 0; Linear conv; bool present = false;
+  el_t* wph = nullptr;      // up-sampler only: the four 2x2 phase panels [4][C][4 C] (ctrlv_pack_up_phase_weight), for up = 2
+};
 struct DownBlock { std::vector<ResBlock> res; std::vector<Transformer> attn; Resample down; };
 struct UpBlock { std::vector<ResBlock> res; std::vector<Transformer> attn; Resample up; };
 struct CrossOut { int off, c; Linear to_out; };
@@ -329,6 +332,15 @@ struct Loader {
     TRY(pack_w(mod + ".weight", N, C, 9, l, C, 0, 0, 0));
     return pack_v(mod + ".bias", N, l.b, 0, 0, 0);
   }
+  // the phase panels of an up-sampler conv (ctrlv_gemm_desc.up = 2), from the parameter itself: taps summed in fp32, one rounding
+  int up_phase(const std::string& mod, int N, int C, el_t** dst) {
+    const ctrlv_tensor_desc* t;
+    TRY(find(mod + ".weight", &t, (long)N * C * 9));
+    const void* src;
+    TRY(dev_ptr(t, &src));
+    TRY(alloc((size_t)16 * N * C * 2, (void**)dst, false));
+    return ctrlv_pack_up_phase_weight(src, t->dtype, N, C, *dst, st);
+  }
   int conv_t(const std::string& mod, int N, int C, Linear& l) {       // k = t*C + c
     TRY(new_linear(l, N, 3 * C, true));
     TRY(pack_w(mod + ".weight", N, C, 3, l, C, 0, 0, 0));
@@ -500,9 +512,9 @@ void gemm_work(const ctrlv_gemm_desc& d, int* fam, double* flops, double* bytes)
   *fam = d.mode == 1 ? CTRLV_FAM_GEMM_CONV3X3 : (d.mode == 2 ? CTRLV_FAM_GEMM_CONV_TEMPORAL : CTRLV_FAM_GEMM_LINEAR);
   const double n_alg = d.geglu ? d.N : (d.N < d.n_store ? d.N : d.n_store);
   const double n_out = d.geglu ? (d.n_store < d.N / 2 ? d.n_store : d.N / 2) : d.n_store;
-  const double K = (double)d.taps * d.Cin;
+  const double K = (double)(d.mode == 1 && d.up == 2 ? 4 : d.taps) * d.Cin;       // (phase form: 2x2 taps per output pixel)
   *flops = 2.0 * d.M * n_alg * K;
-  *bytes = (double)d.M * d.Cin * 2 + (double)d.M * n_out * ((d.out_f32 & 1) ? 4 : 2) + (double)d.N * K * 2 +
+  *bytes = (double)d.M * d.Cin * 2 + (double)d.M * n_out * ((d.out_f32 & 1) ? 4 : 2) + (double)d.N * K * 2 * (d.mode == 1 && d.up == 2 ? 4 : 1) +
            (d.R1 ? (double)d.M * n_out * 2 : 0) + (d.R2 ? (double)d.M * n_out * 2 : 0) +
            ((d.R1_lo ? 1 : 0) + (d.R2_lo ? 1 : 0) + (d.out_lo ? 1 : 0)) * (double)d.M * n_out;       // (lo planes: 1 byte)
 }
@@ -533,7 +545,7 @@ int gemm(Ctx& c, const ctrlv_gemm_desc& d0) {
     if (c.overflow) { ctrlv_set_error("plan forward: workspace too small (need >= %zu bytes)", c.peak); return CTRLV_E_BAD_ARG; }
     int fam; double fl, by;
     gemm_work(d, &fam, &fl, &by);
-    ProfScope ps(c, fam, fl, by, d.M, d.N, d.taps * d.Cin, (d.geglu ? 1 : 0) | ((d.R1 ? 1 : 0) + (d.R2 ? 1 : 0)) << 1 | d.vmode << 3);
+    ProfScope ps(c, fam, fl, by, d.M, d.N, (d.mode == 1 && d.up == 2 ? 4 : d.taps) * d.Cin, (d.geglu ? 1 : 0) | ((d.R1 ? 1 : 0) + (d.R2 ? 1 : 0)) << 1 | d.vmode << 3);
     rc = ctrlv_gemm(&d, c.st);
   }
   c.release(mk);
@@ -880,6 +892,8 @@ int run_resample(Ctx& c, const Resample& r, const Trk& x, int H, int W, bool up,
   ctrlv_gemm_desc d = gd(x.hi, r.C, r.conv, out.hi, r.C, (int)M, r.C, r.C, r.C);
   set_out(d, out);
   d.taps = 9; d.mode = 1; d.H = H; d.Wd = W; d.Ho = Ho; d.Wo = Wo; d.stride = up ? 1 : 2; d.up = up ? 1 : 0;
+  // the up-sampler in phase form (four 2x2 convs, 4/9 of the multiply-adds) where the LAYER's shape is served
+  if (up && r.wph && ctrlv_gemm_up_phase_serves(&d)) { d.up = 2; d.W = r.wph; }
   TRY(gemm(c, d));
   *out_ = out; *Ho_ = Ho; *Wo_ = Wo;
   return CTRLV_OK;
@@ -1209,8 +1223,12 @@ extern "C" int ctrlv_plan_load_weights(ctrlv_plan* p, const ctrlv_tensor_desc* t
       if (p->down[i].down.present)
         TRY(L.conv3x3("down_blocks." + std::to_string(i) + ".downsamplers.0.conv", p->down[i].down.C, p->down[i].down.C,
                       p->down[i].down.conv));
-      if (c.kind == 0 && p->up[i].up.present)
-        TRY(L.conv3x3("up_blocks." + std::to_string(i) + ".upsamplers.0.conv", p->up[i].up.C, p->up[i].up.C, p->up[i].up.conv));
+      if (c.kind == 0 && p->up[i].up.present) {
+        Resample& u = p->up[i].up;
+        const std::string mod = "up_blocks." + std::to_string(i) + ".upsamplers.0.conv";
+        TRY(L.conv3x3(mod, u.C, u.C, u.conv));
+        if (u.conv.n == u.C) TRY(L.up_phase(mod, u.C, u.C, &u.wph));      // (no padded weight rows: the panels are [C][4 C])
+      }
     }
     if (c.kind == 0) {
       TRY(L.norm("conv_norm_out", c0, p->gno));

@@ -456,16 +456,26 @@ class Upsample2D(nn.Module):
         self.C = channels
         self.conv = nn.Conv2d(channels, channels, 3, padding=1)
         self._pk = None
+        self._pk_up = None
 
     def pack(self):
         self._pk = (packing.pack_conv3x3(self.conv.weight), _f32(self.conv.bias))
+        # the four 2x2 phase panels (ops.pack_up_phase_weight; csrc/plan.hip Loader::up_phase), from the parameter itself
+        w = self.conv.weight
+        self._pk_up = ops.pack_up_phase_weight(w, self._pk[0].dtype) if w.is_cuda else None      # (else: at the first run)
 
     def run(self, ctx, x, H, W):
-        """nearest x2 upsample fused into the conv's gather (source pixel = (y>>1, x>>1))."""
+        """nearest x2 upsample + conv: in phase form (four 2x2 convs on the low-resolution input, conv[5] = 2) where the
+        layer's shape is served, else fused into the 3x3 gather (source pixel = (y>>1, x>>1)) -- csrc/plan.hip run_resample."""
         N = ctx.B * ctx.F
         out = ctx.ws.trunk((N * 4 * H * W, self.C))
-        ops.gemm(x, self._pk[0], out, N=self.C, cin=self.C, taps=9, mode=1, conv=(H, W, 2 * H, 2 * W, 1, 1),
-                 bias=self._pk[1], out_lo=_lo(out))
+        kw = dict(N=self.C, cin=self.C, taps=9, mode=1, bias=self._pk[1], out_lo=_lo(out))
+        w, up = self._pk[0], 1
+        if w.shape[0] == self.C and ops.gemm_up_phase_serves(x, w, out, conv=(H, W, 2 * H, 2 * W, 1, 1), **kw):
+            if self._pk_up is None:
+                self._pk_up = ops.pack_up_phase_weight(self.conv.weight, w.dtype)
+            w, up = self._pk_up, 2
+        ops.gemm(x, w, out, conv=(H, W, 2 * H, 2 * W, 1, up), **kw)
         return out, 2 * H, 2 * W
 
 

@@ -249,6 +249,27 @@ def gemm_gn_partials_serves(A, W, out, **kw):
     return bool(_L(A, W).ctrlv_gemm_gn_partials_serves(ctypes.byref(_gemm_desc(A, W, out, **kw))))
 
 
+def gemm_up_phase_serves(A, W, out, **kw):
+    """Whether the nearest-x2 upsampler conv `gemm(A, W, out, **kw)` (mode 1, conv = (H, W, 2H, 2W, 1, 1 or 2)) is served in
+    phase form, i.e. with conv[5] = 2 and W = `pack_up_phase_weight(...)` -- the launcher's own predicate: a function of
+    the layer's shape, never of the image count."""
+    return bool(_L(A, W).ctrlv_gemm_up_phase_serves(ctypes.byref(_gemm_desc(A, W, out, **kw))))
+
+
+def pack_up_phase_weight(weight, dtype=torch.bfloat16):
+    """The four 2x2 phase panels [4, N, 4*Cin] (element type `dtype`) of an upsampler conv's parameter [N, Cin, 3, 3] for
+    `gemm(..., conv=(H, W, 2H, 2W, 1, 2))`: the taps of each phase summed in fp32 and rounded once
+    (ctrlv_pack_up_phase_weight)."""
+    w = weight.detach().contiguous()
+    _need_gpu(w, "weight")
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or w.dtype not in _DT:
+        raise ValueError(f"pack_up_phase_weight: expected a float [N, Cin, 3, 3] parameter, got {tuple(w.shape)} {w.dtype}")
+    N, C = w.shape[:2]
+    dst = torch.empty(4, N, 4 * C, dtype=dtype, device=w.device)
+    check(_L(dst).ctrlv_pack_up_phase_weight(_p(w), _DT[w.dtype], N, C, _p(dst), _stream()), "ctrlv_pack_up_phase_weight")
+    return dst
+
+
 def gemm(A, W, out, **kw):
     """out = epilogue(gather-GEMM(A[, A2], W)).  `conv` = (H, W, Ho, Wo, stride, up); `temporal` = (F, S).
     Keywords: see `_gemm_desc` (the fields of ctrlv_gemm_desc)."""
@@ -263,6 +284,9 @@ def gemm(A, W, out, **kw):
         if need:
             d.splitk_ws = _p(_scratch(A.device, need, "splitk", floor=64 << 20))      # (fp32 partials of the K slices)
     cin, taps, mode, geglu = d.Cin, d.taps, d.mode, d.geglu
+    wf = 1
+    if mode == 1 and d.up == 2:         # phase form of the upsampler conv: 2x2 taps per output pixel, four weight panels
+        taps, wf = 4, 4
     R1, R2, raw_out, act = kw.get("R1"), kw.get("R2"), kw.get("raw_out"), kw.get("act", 0)
     out_f32 = kw.get("out_f32", False)
     ev = _prof.begin()
@@ -272,7 +296,7 @@ def gemm(A, W, out, **kw):
         fam = "gemm_conv3x3" if mode == 1 else ("gemm_conv_temporal" if mode == 2 else "gemm_linear")
         esz = 4 if out_f32 else 2
         n_out = d.n_store if not geglu else min(d.n_store, d.N // 2)
-        nbytes = (d.M * cin * 2 * (1 if mode == 0 else 1) + d.M * n_out * esz + d.N * taps * cin * 2
+        nbytes = (d.M * cin * 2 * (1 if mode == 0 else 1) + d.M * n_out * esz + d.N * taps * cin * 2 * wf
                   + (d.M * n_out * 2 if R1 is not None else 0) + (d.M * n_out * 2 if R2 is not None else 0)
                   + (d.M * n_out * 2 if raw_out is not None else 0))
         _prof.end(ev, fam, 2.0 * d.M * n_alg * taps * cin, float(nbytes),

@@ -90,7 +90,16 @@ typedef struct ctrlv_gemm_desc {
   int32_t M, N, Cin, taps;
   int32_t lda, lda2, c_split;
   int32_t mode;                       /* 0 plain, 1 conv2d 3x3, 2 temporal (3,1,1) */
-  int32_t H, Wd, Ho, Wo, stride, up;  /* mode 1: input H x Wd (before upsample), output Ho x Wo */
+  int32_t H, Wd, Ho, Wo, stride, up;  /* mode 1: input H x Wd (before upsample), output Ho x Wo.  up = 1: nearest-x2 upsample
+                                         fused into the 3x3 gather (source pixel (y >> 1, x >> 1)), W = [N][9 Cin].
+                                         up = 2 (stride 1, Ho = 2 H, Wo = 2 Wd; only where ctrlv_gemm_up_phase_serves(d)): the
+                                         same conv in PHASE FORM -- four 2x2 convs on the low-resolution input, one per output
+                                         parity p = 2 py + px: out[2 i + py, 2 j + px] = sum_{a, b in {0, 1}} W[p][.][(2 a + b) Cin
+                                         + c] x[i - 1 + py + a, j - 1 + px + b][c], pixels outside H x Wd read as zero.  W = the
+                                         four panels [4][N][4 Cin] written by ctrlv_pack_up_phase_weight; M, Ho, Wo, taps = 9
+                                         and every other field as for up = 1.  4/9 of the multiply-adds; each phase weight is
+                                         a sum of 1, 2, 2 or 4 taps rounded once to the element type, so the result equals
+                                         the up = 1 launch up to that one rounding (exactly, where the sums are exact). */
   int32_t F, S;                       /* mode 2: frames per clip, pixels per frame.  mode 0: S = optional rows-per-image
                                          hint (0 = unknown), the shape key of the split plan (ctrlv_gemm_splitk_ws_bytes) */
   int32_t ldo, n_store;               /* output leading dimension; columns >= n_store are not written */
@@ -157,6 +166,15 @@ size_t ctrlv_gemm_splitk_ws_bytes(const ctrlv_gemm_desc* d);
  * block), N = 320 / 640 / 1280, image size a multiple of 64 pixels.  Depends on the layer's shape only, never on the
  * batch size. */
 int ctrlv_gemm_gn_partials_serves(const ctrlv_gemm_desc* d);
+/* 1 if ctrlv_gemm serves this nearest-x2 upsampler conv (mode 1, taps 9, stride 1, up = 1 or 2, Ho = 2 H, Wo = 2 Wd) in phase
+ * form (ctrlv_gemm_desc.up = 2): Wd a power of two <= 256, Cin a multiple of 64, bias-only epilogue, 8-element pitches; out_lo
+ * only in the fp16 library with N a multiple of 320.  Depends on the layer's shape only, never on the image count. */
+int ctrlv_gemm_up_phase_serves(const ctrlv_gemm_desc* d);
+/* Phase weights of such a conv from its parameter w [N][Cin][3][3] (device; dtype 0 fp32 / 1 fp16 / 2 bf16): dst[p][n][(2 a +
+ * b) Cin + c] = sum of w[n][c][ky][kx] over ky in KY(py, a), kx in KY(px, b), p = 2 py + px, where KY(0, 0) = {0}, KY(0, 1) =
+ * {1, 2}, KY(1, 0) = {0, 1}, KY(1, 1) = {2}; summed in fp32 (ky outer, kx inner), rounded once to the element type.  dst: 16 N
+ * Cin elements. */
+int ctrlv_pack_up_phase_weight(const void* w, int dtype, int N, int Cin, void* dst, ctrlv_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * GroupNorm(32) (+SiLU), channels-last.  Replaces nn.GroupNorm + SiLU of ResnetBlock2D.norm1/norm2,
