@@ -137,6 +137,7 @@ SIGNATURES = {
                                       c_int, c_void_p, c_void_p]),
     "ctrlv_axpby_split": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ctrlv_plan_set_trunk_mode": (c_int, [c_void_p, c_int]),
+    "ctrlv_plan_set_ff_precision": (c_int, [c_void_p, c_int]),
     "ctrlv_groupnorm_stats": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
                                       c_void_p]),
     "ctrlv_groupnorm_apply": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
@@ -152,6 +153,10 @@ SIGNATURES = {
     "ctrlv_ff_fused": (c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.POINTER(GemmDesc), c_void_p]),
     "ctrlv_ff_fused_ln": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_int, c_void_p,
                                   c_void_p, ctypes.POINTER(GemmDesc), c_void_p]),
+    "ctrlv_quant_rows_f8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_int,
+                                    c_void_p, c_int, c_void_p, c_void_p]),
+    "ctrlv_gemm_f8": (c_int, [ctypes.POINTER(GemmDesc), c_void_p, c_void_p, c_void_p]),
+    "ctrlv_gemm_f8_serves": (c_int, [ctypes.POINTER(GemmDesc)]),
     "ctrlv_temporal_fused_weight_bytes": (c_size_t, []),
     "ctrlv_temporal_fused_pack": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "ctrlv_temporal_fused": (c_int, [ctypes.POINTER(TemporalFusedDesc), c_void_p]),
@@ -245,7 +250,7 @@ _tls = threading.local()  # .failed = the library whose call returned a negative
 # c_int-returning entry points whose value is NOT a status code
 _NO_STATUS = {"ctrlv_abi_version", "ctrlv_elem_dtype", "ctrlv_build_id", "ctrlv_last_error", "ctrlv_ff_fused_w1f_bytes",
               "ctrlv_gemm_gn_partials_serves", "ctrlv_gemm_up_phase_serves", "ctrlv_ff_fused_serves", "ctrlv_plan_num_down_residuals",
-              "ctrlv_temporal_fused_serves",
+              "ctrlv_temporal_fused_serves", "ctrlv_gemm_f8_serves",
               # size queries (size_t: never wrapped, listed with their kin for the reader)
               "ctrlv_gemm_tokens_ws_bytes", "ctrlv_clip_plan_workspace_bytes", "ctrlv_vae_plan_workspace_bytes"}
 

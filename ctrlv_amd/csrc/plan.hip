@@ -120,6 +120,10 @@ struct FeedFwd {
   Linear proj, out;
   el_t* w1f = nullptr;      // C = 320 only: the fragment-major forms of ctrlv_ff_fused (ff_fused.hip), else null
   el_t* w2f = nullptr;
+  // FF precision 1 (ctrlv_plan_set_ff_precision): the e4m3 codes of proj.w / out.w and their per-row scales
+  // (ctrlv_quant_rows_f8 of the packed weights; only where both K are multiples of 128), else null
+  uint8_t* proj8 = nullptr; float* proj8_s = nullptr;
+  uint8_t* out8 = nullptr; float* out8_s = nullptr;
 };
 struct Transformer {
   int C = 0;
@@ -147,6 +151,8 @@ struct ctrlv_plan {
   int device = 0;
   bool loaded = false;
   int trunk_mode = 0;         // 0: plain residual trunk, 1: SPLIT hi + lo planes (ctrlv_plan_set_trunk_mode)
+  int ff_precision = 0;       // 0: feed-forward GEMMs in the element type, 1: e4m3 operands (ctrlv_plan_set_ff_precision)
+  std::vector<void*> owned_f8;   // the e4m3 feed-forward weights and scales (made when the mode is set / at load_weights)
   std::vector<DownBlock> down;
   ResBlock mid_r0, mid_r1;
   Transformer mid_attn;
@@ -737,6 +743,46 @@ int ln_ff(Ctx& c, const FeedFwd& f, const Norm& nm, const Trk& xraw, const float
                  (double)outd.M * 320 * 2 * (2 + (outd.R1 ? 1 : 0) + (outd.R2 ? 1 : 0)), outd.M, 320, 320, 0x300);
     return ctrlv_ff_fused_ln(xraw.hi, C, nm.g, nm.b, 1e-5f, lnV, lnvdiv, lnvmod, lnldv, f.w1f, f.w2f, &outd, c.st);
   }
+  if (c.p->ff_precision == 1 && f.proj8 && f.out8 && !xraw.lo) {
+    // FF precision 1: LayerNorm + row quantisation in one pass, the GEGLU projection on e4m3 operands, the
+    // row quantisation of u, the output projection on e4m3 operands with the layer's epilogue -- four launches for the three
+    // above, wherever ctrlv_gemm_f8_serves accepts both descriptors (a function of the layer's shape only)
+    ctrlv_gemm_desc p8 = proj, o8 = outd;
+    p8.W = f.proj8; o8.W = f.out8; o8.lda = 4 * C; o8.S = 0;
+    if (ctrlv_gemm_f8_serves(&p8) && ctrlv_gemm_f8_serves(&o8)) {
+      if (*u == nullptr) *u = c.rows(proj.M, 4 * C);
+      const size_t mk = c.mark();
+      const long M = proj.M;
+      uint8_t* q = (uint8_t*)c.alloc((size_t)M * 4 * C);       // codes of the normalised rows (C wide), then of u (4C wide)
+      float* qs = (float*)c.alloc((size_t)M * 4);
+      int rc = CTRLV_OK;
+      if (!c.dry) {
+        if (c.overflow) { ctrlv_set_error("plan forward: workspace too small (need >= %zu bytes)", c.peak); return CTRLV_E_BAD_ARG; }
+        p8.A = q; p8.lda = C; p8.out = *u;
+        o8.A = q; o8.lda = 4 * C;
+        {
+          ProfScope ps(c, CTRLV_FAM_LAYERNORM, 0.0, 3.0 * (double)M * C, (int)M, C, 0, 0x400);
+          rc = ctrlv_quant_rows_f8(xraw.hi, (int)M, C, C, nm.g, nm.b, 1e-5f, lnV, lnvdiv, lnvmod, lnldv, q, C, qs, c.st);
+        }
+        if (rc == CTRLV_OK) {
+          ProfScope ps(c, CTRLV_FAM_GEMM_LINEAR, 2.0 * M * 8.0 * C * C, (double)M * C + (double)M * 4 * C * 2 + 8.0 * C * C, (int)M, 8 * C, C, 0x401);
+          rc = ctrlv_gemm_f8(&p8, qs, f.proj8_s, c.st);
+        }
+        if (rc == CTRLV_OK) {
+          ProfScope ps(c, CTRLV_FAM_LAYERNORM, 0.0, 3.0 * (double)M * 4 * C, (int)M, 4 * C, 0, 0x400);
+          rc = ctrlv_quant_rows_f8(*u, (int)M, 4 * C, 4 * C, nullptr, nullptr, 0.f, nullptr, 1, 1, 0, q, 4 * C, qs, c.st);
+        }
+        if (rc == CTRLV_OK) {
+          ProfScope ps(c, CTRLV_FAM_GEMM_LINEAR, 2.0 * M * 4.0 * C * C,
+                       (double)M * 4 * C + (double)M * C * 2 * (1 + (o8.R1 ? 1 : 0) + (o8.R2 ? 1 : 0)) + 4.0 * C * C, (int)M, C, 4 * C,
+                       0x400 | ((o8.R1 ? 1 : 0) + (o8.R2 ? 1 : 0)) << 1 | o8.vmode << 3);
+          rc = ctrlv_gemm_f8(&o8, qs, f.out8_s, c.st);
+        }
+      }
+      c.release(mk);
+      return rc;
+    }
+  }
   TRY(layernorm(c, xraw, proj.M, C, nm, tt, lnV, lnvdiv, lnvmod, lnldv));
   return ff_pair(c, f, proj, outd, C, u);
 }
@@ -1123,7 +1169,40 @@ int controlnet_forward(ctrlv_plan* p, Ctx& c, const void* sample, const void* co
   return CTRLV_OK;
 }
 
+void free_f8(ctrlv_plan* p) {
+  for (void* d : p->owned_f8) (void)hipFree(d);
+  p->owned_f8.clear();
+  for_each_tr(p, [&](Transformer& t) {
+    for (FeedFwd* f : {&t.s_ff, &t.t_ffin, &t.t_ff}) { f->proj8 = f->out8 = nullptr; f->proj8_s = f->out8_s = nullptr; }
+  });
+}
+// e4m3 codes + per-row scales of every feed-forward whose two contractions the FP8 GEMM can serve (K multiples of 128), from
+// the packed element weights (ctrlv_quant_rows_f8: one scale per output channel, GEGLU rows keep their interleaving)
+int make_f8(ctrlv_plan* p, hipStream_t st) {
+  free_f8(p);
+  int rc = CTRLV_OK;
+  auto one = [&](const Linear& l, uint8_t** q, float** s) -> int {
+    void* d = nullptr;
+    CTRLV_HIP_TRY(hipMalloc(&d, (size_t)l.n * l.k));
+    p->owned_f8.push_back(d);
+    *q = (uint8_t*)d;
+    CTRLV_HIP_TRY(hipMalloc(&d, (size_t)l.n * 4));
+    p->owned_f8.push_back(d);
+    *s = (float*)d;
+    return ctrlv_quant_rows_f8(l.w, l.n, l.k, l.k, nullptr, nullptr, 0.f, nullptr, 1, 1, 0, *q, l.k, *s, st);
+  };
+  for_each_tr(p, [&](Transformer& t) {
+    for (FeedFwd* f : {&t.s_ff, &t.t_ffin, &t.t_ff}) {
+      if (rc != CTRLV_OK || !f->proj.w || !f->out.w || f->proj.k % 128 || f->out.k % 128 || f->out.k > 5120) continue;
+      rc = one(f->proj, &f->proj8, &f->proj8_s);
+      if (rc == CTRLV_OK) rc = one(f->out, &f->out8, &f->out8_s);
+    }
+  });
+  if (rc != CTRLV_OK) free_f8(p);
+  return rc;
+}
 void free_owned(ctrlv_plan* p) {
+  free_f8(p);
   for (void* d : p->owned) (void)hipFree(d);
   p->owned.clear();
   p->xouts.clear();
@@ -1266,6 +1345,7 @@ extern "C" int ctrlv_plan_load_weights(ctrlv_plan* p, const ctrlv_tensor_desc* t
       });
       TRY(rc);
     }
+    if (p->ff_precision == 1) TRY(make_f8(p, L.st));
     return CTRLV_OK;
   };
   const int rc = body();
@@ -1291,8 +1371,31 @@ extern "C" int ctrlv_plan_set_trunk_mode(ctrlv_plan* p, int mode) {
   CTRLV_CHECK_ARG(p != nullptr && (mode == 0 || mode == 1), "plan_set_trunk_mode: mode must be 0 (plain) or 1 (split hi + lo planes)");
   CTRLV_CHECK_ARG(mode == 0 || CTRLV_ELEM_DTYPE == 1, "plan_set_trunk_mode: the split trunk needs the fp16 element library "
                                                       "(libctrlv_hip_f16.so)");
+  CTRLV_CHECK_ARG(mode == 0 || p->ff_precision == 0, "plan_set_trunk_mode: the split trunk does not combine with FF precision 1 "
+                                                     "(ctrlv_plan_set_ff_precision)");
   if (p->trunk_mode != mode) p->ws_cache.clear();       // the workspace grows with the lo planes
   p->trunk_mode = mode;
+  return CTRLV_OK;
+}
+
+extern "C" int ctrlv_plan_set_ff_precision(ctrlv_plan* p, int mode) {
+  CTRLV_CHECK_ARG(p != nullptr && (mode == 0 || mode == 1), "plan_set_ff_precision: mode must be 0 (element type) or 1 (e4m3)");
+  CTRLV_CHECK_ARG(mode == 0 || p->trunk_mode == 0, "plan_set_ff_precision: e4m3 feed-forwards do not combine with the split trunk "
+                                                   "(ctrlv_plan_set_trunk_mode)");
+  if (p->ff_precision == mode) return CTRLV_OK;
+  p->ws_cache.clear();                                  // the workspace grows with the codes and scales
+  if (mode == 1 && p->loaded) {                         // (not loaded yet: ctrlv_plan_load_weights makes them)
+    int dev = 0;
+    const bool sw = hipGetDevice(&dev) == hipSuccess && dev != p->device;
+    if (sw) CTRLV_HIP_TRY(hipSetDevice(p->device));
+    int rc = make_f8(p, nullptr);
+    if (rc == CTRLV_OK && hipDeviceSynchronize() != hipSuccess) { ctrlv_set_error("plan_set_ff_precision: quantising the weights failed"); rc = CTRLV_E_HIP; }
+    if (rc != CTRLV_OK) free_f8(p);
+    if (sw) (void)hipSetDevice(dev);
+    if (rc != CTRLV_OK) return rc;
+  }
+  if (mode == 0) free_f8(p);
+  p->ff_precision = mode;
   return CTRLV_OK;
 }
 

@@ -165,6 +165,43 @@ def _ff_pair(ws, x, ffp, ubox, out, C, rows_per_image=0, **epi):
     ops.gemm(u, wout, out, N=C, cin=4 * C, bias=bout, rows_per_image=rows_per_image, **epi)
 
 
+def _f8_weight(w):
+    """e4m3 codes + per-row scales of a packed feed-forward weight, made once and kept next to it (csrc/plan.hip make_f8)"""
+    f8 = getattr(w, "f8", None)
+    if f8 is None:
+        f8 = w.f8 = ops.quant_rows_f8(w.contiguous())
+    return f8
+
+
+def _ff_f8_route(ws, xraw, ln, ffp, ubox, out, C, ln_V, ln_vdiv, ln_vmod, epi):
+    """The feed-forward on e4m3 operands (ff_dtype "f8"; csrc/plan.hip ln_ff): LayerNorm + row quantisation, the GEGLU
+    projection, the row quantisation of u, the output projection with the layer's epilogue -- where ops.gemm_f8_serves
+    accepts both projections (K multiples of 128).  False: not served, nothing was launched."""
+    wproj, bproj, wout, bout = ffp[:4]
+    if wproj.shape[1] % 128 or wout.shape[1] % 128 or wout.shape[1] > 5120:
+        return False
+    M = xraw.shape[0]
+    epi = _trk_epi(epi, out)
+    (q1w, s1w), (q2w, s2w) = _f8_weight(wproj), _f8_weight(wout)
+    if ubox[0] is None:
+        ubox[0] = ws.alloc((M, 4 * C))
+    u = ubox[0]
+    mk = ws.mark()
+    q = ws.alloc((M * 4 * C,), torch.uint8)
+    qs = ws.alloc((M,), torch.float32)
+    qa, qu = q[:M * C].view(M, C), q.view(M, 4 * C)
+    if not (ops.gemm_f8_serves(qa, q1w, u, N=8 * C, cin=C, bias=bproj, geglu=1)
+            and ops.gemm_f8_serves(qu, q2w, out, N=C, cin=4 * C, bias=bout, **epi)):
+        ws.release(mk)
+        return False
+    ops.quant_rows_f8(xraw, qa, qs, ln=(ln[0], ln[1], 1e-5), V=ln_V, vdiv=ln_vdiv, vmod=ln_vmod)
+    ops.gemm_f8(qa, qs, q1w, s1w, u, N=8 * C, cin=C, bias=bproj, geglu=1)
+    ops.quant_rows_f8(u, qu, qs)
+    ops.gemm_f8(qu, qs, q2w, s2w, out, N=C, cin=4 * C, bias=bout, **epi)
+    ws.release(mk)
+    return True
+
+
 _FF_LN = os.environ.get("CTRLV_FF_LN", "0") not in ("", "0")   # opt-in, the plan's switch (csrc/plan.hip ln_ff)
 
 
@@ -174,6 +211,8 @@ def _ln_ff(ws, xraw, ln, t, ffp, ubox, out, C, ln_V=None, ln_vdiv=1, ln_vmod=1 <
     if _FF_FUSED and _FF_LN and len(ffp) == 6 and _lo(xraw) is None and ops.ff_fused_serves(xraw, out, **_trk_epi(epi, out)):
         ops.ff_fused(xraw, ffp[4], ffp[5], out, bias=ffp[3], ln=(ln[0], ln[1], 1e-5), ln_V=ln_V, ln_vdiv=ln_vdiv,
                      ln_vmod=ln_vmod, **_trk_epi(epi, out))
+        return
+    if getattr(ws, "ff_f8", False) and _lo(xraw) is None and _ff_f8_route(ws, xraw, ln, ffp, ubox, out, C, ln_V, ln_vdiv, ln_vmod, epi):
         return
     if ln_V is not None:
         ops.layernorm(xraw, ln[0], ln[1], 1e-5, t, V=ln_V, vdiv=ln_vdiv, vmod=ln_vmod, x_lo=_lo(xraw))

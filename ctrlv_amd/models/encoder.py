@@ -49,6 +49,10 @@ class SpatioTemporalEncoderBase(HipModelMixin):
     # value like every activation; "fp16x2" = split into an fp16 hi plane + a one-byte e5m2 lo plane (~15 significant bits in 3 bytes) under fp16
     # branches -- fp16 models, both executors; model-level error against the fp32 oracle 1.3e-3 -> < 1e-3.
     trunk_dtype = os.environ.get("CTRLV_TRUNK", "same")
+    # Precision of the transformer feed-forwards: "same" = the element type; "f8" = e4m3 operands on the block-scaled MFMA
+    # for every feed-forward the FP8 GEMM serves (C = 640 / 1280; ops.gemm_f8_serves) -- an opt-in throughput mode with the
+    # error class of bf16 storage, both executors, inference only.  Not with trunk_dtype "fp16x2".
+    ff_dtype = os.environ.get("CTRLV_FF", "same")
 
     def _build_encoder(self, in_channels, down_block_types, block_out_channels, addition_time_embed_dim,
                        projection_class_embeddings_input_dim, layers_per_block, cross_attention_dim,
@@ -144,11 +148,22 @@ class SpatioTemporalEncoderBase(HipModelMixin):
         if self._plan_order != self.time_context_order:
             self._plan.set_time_context_order(self.time_context_order)
             self._plan_order = self.time_context_order
+        if self._plan.ff_mode != self.ff_dtype and self.ff_dtype == "same":
+            self._plan.set_ff_precision("same")   # (leaving the mode comes first: the plan refuses it beside the split trunk)
         if self._plan.trunk_mode != self.trunk_dtype:
             if self.trunk_dtype != "same" and el != torch.float16:
                 raise ValueError('trunk_dtype="fp16x2" needs an fp16 model (the split planes are fp16 elements)')
             self._plan.set_trunk_mode(self.trunk_dtype)
+        if self._plan.ff_mode != self.ff_dtype:
+            self._check_ff_dtype()
+            self._plan.set_ff_precision(self.ff_dtype)
         return self._plan
+
+    def _check_ff_dtype(self):
+        if self.ff_dtype not in ("same", "f8"):
+            raise ValueError(f'ff_dtype must be "same" or "f8" (got {self.ff_dtype!r})')
+        if self.ff_dtype == "f8" and self.trunk_dtype != "same":
+            raise ValueError('ff_dtype="f8" does not combine with trunk_dtype="fp16x2"')
 
     def _plan_inputs(self, sample, timestep, encoder_hidden_states, added_time_ids):
         """Argument checks of _context() + the plain device buffers the C ABI takes (fp32 timestep / added ids,
@@ -240,6 +255,7 @@ class SpatioTemporalEncoderBase(HipModelMixin):
             raise ValueError(f'trunk_dtype must be "same" or "fp16x2" (got {self.trunk_dtype!r})')
         if self.trunk_dtype != "same" and el != torch.float16:
             raise ValueError('trunk_dtype="fp16x2" needs an fp16 model (the split planes are fp16 elements)')
+        self._check_ff_dtype()
         _lib.load(el)                             # raises if the HIP library is missing: no fallback
         if not sample.is_cuda:
             raise _lib.CtrlvHipError("ctrlv_amd models run on a HIP device only; there is no CPU forward "
@@ -259,6 +275,7 @@ class SpatioTemporalEncoderBase(HipModelMixin):
             self._ws = ws
         ws.el = el
         ws.split = self.trunk_dtype == "fp16x2"   # trunk tensors (Workspace.trunk) carry a lo plane, as in the C++ plan
+        ws.ff_f8 = self.ff_dtype == "f8"          # feed-forwards on e4m3 operands where served (blocks._ln_ff), as in the plan
         ws.reset()
         return ws
 

@@ -304,6 +304,65 @@ def gemm(A, W, out, **kw):
     return out
 
 
+def quant_rows_f8(x, q=None, scale=None, ln=None, V=None, vdiv=1, vmod=1 << 30):
+    """Row quantisation to OCP e4m3 (torch.float8_e4m3fn codes as uint8) with one fp32 scale per row: scale[m] = max|y[m]| /
+    448 (1 for an all-zero row), q[m, k] = e4m3(y[m, k] / scale[m]), y = x or -- ln = (gamma, beta, eps) -- the fp32 value
+    of `layernorm(x + V[...])`, never rounded to 16 bits (csrc/quant_f8.hip).  x: [M, K] element rows (row stride a
+    multiple of 8); q: uint8 [M, >= K] (allocated when None), scale: fp32 [M].  Returns (q, scale).  Weights [N, K] are
+    quantised by the same call."""
+    _need_gpu(x, "x")
+    M, K = x.shape
+    if x.stride(1) != 1:
+        raise ValueError("quant_rows_f8: rows must be contiguous")
+    if q is None:
+        q = torch.empty(M, K, dtype=torch.uint8, device=x.device)
+    if scale is None:
+        scale = torch.empty(M, dtype=torch.float32, device=x.device)
+    if q.dtype != torch.uint8 or scale.dtype != torch.float32 or q.shape[0] != M or scale.numel() < M or q.stride(1) != 1:
+        raise ValueError("quant_rows_f8: q must be uint8 [M, >= K] and scale fp32 [M]")
+    g, b, eps = (ln[0], ln[1], float(ln[2])) if ln is not None else (None, None, 0.0)
+    ev = _prof.begin()
+    check(_L(x).ctrlv_quant_rows_f8(_p(x), M, K, x.stride(0), _p(g), _p(b), eps, _p(V), vdiv, vmod,
+                                    V.stride(0) if V is not None else 0, _p(q), q.stride(0), _p(scale), _stream()),
+          "ctrlv_quant_rows_f8")
+    _prof.end(ev, "layernorm", 0.0, 3.0 * M * K, detail=("quant_rows_f8", M, K, 0, 0, 0, 0, 0))
+    return q, scale
+
+
+def _gemm_f8_desc(A, W, out, *, N, cin, el=None, **kw):
+    """(descriptor, library): the element library is the one of `out` / R1 / R2, or -- fp32 output without residuals -- `el`"""
+    if A.dtype != torch.uint8 or W.dtype != torch.uint8:
+        raise ValueError("gemm_f8: A and W hold e4m3 codes as uint8 (quant_rows_f8)")
+    lib = _lib.load(el) if el is not None else _L(out, kw.get("R1"), kw.get("R2"))
+    return _gemm_desc(A, W, out, N=N, cin=cin, **kw), lib
+
+
+def gemm_f8_serves(A, W, out, **kw):
+    """Whether `gemm_f8(A, W, out, ...)` is served (the launcher's own predicate, host code: csrc/gemm_f8.hip) -- mode 0, no
+    lo planes, K a multiple of 128 (so not the C = 320 feed-forward, which keeps ff_fused), N a multiple of 32, 16-byte pitches:
+    a function of the layer's shape only."""
+    d, lib = _gemm_f8_desc(A, W, out, **kw)
+    return bool(lib.ctrlv_gemm_f8_serves(ctypes.byref(d)))
+
+
+def gemm_f8(A, a_scale, W, w_scale, out, **kw):
+    """out = epilogue(a_scale[m] w_scale[n] (A @ W^T)[m, n] + bias[n]) with A [M, K], W [N, K] e4m3 codes (uint8) and fp32 row
+    scales (quant_rows_f8), on the K = 64 block-scaled MFMA at twice the 16-bit rate; epilogue keywords as `gemm` (bias, geglu,
+    R1 / R2 / s1 / s2 / s_acc, V with vmode 1 / 2, n_store, out_f32).  The element library is the one of `out` / R1 / R2; an
+    fp32 output without residuals names it with el=torch.float16 / torch.bfloat16 (default bf16)."""
+    _need_gpu(A, "A")
+    d, lib = _gemm_f8_desc(A, W, out, **kw)
+    ev = _prof.begin()
+    check(lib.ctrlv_gemm_f8(ctypes.byref(d), _p(a_scale), _p(w_scale), _stream()), "ctrlv_gemm_f8")
+    if ev is not None:
+        n_out = d.n_store if not d.geglu else min(d.n_store, d.N // 2)
+        R1, R2 = kw.get("R1"), kw.get("R2")
+        nbytes = d.M * d.Cin + d.N * d.Cin + d.M * n_out * (4 if kw.get("out_f32") else 2) * (1 + (R1 is not None) + (R2 is not None))
+        _prof.end(ev, "gemm_linear", 2.0 * d.M * d.N * d.Cin, float(nbytes),
+                  detail=("gemm_f8", d.M, d.N, d.Cin, int(d.geglu), int(R1 is not None) + int(R2 is not None), d.vmode, 0))
+    return out
+
+
 def ff_fused_pack(w1_packed, b1, w2_packed):
     """Fragment-major copies (w1f, w2f) of a C = 320 feed-forward's packed weights for `ff_fused`: w1_packed = the GEGLU
     projection in the interleaved packed form [2560, 320], b1 = its bias (fp32 [2560], same row order; carried inside w1f),

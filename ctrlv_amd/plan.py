@@ -66,6 +66,7 @@ class Plan:
         check(self._lib.ctrlv_plan_create(ctypes.byref(self._cfg), self.device.index or 0, ctypes.byref(self._h)),
               "ctrlv_plan_create")
         self.trunk_mode = "same"
+        self.ff_mode = "same"
         self._ws = {}            # lane -> uint8 workspace tensor
         self._ws_bytes = {}      # (B, F, H, W) -> bytes
         self.n_down = self._lib.ctrlv_plan_num_down_residuals(self._h)
@@ -121,6 +122,15 @@ class Plan:
         check(self._lib.ctrlv_plan_set_trunk_mode(self._h, 1 if mode == "fp16x2" else 0), "ctrlv_plan_set_trunk_mode")
         self._ws_bytes.clear()          # the workspace grows with the lo planes
         self.trunk_mode = mode
+
+    def set_ff_precision(self, mode):
+        """Precision of the transformer feed-forwards: "same" (the element type) or "f8" (e4m3 operands on the block-scaled
+        MFMA wherever ctrlv_gemm_f8_serves accepts the layer; opt-in throughput mode) -- ctrlv_plan_set_ff_precision."""
+        if mode not in ("same", "f8"):
+            raise ValueError(f'ff_dtype must be "same" or "f8", got {mode!r}')
+        check(self._lib.ctrlv_plan_set_ff_precision(self._h, 1 if mode == "f8" else 0), "ctrlv_plan_set_ff_precision")
+        self._ws_bytes.clear()          # the workspace grows with the codes and scales
+        self.ff_mode = mode
 
     def set_time_context_order(self, order):
         check(self._lib.ctrlv_plan_set_time_context_order(self._h, 0 if order == "sb" else 1),

@@ -14,6 +14,7 @@ plain fp32 torch ops on [B, 1280]-sized tensors.  Multi-GPU: `GradientBuckets` a
 reference's DDP default) over torch.distributed WHILE the backward pass runs (hooks fire as gradients complete);
 `allreduce_gradients` is the simple reduce-after-backward form (RCCL on the GPU box, gloo in the CPU tests).
 """
+import contextlib
 import math
 
 import torch
@@ -165,6 +166,22 @@ def controlnet_train_forward(model, sample, timestep, encoder_hidden_states, add
     return down, mid
 
 
+@contextlib.contextmanager
+def _element_feed_forwards(model):
+    """A training walk does not use the FP8 feed-forward mode (ff_dtype "f8" is an inference mode): the frozen encoder of a
+    training step runs its feed-forwards in the element type whatever the attribute says."""
+    had = "ff_dtype" in model.__dict__
+    prev = model.__dict__.get("ff_dtype")
+    model.__dict__["ff_dtype"] = "same"
+    try:
+        yield
+    finally:
+        if had:
+            model.__dict__["ff_dtype"] = prev
+        else:
+            del model.__dict__["ff_dtype"]
+
+
 def unet_train_forward(unet, sample, timestep, encoder_hidden_states, added_time_ids, down_res, mid_res):
     """Frozen-UNet forward that is differentiable w.r.t. the ControlNet residuals.  Encoder + mid run on the inference
     executor under no_grad (no gradient path: the residuals are added to its OUTPUTS); the decoder runs in training
@@ -172,7 +189,7 @@ def unet_train_forward(unet, sample, timestep, encoder_hidden_states, added_time
     B, F, Cin, h, w = sample.shape
     N, dev = B * F, sample.device
     order = unet.time_context_order
-    with torch.no_grad():
+    with torch.no_grad(), _element_feed_forwards(unet):
         if unet._use_plan():
             # the library-owned C++ plan walks the frozen encoder (ctrlv_unet_encoder_forward): one host call
             plan = unet._ensure_plan(sample)

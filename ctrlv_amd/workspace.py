@@ -19,6 +19,7 @@ class Workspace:
         self.peak = 0
         self.el = torch.bfloat16  # element type of the forward using this arena (default dtype of alloc)
         self.split = False        # residual trunk stored as hi + lo planes (trunk_dtype "fp16x2")
+        self.ff_f8 = False        # transformer feed-forwards on e4m3 operands where served (ff_dtype "f8")
 
     def _block_for(self, nbytes):
         while True:

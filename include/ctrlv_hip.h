@@ -245,6 +245,32 @@ int ctrlv_ff_fused_ln(const void* x, int ldx, const float* ln_gamma, const float
  * s_acc == 1) -- 0 = use the two ctrlv_gemm launches.  The launcher applies exactly these conditions. */
 int ctrlv_ff_fused_serves(const ctrlv_gemm_desc* out_desc, int ldx);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * FP8 linear GEMM (opt-in throughput mode of the feed-forwards; csrc/quant_f8.hip, csrc/gemm_f8.hip).  Additive entry
+ * points: the ABI number does not change.  Codes are OCP e4m3 ("e4m3fn", torch.float8_e4m3fn: largest finite value 448),
+ * round-to-nearest-even, saturating; the NaN codes 0x7f / 0xff are never produced from finite input.
+ *
+ * ctrlv_quant_rows_f8: one pass over [M, K] element rows (pitch ldx elements).  y = x, or with gamma != NULL (beta too)
+ * y = ctrlv_layernorm's value LayerNorm(x + V[(m / vdiv) % vmod]) * gamma + beta kept in fp32 (V optional; V needs gamma).
+ * a = max |y[m, :]|;  scale[m] = a / 448 (a == 0: 1; never below the smallest normal fp32);  q[m, k] = e4m3(y[m, k] /
+ * scale[m]), bytes with pitch ldq.  K a multiple of 8, <= 5120; ldx, ldq multiples of 8.  Weights W[N][K] are quantised by
+ * the same call (one scale per output channel; GEGLU-interleaved rows keep their order).
+ *
+ * ctrlv_gemm_f8: out = epilogue(a_scale[m] w_scale[n] sum_k A[m, k] W[n, k] + bias[n]) with A, W holding e4m3 bytes (lda and
+ * the weight pitch Cin in bytes), fp32 accumulation on v_mfma_scale_f32_32x32x64_f8f6f4 with unit block scales, and the
+ * mode-0 epilogue of ctrlv_gemm behind it: v = s_acc (..) + s1 R1 + s2 R2 + V[vidx(m)], or GEGLU, n_store, out_f32.
+ * ctrlv_gemm_f8_serves (host only) says whether a descriptor is served: mode 0, taps 1, A2 == NULL, no lo planes, no raw_out /
+ * gn_partials / n_scale2 / act / pad_br, tile 0 (chosen by the launch's size: both tiles give the same bits) or 1 / 2, Cin a multiple of 128 (so not 320: that feed-forward stays on ctrlv_ff_fused),
+ * N a multiple of 32, lda a multiple of 16 and >= Cin, ldo / n_store / ldr1 / ldr2 / ldv multiples of 4, out_f32 0 or 1, GEGLU
+ * with bias only, operands aligned (A, W, bias, V 16 bytes; R1, R2, out 8 bytes; out 16 with out_f32).  An unserved
+ * descriptor is CTRLV_E_BAD_SHAPE, a null operand or scale vector CTRLV_E_BAD_ARG, both before any HIP call.  A function of
+ * the layer's shape only: a row's bits do not depend on M.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int ctrlv_quant_rows_f8(const void* x, int M, int K, int ldx, const float* gamma, const float* beta, float eps,
+                        const float* V, int vdiv, int vmod, int ldv, void* q, int ldq, float* scale, ctrlv_stream_t stream);
+int ctrlv_gemm_f8(const ctrlv_gemm_desc* d, const float* a_scale, const float* w_scale, ctrlv_stream_t stream);
+int ctrlv_gemm_f8_serves(const ctrlv_gemm_desc* d);
+
 /* Fused temporal self-attention block at C = 320 (ABI 18; csrc/temporal_fused.hip):
  *     out = R1 + to_out( softmax_f( q k^T / 8 ) v ) + bias + V[clip],     (q | k | v) = x . W_qkv^T
  * over the F <= 32 frames of every pixel -- `TemporalBasicTransformerBlock.attn1` with its residual and the one-key
@@ -603,6 +629,15 @@ int ctrlv_plan_set_time_context_order(ctrlv_plan* plan, int order);
  * (ctrlv_plan_workspace_bytes answers for the current mode).  Model inputs / outputs / residual tensors across the ABI are
  * unchanged. */
 int ctrlv_plan_set_trunk_mode(ctrlv_plan* plan, int mode);
+/* Precision of the transformer feed-forwards of the plan's forwards: 0 = the element type (default), 1 = e4m3 operands on the
+ * block-scaled MFMA (ctrlv_gemm_f8) for every feed-forward whose two projections ctrlv_gemm_f8_serves accepts (K multiples of
+ * 128: C = 640 / 1280 of the SVD model; C = 320 keeps ctrlv_ff_fused): LayerNorm + row quantisation in one launch
+ * (ctrlv_quant_rows_f8), the GEGLU projection, the row quantisation of its output, the output projection with the layer's
+ * epilogue.  A throughput mode with the error class of bf16 storage, opt-in.  The e4m3 weights and their
+ * scales are made here (or at the next ctrlv_plan_load_weights) from the packed weights and owned by the plan; the workspace
+ * grows (ctrlv_plan_workspace_bytes answers for the current mode).  Does not combine with trunk mode 1: CTRLV_E_BAD_ARG from
+ * whichever of the two setters comes second. */
+int ctrlv_plan_set_ff_precision(ctrlv_plan* plan, int mode);
 /* Bytes of workspace one forward of (B clips, F frames, H x W latent) needs; 0 on error (see ctrlv_last_error). */
 size_t ctrlv_plan_workspace_bytes(ctrlv_plan* plan, int B, int F, int H, int W);
 /* Number of residual tensors the ControlNet produces / the UNet consumes on the down path (12 for SVD), and the
