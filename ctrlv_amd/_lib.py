@@ -113,6 +113,20 @@ class VaeConfig(ctypes.Structure):
     ]
 
 
+class ClipRequest(ctypes.Structure):
+    """Mirror of `ctrlv_clip_request` (ctypes clears it: the library requires a cleared struct)."""
+    _fields_ = [
+        ("n_clips", c_int), ("num_frames", c_int), ("height", c_int), ("width", c_int),
+        ("image_u8", c_void_p), ("cond", c_void_p), ("cond_channels", c_int), ("cond_dtype", c_int),
+        ("aug_noise", c_void_p), ("noise_aug_strength", c_float), ("num_steps", c_int),
+        ("latents", c_void_p), ("sigmas", ctypes.POINTER(c_float)), ("timesteps", ctypes.POINTER(c_float)),
+        ("fps", c_int), ("motion_bucket_id", c_int),
+        ("min_guidance", c_float), ("max_guidance", c_float), ("conditioning_scale", c_float), ("decode_chunk", c_int),
+        ("clip_mean", c_float * 3), ("clip_std", c_float * 3),
+        ("out_latents", c_void_p), ("out_frames", c_void_p), ("out_frames_u8", c_void_p),
+    ]
+
+
 # name -> (restype, argtypes); lists every symbol include/ctrlv_hip.h declares (tests/test_abi.py checks this)
 SIGNATURES = {
     "ctrlv_abi_version": (c_int, []),
@@ -243,6 +257,15 @@ SIGNATURES = {
     "ctrlv_vae_decode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_size_t,
                                  c_void_p]),
     "ctrlv_vae_plan_destroy": (c_int, [c_void_p]),
+    "ctrlv_resize_antialias": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int,
+                                       ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_void_p]),
+    "ctrlv_pixels_prepare": (c_int, [c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ctrlv_frames_to_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ctrlv_pipeline_create": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(c_void_p)]),
+    "ctrlv_pipeline_set_overlap": (c_int, [c_void_p, c_int]),
+    "ctrlv_pipeline_workspace_bytes": (c_size_t, [c_void_p, ctypes.POINTER(ClipRequest)]),
+    "ctrlv_pipeline_generate": (c_int, [c_void_p, ctypes.POINTER(ClipRequest), c_void_p, c_size_t, c_void_p]),
+    "ctrlv_pipeline_destroy": (c_int, [c_void_p]),
 }
 
 _libs = {}                # element dtype code (2 bf16 / 1 fp16) -> CDLL
@@ -252,7 +275,8 @@ _NO_STATUS = {"ctrlv_abi_version", "ctrlv_elem_dtype", "ctrlv_build_id", "ctrlv_
               "ctrlv_gemm_gn_partials_serves", "ctrlv_gemm_up_phase_serves", "ctrlv_ff_fused_serves", "ctrlv_plan_num_down_residuals",
               "ctrlv_temporal_fused_serves", "ctrlv_gemm_f8_serves",
               # size queries (size_t: never wrapped, listed with their kin for the reader)
-              "ctrlv_gemm_tokens_ws_bytes", "ctrlv_clip_plan_workspace_bytes", "ctrlv_vae_plan_workspace_bytes"}
+              "ctrlv_gemm_tokens_ws_bytes", "ctrlv_clip_plan_workspace_bytes", "ctrlv_vae_plan_workspace_bytes",
+              "ctrlv_pipeline_workspace_bytes"}
 
 
 def _status_recorder(lib, fn):

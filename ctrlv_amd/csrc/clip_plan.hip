@@ -39,6 +39,12 @@ struct ctrlv_clip_plan {
   std::vector<ClipLayer> layers;
 };
 
+const ctrlv_clip_config* ctrlv_clip_plan_info(const ctrlv_clip_plan* p, int* device, int* loaded) {
+  if (device) *device = p->device;
+  if (loaded) *loaded = p->loaded ? 1 : 0;
+  return &p->cfg;
+}
+
 namespace {
 
 // Which GEMM serves a layer's (N, K): true = ctrlv_gemm_tokens, false = ctrlv_gemm.  Keyed on the weight's shape only, never

@@ -361,6 +361,10 @@ int ctrlv_num_cu(int dev);    // cached hipDeviceAttributeMultiprocessorCount
 // bytes of the counter block at the head of a ctrlv_gemm_tokens workspace for (M, N, K); 0 when the shape is not sliced
 // (csrc/gemm_tokens.hip; the CLIP plan clears exactly this much once per forward)
 size_t ctrlv_gemm_tokens_counter_bytes(int M, int N, int K);
+// what the clip driver (csrc/pipeline.hip) reads of the plans it borrows: the configuration, the device and whether weights are loaded
+const ctrlv_model_config* ctrlv_plan_info(const ctrlv_plan* p, int* device, int* loaded);
+const ctrlv_clip_config* ctrlv_clip_plan_info(const ctrlv_clip_plan* p, int* device, int* loaded);
+const ctrlv_vae_config* ctrlv_vae_plan_info(const ctrlv_vae_plan* p, int* device, int* loaded);
 #define CTRLV_CHECK_ARG(cond, ...)                  \
   do {                                              \
     if (!(cond)) {                                  \

@@ -1,0 +1,398 @@
+// A whole clip as one C call: the driver behind ctrlv_pipeline_generate (include/ctrlv_hip.h).  It owns nothing but a side
+// stream and two events; the four plans are borrowed, every buffer is carved out of the caller's workspace.  What it enqueues is
+// what prepare_clip -> DenoiseStepper (eager) -> finish_clip of ctrlv_amd/pipelines/pipeline_utils.py enqueue, call for call:
+// the plan-level entry points plus the glue kernels of csrc/pipeline_io.hip.
+#include <math.h>
+
+#include <vector>
+
+#include "pipeline_io.h"
+
+struct ctrlv_pipeline {
+  ctrlv_plan* unet = nullptr;
+  ctrlv_plan* cn = nullptr;
+  ctrlv_vae_plan* vae = nullptr;
+  ctrlv_clip_plan* clip = nullptr;
+  int device = 0;
+  int overlap = 1;
+  hipStream_t side = nullptr;            // created by the first generate that overlaps
+  hipEvent_t ev_fork = nullptr, ev_res = nullptr;
+  std::vector<float> consts;             // host staging of the one upload (timesteps | guidance | added time ids)
+};
+
+namespace {
+
+constexpr int kMaxSteps = 1024;
+constexpr size_t kAlign = 256;
+inline size_t up(size_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
+
+// the element type's rounding on the host (added time ids: torch.tensor([...], dtype=<model dtype>))
+float round_el(float v) {
+#ifdef CTRLV_ELEM_F16
+  return (float)(_Float16)v;
+#else
+  uint32_t u;
+  memcpy(&u, &v, 4);
+  u += 0x7fffu + ((u >> 16) & 1u);
+  u &= 0xffff0000u;
+  float r;
+  memcpy(&r, &u, 4);
+  return r;
+#endif
+}
+
+struct Geo {                 // a validated request's derived sizes
+  int B, F, H, W, h, w, hw, L, nb, cfg, D, S;      // nb = model batch (2 B with cfg), D = embedding width, S = CLIP image size
+  bool decode;
+};
+
+struct Layout {              // byte offsets into the workspace
+  size_t consts, ehs, first, lmi, scaled, pred, cond_em, res[CTRLV_MAX_BLOCKS * 8 + 1], phase, total;
+  int n_res;                 // residual tensors (down + mid), 0 without a ControlNet
+  // loop phase
+  size_t unet_ws, unet_bytes, cn_ws, cn_bytes;
+  // CLIP phase
+  size_t clip_px, clip_emb, clip_ws, clip_bytes;
+  // VAE encode phase
+  size_t enc_px, enc_lat, enc_ws, enc_bytes;
+  // decode phase
+  size_t dec_z, dec_frames, dec_ws, dec_bytes;
+};
+
+int validate(const ctrlv_pipeline* p, const ctrlv_clip_request* r, Geo* g) {
+  CTRLV_CHECK_ARG(p != nullptr, "pipeline: null pipeline");
+  CTRLV_CHECK_ARG(r != nullptr, "pipeline: null request");
+  const ctrlv_model_config* uc = ctrlv_plan_info(p->unet, nullptr, nullptr);
+  const ctrlv_vae_config* vc = ctrlv_vae_plan_info(p->vae, nullptr, nullptr);
+  const ctrlv_clip_config* cc = ctrlv_clip_plan_info(p->clip, nullptr, nullptr);
+  CTRLV_CHECK_SHAPE(r->n_clips >= 1 && r->n_clips <= 4096, "pipeline: n_clips=%d must be in [1, 4096]", r->n_clips);
+  CTRLV_CHECK_SHAPE(r->num_frames >= 1 && r->num_frames <= 32, "pipeline: num_frames=%d must be in [1, 32] (the temporal "
+                    "attention's limit)", r->num_frames);
+  const int m = 8 * (1 << (uc->n_blocks - 1));
+  CTRLV_CHECK_SHAPE(r->height > 0 && r->width > 0 && r->height % m == 0 && r->width % m == 0,
+                    "pipeline: height=%d / width=%d must be positive multiples of %d (8 for the VAE times %d for the UNet's levels)",
+                    r->height, r->width, m, m / 8);
+  const int h = r->height / 8, w = r->width / 8;
+  CTRLV_CHECK_SHAPE((h * w) % 64 == 0 && h * w <= 16384, "pipeline: height=%d / width=%d give %d latent pixels; the VAE's attention "
+                    "takes a multiple of 64, at most 16384", r->height, r->width, h * w);
+  CTRLV_CHECK_ARG(r->image_u8 != nullptr, "pipeline: image_u8 is null");
+  CTRLV_CHECK_ARG(r->latents != nullptr, "pipeline: latents is null");
+  CTRLV_CHECK_ARG(r->out_latents != nullptr, "pipeline: out_latents is null");
+  if (p->cn) {
+    CTRLV_CHECK_ARG(r->cond != nullptr, "pipeline: cond is null but the pipeline has a ControlNet");
+  }
+  if (r->cond) {
+    CTRLV_CHECK_SHAPE(r->cond_channels == 3 || r->cond_channels == vc->latent_channels,
+                      "pipeline: cond_channels=%d must be 3 (pixels) or %d (latents)", r->cond_channels, vc->latent_channels);
+    if (r->cond_dtype < 0 || r->cond_dtype > 2) {
+      ctrlv_set_error("pipeline: cond_dtype code %d (0 fp32, 1 fp16, 2 bf16)", r->cond_dtype);
+      return CTRLV_E_BAD_DTYPE;
+    }
+  }
+  CTRLV_CHECK_SHAPE(r->num_steps >= 1 && r->num_steps <= kMaxSteps, "pipeline: num_steps=%d must be in [1, %d]", r->num_steps,
+                    kMaxSteps);
+  CTRLV_CHECK_ARG(r->sigmas != nullptr && r->timesteps != nullptr, "pipeline: sigmas / timesteps are null (host arrays)");
+  for (int i = 0; i < r->num_steps; ++i) {
+    CTRLV_CHECK_ARG(isfinite(r->sigmas[i]) && r->sigmas[i] > 0.f && r->sigmas[i + 1] >= 0.f && r->sigmas[i + 1] < r->sigmas[i],
+                    "pipeline: sigmas must be positive and strictly decreasing (sigmas[%d]=%g, sigmas[%d]=%g)", i,
+                    (double)r->sigmas[i], i + 1, (double)r->sigmas[i + 1]);
+  }
+  CTRLV_CHECK_ARG(r->noise_aug_strength >= 0.f && isfinite(r->noise_aug_strength), "pipeline: noise_aug_strength=%g",
+                  (double)r->noise_aug_strength);
+  CTRLV_CHECK_ARG(isfinite(r->min_guidance) && isfinite(r->max_guidance), "pipeline: min_guidance / max_guidance are not finite");
+  const bool decode = r->out_frames != nullptr || r->out_frames_u8 != nullptr;
+  if (decode) {
+    CTRLV_CHECK_SHAPE(r->decode_chunk >= 1, "pipeline: decode_chunk=%d must be >= 1 when frames are asked for", r->decode_chunk);
+    CTRLV_CHECK_ARG(((uintptr_t)r->out_frames_u8 & 3) == 0, "pipeline: out_frames_u8 must be 4-byte aligned");
+  }
+  bool zero = true;
+  for (int c = 0; c < 3; ++c) zero = zero && r->clip_mean[c] == 0.f && r->clip_std[c] == 0.f;
+  if (!zero) {
+    for (int c = 0; c < 3; ++c) CTRLV_CHECK_ARG(r->clip_std[c] > 0.f, "pipeline: clip_std[%d]=%g", c, (double)r->clip_std[c]);
+  }
+  const int rc = ctrlv_resize_check(r->n_clips, r->height, r->width, cc->image_size, cc->image_size);
+  if (rc != CTRLV_OK) return rc;
+  g->B = r->n_clips; g->F = r->num_frames; g->H = r->height; g->W = r->width; g->h = h; g->w = w; g->hw = h * w;
+  g->L = vc->latent_channels;
+  g->cfg = r->max_guidance > 1.f ? 1 : 0;
+  g->nb = g->cfg ? 2 * g->B : g->B;
+  g->D = cc->projection_dim;
+  g->S = cc->image_size;
+  g->decode = decode;
+  return CTRLV_OK;
+}
+
+int layout(ctrlv_pipeline* p, const ctrlv_clip_request* r, const Geo& g, Layout* L) {
+  int lu = 0, lv = 0, lc = 0, ln = 1;
+  ctrlv_plan_info(p->unet, nullptr, &lu);
+  ctrlv_vae_plan_info(p->vae, nullptr, &lv);
+  ctrlv_clip_plan_info(p->clip, nullptr, &lc);
+  if (p->cn) ctrlv_plan_info(p->cn, nullptr, &ln);
+  CTRLV_CHECK_ARG(lu && lv && lc && ln, "pipeline: plan not loaded (load the weights of every plan first)");
+  const size_t el = sizeof(el_t);
+  const size_t lat = (size_t)g.B * g.F * g.L * g.hw;              // elements of the latents of the B clips
+  size_t o = 0;
+  auto take = [&](size_t bytes) { const size_t at = o; o += up(bytes); return at; };
+  L->consts = take((size_t)(kMaxSteps + 32 + 3 * 2 * 4096) * sizeof(float));
+  L->ehs = take((size_t)g.nb * g.D * el);
+  L->first = take((size_t)g.B * g.L * g.hw * el);
+  L->lmi = take((size_t)g.nb * g.F * 2 * g.L * g.hw * el);
+  L->scaled = take(lat * el);
+  L->pred = take((size_t)g.nb * g.F * g.L * g.hw * el);
+  L->cond_em = 0;
+  L->n_res = 0;
+  if (p->cn) {
+    L->cond_em = take((size_t)g.nb * g.F * g.L * g.hw * el);
+    const int nd = ctrlv_plan_num_down_residuals(p->cn);
+    CTRLV_CHECK_SHAPE(nd + 1 <= (int)(sizeof(L->res) / sizeof(L->res[0])), "pipeline: %d residual tensors", nd + 1);
+    for (int i = 0; i <= nd; ++i) {
+      int64_t rows = 0;
+      int32_t ch = 0;
+      const int rc = ctrlv_plan_residual_shape(p->cn, i, g.nb, g.F, g.h, g.w, &rows, &ch);
+      if (rc != CTRLV_OK) return rc;
+      L->res[i] = take((size_t)rows * ch * el);
+    }
+    L->n_res = nd + 1;
+  }
+  L->phase = o;
+  size_t end = o;
+  // the loop: UNet and ControlNet work side by side in disjoint regions
+  L->unet_bytes = ctrlv_plan_workspace_bytes(p->unet, g.nb, g.F, g.h, g.w);
+  if (L->unet_bytes == 0) return CTRLV_E_BAD_SHAPE;
+  L->cn_bytes = 0;
+  if (p->cn) {
+    L->cn_bytes = ctrlv_plan_workspace_bytes(p->cn, g.nb, g.F, g.h, g.w);
+    if (L->cn_bytes == 0) return CTRLV_E_BAD_SHAPE;
+  }
+  o = L->phase;
+  L->unet_ws = take(L->unet_bytes);
+  L->cn_ws = take(L->cn_bytes);
+  end = o > end ? o : end;
+  // CLIP: resized pixels, embeddings, the tower's workspace
+  L->clip_bytes = ctrlv_clip_plan_workspace_bytes(p->clip, g.B);
+  if (L->clip_bytes == 0) return CTRLV_E_BAD_SHAPE;
+  o = L->phase;
+  L->clip_px = take((size_t)g.B * 3 * g.S * g.S * el);
+  L->clip_emb = take((size_t)g.B * g.D * el);
+  L->clip_ws = take(L->clip_bytes);
+  end = o > end ? o : end;
+  // VAE encode: the image's pixels, the condition's latents, the encoder's workspace (the larger of the two calls)
+  L->enc_bytes = ctrlv_vae_plan_workspace_bytes(p->vae, 0, g.B, 1, g.H, g.W);
+  if (L->enc_bytes == 0) return CTRLV_E_BAD_SHAPE;
+  const bool enc_cond = p->cn && r->cond_channels == 3;
+  if (enc_cond) {
+    const size_t b2 = ctrlv_vae_plan_workspace_bytes(p->vae, 0, g.B * g.F, 1, g.H, g.W);
+    if (b2 == 0) return CTRLV_E_BAD_SHAPE;
+    L->enc_bytes = b2 > L->enc_bytes ? b2 : L->enc_bytes;
+  }
+  o = L->phase;
+  L->enc_px = take((size_t)g.B * 3 * g.H * g.W * el);
+  L->enc_lat = take(enc_cond ? lat * el : 0);
+  L->enc_ws = take(L->enc_bytes);
+  end = o > end ? o : end;
+  // decode: the scaled latents, the frames (unless the caller takes them), the decoder's workspace
+  L->dec_bytes = 0;
+  if (g.decode) {
+    const int total = g.B * g.F, chunk = r->decode_chunk < total ? r->decode_chunk : total, last = total % chunk;
+    L->dec_bytes = ctrlv_vae_plan_workspace_bytes(p->vae, 1, chunk, chunk, g.h, g.w);
+    if (L->dec_bytes == 0) return CTRLV_E_BAD_SHAPE;
+    if (last) {
+      const size_t b2 = ctrlv_vae_plan_workspace_bytes(p->vae, 1, last, last, g.h, g.w);
+      if (b2 == 0) return CTRLV_E_BAD_SHAPE;
+      L->dec_bytes = b2 > L->dec_bytes ? b2 : L->dec_bytes;
+    }
+    o = L->phase;
+    L->dec_z = take(lat * el);
+    L->dec_frames = take(r->out_frames ? 0 : (size_t)total * 3 * g.H * g.W * el);
+    L->dec_ws = take(L->dec_bytes);
+    end = o > end ? o : end;
+  }
+  L->total = end;
+  return CTRLV_OK;
+}
+
+#define TRY(expr)                   \
+  do {                              \
+    const int rc__ = (expr);        \
+    if (rc__ != CTRLV_OK) return rc__; \
+  } while (0)
+
+}  // namespace
+
+extern "C" int ctrlv_pipeline_create(ctrlv_plan* unet, ctrlv_plan* controlnet, ctrlv_vae_plan* vae, ctrlv_clip_plan* clip,
+                                     int device, ctrlv_pipeline** out) {
+  CTRLV_CHECK_ARG(out != nullptr, "pipeline_create: null output");
+  *out = nullptr;
+  CTRLV_CHECK_ARG(unet != nullptr, "pipeline_create: the UNet plan is null");
+  CTRLV_CHECK_ARG(vae != nullptr, "pipeline_create: the VAE plan is null");
+  CTRLV_CHECK_ARG(clip != nullptr, "pipeline_create: the CLIP plan is null");
+  CTRLV_CHECK_ARG(device >= 0 && device < CTRLV_MAX_DEVICES, "pipeline_create: device %d", device);
+  int du = 0, dv = 0, dc = 0, dn = device;
+  const ctrlv_model_config* uc = ctrlv_plan_info(unet, &du, nullptr);
+  const ctrlv_vae_config* vc = ctrlv_vae_plan_info(vae, &dv, nullptr);
+  const ctrlv_clip_config* cc = ctrlv_clip_plan_info(clip, &dc, nullptr);
+  CTRLV_CHECK_ARG(uc->kind == 0, "pipeline_create: the first plan must be a UNet plan (kind 0)");
+  if (controlnet) {
+    const ctrlv_model_config* nc = ctrlv_plan_info(controlnet, &dn, nullptr);
+    CTRLV_CHECK_ARG(nc->kind == 1, "pipeline_create: the second plan must be a ControlNet plan (kind 1)");
+    CTRLV_CHECK_SHAPE(nc->in_channels == uc->in_channels && nc->n_blocks == uc->n_blocks &&
+                      nc->cross_attention_dim == uc->cross_attention_dim,
+                      "pipeline_create: the ControlNet's in_channels / blocks / cross_attention_dim differ from the UNet's");
+  }
+  CTRLV_CHECK_ARG(du == device && dv == device && dc == device && dn == device,
+                  "pipeline_create: the plans live on devices %d / %d / %d / %d, the pipeline on %d", du, dn, dv, dc, device);
+  CTRLV_CHECK_SHAPE(uc->in_channels == 2 * vc->latent_channels && uc->out_channels == vc->latent_channels,
+                    "pipeline_create: the UNet takes %d and gives %d channels, the VAE has %d latent channels", uc->in_channels,
+                    uc->out_channels, vc->latent_channels);
+  CTRLV_CHECK_SHAPE(cc->projection_dim == uc->cross_attention_dim, "pipeline_create: the CLIP projection has %d columns, the "
+                    "UNet's cross_attention_dim is %d", cc->projection_dim, uc->cross_attention_dim);
+  CTRLV_CHECK_SHAPE(vc->in_channels == 3 && vc->out_channels == 3, "pipeline_create: the VAE has %d / %d image channels, not 3",
+                    vc->in_channels, vc->out_channels);
+  CTRLV_CHECK_ARG(vc->scaling_factor > 0.f, "pipeline_create: the VAE's scaling_factor is %g", (double)vc->scaling_factor);
+  ctrlv_pipeline* p = new ctrlv_pipeline();
+  p->unet = unet; p->cn = controlnet; p->vae = vae; p->clip = clip; p->device = device;
+  *out = p;
+  return CTRLV_OK;
+}
+
+extern "C" int ctrlv_pipeline_set_overlap(ctrlv_pipeline* p, int on) {
+  CTRLV_CHECK_ARG(p != nullptr && (on == 0 || on == 1), "pipeline_set_overlap: on must be 0 or 1");
+  p->overlap = on;
+  return CTRLV_OK;
+}
+
+extern "C" int ctrlv_pipeline_destroy(ctrlv_pipeline* p) {
+  if (!p) return CTRLV_OK;
+  if (p->ev_fork) (void)hipEventDestroy(p->ev_fork);
+  if (p->ev_res) (void)hipEventDestroy(p->ev_res);
+  if (p->side) (void)hipStreamDestroy(p->side);
+  delete p;
+  return CTRLV_OK;
+}
+
+extern "C" size_t ctrlv_pipeline_workspace_bytes(ctrlv_pipeline* p, const ctrlv_clip_request* r) {
+  Geo g;
+  Layout L;
+  if (validate(p, r, &g) != CTRLV_OK) return 0;
+  if (layout(p, r, g, &L) != CTRLV_OK) return 0;
+  return L.total;
+}
+
+extern "C" int ctrlv_pipeline_generate(ctrlv_pipeline* p, const ctrlv_clip_request* r, void* ws, size_t ws_bytes,
+                                       ctrlv_stream_t stream) {
+  Geo g;
+  Layout L;
+  TRY(validate(p, r, &g));
+  TRY(layout(p, r, g, &L));
+  CTRLV_CHECK_ARG(ws != nullptr && ((uintptr_t)ws & (kAlign - 1)) == 0, "pipeline_generate: the workspace must be non-null and "
+                  "256-byte aligned");
+  if (ws_bytes < L.total) {
+    ctrlv_set_error("pipeline_generate: ws_bytes=%zu is smaller than the %zu bytes this request needs "
+                    "(ctrlv_pipeline_workspace_bytes)", ws_bytes, L.total);
+    return CTRLV_E_WORKSPACE;
+  }
+  const hipStream_t s = (hipStream_t)stream;
+  char* base = (char*)ws;
+  const bool overlap = p->cn && p->overlap;
+  if (overlap && !p->side) {
+    CTRLV_HIP_TRY(hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking));
+    CTRLV_HIP_TRY(hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming));
+    CTRLV_HIP_TRY(hipEventCreateWithFlags(&p->ev_res, hipEventDisableTiming));
+  }
+  const int B = g.B, F = g.F, Lc = g.L, hw = g.hw, nb = g.nb;
+  const long lat = (long)B * F * Lc * hw;
+  const float scaling = ctrlv_vae_plan_info(p->vae, nullptr, nullptr)->scaling_factor;
+
+  // ---- the one upload: timesteps | guidance ramp | added time ids
+  float* c_t = (float*)(base + L.consts);
+  float* c_g = c_t + kMaxSteps;
+  float* c_ids = c_g + 32;
+  {
+    std::vector<float>& hb = p->consts;
+    hb.assign((size_t)kMaxSteps + 32 + 3 * (size_t)nb, 0.f);
+    for (int i = 0; i < r->num_steps; ++i) hb[i] = r->timesteps[i];
+    // torch.linspace: the first half counts up from the start, the second down from the end
+    const float step = F > 1 ? (r->max_guidance - r->min_guidance) / (float)(F - 1) : 0.f;
+    for (int f = 0; f < F; ++f)
+      hb[kMaxSteps + f] = f < F / 2 ? r->min_guidance + step * (float)f : r->max_guidance - step * (float)(F - 1 - f);
+    for (int b = 0; b < nb; ++b) {
+      float* id = &hb[(size_t)kMaxSteps + 32 + 3 * (size_t)b];
+      id[0] = round_el((float)(r->fps - 1));
+      id[1] = round_el((float)r->motion_bucket_id);
+      id[2] = round_el(r->noise_aug_strength);
+    }
+    CTRLV_HIP_TRY(hipMemcpyAsync(c_t, hb.data(), hb.size() * sizeof(float), hipMemcpyHostToDevice, s));
+  }
+
+  // ---- 1. CLIP embedding of the conditioning image
+  static const float kClipMean[3] = {0.48145466f, 0.4578275f, 0.40821073f}, kClipStd[3] = {0.26862954f, 0.26130258f, 0.27577711f};
+  bool own = false;
+  for (int c = 0; c < 3; ++c) own = own || r->clip_mean[c] != 0.f || r->clip_std[c] != 0.f;
+  TRY(ctrlv_resize_antialias(r->image_u8, 1, B, g.H, g.W, base + L.clip_px, CTRLV_ELEM_DTYPE, g.S, g.S,
+                             own ? r->clip_mean : kClipMean, own ? r->clip_std : kClipStd, stream));
+  TRY(ctrlv_clip_forward(p->clip, base + L.clip_px, CTRLV_ELEM_DTYPE, B, base + L.clip_emb, nullptr, base + L.clip_ws,
+                         L.clip_bytes, stream));
+  TRY(ctrlv_pio_cfg_double(base + L.clip_emb, CTRLV_ELEM_DTYPE, base + L.ehs, B, g.D, g.cfg, s));
+
+  // ---- 2. VAE latents of the (noise-augmented) image and of the condition
+  TRY(ctrlv_pixels_prepare(r->image_u8, r->aug_noise, r->noise_aug_strength, B, g.H, g.W, base + L.enc_px, stream));
+  TRY(ctrlv_vae_encode(p->vae, base + L.enc_px, CTRLV_ELEM_DTYPE, B, g.H, g.W, nullptr, 1.0f, base + L.first, nullptr,
+                       CTRLV_ELEM_DTYPE, base + L.enc_ws, L.enc_bytes, stream));
+  TRY(ctrlv_pio_lmi_cond(base + L.first, base + L.lmi, B, F, Lc, hw, g.cfg, s));
+  if (p->cn) {
+    if (r->cond_channels == 3) {
+      TRY(ctrlv_vae_encode(p->vae, r->cond, r->cond_dtype, B * F, g.H, g.W, nullptr, 1.0f, base + L.enc_lat, nullptr,
+                           CTRLV_ELEM_DTYPE, base + L.enc_ws, L.enc_bytes, stream));
+      TRY(ctrlv_pio_cfg_double(base + L.enc_lat, CTRLV_ELEM_DTYPE, base + L.cond_em, B, (long)F * Lc * hw, g.cfg, s));
+    } else {
+      TRY(ctrlv_pio_cfg_double(r->cond, r->cond_dtype, base + L.cond_em, B, (long)F * Lc * hw, g.cfg, s));
+    }
+  }
+
+  // ---- 3. / 4. the loop
+  // torch divides a tensor by a host scalar as a multiplication by the reciprocal, formed in double and rounded once
+  const float inv0 = (float)(1.0 / sqrt((double)r->sigmas[0] * (double)r->sigmas[0] + 1.0));
+  TRY(ctrlv_pio_scale_latents(r->latents, r->out_latents, base + L.scaled, lat, inv0, s));
+  void* res[CTRLV_MAX_BLOCKS * 8 + 1];
+  for (int i = 0; i < L.n_res; ++i) res[i] = base + L.res[i];
+  for (int i = 0; i < r->num_steps; ++i) {
+    TRY(ctrlv_pio_lmi_scatter(base + L.scaled, base + L.lmi, B, F, Lc, hw, g.cfg, s));
+    void* ev = nullptr;
+    if (p->cn) {
+      hipStream_t sc = s;
+      if (overlap) {
+        CTRLV_HIP_TRY(hipEventRecord(p->ev_fork, s));
+        CTRLV_HIP_TRY(hipStreamWaitEvent(p->side, p->ev_fork, 0));
+        sc = p->side;
+      }
+      TRY(ctrlv_controlnet_forward(p->cn, base + L.lmi, base + L.cond_em, CTRLV_ELEM_DTYPE, c_t + i, 1, base + L.ehs, c_ids, 3,
+                                   r->conditioning_scale, res, res[L.n_res - 1], nb, F, g.h, g.w, base + L.cn_ws, L.cn_bytes,
+                                   (ctrlv_stream_t)sc));
+      if (overlap) {
+        CTRLV_HIP_TRY(hipEventRecord(p->ev_res, p->side));
+        ev = (void*)p->ev_res;
+      }
+    }
+    TRY(ctrlv_unet_forward(p->unet, base + L.lmi, CTRLV_ELEM_DTYPE, c_t + i, 1, base + L.ehs, c_ids, 3,
+                           p->cn ? (const void* const*)res : nullptr, p->cn ? res[L.n_res - 1] : nullptr, ev, base + L.pred, nb, F,
+                           g.h, g.w, base + L.unet_ws, L.unet_bytes, stream));
+    TRY(ctrlv_cfg_euler_step(r->out_latents, base + L.pred, CTRLV_ELEM_DTYPE, g.cfg, c_g, B, F, Lc * hw, r->sigmas[i],
+                             r->sigmas[i + 1], base + L.scaled, stream));
+  }
+
+  // ---- 5. / 6. decode and convert
+  if (g.decode) {
+    const float inv_sf = (float)(1.0 / (double)scaling);
+    TRY(ctrlv_pio_decode_input(r->out_latents, base + L.dec_z, lat, inv_sf, s));
+    char* frames = r->out_frames ? (char*)r->out_frames : base + L.dec_frames;
+    const int total = B * F;
+    for (int i0 = 0; i0 < total; i0 += r->decode_chunk) {
+      const int nf = total - i0 < r->decode_chunk ? total - i0 : r->decode_chunk;
+      TRY(ctrlv_vae_decode(p->vae, base + L.dec_z + (size_t)i0 * Lc * hw * sizeof(el_t), CTRLV_ELEM_DTYPE, nf, nf, g.h, g.w,
+                           frames + (size_t)i0 * 3 * g.H * g.W * sizeof(el_t), CTRLV_ELEM_DTYPE, base + L.dec_ws, L.dec_bytes,
+                           stream));
+    }
+    if (r->out_frames_u8) TRY(ctrlv_frames_to_u8(frames, total, g.H, g.W, r->out_frames_u8, stream));
+  }
+  return CTRLV_OK;
+}

@@ -1,0 +1,349 @@
+// Image pre- / post-processing and classifier-free-guidance assembly of a whole clip (gfx950): what sits between the plan-level
+// calls of StableVideoControlPipeline.__call__ and so far existed only as torch ops in ctrlv_amd/pipelines/pipeline_utils.py.
+//   ctrlv_resize_antialias   _resize_with_antialiasing (Gaussian pre-blur + bicubic, align_corners) fused with the affine steps
+//                            around it: uint8 -> [-1, 1] in front, the CLIP normalisation behind
+//   ctrlv_pixels_prepare     VaeImageProcessor.preprocess + the noise augmentation of prepare_clip
+//   ctrlv_frames_to_u8       VaeImageProcessor.postprocess + numpy_to_pil's (x * 255).round()
+//   ctrlv_pio_*              the doubling / repeating / scattering of the loop's inputs (pipeline_io.h; csrc/pipeline.hip)
+// All arithmetic is fp32.  Where the Python expression is a multiply followed by an add that a test compares bit for bit the two
+// roundings are kept (__fmul_rn / __fadd_rn: never contracted into an fma).  Once per clip, HBM-bound, no atomics.
+#include <math.h>
+
+#include "pipeline_io.h"
+
+namespace {
+
+constexpr int kMaxTaps = 15;     // Gaussian taps per axis: ks = int(max(4 sigma, 3)) made odd, sigma = (factor - 1) / 2, factor <= 8
+constexpr int kTileW = 32;       // output columns per workgroup (256 threads: up to 8 output rows)
+
+struct ResizeParams {
+  int n, H, W, h, w;
+  int ksy, ksx;
+  float ky[kMaxTaps], kx[kMaxTaps];
+  float sy, sx;                  // align_corners source step per output pixel: (in - 1) / (out - 1), 0 for one output pixel
+  int th, span_y, span_x;        // output rows per workgroup; rows / columns of the LDS tile (upper bounds of what a tile needs)
+  int src_u8, dst_dtype, normalize;
+  float mean[3], stdv[3];
+};
+
+// fp32 -> element as its OWN rounding: the empty asm keeps the compiler from folding the fp32 operation in front of it into a
+// mixed-precision instruction (v_fma_mixlo_f16 rounds the exact product once; torch rounds to fp32 first, then to fp16)
+__device__ __forceinline__ el_t round_to_el(float v) {
+  asm volatile("" : "+v"(v));
+  return f32_to_el(v);
+}
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+// index of F.pad(mode="reflect") for i in [-(n - 1), 2 (n - 1)]; the clamp only guards the address
+__device__ __forceinline__ int reflecti(int i, int n) { return clampi(i < 0 ? -i : (i >= n ? 2 * (n - 1) - i : i), 0, n - 1); }
+
+// cubic convolution weights of torch's upsample_bicubic2d (A = -0.75) for the taps at -1, 0, 1, 2 around floor(x), t = frac(x)
+__device__ __forceinline__ void cubic_weights(float t, float* w) {
+  const float A = -0.75f;
+  const float x0 = t + 1.f, x3 = 2.f - t, u = 1.f - t;
+  w[0] = ((A * x0 - 5.f * A) * x0 + 8.f * A) * x0 - 4.f * A;
+  w[1] = ((A + 2.f) * t - (A + 3.f)) * t * t + 1.f;
+  w[2] = ((A + 2.f) * u - (A + 3.f)) * u * u + 1.f;
+  w[3] = ((A * x3 - 5.f * A) * x3 + 8.f * A) * x3 - 4.f * A;
+}
+
+// One workgroup = one (image, channel) and a th x 32 tile of OUTPUT pixels.  Stage 1 writes the vertically blurred source rows
+// the tile's bicubic taps touch (plus the horizontal blur's halo columns) into LDS -- the only pass over the source; stage 2
+// forms, per output pixel, the 4 x 4 horizontally blurred values from LDS and interpolates.  The blurred image never reaches
+// HBM.  One kernel for every input / output form (runtime branches at the load and the store only): the element-type output is
+// the fp32 output's value rounded once, and the normalised output is the plain output's value pushed through the epilogue.
+__global__ __launch_bounds__(256) void resize_antialias_kernel(const void* __restrict__ src, void* __restrict__ dst,
+                                                               const ResizeParams P) {
+  extern __shared__ __attribute__((aligned(16))) float vb[];
+  const int tid = threadIdx.x;
+  const int c = blockIdx.z % 3, img = blockIdx.z / 3;
+  const int H = P.H, W = P.W;
+  const int ox0 = blockIdx.x * kTileW, oy0 = blockIdx.y * P.th;
+  const int ox1 = min(ox0 + kTileW, P.w) - 1, oy1 = min(oy0 + P.th, P.h) - 1;
+  const int ry = P.ksy / 2, rx = P.ksx / 2;
+  // source rows / columns the tile's taps touch after the clamp to the image, and the columns the horizontal blur reads
+  const int ylo = clampi((int)floorf(P.sy * (float)oy0) - 1, 0, H - 1), yhi = clampi((int)floorf(P.sy * (float)oy1) + 2, 0, H - 1);
+  const int xlo = clampi((int)floorf(P.sx * (float)ox0) - 1, 0, W - 1), xhi = clampi((int)floorf(P.sx * (float)ox1) + 2, 0, W - 1);
+  const int plo = max(xlo - rx, 0), phi = min(xhi + rx, W - 1);
+  const int rows = min(yhi - ylo + 1, P.span_y), cols = min(phi - plo + 1, P.span_x);
+
+  for (int i = tid; i < rows * cols; i += 256) {
+    const int r = ylo + i / cols, q = plo + i % cols;
+    float acc = 0.f;
+    for (int t = 0; t < P.ksy; ++t) {
+      const int yy = reflecti(r + t - ry, H);
+      float v;
+      if (P.src_u8) {
+        const float b = (float)((const uint8_t*)src)[(((long)img * H + yy) * W + q) * 3 + c];
+        v = __fsub_rn(__fmul_rn(__fdiv_rn(b, 255.0f), 2.0f), 1.0f);
+      } else {
+        v = ((const float*)src)[(((long)img * 3 + c) * H + yy) * W + q];
+      }
+      acc += P.ky[t] * v;
+    }
+    vb[i] = acc;
+  }
+  __syncthreads();
+
+  for (int o = tid; o < P.th * kTileW; o += 256) {
+    const int oy = oy0 + o / kTileW, ox = ox0 + o % kTileW;
+    if (oy > oy1 || ox > ox1) continue;
+    const float fy = P.sy * (float)oy, fx = P.sx * (float)ox;
+    const float gy = floorf(fy), gx = floorf(fx);
+    float wy[4], wx[4];
+    cubic_weights(fy - gy, wy);
+    cubic_weights(fx - gx, wx);
+    const int iy = (int)gy, ix = (int)gx;
+    float out = 0.f;
+    for (int a = 0; a < 4; ++a) {
+      const int row = clampi(clampi(iy - 1 + a, 0, H - 1) - ylo, 0, rows - 1);
+      const float* line = vb + row * cols;
+      float rv = 0.f;
+      for (int b = 0; b < 4; ++b) {
+        const int col = clampi(ix - 1 + b, 0, W - 1);
+        float hb = 0.f;
+        for (int j = 0; j < P.ksx; ++j) hb += P.kx[j] * line[clampi(reflecti(col + j - rx, W) - plo, 0, cols - 1)];
+        rv += wx[b] * hb;
+      }
+      out += wy[a] * rv;
+    }
+    if (P.normalize) out = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(out, 1.0f), 0.5f), P.mean[c]), P.stdv[c]);
+    const long di = (((long)img * 3 + c) * P.h + oy) * P.w + ox;
+    if (P.dst_dtype == 0) ((float*)dst)[di] = out;
+    else ((el_t*)dst)[di] = round_to_el(out);
+  }
+}
+
+// one thread per pixel: three bytes in, one element into each of the three channel planes (coalesced over pixels)
+__global__ void pixels_prepare_kernel(const uint8_t* __restrict__ img, const float* __restrict__ noise, float strength, int n,
+                                      long HW, el_t* __restrict__ out) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long)n * HW) return;
+  const long b = idx / HW, p = idx % HW;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const long oi = (b * 3 + c) * HW + p;
+    float v = __fsub_rn(__fmul_rn(2.0f, __fdiv_rn((float)img[idx * 3 + c], 255.0f)), 1.0f);
+    if (noise) v = __fadd_rn(v, __fmul_rn(strength, noise[oi]));
+    out[oi] = round_to_el(v);
+  }
+}
+
+__device__ __forceinline__ unsigned to_u8(float x) {
+  const float v = fminf(fmaxf(__fadd_rn(__fmul_rn(x, 0.5f), 0.5f), 0.0f), 1.0f);
+  return (unsigned)rintf(__fmul_rn(v, 255.0f));          // rintf: round half to even, like numpy's round
+}
+
+// One thread per FOUR consecutive pixels of the flat (frame, y, x) order: 12 output bytes = three aligned dword stores; the last
+// group of the tensor (m H W not a multiple of 4) stores its bytes one by one.  A group may straddle two frames: every pixel
+// finds its own frame.
+__global__ void frames_to_u8_kernel(const el_t* __restrict__ frames, long total, long HW, uint8_t* __restrict__ out) {
+  const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long p0 = g * 4;
+  if (p0 >= total) return;
+  unsigned bytes[12];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const long p = p0 + k < total ? p0 + k : total - 1;
+    const long f = p / HW, s = p % HW;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) bytes[k * 3 + c] = to_u8(el_to_f32(frames[(f * 3 + c) * HW + s]));
+  }
+  if (p0 + 4 <= total) {
+    uint32_t* o = (uint32_t*)(out + p0 * 3);
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+      o[d] = bytes[4 * d] | (bytes[4 * d + 1] << 8) | (bytes[4 * d + 2] << 16) | (bytes[4 * d + 3] << 24);
+  } else {
+    const int left = (int)(total - p0) * 3;
+    for (int i = 0; i < left; ++i) out[p0 * 3 + i] = (uint8_t)bytes[i];
+  }
+}
+
+__device__ __forceinline__ float pio_load(const void* p, int dtype, long i) {
+  if (dtype == 0) return ((const float*)p)[i];
+  if (dtype == 1) return (float)((const _Float16*)p)[i];
+  return bf16_to_f32(((const bf16_t*)p)[i]);
+}
+
+__global__ void cfg_double_kernel(const void* __restrict__ src, int dtype, el_t* __restrict__ dst, long n_src, int cfg) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_src) return;
+  const el_t v = f32_to_el(pio_load(src, dtype, i));
+  if (cfg) {
+    dst[i] = 0;
+    dst[n_src + i] = v;
+  } else {
+    dst[i] = v;
+  }
+}
+
+__global__ void lmi_cond_kernel(const el_t* __restrict__ first, el_t* __restrict__ lmi, int B, int F, int c_lat, int hw, int cfg) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;          // over (half, b, f, c, s)
+  const long per = (long)c_lat * hw, total = (long)(cfg ? 2 : 1) * B * F * per;
+  if (i >= total) return;
+  const long cs = i % per, bf = i / per;                               // bf = (half * B + b) * F + f
+  const long hb = bf / F;
+  const int half = (int)(hb / B), b = (int)(hb % B);
+  const bool cond = !cfg || half == 1;
+  lmi[bf * 2 * per + per + cs] = cond ? first[(long)b * per + cs] : (el_t)0;
+}
+
+__global__ void lmi_scatter_kernel(const el_t* __restrict__ scaled, el_t* __restrict__ lmi, long n_half, long per, int cfg) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;          // over (b, f, c, s) of `scaled`
+  if (i >= n_half) return;
+  const long cs = i % per, bf = i / per;
+  const el_t v = scaled[i];
+  lmi[bf * 2 * per + cs] = v;
+  if (cfg) lmi[(n_half / per + bf) * 2 * per + cs] = v;
+}
+
+__global__ void scale_latents_kernel(const float* x, float* out, el_t* __restrict__ scaled, long n,
+                                     float inv) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float v = x[i];
+  if (out != x) out[i] = v;
+  scaled[i] = round_to_el(__fmul_rn(v, inv));
+}
+
+__global__ void decode_input_kernel(const float* __restrict__ x, el_t* __restrict__ z, long n, float inv) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  z[i] = round_to_el(__fmul_rn(el_to_f32(round_to_el(x[i])), inv));
+}
+
+inline unsigned blocks_for(long n) { return (unsigned)((n + 255) / 256); }
+constexpr long kMaxThreads = 0x7fffffffL * 256;      // one-dimensional grids: 2^31 - 1 workgroups of 256
+
+// ks and the normalised weights of _gaussian_kernel1d for one axis (fp32 like the torch restatement)
+int gaussian_taps(int in, int out, float* k) {
+  const double factor = (double)in / (double)out;
+  const double sigma = fmax((factor - 1.0) / 2.0, 0.001);
+  int ks = (int)fmax(2.0 * 2 * sigma, 3.0);
+  if (ks % 2 == 0) ks += 1;
+  if (ks > kMaxTaps) return ks;
+  const float den = (float)(2 * sigma * sigma);
+  float sum = 0.f;
+  for (int i = 0; i < ks; ++i) {
+    const float x = (float)(i - ks / 2);
+    k[i] = expf(-(x * x) / den);
+    sum += k[i];
+  }
+  for (int i = 0; i < ks; ++i) k[i] /= sum;
+  return ks;
+}
+
+}  // namespace
+
+// Host-side validation of one resize (shared with the clip driver, which must refuse a request before its first launch).
+int ctrlv_resize_check(int n, int H, int W, int h, int w) {
+  CTRLV_CHECK_SHAPE(n > 0 && H > 0 && W > 0 && h > 0 && w > 0 && (long)n * 3 <= 65535, "resize_antialias: n, H, W, h, w must be "
+                    "positive and n <= 21845 (got n=%d, %dx%d -> %dx%d)", n, H, W, h, w);
+  CTRLV_CHECK_SHAPE((long)H <= 8L * h && (long)W <= 8L * w, "resize_antialias: a down-scale factor above 8 (%dx%d -> %dx%d) needs "
+                    "more than %d blur taps", H, W, h, w, kMaxTaps);
+  float k[kMaxTaps];
+  const int ksy = gaussian_taps(H, h, k), ksx = gaussian_taps(W, w, k);
+  CTRLV_CHECK_SHAPE(ksy <= kMaxTaps && ksx <= kMaxTaps, "resize_antialias: %d / %d blur taps, at most %d", ksy, ksx, kMaxTaps);
+  CTRLV_CHECK_SHAPE(ksy / 2 < H && ksx / 2 < W, "resize_antialias: the blur's reflect padding (%d rows, %d columns) is undefined "
+                    "for a %dx%d image", ksy / 2, ksx / 2, H, W);
+  return CTRLV_OK;
+}
+
+extern "C" int ctrlv_resize_antialias(const void* src, int src_u8, int n, int H, int W, void* dst, int dst_dtype, int h, int w,
+                                      const float* mean, const float* std, ctrlv_stream_t stream) {
+  CTRLV_CHECK_ARG(src && dst, "resize_antialias: null pointer");
+  CTRLV_CHECK_ARG((mean == nullptr) == (std == nullptr), "resize_antialias: mean and std come together");
+  if (dst_dtype != 0 && dst_dtype != CTRLV_ELEM_DTYPE) {
+    ctrlv_set_error("resize_antialias: dst dtype code %d (0 fp32 or %d, this library's element type)", dst_dtype, CTRLV_ELEM_DTYPE);
+    return CTRLV_E_BAD_DTYPE;
+  }
+  const int rc = ctrlv_resize_check(n, H, W, h, w);
+  if (rc != CTRLV_OK) return rc;
+  ResizeParams P;
+  memset(&P, 0, sizeof(P));
+  P.n = n; P.H = H; P.W = W; P.h = h; P.w = w;
+  P.ksy = gaussian_taps(H, h, P.ky);
+  P.ksx = gaussian_taps(W, w, P.kx);
+  P.sy = h > 1 ? (float)(H - 1) / (float)(h - 1) : 0.f;
+  P.sx = w > 1 ? (float)(W - 1) / (float)(w - 1) : 0.f;
+  P.src_u8 = src_u8 ? 1 : 0;
+  P.dst_dtype = dst_dtype;
+  P.normalize = mean ? 1 : 0;
+  for (int c = 0; c < 3; ++c) {
+    P.mean[c] = mean ? mean[c] : 0.f;
+    P.stdv[c] = std ? std[c] : 1.f;
+    CTRLV_CHECK_ARG(P.stdv[c] != 0.f, "resize_antialias: std[%d] is zero", c);
+  }
+  // the LDS tile: an upper bound of the source rows / columns a th x 32 output tile touches (the kernel clamps to it)
+  P.span_x = (int)fmin((double)W, floor((kTileW - 1) * (double)P.sx) + 6 + 2 * (P.ksx / 2));
+  size_t lds = 0;
+  for (P.th = 8; P.th >= 1; P.th >>= 1) {
+    P.span_y = (int)fmin((double)H, floor((P.th - 1) * (double)P.sy) + 6);
+    lds = (size_t)P.span_y * P.span_x * sizeof(float);
+    if (lds <= 64 * 1024) break;
+  }
+  CTRLV_CHECK_SHAPE(P.th >= 1, "resize_antialias: a one-row tile needs %zu bytes of LDS", lds);
+  const dim3 grid((unsigned)((w + kTileW - 1) / kTileW), (unsigned)((h + P.th - 1) / P.th), (unsigned)(n * 3));
+  CTRLV_CHECK_SHAPE(grid.y <= 65535, "resize_antialias: %d output rows in tiles of %d", h, P.th);
+  hipLaunchKernelGGL(resize_antialias_kernel, grid, dim3(256), lds, (hipStream_t)stream, src, dst, P);
+  CTRLV_LAUNCH_CHECK();
+  return CTRLV_OK;
+}
+
+extern "C" int ctrlv_pixels_prepare(const void* image_u8, const float* noise, float strength, int n, int H, int W, void* out,
+                                    ctrlv_stream_t stream) {
+  CTRLV_CHECK_ARG(image_u8 && out, "pixels_prepare: null pointer");
+  CTRLV_CHECK_SHAPE(n > 0 && H > 0 && W > 0 && (long)n * H * W <= kMaxThreads, "pixels_prepare: n, H, W must be positive");
+  const long HW = (long)H * W;
+  hipLaunchKernelGGL(pixels_prepare_kernel, dim3(blocks_for(n * HW)), dim3(256), 0, (hipStream_t)stream,
+                     (const uint8_t*)image_u8, noise, strength, n, HW, (el_t*)out);
+  CTRLV_LAUNCH_CHECK();
+  return CTRLV_OK;
+}
+
+extern "C" int ctrlv_frames_to_u8(const void* frames, int m, int H, int W, void* out_u8, ctrlv_stream_t stream) {
+  CTRLV_CHECK_ARG(frames && out_u8, "frames_to_u8: null pointer");
+  CTRLV_CHECK_SHAPE(m > 0 && H > 0 && W > 0, "frames_to_u8: m, H, W must be positive");
+  CTRLV_CHECK_ARG(((uintptr_t)out_u8 & 3) == 0, "frames_to_u8: the output must be 4-byte aligned");
+  const long HW = (long)H * W, total = (long)m * HW;
+  hipLaunchKernelGGL(frames_to_u8_kernel, dim3(blocks_for((total + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                     (const el_t*)frames, total, HW, (uint8_t*)out_u8);
+  CTRLV_LAUNCH_CHECK();
+  return CTRLV_OK;
+}
+
+int ctrlv_pio_cfg_double(const void* src, int src_dtype, void* dst, int B, long per, int cfg, hipStream_t s) {
+  const long n = (long)B * per;
+  hipLaunchKernelGGL(cfg_double_kernel, dim3(blocks_for(n)), dim3(256), 0, s, src, src_dtype, (el_t*)dst, n, cfg);
+  CTRLV_LAUNCH_CHECK();
+  return CTRLV_OK;
+}
+
+int ctrlv_pio_lmi_cond(const void* first, void* lmi, int B, int F, int c_lat, int hw, int cfg, hipStream_t s) {
+  const long total = (long)(cfg ? 2 : 1) * B * F * c_lat * hw;
+  hipLaunchKernelGGL(lmi_cond_kernel, dim3(blocks_for(total)), dim3(256), 0, s, (const el_t*)first, (el_t*)lmi, B, F, c_lat, hw,
+                     cfg);
+  CTRLV_LAUNCH_CHECK();
+  return CTRLV_OK;
+}
+
+int ctrlv_pio_lmi_scatter(const void* scaled, void* lmi, int B, int F, int c_lat, int hw, int cfg, hipStream_t s) {
+  const long per = (long)c_lat * hw, n_half = (long)B * F * per;
+  hipLaunchKernelGGL(lmi_scatter_kernel, dim3(blocks_for(n_half)), dim3(256), 0, s, (const el_t*)scaled, (el_t*)lmi, n_half, per,
+                     cfg);
+  CTRLV_LAUNCH_CHECK();
+  return CTRLV_OK;
+}
+
+int ctrlv_pio_scale_latents(const float* x, float* out, void* scaled, long n, float inv, hipStream_t s) {
+  hipLaunchKernelGGL(scale_latents_kernel, dim3(blocks_for(n)), dim3(256), 0, s, x, out, (el_t*)scaled, n, inv);
+  CTRLV_LAUNCH_CHECK();
+  return CTRLV_OK;
+}
+
+int ctrlv_pio_decode_input(const float* x, void* z, long n, float inv, hipStream_t s) {
+  hipLaunchKernelGGL(decode_input_kernel, dim3(blocks_for(n)), dim3(256), 0, s, x, (el_t*)z, n, inv);
+  CTRLV_LAUNCH_CHECK();
+  return CTRLV_OK;
+}

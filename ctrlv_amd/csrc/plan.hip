@@ -173,6 +173,12 @@ struct ctrlv_plan {
   std::vector<ProfRec> prof;
 };
 
+const ctrlv_model_config* ctrlv_plan_info(const ctrlv_plan* p, int* device, int* loaded) {
+  if (device) *device = p->device;
+  if (loaded) *loaded = p->loaded ? 1 : 0;
+  return &p->cfg;
+}
+
 namespace {
 
 // ------------------------------------------------------------------------------------------------ graph construction

@@ -67,6 +67,12 @@ struct ctrlv_vae_plan {
   float* tco_b = nullptr;
 };
 
+const ctrlv_vae_config* ctrlv_vae_plan_info(const ctrlv_vae_plan* p, int* device, int* loaded) {
+  if (device) *device = p->device;
+  if (loaded) *loaded = p->loaded ? 1 : 0;
+  return &p->cfg;
+}
+
 namespace {
 
 __device__ __forceinline__ float vld_any(const void* p, int dtype, long i) {

@@ -806,3 +806,57 @@ def time_conv_rows_to_nchw_bwd(dout, rows, n_frames, clip_frames, C, HW, weight,
                                                            _p(weight), _p(drows), drows.stride(0), _p(dweight), _p(dbias),
                                                            _p(scratch), _stream()), "ctrlv_time_conv_rows_to_nchw_bwd")
     return drows
+
+
+def resize_antialias(image, size, mean=None, std=None, out_dtype=torch.float32):
+    """`_resize_with_antialiasing(image, size)` (Gaussian pre-blur + bicubic, align_corners) as one kernel
+    (ctrlv_resize_antialias).  image: (n, H, W, 3) uint8 -- read as (v / 255) * 2 - 1 -- or (n, 3, H, W) fp32.  mean / std
+    (three floats each): the epilogue ((y + 1) / 2 - mean) / std.  Returns (n, 3, h, w) in fp32 or in an element type (the fp32
+    value rounded once)."""
+    _need_gpu(image, "image")
+    u8 = image.dtype == torch.uint8
+    if image.dim() != 4 or (image.shape[3] if u8 else image.shape[1]) != 3 or (not u8 and image.dtype != torch.float32):
+        raise ValueError("resize_antialias: image must be (n, H, W, 3) uint8 or (n, 3, H, W) fp32")
+    if (mean is None) != (std is None):
+        raise ValueError("resize_antialias: mean and std come together")
+    image = image.contiguous()
+    n = image.shape[0]
+    H, W = (image.shape[1], image.shape[2]) if u8 else (image.shape[2], image.shape[3])
+    out = torch.empty(n, 3, int(size[0]), int(size[1]), dtype=out_dtype, device=image.device)
+    f3 = ctypes.c_float * 3
+    m = f3(*[float(v) for v in mean]) if mean is not None else None
+    sd = f3(*[float(v) for v in std]) if std is not None else None
+    check(_L(out).ctrlv_resize_antialias(_p(image), 1 if u8 else 0, n, H, W, _p(out), _DT[out_dtype], int(size[0]),
+                                         int(size[1]), m, sd, _stream()), "ctrlv_resize_antialias")
+    return out
+
+
+def pixels_prepare(image_u8, noise=None, strength=0.0, dtype=torch.bfloat16):
+    """(n, H, W, 3) uint8 -> (n, 3, H, W) of the element type `dtype`: 2 * (v / 255) - 1 + strength * noise, noise fp32
+    (n, 3, H, W) or None (ctrlv_pixels_prepare): VaeImageProcessor.preprocess + the noise augmentation + the cast."""
+    _need_gpu(image_u8, "image_u8")
+    if image_u8.dtype != torch.uint8 or image_u8.dim() != 4 or image_u8.shape[3] != 3:
+        raise ValueError("pixels_prepare: image_u8 must be (n, H, W, 3) uint8")
+    image_u8 = image_u8.contiguous()
+    n, H, W, _ = image_u8.shape
+    if noise is not None:
+        if noise.dtype != torch.float32 or tuple(noise.shape) != (n, 3, H, W) or noise.device != image_u8.device:
+            raise ValueError(f"pixels_prepare: noise must be fp32 {(n, 3, H, W)} on the image's device")
+        noise = noise.contiguous()
+    out = torch.empty(n, 3, H, W, dtype=dtype, device=image_u8.device)
+    check(_L(out).ctrlv_pixels_prepare(_p(image_u8), _p(noise), float(strength), n, H, W, _p(out), _stream()),
+          "ctrlv_pixels_prepare")
+    return out
+
+
+def frames_to_u8(frames):
+    """(m, 3, H, W) element frames in [-1, 1] -> (m, H, W, 3) uint8: rint(clamp(x / 2 + 0.5, 0, 1) * 255)
+    (ctrlv_frames_to_u8): VaeImageProcessor.postprocess + numpy_to_pil's rounding."""
+    _need_gpu(frames, "frames")
+    if frames.dim() != 4 or frames.shape[1] != 3 or frames.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError("frames_to_u8: frames must be (m, 3, H, W) fp16 / bf16")
+    frames = frames.contiguous()
+    m, _, H, W = frames.shape
+    out = torch.empty(m, H, W, 3, dtype=torch.uint8, device=frames.device)
+    check(_L(frames).ctrlv_frames_to_u8(_p(frames), m, H, W, _p(out), _stream()), "ctrlv_frames_to_u8")
+    return out

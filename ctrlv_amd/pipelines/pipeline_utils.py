@@ -242,6 +242,28 @@ def resolve_pretrained_dir(name_or_path):
         return None
 
 
+PLAN_ROUTE_OUTPUTS = ("np", "pt", "pil", "latent")
+
+
+def pipeline_route(image, callback_on_step_end, output_type, plans_serve, env=None):
+    """Which route a pipeline call takes: "plan" (the whole clip as ONE C call, ctrlv_pipeline_generate through
+    plan.PipelinePlan) or "python" (prepare_clip -> _denoise -> finish_clip, the default).  Pure host logic.  "plan" is opt-in
+    -- CTRLV_PIPELINE=plan -- and taken only for a PIL image (or a non-empty list of PIL images), without a
+    callback_on_step_end, with output_type np / pt / pil / latent, and where the VAE, CLIP and model plans all serve the call
+    (`plans_serve`: a bool or a callable asked last)."""
+    env = os.environ if env is None else env
+    if env.get("CTRLV_PIPELINE") != "plan":
+        return "python"
+    if PIL is None:
+        return "python"
+    images = image if isinstance(image, list) else [image]
+    if not images or not all(isinstance(im, PIL.Image.Image) for im in images):
+        return "python"
+    if callback_on_step_end is not None or output_type not in PLAN_ROUTE_OUTPUTS:
+        return "python"
+    return "plan" if (plans_serve() if callable(plans_serve) else plans_serve) else "python"
+
+
 class ClipJob:
     """Everything one pipeline call has prepared before its denoising loop (SVDPipelineBase.prepare_clip)."""
     __slots__ = ("height", "width", "num_frames", "decode_chunk", "clips", "device", "clip_embeds", "cond_latents",
@@ -543,6 +565,110 @@ class SVDPipelineBase:
             self.vae.to(dtype=torch.float16)
         self.maybe_free_model_hooks()
         return StableVideoDiffusionPipelineOutput(frames=frames) if return_dict else frames
+
+    # ------------------------------------------------------------------------------------------- the one-call route
+    def _pipeline_plan(self):
+        """The PipelinePlan of this pipeline's modules (cached while the four plans stay the same objects), or None where one
+        of them does not serve: models not on the plan executor or with a split trunk, modules that are not all bf16 on one
+        HIP device (the VAE plan is validated in the bf16 library only), a VAE or CLIP module the plans do not take.  The
+        models' own plans are borrowed as they are (feed-forward precision, merged adapters)."""
+        from ..models import clip_vision_hip
+        from ..plan import PipelinePlan, vae_plan
+        unet, cn = self.unet, getattr(self, "controlnet", None)
+        el = getattr(unet, "el_dtype", None)
+        if el != torch.bfloat16 or unet.dtype != el:
+            return None
+        for m in (unet, cn):
+            if m is None:
+                continue
+            if not m._use_plan() or m.el_dtype != el or m.dtype != el or m.trunk_dtype != "same" or m.device != unet.device:
+                return None
+        dev = unet.device
+        if dev.type != "cuda":
+            return None
+        vae, enc = self.vae, self.image_encoder
+        for m in (vae, enc):
+            ps = list(m.parameters())
+            if not ps or any(q.dtype != el or q.device != dev for q in ps):
+                return None
+        if not (hasattr(vae, "encoder") and hasattr(vae, "decoder") and hasattr(vae, "quant_conv")):
+            return None
+        if clip_vision_hip._parts(enc) is None or len({n.eps for n in clip_vision_hip._norms(enc)}) != 1:
+            return None
+        probe = torch.empty(0, device=dev)
+        try:
+            plans = (unet._ensure_plan(probe), cn._ensure_plan(probe) if cn is not None else None, vae_plan(vae),
+                     clip_vision_hip._plan(enc))
+        except (ValueError, KeyError):
+            return None
+        hit = getattr(self, "_pipeline_plan_cache", None)
+        if hit is None or any(a is not b for a, b in zip(hit[0], plans)):
+            try:
+                hit = self._pipeline_plan_cache = (plans, PipelinePlan(*plans))
+            except ValueError:
+                return None
+        return hit[1]
+
+    def _generate_plan(self, image, cond_images, check, *, height, width, num_frames, decode_chunk_size, fps, motion_bucket_id,
+                       noise_aug_strength, num_videos_per_prompt, generator, latents, latent_channels, min_guidance_scale,
+                       max_guidance_scale, num_inference_steps, control_condition_scale, output_type, return_dict,
+                       callback_on_step_end):
+        """The call through ctrlv_pipeline_generate, or None where the route is not taken (nothing has been drawn or changed
+        then).  The PIL Lanczos resize to the working size and the two random draws stay here, in the reference's order
+        (augmentation noise first, latents second); CLIP sees the working-size image."""
+        if num_videos_per_prompt != 1 or (cond_images is not None and not torch.is_tensor(cond_images)):
+            return None
+        if getattr(self, "controlnet", None) is not None and cond_images is None:
+            return None
+        if pipeline_route(image, callback_on_step_end, output_type, lambda: self._pipeline_plan() is not None) != "plan":
+            return None
+        pp = self._pipeline_plan()
+        unet_cfg = self.unet.config
+        height = height or unet_cfg.sample_size * self.vae_scale_factor
+        width = width or unet_cfg.sample_size * self.vae_scale_factor
+        F = unet_cfg.num_frames if num_frames is None else num_frames
+        chunk = F if decode_chunk_size is None else decode_chunk_size
+        check(height, width)
+        images = image if isinstance(image, list) else [image]
+        images = [im if im.size == (width, height) else im.resize((width, height), resample=PIL.Image.LANCZOS) for im in images]
+        arr = [np.asarray(im) for im in images]
+        if any(a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 for a in arr):
+            return None
+        dev, el = pp.device, pp.dtype
+        n = len(arr)
+        sched = self.scheduler                           # (from here on the route is taken: state changes and draws)
+        sched.set_timesteps(num_inference_steps, device=dev)
+        sigmas, timesteps = list(sched._sigmas_host), list(sched._timesteps_host)
+        cond = None
+        if getattr(self, "controlnet", None) is not None:
+            cond = cond_images.to(dev)
+            if cond.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+                cond = cond.float()
+        self._guidance_scale = max_guidance_scale
+        self._num_timesteps = len(timesteps)
+        image_u8 = torch.from_numpy(np.stack(arr)).to(dev)
+        aug = randn_tensor((n, 3, height, width), generator=generator, device=dev, dtype=torch.float32)       # random draw 1
+        lat = self.prepare_latents(n, F, latent_channels, height, width, el, dev, generator, latents)           # random draw 2
+        fe = self.feature_extractor
+        mean, std = getattr(fe, "image_mean", None), getattr(fe, "image_std", None)
+        want_frames = output_type != "latent"
+        out_lat, frames, u8 = pp.generate(
+            image_u8, lat.float(), sigmas, timesteps, cond=cond, aug_noise=aug, noise_aug_strength=noise_aug_strength, fps=fps,
+            motion_bucket_id=motion_bucket_id, min_guidance=min_guidance_scale, max_guidance=max_guidance_scale,
+            conditioning_scale=control_condition_scale, decode_chunk=chunk, clip_mean=mean, clip_std=std,
+            frames=want_frames and output_type != "pil", frames_u8=output_type == "pil")
+        ramp = torch.linspace(min_guidance_scale, max_guidance_scale, F, device="cpu")
+        self._guidance_scale = ramp.to(dev, el).unsqueeze(0).repeat(n, 1)[:, :, None, None, None]
+        if output_type == "latent":
+            out = out_lat.to(el)
+        elif output_type == "pil":
+            host = u8.cpu().numpy()
+            out = [[PIL.Image.fromarray(host[b, f]) for f in range(F)] for b in range(n)]
+        else:
+            video = frames.reshape(n, F, 3, height, width).permute(0, 2, 1, 3, 4).float()
+            out = tensor2vid(video, self.image_processor, output_type=output_type)
+        self.maybe_free_model_hooks()
+        return StableVideoDiffusionPipelineOutput(frames=out) if return_dict else out
 
     def _denoise(self, latents, image_latents, image_embeddings, added_time_ids, cond_em, num_inference_steps,
                  min_guidance_scale, max_guidance_scale, control_condition_scale, callback_on_step_end,

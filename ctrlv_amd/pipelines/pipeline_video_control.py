@@ -58,6 +58,17 @@ class StableVideoControlPipeline(SVDPipelineBase):
         callback_on_step_end_tensor_inputs: List[str] = ["latents"],
         return_dict: bool = True,
     ):
+        # opt-in (CTRLV_PIPELINE=plan): the whole clip as one C call where the plans serve it (pipeline_utils.pipeline_route)
+        done = self._generate_plan(
+            image, cond_images, lambda h, w: self.check_inputs(image, cond_images, h, w), height=height, width=width,
+            num_frames=num_frames, decode_chunk_size=decode_chunk_size, fps=fps, motion_bucket_id=motion_bucket_id,
+            noise_aug_strength=noise_aug_strength, num_videos_per_prompt=num_videos_per_prompt, generator=generator,
+            latents=latents, latent_channels=self.unet.config.out_channels * 2, min_guidance_scale=min_guidance_scale,
+            max_guidance_scale=max_guidance_scale, num_inference_steps=num_inference_steps,
+            control_condition_scale=control_condition_scale, output_type=output_type, return_dict=return_dict,
+            callback_on_step_end=callback_on_step_end) if cond_images is not None else None
+        if done is not None:
+            return done
         job = self.prepare_clip(
             image, lambda h, w: self.check_inputs(image, cond_images, h, w), height=height, width=width,
             num_frames=num_frames, decode_chunk_size=decode_chunk_size, fps=fps, motion_bucket_id=motion_bucket_id,

@@ -291,11 +291,13 @@ class VaePlan:
     `load_state_dict` (diffusers keys: encoder.*, decoder.*, quant_conv.*), workspace, `encode` / `decode`
     (include/ctrlv_hip.h).  The plan runs in bf16 elements: the Python layer routes the VAE to libctrlv_hip.so."""
 
-    def __init__(self, config, device, offset_limit_bytes=0):
-        """config: the fields of AutoencoderKLTemporalDecoder's config (a dict or its config object)."""
+    def __init__(self, config, device, offset_limit_bytes=0, dtype=torch.bfloat16):
+        """config: the fields of AutoencoderKLTemporalDecoder's config (a dict or its config object).  dtype: the element type;
+        torch.float16 selects libctrlv_hip_f16.so's build of the same walk (what a PipelinePlan of fp16 models borrows)."""
         get = config.get if isinstance(config, dict) else (lambda k, d=None: getattr(config, k, d))
         self.device = torch.device(device)
-        self._lib = _lib.load(torch.bfloat16)
+        self.dtype = dtype
+        self._lib = _lib.load(dtype)
         self._h = ctypes.c_void_p()
         c = self._cfg = _lib.VaeConfig()
         boc = tuple(get("block_out_channels"))
@@ -397,21 +399,131 @@ class VaePlan:
         return out
 
 
+class PipelinePlan:
+    """Owns one `ctrlv_pipeline`: a whole clip as one C call (include/ctrlv_hip.h: ctrlv_pipeline_generate) on four borrowed
+    plans of ONE library -- `Plan("unet")`, `Plan("controlnet")` or None, `VaePlan`, `ClipPlan`.  The object keeps them alive."""
+
+    def __init__(self, unet_plan, controlnet_plan, vae_plan, clip_plan):
+        self.unet, self.controlnet, self.vae, self.clip = unet_plan, controlnet_plan, vae_plan, clip_plan
+        self.dtype = unet_plan.dtype
+        self.device = unet_plan.device
+        self._lib = unet_plan._lib
+        for q in (controlnet_plan, vae_plan, clip_plan):
+            if q is not None and q._lib is not self._lib:
+                raise ValueError("PipelinePlan: the four plans must come from one library (one element type)")
+        self._h = ctypes.c_void_p()
+        check(self._lib.ctrlv_pipeline_create(unet_plan._h, controlnet_plan._h if controlnet_plan is not None else None,
+                                              vae_plan._h, clip_plan._h, self.device.index or 0, ctypes.byref(self._h)),
+              "ctrlv_pipeline_create")
+        self._ws = None
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                self._lib.ctrlv_pipeline_destroy(h)
+            except Exception:       # noqa: BLE001  (interpreter shutdown)
+                pass
+
+    def set_overlap(self, on):
+        check(self._lib.ctrlv_pipeline_set_overlap(self._h, 1 if on else 0), "ctrlv_pipeline_set_overlap")
+
+    def request(self, image_u8, latents, sigmas, timesteps, *, cond=None, aug_noise=None, noise_aug_strength=0.02, fps=7,
+                motion_bucket_id=127, min_guidance=1.0, max_guidance=3.0, conditioning_scale=1.0, decode_chunk=None,
+                clip_mean=None, clip_std=None, out_latents=None, out_frames=None, out_frames_u8=None):
+        """The `ctrlv_clip_request` of a call plus the objects its pointers refer to (keep the pair together)."""
+        n, H, W, _ = image_u8.shape
+        F = latents.shape[1]
+        sig = (ctypes.c_float * len(sigmas))(*[float(v) for v in sigmas])
+        ts = (ctypes.c_float * len(timesteps))(*[float(v) for v in timesteps])
+        r = _lib.ClipRequest()
+        r.n_clips, r.num_frames, r.height, r.width = n, F, H, W
+        r.image_u8 = image_u8.data_ptr()
+        if cond is not None:
+            r.cond, r.cond_channels, r.cond_dtype = cond.data_ptr(), cond.shape[2], _DT[cond.dtype]
+        if aug_noise is not None:
+            r.aug_noise = aug_noise.data_ptr()
+        r.noise_aug_strength = float(noise_aug_strength)
+        r.num_steps = len(timesteps)
+        r.latents = latents.data_ptr()
+        r.sigmas, r.timesteps = sig, ts
+        r.fps, r.motion_bucket_id = int(fps), int(motion_bucket_id)
+        r.min_guidance, r.max_guidance = float(min_guidance), float(max_guidance)
+        r.conditioning_scale = float(conditioning_scale)
+        r.decode_chunk = int(F if decode_chunk is None else decode_chunk)
+        if clip_mean is not None:
+            for i in range(3):
+                r.clip_mean[i], r.clip_std[i] = float(clip_mean[i]), float(clip_std[i])
+        for name, t in (("out_latents", out_latents), ("out_frames", out_frames), ("out_frames_u8", out_frames_u8)):
+            if t is not None:
+                setattr(r, name, t.data_ptr())
+        return r, (sig, ts, image_u8, latents, cond, aug_noise, out_latents, out_frames, out_frames_u8)
+
+    def workspace_bytes(self, request):
+        n = self._lib.ctrlv_pipeline_workspace_bytes(self._h, ctypes.byref(request))
+        if n == 0:
+            check(-2, "ctrlv_pipeline_workspace_bytes", lib=self._lib)
+        return n
+
+    def generate(self, image_u8, latents, sigmas, timesteps, *, cond=None, aug_noise=None, frames=True, frames_u8=True, **kw):
+        """image_u8 (n, H, W, 3) uint8 at the working size; latents fp32 (n, F, L, h, w) already multiplied by
+        init_noise_sigma; sigmas [steps + 1] / timesteps [steps]: the scheduler's values (host floats); cond (n, F, 3, H, W)
+        pixels or (n, F, L, h, w) latents; aug_noise fp32 (n, 3, H, W) or None; the other fields of `request` by keyword.
+        Everything on the plan's device, enqueued on torch's current stream.  Returns (latents fp32, frames (n F, 3, H, W) in
+        the element type or None, frames_u8 (n, F, H, W, 3) or None)."""
+        dev = self.device
+        for name, t in (("image_u8", image_u8), ("latents", latents), ("cond", cond), ("aug_noise", aug_noise)):
+            if t is not None and (not t.is_cuda or (t.device.index or 0) != (dev.index or 0)):
+                raise ValueError(f"PipelinePlan.generate: {name} on {t.device}, the plans' weights on {dev}")
+        if image_u8.dtype != torch.uint8 or image_u8.dim() != 4 or image_u8.shape[3] != 3:
+            raise ValueError("PipelinePlan.generate: image_u8 must be (n, H, W, 3) uint8")
+        if latents.dtype != torch.float32 or latents.dim() != 5:
+            raise ValueError("PipelinePlan.generate: latents must be fp32 (n, F, L, h, w)")
+        n, H, W, _ = image_u8.shape
+        F = latents.shape[1]
+        if tuple(latents.shape) != (n, F, latents.shape[2], H // 8, W // 8):
+            raise ValueError(f"PipelinePlan.generate: latents {tuple(latents.shape)} do not match a {n} x {H} x {W} image")
+        if cond is not None:
+            want = (n, F, 3, H, W) if cond.dim() == 5 and cond.shape[2] == 3 else (n, F, latents.shape[2], H // 8, W // 8)
+            if tuple(cond.shape) != want or cond.dtype not in _DT:
+                raise ValueError(f"PipelinePlan.generate: cond {tuple(cond.shape)} must be {want} in fp32 / fp16 / bf16")
+            cond = cond.contiguous()
+        if aug_noise is not None:
+            if aug_noise.dtype != torch.float32 or tuple(aug_noise.shape) != (n, 3, H, W):
+                raise ValueError(f"PipelinePlan.generate: aug_noise must be fp32 {(n, 3, H, W)}")
+            aug_noise = aug_noise.contiguous()
+        image_u8, latents = image_u8.contiguous(), latents.contiguous()
+        out_lat = torch.empty_like(latents)
+        out_fr = torch.empty(n * F, 3, H, W, dtype=self.dtype, device=dev) if frames else None
+        out_u8 = torch.empty(n, F, H, W, 3, dtype=torch.uint8, device=dev) if frames_u8 else None
+        r, keep = self.request(image_u8, latents, sigmas, timesteps, cond=cond, aug_noise=aug_noise, out_latents=out_lat,
+                               out_frames=out_fr, out_frames_u8=out_u8, **kw)
+        need = self.workspace_bytes(r)
+        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        check(self._lib.ctrlv_pipeline_generate(self._h, ctypes.byref(r), self._ws.data_ptr(), self._ws.numel(), st),
+              "ctrlv_pipeline_generate")
+        del keep
+        return out_lat, out_fr, out_u8
+
+
 _VAE_PLANS = {}
 
 
-def vae_plan(vae, offset_limit_bytes=0):
+def vae_plan(vae, offset_limit_bytes=0, dtype=torch.bfloat16):
     """The `VaePlan` of an AutoencoderKLTemporalDecoder module, cached per object and keyed on the parameters' versions and
-    storage (as the per-op executors' `_pack`): an in-place parameter update reloads the weights."""
+    storage (as the per-op executors' `_pack`): an in-place parameter update reloads the weights.  dtype: the plan's element
+    type (bf16 for the module's own encode / decode routes)."""
     import weakref
-    key = (id(vae), int(offset_limit_bytes))
+    key = (id(vae), int(offset_limit_bytes)) if dtype == torch.bfloat16 else (id(vae), int(offset_limit_bytes), dtype)
     params = list(vae.parameters())
     ver = tuple(p._version for p in params) + (params[0].data_ptr(),)
     hit = _VAE_PLANS.get(key)
     if hit is not None and hit[0] == ver and hit[1]() is vae:
         return hit[2]
     plan = hit[2] if hit is not None and hit[1]() is vae and hit[2].device == params[0].device else \
-        VaePlan(vae.config, params[0].device, offset_limit_bytes)
+        VaePlan(vae.config, params[0].device, offset_limit_bytes, dtype)
     plan.load_state_dict(vae.state_dict())
     _VAE_PLANS[key] = (ver, weakref.ref(vae), plan)
     return plan

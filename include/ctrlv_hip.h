@@ -45,7 +45,8 @@ enum {
  * decoder's training walk, ctrlv_softmax_rows_bwd and ctrlv_time_conv_rows_to_nchw_bwd).  Purely ADDITIVE entry points do not
  * bump the number: a host built against 22 runs unchanged on a library that also exports the CLIP vision kernels
  * (ctrlv_attention_tokens, ctrlv_clip_patch_rows, ctrlv_clip_tokens, ctrlv_act_rows) or ctrlv_gemm_tokens and the CLIP plan
- * (ctrlv_clip_*) ctrlv_vae_posterior or the VAE plan (ctrlv_vae_*), and a host that needs them fails at symbol lookup on a library without them.
+ * (ctrlv_clip_*) ctrlv_vae_posterior or the VAE plan (ctrlv_vae_*) or the whole-clip driver and its I/O kernels (ctrlv_pipeline_*,
+ * ctrlv_resize_antialias, ctrlv_pixels_prepare, ctrlv_frames_to_u8), and a host that needs them fails at symbol lookup on a library without them.
  * NOT neutral, although the number did not move: ctrlv_gemm_desc.pad_br gives meaning to four bytes that were alignment
  * padding, so descriptors must now be zero-initialised (see the field). */
 int ctrlv_abi_version(void);
@@ -792,6 +793,87 @@ int ctrlv_vae_encode(ctrlv_vae_plan* plan, const void* pixels, int dtype, int n,
 int ctrlv_vae_decode(ctrlv_vae_plan* plan, const void* z, int dtype, int n, int num_frames, int h, int w, void* frames,
                      int out_dtype, void* workspace, size_t workspace_bytes, ctrlv_stream_t stream);
 int ctrlv_vae_plan_destroy(ctrlv_vae_plan* plan);
+
+/* ==================================================================================================================
+ * A whole clip as ONE call (csrc/pipeline.hip, csrc/pipeline_io.hip): what StableVideoControlPipeline.__call__
+ * (pipeline_video_control.py:196-350) / VideoDiffusionPipeline.__call__ compute between a uint8 conditioning image (plus the box
+ * frames) and uint8 video frames -- prepare_clip -> the denoising loop -> finish_clip of ctrlv_amd/pipelines/pipeline_utils.py --
+ * for a host in any language.  Additive entry points: the ABI number does not change.
+ * ================================================================================================================== */
+/* _resize_with_antialiasing (Gaussian pre-blur, reflect padding; bicubic, align_corners=True, A = -0.75, indices clamped to the
+ * image) fused with the affine steps around it.  src: src_u8 = 1: (n, H, W, 3) uint8, read as (v / 255) * 2 - 1; src_u8 = 0:
+ * (n, 3, H, W) fp32.  Per axis sigma = max((factor - 1) / 2, 0.001), ks = int(max(4 sigma, 3)) made odd, weights exp(-x^2 / (2
+ * sigma^2)) normalised (fp32, formed on the host).  mean / std: host float[3], both or neither: the epilogue ((y + 1) / 2 -
+ * mean[c]) / std[c] (CLIP's normalisation).  dst (n, 3, h, w): dst_dtype 0 fp32, or the library's element code: the fp32 value
+ * rounded to nearest even.  The blurred rows of an output tile are staged in LDS: the blurred image never reaches memory.
+ * CTRLV_E_BAD_SHAPE (host validation): ks / 2 >= H or >= W (reflect padding undefined), a per-axis factor above 8 (more than 15
+ * taps), n > 21845. */
+int ctrlv_resize_antialias(const void* src, int src_u8, int n, int H, int W, void* dst, int dst_dtype, int h, int w,
+                           const float* mean, const float* std, ctrlv_stream_t stream);
+/* The VAE encoder's pixel input: image_u8 (n, H, W, 3) uint8, noise fp32 (n, 3, H, W) or NULL -> out (n, 3, H, W) elements =
+ * rne(2 * (v / 255) - 1 + strength * noise), every operation rounded in fp32 (VaeImageProcessor.preprocess + the noise
+ * augmentation of prepare_clip + the cast to the VAE's dtype). */
+int ctrlv_pixels_prepare(const void* image_u8, const float* noise, float strength, int n, int H, int W, void* out,
+                         ctrlv_stream_t stream);
+/* Decoded frames to display bytes: frames (m, 3, H, W) elements (as ctrlv_vae_decode writes them) -> out_u8 (m, H, W, 3) uint8
+ * (4-byte aligned) = rint(clamp(x / 2 + 0.5, 0, 1) * 255), half to even (VaeImageProcessor.postprocess + numpy_to_pil). */
+int ctrlv_frames_to_u8(const void* frames, int m, int H, int W, void* out_u8, ctrlv_stream_t stream);
+
+/* One clip request.  The caller MUST clear the struct (memset / calloc / `= {0}` / ctypes) before setting fields, as with
+ * ctrlv_gemm_desc.  Device pointers unless said otherwise; h = height / 8, w = width / 8, L = the VAE's latent channels. */
+typedef struct ctrlv_clip_request {
+  int32_t n_clips, num_frames, height, width;   /* clips, frames per clip (<= 32), pixels (multiples of what the plans need) */
+  const void* image_u8;          /* (n, H, W, 3) uint8, already at the working size */
+  const void* cond;              /* cond_channels 3: (n, F, 3, H, W) pixels in [-1, 1]; 4: latents (n, F, L, h, w).  NULL only
+                                    without a ControlNet */
+  int32_t cond_channels;
+  int32_t cond_dtype;            /* dtype code of cond (0 fp32, 1 fp16, 2 bf16) */
+  const float* aug_noise;        /* fp32 (n, 3, H, W) or NULL: the library draws no random numbers */
+  float noise_aug_strength;      /* applied to aug_noise, and the third added time id */
+  int32_t num_steps;             /* 1 .. 1024 */
+  const float* latents;          /* fp32 (n, F, L, h, w): the initial noise ALREADY multiplied by init_noise_sigma */
+  const float* sigmas;           /* HOST float[num_steps + 1], the scheduler's own values, strictly decreasing, sigmas[i] > 0 for
+                                    i < num_steps (the host keeps the schedule) */
+  const float* timesteps;        /* HOST float[num_steps] */
+  int32_t fps, motion_bucket_id; /* added time ids = [fps - 1, motion_bucket_id, noise_aug_strength], each rounded to the element
+                                    type as the pipelines' _get_add_time_ids does */
+  float min_guidance, max_guidance;   /* per-frame ramp linspace(min, max, F); classifier-free guidance is on iff max > 1 */
+  float conditioning_scale;      /* of the ControlNet residuals */
+  int32_t decode_chunk;          /* frames per ctrlv_vae_decode call over the n F frames in order (the last chunk may be shorter);
+                                    needed when frames are asked for */
+  float clip_mean[3], clip_std[3];    /* the feature extractor's image_mean / image_std; all six zero = CLIP's own values */
+  float* out_latents;            /* fp32 (n, F, L, h, w), always written (may be `latents` itself) */
+  void* out_frames;              /* (n F, 3, H, W) elements in [-1, 1] as decoded, or NULL */
+  void* out_frames_u8;           /* (n, F, H, W, 3) uint8, or NULL */
+} ctrlv_clip_request;
+typedef struct ctrlv_pipeline ctrlv_pipeline;
+/* Borrows the four plans (they must outlive the pipeline, be of THIS library and on `device`); controlnet may be NULL (the
+ * SVD-only pipeline).  Host-only validation: needs no GPU.  The side stream and the two events of the ControlNet overlap are
+ * created by the first ctrlv_pipeline_generate that uses them and released by ctrlv_pipeline_destroy. */
+int ctrlv_pipeline_create(ctrlv_plan* unet, ctrlv_plan* controlnet, ctrlv_vae_plan* vae, ctrlv_clip_plan* clip, int device,
+                          ctrlv_pipeline** out);
+/* on = 1 (default): the ControlNet forward of a step runs on the driver's side stream beside the UNet's down / mid blocks
+ * (ctrlv_unet_forward's residual_event); 0: one chain on the caller's stream.  Same bits either way. */
+int ctrlv_pipeline_set_overlap(ctrlv_pipeline* p, int on);
+/* Bytes of workspace ctrlv_pipeline_generate needs for `r` (pure host arithmetic: the geometry, cond_channels, decode_chunk and
+ * which outputs are asked for; never num_steps); 0 on error (a request generate would refuse, or plans without weights:
+ * ctrlv_last_error). */
+size_t ctrlv_pipeline_workspace_bytes(ctrlv_pipeline* p, const ctrlv_clip_request* r);
+/* The clip, enqueued on `stream` (and, with overlap, on the side stream, which is joined to `stream` before the call returns):
+ *   1. ctrlv_resize_antialias to the CLIP plan's image_size with the normalisation, ctrlv_clip_forward; ehs = (0 | embeds)
+ *   2. ctrlv_pixels_prepare, ctrlv_vae_encode (mode, scale 1) of the image -- repeated over the frames as the conditioning
+ *      channels of the model input (0 | latent) -- and of cond when it has 3 channels; control_cond = (0 | cond latents)
+ *   3. added time ids, guidance ramp, timesteps: ONE upload in front of the loop (step i passes &t_dev[i])
+ *   4. step 0's scaled input = rne(latents * (float) (1 / sqrt(sigma_0^2 + 1))), the reciprocal formed in double
+ *      (DenoiseStepper.set_latents: torch's division of a device tensor by a host scalar); per step: the
+ *      scaled input into both halves, ctrlv_controlnet_forward, ctrlv_unet_forward, ctrlv_cfg_euler_step.  No host-device copy
+ *      and no synchronisation inside the loop
+ *   5. z = rne(rne(latents) * (float) (1 / scaling_factor)), ctrlv_vae_decode per chunk;  6. ctrlv_frames_to_u8
+ * Every argument and size is validated on the host before the first launch; `ws` (256-byte aligned, caller-owned) smaller than
+ * ctrlv_pipeline_workspace_bytes is CTRLV_E_WORKSPACE.  UNet and ControlNet work in disjoint regions; the CLIP, VAE-encode and
+ * VAE-decode phases alias them.  No HIP-graph capture inside.  Not thread-safe on one pipeline. */
+int ctrlv_pipeline_generate(ctrlv_pipeline* p, const ctrlv_clip_request* r, void* ws, size_t ws_bytes, ctrlv_stream_t stream);
+int ctrlv_pipeline_destroy(ctrlv_pipeline* p);
 
 #ifdef __cplusplus
 }
