@@ -7,21 +7,15 @@
 // ctrlv_gemm_tokens, cleared once per forward: every sliced launch leaves them zero for the next; two shapes for ViT-H) and
 // one strided copy node (the class rows).  One stream, one chain.
 #include <string>
-#include <unordered_map>
 #include <vector>
 
-#include "common.h"
-
-#define TRY(expr)                      \
-  do {                                 \
-    const int rc__ = (expr);           \
-    if (rc__ != CTRLV_OK) return rc__; \
-  } while (0)
+#include "weight_loader.h"
 
 namespace {
 
-struct ClipLinear { el_t* w = nullptr; float* b = nullptr; int n = 0, k = 0; };
-struct ClipNorm { float* g = nullptr; float* b = nullptr; };
+using ctrlv_load::WeightLoader;
+using ClipLinear = ctrlv_load::PackedLinear;
+using ClipNorm = ctrlv_load::NormParams;
 struct ClipLayer { ClipNorm ln1, ln2; ClipLinear qkv, out, fc1, fc2; };
 
 }  // namespace
@@ -63,97 +57,6 @@ namespace {
 // on 10 workgroups.
 inline bool use_tokens(int N, int K) { return K >= 4096 && K >= 4 * N; }
 
-__device__ __forceinline__ float ld_any(const void* p, int dtype, long i) {
-  if (dtype == 0) return ((const float*)p)[i];
-  if (dtype == 1) return (float)((const _Float16*)p)[i];
-  return bf16_to_f32(((const bf16_t*)p)[i]);
-}
-// dst[(n_off + n) * ld + c] = src[n * C + c]   (dst pre-zeroed: the K padding)
-__global__ void clip_pack_rows_kernel(const void* __restrict__ src, int dtype, long total, int C, el_t* __restrict__ dst, int ld,
-                                      int n_off) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x)
-    dst[(i / C + n_off) * ld + i % C] = f32_to_el(ld_any(src, dtype, i));
-}
-__global__ void clip_pack_f32_kernel(const void* __restrict__ src, int dtype, long total, float* __restrict__ dst) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x)
-    dst[i] = ld_any(src, dtype, i);
-}
-
-inline unsigned blocks_for(long total) { return (unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096); }
-
-struct ClipLoader {
-  ctrlv_clip_plan* p;
-  std::unordered_map<std::string, const ctrlv_tensor_desc*> map;
-  std::vector<void*> staged;
-
-  int find(const std::string& name, long numel, const void** src, int* dtype) {
-    auto it = map.find(name);
-    if (it == map.end()) { ctrlv_set_error("clip_plan_load_weights: missing tensor '%s'", name.c_str()); return CTRLV_E_BAD_ARG; }
-    const ctrlv_tensor_desc* t = it->second;
-    if (t->numel != numel) {
-      ctrlv_set_error("clip_plan_load_weights: '%s' has %ld elements, expected %ld", name.c_str(), (long)t->numel, numel);
-      return CTRLV_E_BAD_SHAPE;
-    }
-    if (t->dtype < 0 || t->dtype > 2 || !t->data) {
-      ctrlv_set_error("clip_plan_load_weights: '%s': dtype code %d / null data", name.c_str(), t->dtype);
-      return CTRLV_E_BAD_DTYPE;
-    }
-    *dtype = t->dtype;
-    if (t->on_device) { *src = t->data; return CTRLV_OK; }
-    const size_t bytes = (size_t)t->numel * (t->dtype == 0 ? 4 : 2);
-    void* d = nullptr;
-    CTRLV_HIP_TRY(hipMalloc(&d, bytes));
-    staged.push_back(d);
-    CTRLV_HIP_TRY(hipMemcpy(d, t->data, bytes, hipMemcpyHostToDevice));
-    *src = d;
-    return CTRLV_OK;
-  }
-  int alloc(size_t bytes, void** out, bool zero) {
-    void* d = nullptr;
-    CTRLV_HIP_TRY(hipMalloc(&d, bytes ? bytes : 256));
-    p->owned.push_back(d);
-    if (zero) CTRLV_HIP_TRY(hipMemsetAsync(d, 0, bytes ? bytes : 256, nullptr));
-    *out = d;
-    return CTRLV_OK;
-  }
-  int rows(const std::string& name, int N, int C, ClipLinear& l, int n_off) {
-    const void* src;
-    int dt;
-    TRY(find(name, (long)N * C, &src, &dt));
-    clip_pack_rows_kernel<<<blocks_for((long)N * C), 256, 0, nullptr>>>(src, dt, (long)N * C, C, l.w, l.k, n_off);
-    CTRLV_LAUNCH_CHECK();
-    return CTRLV_OK;
-  }
-  int vec(const std::string& name, long n, float* dst) {
-    const void* src;
-    int dt;
-    TRY(find(name, n, &src, &dt));
-    clip_pack_f32_kernel<<<blocks_for(n), 256, 0, nullptr>>>(src, dt, n, dst);
-    CTRLV_LAUNCH_CHECK();
-    return CTRLV_OK;
-  }
-  int new_linear(ClipLinear& l, int N, int K, bool bias) {
-    l.n = (N + 31) / 32 * 32;
-    l.k = (K + 63) / 64 * 64;
-    TRY(alloc((size_t)l.n * l.k * 2, (void**)&l.w, true));
-    l.b = nullptr;
-    if (bias) TRY(alloc((size_t)l.n * 4, (void**)&l.b, true));
-    return CTRLV_OK;
-  }
-  int linear(const std::string& mod, int N, int K, ClipLinear& l, bool bias) {
-    TRY(new_linear(l, N, K, bias));
-    TRY(rows(mod + ".weight", N, K, l, 0));
-    if (bias) TRY(vec(mod + ".bias", N, l.b));
-    return CTRLV_OK;
-  }
-  int norm(const std::string& mod, int C, ClipNorm& nm) {
-    TRY(alloc((size_t)C * 4, (void**)&nm.g, false));
-    TRY(alloc((size_t)C * 4, (void**)&nm.b, false));
-    TRY(vec(mod + ".weight", C, nm.g));
-    return vec(mod + ".bias", C, nm.b);
-  }
-};
-
 void free_owned(ctrlv_clip_plan* p) {
   for (void* d : p->owned) (void)hipFree(d);
   p->owned.clear();
@@ -161,38 +64,33 @@ void free_owned(ctrlv_clip_plan* p) {
   p->loaded = false;
 }
 
-int load_all(ClipLoader& L) {
-  ctrlv_clip_plan* p = L.p;
+int load_all(WeightLoader& L, ctrlv_clip_plan* p) {
   const ctrlv_clip_config& c = p->cfg;
   const int C = c.hidden_size, I = c.intermediate_size, pp3 = 3 * c.patch_size * c.patch_size;
   const std::string vm = "vision_model.";
-  TRY(L.linear(vm + "embeddings.patch_embedding", C, pp3, p->patch, false));
-  TRY(L.alloc((size_t)C * 4, (void**)&p->cls, false));
-  TRY(L.vec(vm + "embeddings.class_embedding", C, p->cls));
-  TRY(L.alloc((size_t)p->tokens * C * 4, (void**)&p->pos, false));
-  TRY(L.vec(vm + "embeddings.position_embedding.weight", (long)p->tokens * C, p->pos));
-  TRY(L.norm(vm + "pre_layrnorm", C, p->pre));
+  CTRLV_TRY(L.linear(vm + "embeddings.patch_embedding", C, pp3, p->patch, false));
+  CTRLV_TRY(L.vec(vm + "embeddings.class_embedding", C, &p->cls));
+  CTRLV_TRY(L.vec(vm + "embeddings.position_embedding.weight", (long)p->tokens * C, &p->pos));
+  CTRLV_TRY(L.norm(vm + "pre_layrnorm", C, p->pre));
   p->layers.resize(c.num_hidden_layers);
   for (int i = 0; i < c.num_hidden_layers; ++i) {
     ClipLayer& l = p->layers[i];
     const std::string b = vm + "encoder.layers." + std::to_string(i) + ".";
-    TRY(L.norm(b + "layer_norm1", C, l.ln1));
-    TRY(L.norm(b + "layer_norm2", C, l.ln2));
-    TRY(L.new_linear(l.qkv, 3 * C, C, true));
+    CTRLV_TRY(L.norm(b + "layer_norm1", C, l.ln1));
+    CTRLV_TRY(L.norm(b + "layer_norm2", C, l.ln2));
+    CTRLV_TRY(L.new_linear(l.qkv, 3 * C, pad_to(C, 64), true));
     const char* names[3] = {"q_proj", "k_proj", "v_proj"};
     for (int j = 0; j < 3; ++j) {
-      TRY(L.rows(b + "self_attn." + names[j] + ".weight", C, C, l.qkv, j * C));
-      TRY(L.vec(b + "self_attn." + names[j] + ".bias", C, l.qkv.b + j * C));
+      CTRLV_TRY(L.pack_w(b + "self_attn." + names[j] + ".weight", C, C, 1, l.qkv, 0, 0, j * C, 0));
+      CTRLV_TRY(L.pack_v(b + "self_attn." + names[j] + ".bias", C, l.qkv.b, j * C, 0, 0));
     }
-    TRY(L.linear(b + "self_attn.out_proj", C, C, l.out, true));
-    TRY(L.linear(b + "mlp.fc1", I, C, l.fc1, true));
-    TRY(L.linear(b + "mlp.fc2", C, I, l.fc2, true));
+    CTRLV_TRY(L.linear(b + "self_attn.out_proj", C, C, l.out));
+    CTRLV_TRY(L.linear(b + "mlp.fc1", I, C, l.fc1));
+    CTRLV_TRY(L.linear(b + "mlp.fc2", C, I, l.fc2));
   }
-  TRY(L.norm(vm + "post_layernorm", C, p->post));
+  CTRLV_TRY(L.norm(vm + "post_layernorm", C, p->post));
   return L.linear("visual_projection", c.projection_dim, C, p->proj, false);
 }
-
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 
 // One ctrlv_gemm_tokens workspace per sliced weight shape: the counter block at its head is sized by the shape, so two shapes
 // must not share one (the slabs of the smaller block would overwrite the counters of the larger).
@@ -265,13 +163,8 @@ int gemm_any(const Fwd& f, const el_t* A, const ClipLinear& l, int M, int N, el_
     d.ws_zeroed = 1;            // forward() cleared this shape's counters once; every sliced launch leaves them zero
     return ctrlv_gemm_tokens(&d, f.st);
   }
-  ctrlv_gemm_desc d;
-  memset(&d, 0, sizeof d);
-  d.A = A; d.W = l.w; d.out = out; d.bias = l.b; d.R1 = R1;
-  d.M = M; d.N = N; d.Cin = l.k; d.taps = 1;
-  d.lda = l.k; d.ldo = N; d.n_store = N; d.ldr1 = R1 ? N : 0;
-  d.s_acc = 1.0f; d.s1 = 1.0f; d.s2 = 1.0f;
-  d.vdiv = 1; d.vmod = 1 << 30; d.vS = 1;
+  ctrlv_gemm_desc d = ctrlv_linear_desc(A, l.k, l, out, N, M, N, l.k, N);
+  d.R1 = R1; d.ldr1 = R1 ? N : 0;
   return ctrlv_gemm(&d, f.st);
 }
 
@@ -281,30 +174,30 @@ int forward(ctrlv_clip_plan* p, const Regions& r, const void* px, int dtype, int
   const float eps = c.layer_norm_eps;
   const Fwd f{&r, st};
   for (int i = 0; i < r.n_tws; ++i) CTRLV_HIP_TRY(hipMemsetAsync(r.tws[i].p, 0, r.tws[i].cnt, st));
-  TRY(ctrlv_clip_patch_rows(px, dtype, n, c.image_size, c.image_size, c.patch_size, r.pr, p->kp, st));
-  TRY(gemm_any(f, r.pr, p->patch, n * P, C, r.pe, nullptr, 0));
-  TRY(ctrlv_clip_tokens(r.pe, p->cls, p->pos, n, P, C, r.tok, st));
+  CTRLV_TRY(ctrlv_clip_patch_rows(px, dtype, n, c.image_size, c.image_size, c.patch_size, r.pr, p->kp, st));
+  CTRLV_TRY(gemm_any(f, r.pr, p->patch, n * P, C, r.pe, nullptr, 0));
+  CTRLV_TRY(ctrlv_clip_tokens(r.pe, p->cls, p->pos, n, P, C, r.tok, st));
   el_t* x = r.x;
   el_t* x2 = r.x2;
-  TRY(ctrlv_layernorm(r.tok, M, C, p->pre.g, p->pre.b, eps, nullptr, 1, 1 << 30, 0, x, st));
+  CTRLV_TRY(ctrlv_layernorm(r.tok, M, C, p->pre.g, p->pre.b, eps, nullptr, 1, 1 << 30, 0, x, st));
   const int L = (int)p->layers.size();
   for (int i = 0; i < L; ++i) {
     const ClipLayer& l = p->layers[i];
-    TRY(ctrlv_layernorm(x, M, C, l.ln1.g, l.ln1.b, eps, nullptr, 1, 1 << 30, 0, r.hn, st));
-    TRY(gemm_any(f, r.hn, l.qkv, M, 3 * C, r.qkv, nullptr, 0));
-    TRY(ctrlv_attention_tokens(r.qkv, r.att, n, S, C, C / c.num_attention_heads, st));
-    TRY(gemm_any(f, r.att, l.out, M, C, x2, x, 0));
+    CTRLV_TRY(ctrlv_layernorm(x, M, C, l.ln1.g, l.ln1.b, eps, nullptr, 1, 1 << 30, 0, r.hn, st));
+    CTRLV_TRY(gemm_any(f, r.hn, l.qkv, M, 3 * C, r.qkv, nullptr, 0));
+    CTRLV_TRY(ctrlv_attention_tokens(r.qkv, r.att, n, S, C, C / c.num_attention_heads, st));
+    CTRLV_TRY(gemm_any(f, r.att, l.out, M, C, x2, x, 0));
     std::swap(x, x2);
-    TRY(ctrlv_layernorm(x, M, C, l.ln2.g, l.ln2.b, eps, nullptr, 1, 1 << 30, 0, r.hn, st));
-    TRY(gemm_any(f, r.hn, l.fc1, M, I, r.u, nullptr, 1 + c.hidden_act));
+    CTRLV_TRY(ctrlv_layernorm(x, M, C, l.ln2.g, l.ln2.b, eps, nullptr, 1, 1 << 30, 0, r.hn, st));
+    CTRLV_TRY(gemm_any(f, r.hn, l.fc1, M, I, r.u, nullptr, 1 + c.hidden_act));
     el_t* dst = (i == L - 1 && lhs) ? lhs : x2;        // the last layer writes last_hidden_state in place
-    TRY(gemm_any(f, r.u, l.fc2, M, C, dst, x, 0));
+    CTRLV_TRY(gemm_any(f, r.u, l.fc2, M, C, dst, x, 0));
     x2 = x;
     x = dst;
   }
   // class rows: row 0 of every image (a strided copy node), then post_layernorm and the projection at M = n
   CTRLV_HIP_TRY(hipMemcpy2DAsync(r.cls, (size_t)C * 2, x, (size_t)S * C * 2, (size_t)C * 2, n, hipMemcpyDeviceToDevice, st));
-  TRY(ctrlv_layernorm(r.cls, n, C, p->post.g, p->post.b, eps, nullptr, 1, 1 << 30, 0, r.pn, st));
+  CTRLV_TRY(ctrlv_layernorm(r.cls, n, C, p->post.g, p->post.b, eps, nullptr, 1, 1 << 30, 0, r.pn, st));
   return gemm_any(f, r.pn, p->proj, n, c.projection_dim, embeds, nullptr, 0);
 }
 
@@ -354,24 +247,13 @@ extern "C" int ctrlv_clip_plan_destroy(ctrlv_clip_plan* p) {
 
 extern "C" int ctrlv_clip_plan_load_weights(ctrlv_clip_plan* p, const ctrlv_tensor_desc* tensors, size_t n) {
   CTRLV_CHECK_ARG(p && tensors, "clip_plan_load_weights: null argument");
-  int prev = 0;
-  const bool sw = hipGetDevice(&prev) == hipSuccess && prev != p->device;
-  CTRLV_HIP_TRY(hipSetDevice(p->device));
-  free_owned(p);
-  ClipLoader L;
-  L.p = p;
-  for (size_t i = 0; i < n; ++i)
-    if (tensors[i].name) L.map[tensors[i].name] = &tensors[i];
-  const int rc = load_all(L);
-  const hipError_t e = hipDeviceSynchronize();
-  for (void* d : L.staged) (void)hipFree(d);
-  if (sw) (void)hipSetDevice(prev);                              // the caller's device, as ctrlv_clip_plan_destroy leaves it
-  if (rc != CTRLV_OK) { free_owned(p); return rc; }
-  if (e != hipSuccess) {
+  WeightLoader L("clip_plan_load_weights", &p->owned);
+  const int rc = ctrlv_load::run_load(L, p->device, true, [&]() -> int {       // (the caller's device, as _destroy leaves it)
     free_owned(p);
-    ctrlv_set_error("clip_plan_load_weights: %s", hipGetErrorString(e));
-    return CTRLV_E_HIP;
-  }
+    L.add(tensors, n);
+    return load_all(L, p);
+  });
+  if (rc != CTRLV_OK) { free_owned(p); return rc; }
   p->loaded = true;
   return CTRLV_OK;
 }

@@ -388,3 +388,24 @@ const ctrlv_vae_config* ctrlv_vae_plan_info(const ctrlv_vae_plan* p, int* device
     }                                                                                   \
   } while (0)
 #define CTRLV_LAUNCH_CHECK() CTRLV_HIP_TRY(hipGetLastError())
+#define CTRLV_TRY(expr)                    \
+  do {                                     \
+    const int rc__ = (expr);               \
+    if (rc__ != CTRLV_OK) return rc__;     \
+  } while (0)
+inline int pad_to(int v, int m) { return (v + m - 1) / m * m; }
+inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
+// out[M, n_store] = A[M, cin] . w.w^T + w.b: the plain nn.Linear / 1x1-conv launch on a packed weight (any {w, b} holder, e.g.
+// PackedLinear of weight_loader.h); conv modes, residuals and scales are set on the result
+template <class W>
+inline ctrlv_gemm_desc ctrlv_linear_desc(const void* A, int lda, const W& w, void* out, int ldo, long M, int N, int cin,
+                                         int n_store) {
+  ctrlv_gemm_desc d;
+  memset(&d, 0, sizeof(d));
+  d.A = A; d.W = w.w; d.out = out; d.bias = w.b;
+  d.M = (int)M; d.N = N; d.Cin = cin; d.taps = 1;
+  d.lda = lda; d.ldo = ldo; d.n_store = n_store;
+  d.s_acc = d.s1 = d.s2 = 1.0f;
+  d.vdiv = 1; d.vmod = 1 << 30; d.vS = 1;
+  return d;
+}

@@ -211,12 +211,6 @@ int layout(ctrlv_pipeline* p, const ctrlv_clip_request* r, const Geo& g, Layout*
   return CTRLV_OK;
 }
 
-#define TRY(expr)                   \
-  do {                              \
-    const int rc__ = (expr);        \
-    if (rc__ != CTRLV_OK) return rc__; \
-  } while (0)
-
 }  // namespace
 
 extern "C" int ctrlv_pipeline_create(ctrlv_plan* unet, ctrlv_plan* controlnet, ctrlv_vae_plan* vae, ctrlv_clip_plan* clip,
@@ -282,8 +276,8 @@ extern "C" int ctrlv_pipeline_generate(ctrlv_pipeline* p, const ctrlv_clip_reque
                                        ctrlv_stream_t stream) {
   Geo g;
   Layout L;
-  TRY(validate(p, r, &g));
-  TRY(layout(p, r, g, &L));
+  CTRLV_TRY(validate(p, r, &g));
+  CTRLV_TRY(layout(p, r, g, &L));
   CTRLV_CHECK_ARG(ws != nullptr && ((uintptr_t)ws & (kAlign - 1)) == 0, "pipeline_generate: the workspace must be non-null and "
                   "256-byte aligned");
   if (ws_bytes < L.total) {
@@ -328,35 +322,35 @@ extern "C" int ctrlv_pipeline_generate(ctrlv_pipeline* p, const ctrlv_clip_reque
   static const float kClipMean[3] = {0.48145466f, 0.4578275f, 0.40821073f}, kClipStd[3] = {0.26862954f, 0.26130258f, 0.27577711f};
   bool own = false;
   for (int c = 0; c < 3; ++c) own = own || r->clip_mean[c] != 0.f || r->clip_std[c] != 0.f;
-  TRY(ctrlv_resize_antialias(r->image_u8, 1, B, g.H, g.W, base + L.clip_px, CTRLV_ELEM_DTYPE, g.S, g.S,
+  CTRLV_TRY(ctrlv_resize_antialias(r->image_u8, 1, B, g.H, g.W, base + L.clip_px, CTRLV_ELEM_DTYPE, g.S, g.S,
                              own ? r->clip_mean : kClipMean, own ? r->clip_std : kClipStd, stream));
-  TRY(ctrlv_clip_forward(p->clip, base + L.clip_px, CTRLV_ELEM_DTYPE, B, base + L.clip_emb, nullptr, base + L.clip_ws,
+  CTRLV_TRY(ctrlv_clip_forward(p->clip, base + L.clip_px, CTRLV_ELEM_DTYPE, B, base + L.clip_emb, nullptr, base + L.clip_ws,
                          L.clip_bytes, stream));
-  TRY(ctrlv_pio_cfg_double(base + L.clip_emb, CTRLV_ELEM_DTYPE, base + L.ehs, B, g.D, g.cfg, s));
+  CTRLV_TRY(ctrlv_pio_cfg_double(base + L.clip_emb, CTRLV_ELEM_DTYPE, base + L.ehs, B, g.D, g.cfg, s));
 
   // ---- 2. VAE latents of the (noise-augmented) image and of the condition
-  TRY(ctrlv_pixels_prepare(r->image_u8, r->aug_noise, r->noise_aug_strength, B, g.H, g.W, base + L.enc_px, stream));
-  TRY(ctrlv_vae_encode(p->vae, base + L.enc_px, CTRLV_ELEM_DTYPE, B, g.H, g.W, nullptr, 1.0f, base + L.first, nullptr,
+  CTRLV_TRY(ctrlv_pixels_prepare(r->image_u8, r->aug_noise, r->noise_aug_strength, B, g.H, g.W, base + L.enc_px, stream));
+  CTRLV_TRY(ctrlv_vae_encode(p->vae, base + L.enc_px, CTRLV_ELEM_DTYPE, B, g.H, g.W, nullptr, 1.0f, base + L.first, nullptr,
                        CTRLV_ELEM_DTYPE, base + L.enc_ws, L.enc_bytes, stream));
-  TRY(ctrlv_pio_lmi_cond(base + L.first, base + L.lmi, B, F, Lc, hw, g.cfg, s));
+  CTRLV_TRY(ctrlv_pio_lmi_cond(base + L.first, base + L.lmi, B, F, Lc, hw, g.cfg, s));
   if (p->cn) {
     if (r->cond_channels == 3) {
-      TRY(ctrlv_vae_encode(p->vae, r->cond, r->cond_dtype, B * F, g.H, g.W, nullptr, 1.0f, base + L.enc_lat, nullptr,
+      CTRLV_TRY(ctrlv_vae_encode(p->vae, r->cond, r->cond_dtype, B * F, g.H, g.W, nullptr, 1.0f, base + L.enc_lat, nullptr,
                            CTRLV_ELEM_DTYPE, base + L.enc_ws, L.enc_bytes, stream));
-      TRY(ctrlv_pio_cfg_double(base + L.enc_lat, CTRLV_ELEM_DTYPE, base + L.cond_em, B, (long)F * Lc * hw, g.cfg, s));
+      CTRLV_TRY(ctrlv_pio_cfg_double(base + L.enc_lat, CTRLV_ELEM_DTYPE, base + L.cond_em, B, (long)F * Lc * hw, g.cfg, s));
     } else {
-      TRY(ctrlv_pio_cfg_double(r->cond, r->cond_dtype, base + L.cond_em, B, (long)F * Lc * hw, g.cfg, s));
+      CTRLV_TRY(ctrlv_pio_cfg_double(r->cond, r->cond_dtype, base + L.cond_em, B, (long)F * Lc * hw, g.cfg, s));
     }
   }
 
   // ---- 3. / 4. the loop
   // torch divides a tensor by a host scalar as a multiplication by the reciprocal, formed in double and rounded once
   const float inv0 = (float)(1.0 / sqrt((double)r->sigmas[0] * (double)r->sigmas[0] + 1.0));
-  TRY(ctrlv_pio_scale_latents(r->latents, r->out_latents, base + L.scaled, lat, inv0, s));
+  CTRLV_TRY(ctrlv_pio_scale_latents(r->latents, r->out_latents, base + L.scaled, lat, inv0, s));
   void* res[CTRLV_MAX_BLOCKS * 8 + 1];
   for (int i = 0; i < L.n_res; ++i) res[i] = base + L.res[i];
   for (int i = 0; i < r->num_steps; ++i) {
-    TRY(ctrlv_pio_lmi_scatter(base + L.scaled, base + L.lmi, B, F, Lc, hw, g.cfg, s));
+    CTRLV_TRY(ctrlv_pio_lmi_scatter(base + L.scaled, base + L.lmi, B, F, Lc, hw, g.cfg, s));
     void* ev = nullptr;
     if (p->cn) {
       hipStream_t sc = s;
@@ -365,7 +359,7 @@ extern "C" int ctrlv_pipeline_generate(ctrlv_pipeline* p, const ctrlv_clip_reque
         CTRLV_HIP_TRY(hipStreamWaitEvent(p->side, p->ev_fork, 0));
         sc = p->side;
       }
-      TRY(ctrlv_controlnet_forward(p->cn, base + L.lmi, base + L.cond_em, CTRLV_ELEM_DTYPE, c_t + i, 1, base + L.ehs, c_ids, 3,
+      CTRLV_TRY(ctrlv_controlnet_forward(p->cn, base + L.lmi, base + L.cond_em, CTRLV_ELEM_DTYPE, c_t + i, 1, base + L.ehs, c_ids, 3,
                                    r->conditioning_scale, res, res[L.n_res - 1], nb, F, g.h, g.w, base + L.cn_ws, L.cn_bytes,
                                    (ctrlv_stream_t)sc));
       if (overlap) {
@@ -373,26 +367,26 @@ extern "C" int ctrlv_pipeline_generate(ctrlv_pipeline* p, const ctrlv_clip_reque
         ev = (void*)p->ev_res;
       }
     }
-    TRY(ctrlv_unet_forward(p->unet, base + L.lmi, CTRLV_ELEM_DTYPE, c_t + i, 1, base + L.ehs, c_ids, 3,
+    CTRLV_TRY(ctrlv_unet_forward(p->unet, base + L.lmi, CTRLV_ELEM_DTYPE, c_t + i, 1, base + L.ehs, c_ids, 3,
                            p->cn ? (const void* const*)res : nullptr, p->cn ? res[L.n_res - 1] : nullptr, ev, base + L.pred, nb, F,
                            g.h, g.w, base + L.unet_ws, L.unet_bytes, stream));
-    TRY(ctrlv_cfg_euler_step(r->out_latents, base + L.pred, CTRLV_ELEM_DTYPE, g.cfg, c_g, B, F, Lc * hw, r->sigmas[i],
+    CTRLV_TRY(ctrlv_cfg_euler_step(r->out_latents, base + L.pred, CTRLV_ELEM_DTYPE, g.cfg, c_g, B, F, Lc * hw, r->sigmas[i],
                              r->sigmas[i + 1], base + L.scaled, stream));
   }
 
   // ---- 5. / 6. decode and convert
   if (g.decode) {
     const float inv_sf = (float)(1.0 / (double)scaling);
-    TRY(ctrlv_pio_decode_input(r->out_latents, base + L.dec_z, lat, inv_sf, s));
+    CTRLV_TRY(ctrlv_pio_decode_input(r->out_latents, base + L.dec_z, lat, inv_sf, s));
     char* frames = r->out_frames ? (char*)r->out_frames : base + L.dec_frames;
     const int total = B * F;
     for (int i0 = 0; i0 < total; i0 += r->decode_chunk) {
       const int nf = total - i0 < r->decode_chunk ? total - i0 : r->decode_chunk;
-      TRY(ctrlv_vae_decode(p->vae, base + L.dec_z + (size_t)i0 * Lc * hw * sizeof(el_t), CTRLV_ELEM_DTYPE, nf, nf, g.h, g.w,
+      CTRLV_TRY(ctrlv_vae_decode(p->vae, base + L.dec_z + (size_t)i0 * Lc * hw * sizeof(el_t), CTRLV_ELEM_DTYPE, nf, nf, g.h, g.w,
                            frames + (size_t)i0 * 3 * g.H * g.W * sizeof(el_t), CTRLV_ELEM_DTYPE, base + L.dec_ws, L.dec_bytes,
                            stream));
     }
-    if (r->out_frames_u8) TRY(ctrlv_frames_to_u8(frames, total, g.H, g.W, r->out_frames_u8, stream));
+    if (r->out_frames_u8) CTRLV_TRY(ctrlv_frames_to_u8(frames, total, g.H, g.W, r->out_frames_u8, stream));
   }
   return CTRLV_OK;
 }

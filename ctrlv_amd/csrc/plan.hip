@@ -12,81 +12,16 @@
 #include <math.h>
 
 #include <string>
-#include <unordered_map>
 #include <vector>
 
-#include "common.h"
-
-#define TRY(expr)                   \
-  do {                              \
-    int rc__ = (expr);              \
-    if (rc__ != CTRLV_OK) return rc__; \
-  } while (0)
+#include "weight_loader.h"
 
 namespace {
 
-// ------------------------------------------------------------------------------------------------ packing kernels
-__device__ __forceinline__ float ld_any(const void* p, int dtype, long i) {
-  if (dtype == 0) return ((const float*)p)[i];
-  if (dtype == 1) return (float)((const _Float16*)p)[i];
-  return bf16_to_f32(((const bf16_t*)p)[i]);
-}
-// GEGLU row interleave (packing.geglu_interleave): rows [a_0..a_{I-1} | g_0..g_{I-1}] -> alternating 16-row blocks
-__device__ __forceinline__ int row_map(int n, int N, int geglu) {
-  if (!geglu) return n;
-  const int inner = N >> 1, isg = n >= inner, r = isg ? n - inner : n;
-  return ((r >> 4) * 2 + isg) * 16 + (r & 15);
-}
-// dst[(n_off + rowmap(n)) * ld + tap * cp + c_off + c] = src[(n * C + c) * taps + tap]   (dst pre-zeroed)
-// covers nn.Linear / 1x1 conv (taps 1), Conv2d 3x3 (taps 9, tap = ky*3+kx), Conv3d (3,1,1) (taps 3), the shared
-// conv_in | control_conv_in im2col slots (cp = slot width, c_off = slot offset) and row concatenation (n_off).
-__global__ void pack_weight_kernel(const void* __restrict__ src, int dtype, int N, int C, int taps, el_t* __restrict__ dst,
-                                   int ld, int cp, int c_off, int n_off, int geglu) {
-  const long total = (long)N * C * taps;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int tap = (int)(i % taps);
-    const long nc = i / taps;
-    const int c = (int)(nc % C), n = (int)(nc / C);
-    dst[(long)(n_off + row_map(n, N, geglu)) * ld + tap * cp + c_off + c] = f32_to_el(ld_any(src, dtype, i));
-  }
-}
-// Role-swapped (dgrad) form of a weight: dst[c][(taps - 1 - tap) * Np + n] = src[(n * C + c) * taps + tap]  -- taps
-// reversed, output and input channels transposed (autograd.py::gemm_grads); columns n in [N, Np) are zeros.
-// A transpose: 32 output rows n x 64 consecutive (c, tap) source elements per workgroup go through LDS, so that reads are
-// contiguous along a source row and writes are 32 consecutive n (64 B) per (c, tap).   grid (ceil(C*taps/64), ceil(Np/32))
-__global__ __launch_bounds__(256) void pack_weight_swapped_kernel(const void* __restrict__ src, int dtype, int N, int C,
-                                                                  int taps, int Np, el_t* __restrict__ dst, int ld) {
-  __shared__ float tile[32][65];
-  const int k0 = blockIdx.x * 64, n0 = blockIdx.y * 32, ktot = C * taps;
-  for (int i = threadIdx.x; i < 32 * 64; i += 256) {
-    const int r = i >> 6, kk = i & 63, n = n0 + r, k = k0 + kk;
-    tile[r][kk] = (n < N && k < ktot) ? ld_any(src, dtype, (long)n * ktot + k) : 0.f;
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 64 * 32; i += 256) {
-    const int kk = i >> 5, r = i & 31, k = k0 + kk, n = n0 + r;
-    if (k >= ktot || n >= Np) continue;
-    const int c = k / taps, tap = k - c * taps;
-    dst[(long)c * ld + (long)(taps - 1 - tap) * Np + n] = f32_to_el(tile[r][kk]);
-  }
-}
-// Forward form with coalesced writes: dst[rowmap(n)][tap * C + c] = src[(n * C + c) * taps + tap]   grid (ceil(taps*C/256), N)
-__global__ void pack_weight_rows_kernel(const void* __restrict__ src, int dtype, int N, int C, int taps,
-                                        el_t* __restrict__ dst, int ld, int geglu) {
-  const int n = blockIdx.y;
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= taps * C) return;
-  const int tap = k / C, c = k - tap * C;
-  dst[(long)row_map(n, N, geglu) * ld + k] = f32_to_el(ld_any(src, dtype, ((long)n * C + c) * taps + tap));
-}
-__global__ void pack_vector_kernel(const void* __restrict__ src, int dtype, int N, float* __restrict__ dst, int n_off,
-                                   int geglu, int accumulate) {
-  const int n = blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= N) return;
-  const float v = ld_any(src, dtype, n);
-  float* d = dst + n_off + row_map(n, N, geglu);
-  *d = accumulate ? *d + v : v;
-}
+using ctrlv_load::WeightLoader;
+using Linear = ctrlv_load::PackedLinear;
+using Norm = ctrlv_load::NormParams;
+
 __global__ void arange_kernel(float* dst, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) dst[i] = (float)i;
@@ -96,16 +31,7 @@ __global__ void expand_f32_kernel(const float* __restrict__ src, int n_src, floa
   if (i < n) dst[i] = src[n_src == 1 ? 0 : i];
 }
 
-inline int pad_to(int v, int m) { return (v + m - 1) / m * m; }
-
 // ------------------------------------------------------------------------------------------------ plan data
-struct Linear {      // packed GEMM weight: bf16 [n][k] (n % 32 == 0, k % 64 == 0 for taps == 1) + fp32 bias [n] (or null)
-  el_t* w = nullptr;
-  float* b = nullptr;
-  int n = 0, k = 0;  // padded rows, total K (taps * cin)
-};
-struct Norm { float* g = nullptr; float* b = nullptr; };
-
 struct ResBlock {
   int cin = 0, cout = 0;
   float eps = 1e-6f;
@@ -266,192 +192,86 @@ void for_each_tr(ctrlv_plan* p, Fn fn) {
 }
 
 // ------------------------------------------------------------------------------------------------ weight loading
-struct Loader {
-  ctrlv_plan* p;
-  std::unordered_map<std::string, const ctrlv_tensor_desc*> map;
-  std::vector<void*> staged;      // temporary device copies of host tensors
-  hipStream_t st = nullptr;
+// the phase panels of an up-sampler conv (ctrlv_gemm_desc.up = 2), from the parameter itself: taps summed in fp32, one rounding
+int up_phase(WeightLoader& L, const std::string& mod, int N, int C, el_t** dst) {
+  const ctrlv_tensor_desc* t;
+  CTRLV_TRY(L.find(mod + ".weight", (long)N * C * 9, &t));
+  const void* src;
+  CTRLV_TRY(L.dev_ptr(t, &src));
+  CTRLV_TRY(L.alloc((size_t)16 * N * C * 2, (void**)dst, false));
+  return ctrlv_pack_up_phase_weight(src, t->dtype, N, C, *dst, L.st);
+}
+int ff(WeightLoader& L, const std::string& mod, int C, int C_out, FeedFwd& f) {     // FeedForward: GEGLU(C -> 8C) then Linear(4C -> C_out)
+  CTRLV_TRY(L.linear(mod + ".net.0.proj", 8 * C, C, f.proj, true, 1));
+  CTRLV_TRY(L.linear(mod + ".net.2", C_out, 4 * C, f.out));
+  if (C == 320 && C_out == 320 && f.proj.n == 2560 && f.proj.k == 320 && f.out.n == 320 && f.out.k == 1280) {
+    CTRLV_TRY(L.alloc((size_t)ctrlv_ff_fused_w1f_bytes(), (void**)&f.w1f, false));
+    CTRLV_TRY(L.alloc((size_t)320 * 1280 * 2, (void**)&f.w2f, false));
+    CTRLV_TRY(ctrlv_ff_fused_pack(f.proj.w, f.proj.b, f.out.w, f.w1f, f.w2f, L.st));
+  }
+  return CTRLV_OK;
+}
+int qkv(WeightLoader& L, const std::string& mod, int C, Linear& l) {
+  CTRLV_TRY(L.new_linear(l, 3 * C, pad_to(C, 64), false));
+  CTRLV_TRY(L.pack_w(mod + ".to_q.weight", C, C, 1, l, 0, 0, 0, 0));
+  CTRLV_TRY(L.pack_w(mod + ".to_k.weight", C, C, 1, l, 0, 0, C, 0));
+  return L.pack_w(mod + ".to_v.weight", C, C, 1, l, 0, 0, 2 * C, 0);
+}
 
-  int find(const std::string& name, const ctrlv_tensor_desc** out, long expect_numel) {
-    auto it = map.find(name);
-    if (it == map.end()) { ctrlv_set_error("plan_load_weights: missing tensor '%s'", name.c_str()); return CTRLV_E_BAD_ARG; }
-    const ctrlv_tensor_desc* t = it->second;
-    if (expect_numel >= 0 && t->numel != expect_numel) {
-      ctrlv_set_error("plan_load_weights: '%s' has %ld elements, expected %ld", name.c_str(), (long)t->numel, expect_numel);
-      return CTRLV_E_BAD_SHAPE;
-    }
-    *out = t;
-    return CTRLV_OK;
-  }
-  int dev_ptr(const ctrlv_tensor_desc* t, const void** out) {
-    if (t->on_device) { *out = t->data; return CTRLV_OK; }
-    const size_t es = t->dtype == 0 ? 4 : 2;
-    void* d = nullptr;
-    CTRLV_HIP_TRY(hipMalloc(&d, t->numel * es));
-    staged.push_back(d);
-    CTRLV_HIP_TRY(hipMemcpy(d, t->data, t->numel * es, hipMemcpyHostToDevice));
-    *out = d;
-    return CTRLV_OK;
-  }
-  int alloc(size_t bytes, void** out, bool zero) {
-    void* d = nullptr;
-    CTRLV_HIP_TRY(hipMalloc(&d, bytes ? bytes : 256));
-    p->owned.push_back(d);
-    if (zero) CTRLV_HIP_TRY(hipMemsetAsync(d, 0, bytes ? bytes : 256, st));
-    *out = d;
-    return CTRLV_OK;
-  }
-  // one weight tensor [N][C][taps] -> rows [n_off, n_off+N) of `dst`
-  int pack_w(const std::string& name, int N, int C, int taps, Linear& dst, int cp, int c_off, int n_off, int geglu) {
-    const ctrlv_tensor_desc* t;
-    TRY(find(name, &t, (long)N * C * taps));
-    const void* src;
-    TRY(dev_ptr(t, &src));
-    const long total = (long)N * C * taps;
-    const unsigned blocks = (unsigned)((total + 255) / 256 < 65535 ? (total + 255) / 256 : 65535);
-    hipLaunchKernelGGL(pack_weight_kernel, dim3(blocks), dim3(256), 0, st, src, t->dtype, N, C, taps, dst.w, dst.k, cp,
-                       c_off, n_off, geglu);
-    CTRLV_LAUNCH_CHECK();
-    return CTRLV_OK;
-  }
-  int pack_v(const std::string& name, int N, float* dst, int n_off, int geglu, int accumulate) {
-    const ctrlv_tensor_desc* t;
-    TRY(find(name, &t, N));
-    const void* src;
-    TRY(dev_ptr(t, &src));
-    hipLaunchKernelGGL(pack_vector_kernel, dim3((N + 255) / 256), dim3(256), 0, st, src, t->dtype, N, dst, n_off, geglu,
-                       accumulate);
-    CTRLV_LAUNCH_CHECK();
-    return CTRLV_OK;
-  }
-  int new_linear(Linear& l, int n_rows, int k_total, bool bias) {
-    l.n = pad_to(n_rows, 32);
-    l.k = k_total;
-    TRY(alloc((size_t)l.n * l.k * 2, (void**)&l.w, true));
-    l.b = nullptr;
-    if (bias) TRY(alloc((size_t)l.n * 4, (void**)&l.b, true));
-    return CTRLV_OK;
-  }
-  // nn.Linear / 1x1 conv [N][K] -> [N32][K64]
-  int linear(const std::string& mod, int N, int K, Linear& l, bool bias = true, int geglu = 0) {
-    TRY(new_linear(l, N, pad_to(K, 64), bias));
-    TRY(pack_w(mod + ".weight", N, K, 1, l, 0, 0, 0, geglu));
-    if (bias) TRY(pack_v(mod + ".bias", N, l.b, 0, geglu, 0));
-    return CTRLV_OK;
-  }
-  int conv3x3(const std::string& mod, int N, int C, Linear& l) {      // k = (ky*3+kx)*C + c
-    TRY(new_linear(l, N, 9 * C, true));
-    TRY(pack_w(mod + ".weight", N, C, 9, l, C, 0, 0, 0));
-    return pack_v(mod + ".bias", N, l.b, 0, 0, 0);
-  }
-  // the phase panels of an up-sampler conv (ctrlv_gemm_desc.up = 2), from the parameter itself: taps summed in fp32, one rounding
-  int up_phase(const std::string& mod, int N, int C, el_t** dst) {
-    const ctrlv_tensor_desc* t;
-    TRY(find(mod + ".weight", &t, (long)N * C * 9));
-    const void* src;
-    TRY(dev_ptr(t, &src));
-    TRY(alloc((size_t)16 * N * C * 2, (void**)dst, false));
-    return ctrlv_pack_up_phase_weight(src, t->dtype, N, C, *dst, st);
-  }
-  int conv_t(const std::string& mod, int N, int C, Linear& l) {       // k = t*C + c
-    TRY(new_linear(l, N, 3 * C, true));
-    TRY(pack_w(mod + ".weight", N, C, 3, l, C, 0, 0, 0));
-    return pack_v(mod + ".bias", N, l.b, 0, 0, 0);
-  }
-  int norm(const std::string& mod, int C, Norm& nm) {
-    TRY(alloc((size_t)C * 4, (void**)&nm.g, false));
-    TRY(alloc((size_t)C * 4, (void**)&nm.b, false));
-    TRY(pack_v(mod + ".weight", C, nm.g, 0, 0, 0));
-    return pack_v(mod + ".bias", C, nm.b, 0, 0, 0);
-  }
-  int mix_alpha(const std::string& name, double* alpha) {             // sigmoid(mix_factor): AlphaBlender, scalar
-    const ctrlv_tensor_desc* t;
-    TRY(find(name, &t, 1));
-    unsigned char raw[4] = {0, 0, 0, 0};
-    const size_t es = t->dtype == 0 ? 4 : 2;
-    if (t->on_device) CTRLV_HIP_TRY(hipMemcpy(raw, t->data, es, hipMemcpyDeviceToHost));
-    else memcpy(raw, t->data, es);
-    float v;
-    if (t->dtype == 0) memcpy(&v, raw, 4);
-    else if (t->dtype == 1) { _Float16 h; memcpy(&h, raw, 2); v = (float)h; }
-    else { uint32_t u = ((uint32_t)raw[1] << 24) | ((uint32_t)raw[0] << 16); memcpy(&v, &u, 4); }
-    *alpha = 1.0 / (1.0 + exp(-(double)v));
-    return CTRLV_OK;
-  }
-  int ff(const std::string& mod, int C, int C_out, FeedFwd& f) {     // FeedForward: GEGLU(C -> 8C) then Linear(4C -> C_out)
-    TRY(linear(mod + ".net.0.proj", 8 * C, C, f.proj, true, 1));
-    TRY(linear(mod + ".net.2", C_out, 4 * C, f.out));
-    if (C == 320 && C_out == 320 && f.proj.n == 2560 && f.proj.k == 320 && f.out.n == 320 && f.out.k == 1280) {
-      TRY(alloc((size_t)ctrlv_ff_fused_w1f_bytes(), (void**)&f.w1f, false));
-      TRY(alloc((size_t)320 * 1280 * 2, (void**)&f.w2f, false));
-      TRY(ctrlv_ff_fused_pack(f.proj.w, f.proj.b, f.out.w, f.w1f, f.w2f, st));
-    }
-    return CTRLV_OK;
-  }
-  int qkv(const std::string& mod, int C, Linear& l) {
-    TRY(new_linear(l, 3 * C, pad_to(C, 64), false));
-    TRY(pack_w(mod + ".to_q.weight", C, C, 1, l, 0, 0, 0, 0));
-    TRY(pack_w(mod + ".to_k.weight", C, C, 1, l, 0, 0, C, 0));
-    return pack_w(mod + ".to_v.weight", C, C, 1, l, 0, 0, 2 * C, 0);
-  }
-};
-
-int load_res(Loader& L, ResBlock& r, int ted) {
+int load_res(WeightLoader& L, ctrlv_plan* p, ResBlock& r, int ted) {
   const std::string s = r.name + ".spatial_res_block", t = r.name + ".temporal_res_block";
-  TRY(L.norm(s + ".norm1", r.cin, r.n1));
-  TRY(L.conv3x3(s + ".conv1", r.cout, r.cin, r.c1));
-  TRY(L.norm(s + ".norm2", r.cout, r.n2));
-  TRY(L.conv3x3(s + ".conv2", r.cout, r.cout, r.c2));
-  if (r.has_sc) TRY(L.linear(s + ".conv_shortcut", r.cout, r.cin, r.sc));
-  TRY(L.norm(t + ".norm1", r.cout, r.tn1));
-  TRY(L.conv_t(t + ".conv1", r.cout, r.cout, r.tc1));
-  TRY(L.norm(t + ".norm2", r.cout, r.tn2));
-  TRY(L.conv_t(t + ".conv2", r.cout, r.cout, r.tc2));
-  TRY(L.mix_alpha(r.name + ".time_mixer.mix_factor", &r.alpha));
+  CTRLV_TRY(L.norm(s + ".norm1", r.cin, r.n1));
+  CTRLV_TRY(L.conv3x3(s + ".conv1", r.cout, r.cin, r.c1));
+  CTRLV_TRY(L.norm(s + ".norm2", r.cout, r.n2));
+  CTRLV_TRY(L.conv3x3(s + ".conv2", r.cout, r.cout, r.c2));
+  if (r.has_sc) CTRLV_TRY(L.linear(s + ".conv_shortcut", r.cout, r.cin, r.sc));
+  CTRLV_TRY(L.norm(t + ".norm1", r.cout, r.tn1));
+  CTRLV_TRY(L.conv_t(t + ".conv1", r.cout, r.cout, r.tc1));
+  CTRLV_TRY(L.norm(t + ".norm2", r.cout, r.tn2));
+  CTRLV_TRY(L.conv_t(t + ".conv2", r.cout, r.cout, r.tc2));
+  CTRLV_TRY(L.mix_alpha(r.name + ".time_mixer.mix_factor", &r.alpha));
   // the two time_emb_proj rows go into the model-wide [sum Cout, ted] GEMM
-  ctrlv_plan* p = L.p;
   const std::string tp[2] = {s + ".time_emb_proj", t + ".time_emb_proj"};
   for (int k = 0; k < 2; ++k) {
-    TRY(L.pack_w(tp[k] + ".weight", r.cout, ted, 1, p->temb, 0, 0, r.temb_off[k], 0));
-    TRY(L.pack_v(tp[k] + ".bias", r.cout, p->temb.b, r.temb_off[k], 0, 0));
+    CTRLV_TRY(L.pack_w(tp[k] + ".weight", r.cout, ted, 1, p->temb, 0, 0, r.temb_off[k], 0));
+    CTRLV_TRY(L.pack_v(tp[k] + ".bias", r.cout, p->temb.b, r.temb_off[k], 0, 0));
   }
   return CTRLV_OK;
 }
 
-int load_tr(Loader& L, Transformer& t, int cross_dim) {
+int load_tr(WeightLoader& L, ctrlv_plan* p, Transformer& t, int cross_dim) {
   const int C = t.C;
   const std::string sb = t.name + ".transformer_blocks.0", tb = t.name + ".temporal_transformer_blocks.0";
-  TRY(L.norm(t.name + ".norm", C, t.gn));
-  TRY(L.linear(t.name + ".proj_in", C, C, t.pin));
-  TRY(L.linear(t.name + ".proj_out", C, C, t.pout));
-  TRY(L.norm(sb + ".norm1", C, t.s_ln1));
-  TRY(L.norm(sb + ".norm3", C, t.s_ln3));
-  TRY(L.qkv(sb + ".attn1", C, t.s_qkv));
-  TRY(L.linear(sb + ".attn1.to_out.0", C, C, t.s_o));
-  TRY(L.ff(sb + ".ff", C, C, t.s_ff));
-  TRY(L.norm(tb + ".norm_in", C, t.t_lnin));
-  TRY(L.norm(tb + ".norm1", C, t.t_ln1));
-  TRY(L.norm(tb + ".norm3", C, t.t_ln3));
-  TRY(L.ff(tb + ".ff_in", C, C, t.t_ffin));
-  TRY(L.qkv(tb + ".attn1", C, t.t_qkv));
-  TRY(L.linear(tb + ".attn1.to_out.0", C, C, t.t_o));
-  TRY(L.ff(tb + ".ff", C, C, t.t_ff));
+  CTRLV_TRY(L.norm(t.name + ".norm", C, t.gn));
+  CTRLV_TRY(L.linear(t.name + ".proj_in", C, C, t.pin));
+  CTRLV_TRY(L.linear(t.name + ".proj_out", C, C, t.pout));
+  CTRLV_TRY(L.norm(sb + ".norm1", C, t.s_ln1));
+  CTRLV_TRY(L.norm(sb + ".norm3", C, t.s_ln3));
+  CTRLV_TRY(qkv(L, sb + ".attn1", C, t.s_qkv));
+  CTRLV_TRY(L.linear(sb + ".attn1.to_out.0", C, C, t.s_o));
+  CTRLV_TRY(ff(L, sb + ".ff", C, C, t.s_ff));
+  CTRLV_TRY(L.norm(tb + ".norm_in", C, t.t_lnin));
+  CTRLV_TRY(L.norm(tb + ".norm1", C, t.t_ln1));
+  CTRLV_TRY(L.norm(tb + ".norm3", C, t.t_ln3));
+  CTRLV_TRY(ff(L, tb + ".ff_in", C, C, t.t_ffin));
+  CTRLV_TRY(qkv(L, tb + ".attn1", C, t.t_qkv));
+  CTRLV_TRY(L.linear(tb + ".attn1.to_out.0", C, C, t.t_o));
+  CTRLV_TRY(ff(L, tb + ".ff", C, C, t.t_ff));
   if (C == 320 && t.t_qkv.n == 960 && t.t_qkv.k == 320 && t.t_o.n == 320 && t.t_o.k == 320) {
-    TRY(L.alloc(ctrlv_temporal_fused_weight_bytes(), (void**)&t.t_wf, false));
-    TRY(ctrlv_temporal_fused_pack(t.t_qkv.w, t.t_qkv.k, t.t_o.w, t.t_o.k, t.t_wf, L.st));
+    CTRLV_TRY(L.alloc(ctrlv_temporal_fused_weight_bytes(), (void**)&t.t_wf, false));
+    CTRLV_TRY(ctrlv_temporal_fused_pack(t.t_qkv.w, t.t_qkv.k, t.t_o.w, t.t_o.k, t.t_wf, L.st));
   }
-  TRY(L.linear(t.name + ".time_pos_embed.linear_1", 4 * C, C, t.tpe1));
-  TRY(L.linear(t.name + ".time_pos_embed.linear_2", C, 4 * C, t.tpe2));
-  TRY(L.mix_alpha(t.name + ".time_mixer.mix_factor", &t.alpha));
+  CTRLV_TRY(L.linear(t.name + ".time_pos_embed.linear_1", 4 * C, C, t.tpe1));
+  CTRLV_TRY(L.linear(t.name + ".time_pos_embed.linear_2", C, 4 * C, t.tpe2));
+  CTRLV_TRY(L.mix_alpha(t.name + ".time_mixer.mix_factor", &t.alpha));
   // cross-attentions (1 key: attn2(x) = to_out(to_v(e)), SURVEY finding 8): to_v rows into the model-wide GEMM
-  ctrlv_plan* p = L.p;
   const std::string a2[2] = {sb + ".attn2", tb + ".attn2"};
   for (int k = 0; k < 2; ++k) {
-    TRY(L.pack_w(a2[k] + ".to_v.weight", C, cross_dim, 1, p->xv, 0, 0, t.xattn_off[k], 0));
+    CTRLV_TRY(L.pack_w(a2[k] + ".to_v.weight", C, cross_dim, 1, p->xv, 0, 0, t.xattn_off[k], 0));
     CrossOut xo;
     xo.off = t.xattn_off[k];
     xo.c = C;
-    TRY(L.linear(a2[k] + ".to_out.0", C, C, xo.to_out));
+    CTRLV_TRY(L.linear(a2[k] + ".to_out.0", C, C, xo.to_out));
     p->xouts.push_back(xo);
   }
   return CTRLV_OK;
@@ -535,16 +355,6 @@ inline void set_r1(ctrlv_gemm_desc& d, const Trk& t, int ld) { d.R1 = t.hi; d.R1
 inline void set_r2(ctrlv_gemm_desc& d, const Trk& t, int ld) { d.R2 = t.hi; d.R2_lo = t.lo; d.ldr2 = ld; }
 inline void set_out(ctrlv_gemm_desc& d, const Trk& t) { d.out = t.hi; d.out_lo = t.lo; }
 
-ctrlv_gemm_desc gd(const void* A, int lda, const Linear& w, void* out, int ldo, int M, int N, int cin, int n_store) {
-  ctrlv_gemm_desc d;
-  memset(&d, 0, sizeof(d));
-  d.A = A; d.W = w.w; d.out = out; d.bias = w.b;
-  d.M = M; d.N = N; d.Cin = cin; d.taps = 1;
-  d.lda = lda; d.ldo = ldo; d.n_store = n_store;
-  d.s_acc = d.s1 = d.s2 = 1.0f;
-  d.vdiv = 1; d.vmod = 1 << 30; d.vS = 1;
-  return d;
-}
 int gemm(Ctx& c, const ctrlv_gemm_desc& d0) {
   // split contraction of the small-image long-K convs (gemm.hip splitk_plan): its scratch comes from the arena for the
   // duration of the launch (the plan depends on the layer's shape only, so the measuring walk sees the same sizes)
@@ -587,7 +397,7 @@ int groupnorm(Ctx& c, const Trk& x, const Trk& x2, int c_split, int n_img, int S
 int gemm_groupnorm(Ctx& c, ctrlv_gemm_desc d, int n_img, int S, int C, int ips, const Norm& nm, float eps, int silu, el_t* y) {
   const Trk dout{(el_t*)d.out, (lo_t*)d.out_lo};
   if (S % 64 != 0) {
-    TRY(gemm(c, d));
+    CTRLV_TRY(gemm(c, d));
     return groupnorm(c, dout, Trk{}, 0, n_img, S, C, ips, nm, eps, silu, y);
   }
   const size_t m = c.mark();
@@ -604,7 +414,7 @@ int gemm_groupnorm(Ctx& c, ctrlv_gemm_desc d, int n_img, int S, int C, int ips, 
     return rc;
   }
   c.release(m);
-  TRY(gemm(c, d));
+  CTRLV_TRY(gemm(c, d));
   return groupnorm(c, dout, Trk{}, 0, n_img, S, C, ips, nm, eps, silu, y);
 }
 int layernorm(Ctx& c, const Trk& x, int M, int C, const Norm& nm, el_t* y, const float* V = nullptr, int vdiv = 1,
@@ -629,43 +439,43 @@ int run_res(Ctx& c, const ResBlock& r, const Trk& x, const Trk& x2, int c1, int 
   const size_t mk = c.mark();
   const int lda_x = x2.hi ? c1 : cin;
   el_t* xn = c.rows(M, cin);
-  TRY(groupnorm(c, x, x2, x2.hi ? c1 : 0, N, S, cin, 1, r.n1, r.eps, 1, xn));
+  CTRLV_TRY(groupnorm(c, x, x2, x2.hi ? c1 : 0, N, S, cin, 1, r.n1, r.eps, 1, xn));
   el_t* h = c.rows(M, cout);
   el_t* hn = nullptr;
   {
-    ctrlv_gemm_desc d = gd(xn, cin, r.c1, h, cout, (int)M, cout, cin, cout);
+    ctrlv_gemm_desc d = ctrlv_linear_desc(xn, cin, r.c1, h, cout, (int)M, cout, cin, cout);
     d.taps = 9; d.mode = 1; d.H = H; d.Wd = W; d.Ho = H; d.Wo = W; d.stride = 1; d.up = 0;
     d.V = c.temb + r.temb_off[0]; d.ldv = c.ldtemb; d.vmode = 1; d.vdiv = F * S;
     hn = c.rows(M, cout);
-    TRY(gemm_groupnorm(c, d, N, S, cout, 1, r.n2, r.eps, 1, hn));
+    CTRLV_TRY(gemm_groupnorm(c, d, N, S, cout, 1, r.n2, r.eps, 1, hn));
   }
   Trk res = x;
   int ldres = cin;
   if (r.has_sc) {
     const Trk rs = c.trunk(M, cout);
-    ctrlv_gemm_desc d = gd(x.hi, lda_x, r.sc, rs.hi, cout, (int)M, cout, cin, cout);
+    ctrlv_gemm_desc d = ctrlv_linear_desc(x.hi, lda_x, r.sc, rs.hi, cout, (int)M, cout, cin, cout);
     set_out(d, rs);
     if (x2.hi) { d.A2 = x2.hi; d.lda2 = cin - c1; d.c_split = c1; }
-    TRY(gemm(c, d));
+    CTRLV_TRY(gemm(c, d));
     res = rs;
     ldres = cout;
   }
   const Trk xs = c.trunk(M, cout);
   {
-    ctrlv_gemm_desc d = gd(hn, cout, r.c2, xs.hi, cout, (int)M, cout, cout, cout);
+    ctrlv_gemm_desc d = ctrlv_linear_desc(hn, cout, r.c2, xs.hi, cout, (int)M, cout, cout, cout);
     d.taps = 9; d.mode = 1; d.H = H; d.Wd = W; d.Ho = H; d.Wo = W; d.stride = 1;
     set_out(d, xs);
     set_r1(d, res, ldres);
-    TRY(gemm_groupnorm(c, d, N, S, cout, F, r.tn1, r.eps, 1, hn));
+    CTRLV_TRY(gemm_groupnorm(c, d, N, S, cout, F, r.tn1, r.eps, 1, hn));
   }
   {
-    ctrlv_gemm_desc d = gd(hn, cout, r.tc1, h, cout, (int)M, cout, cout, cout);
+    ctrlv_gemm_desc d = ctrlv_linear_desc(hn, cout, r.tc1, h, cout, (int)M, cout, cout, cout);
     d.taps = 3; d.mode = 2; d.F = F; d.S = S;
     d.V = c.temb + r.temb_off[1]; d.ldv = c.ldtemb; d.vmode = 1; d.vdiv = F * S;
-    TRY(gemm_groupnorm(c, d, N, S, cout, F, r.tn2, r.eps, 1, hn));
+    CTRLV_TRY(gemm_groupnorm(c, d, N, S, cout, F, r.tn2, r.eps, 1, hn));
   }
   {   // AlphaBlender: a*xs + (1-a)*(xs + conv2) = xs + (1-a)*conv2
-    ctrlv_gemm_desc d = gd(hn, cout, r.tc2, out.hi, cout, (int)M, cout, cout, cout);
+    ctrlv_gemm_desc d = ctrlv_linear_desc(hn, cout, r.tc2, out.hi, cout, (int)M, cout, cout, cout);
     d.taps = 3; d.mode = 2; d.F = F; d.S = S;
     d.s_acc = (float)(1.0 - r.alpha);
     set_out(d, out);
@@ -674,7 +484,7 @@ int run_res(Ctx& c, const ResBlock& r, const Trk& x, const Trk& x2, int c1, int 
       d.gn_partials = c.gn_cross;       // the transformer behind this block opens with a GroupNorm of `out`
       c.gn_cross_valid = true;
     }
-    TRY(gemm(c, d));
+    CTRLV_TRY(gemm(c, d));
   }
   c.release(mk);
   *out_ = out;
@@ -695,21 +505,21 @@ int frame_embedding(Ctx& c, const Transformer& t, int F, float* e) {
     CTRLV_LAUNCH_CHECK();
     if (kp != C) {       // K zero padding (tiny configs only): sinusoid into a compact buffer, then strided copy
       CTRLV_HIP_TRY(hipMemsetAsync(te, 0, (size_t)F * kp * 2, c.st));
-      TRY(ctrlv_timestep_embedding(ar, F, C, tmp, c.st));
+      CTRLV_TRY(ctrlv_timestep_embedding(ar, F, C, tmp, c.st));
       CTRLV_HIP_TRY(hipMemcpy2DAsync(te, (size_t)kp * 2, tmp, (size_t)C * 2, (size_t)C * 2, F, hipMemcpyDeviceToDevice, c.st));
     } else {
-      TRY(ctrlv_timestep_embedding(ar, F, C, te, c.st));
+      CTRLV_TRY(ctrlv_timestep_embedding(ar, F, C, te, c.st));
     }
   }
   {
-    ctrlv_gemm_desc d = gd(te, kp, t.tpe1, hh, 4 * C, F, t.tpe1.n, kp, 4 * C);
+    ctrlv_gemm_desc d = ctrlv_linear_desc(te, kp, t.tpe1, hh, 4 * C, F, t.tpe1.n, kp, 4 * C);
     d.act = 1;
-    TRY(gemm(c, d));
+    CTRLV_TRY(gemm(c, d));
   }
   {
-    ctrlv_gemm_desc d = gd(hh, 4 * C, t.tpe2, e, C, F, t.tpe2.n, 4 * C, C);
+    ctrlv_gemm_desc d = ctrlv_linear_desc(hh, 4 * C, t.tpe2, e, C, F, t.tpe2.n, 4 * C, C);
     d.out_f32 = 1;
-    TRY(gemm(c, d));
+    CTRLV_TRY(gemm(c, d));
   }
   c.release(mk);
   return CTRLV_OK;
@@ -731,8 +541,8 @@ int ff_pair(Ctx& c, const FeedFwd& f, ctrlv_gemm_desc proj, ctrlv_gemm_desc outd
   if (*u == nullptr) *u = c.rows(proj.M, 4 * C);
   proj.out = *u;
   outd.A = *u;
-  TRY(gemm(c, proj));
-  TRY(gemm(c, outd));
+  CTRLV_TRY(gemm(c, proj));
+  CTRLV_TRY(gemm(c, outd));
   return CTRLV_OK;
 }
 
@@ -789,7 +599,7 @@ int ln_ff(Ctx& c, const FeedFwd& f, const Norm& nm, const Trk& xraw, const float
       return rc;
     }
   }
-  TRY(layernorm(c, xraw, proj.M, C, nm, tt, lnV, lnvdiv, lnvmod, lnldv));
+  CTRLV_TRY(layernorm(c, xraw, proj.M, C, nm, tt, lnV, lnvdiv, lnvmod, lnldv));
   return ff_pair(c, f, proj, outd, C, u);
 }
 
@@ -802,66 +612,66 @@ int run_tr(Ctx& c, const Transformer& t, const Trk& x, int H, int W, Trk* out_) 
   const float* emb = t.frame_emb;
   if (F != c.p->cfg.num_frames || emb == nullptr) {
     float* e = (float*)c.alloc((size_t)F * C * 4);
-    TRY(frame_embedding(c, t, F, e));
+    CTRLV_TRY(frame_embedding(c, t, F, e));
     emb = e;
   }
   el_t* tt = c.rows(M, C);
   if (c.gn_cross_valid && !c.dry) {     // statistics from the res block's last GEMM (run_res, feeds_norm)
     c.gn_cross_valid = false;
     ProfScope ps(c, CTRLV_FAM_GROUPNORM, 0.0, 2.0 * 2 * N * (double)S * C, N * S, C, 1);
-    TRY(ctrlv_groupnorm_from_partials_split(x.hi, x.lo, N, S, C, 1, 1e-6f, c.gn_cross, t.gn.g, t.gn.b, 0, tt, c.st));
+    CTRLV_TRY(ctrlv_groupnorm_from_partials_split(x.hi, x.lo, N, S, C, 1, 1e-6f, c.gn_cross, t.gn.g, t.gn.b, 0, tt, c.st));
   } else {
-    TRY(groupnorm(c, x, Trk{}, 0, N, S, C, 1, t.gn, 1e-6f, 0, tt));
+    CTRLV_TRY(groupnorm(c, x, Trk{}, 0, N, S, C, 1, t.gn, 1e-6f, 0, tt));
   }
   const Trk h0 = c.trunk(M, C);
   {
-    ctrlv_gemm_desc d = gd(tt, C, t.pin, h0.hi, C, (int)M, C, C, C);
+    ctrlv_gemm_desc d = ctrlv_linear_desc(tt, C, t.pin, h0.hi, C, (int)M, C, C, C);
     set_out(d, h0);
-    TRY(gemm(c, d));
+    CTRLV_TRY(gemm(c, d));
   }
   // ---- spatial BasicTransformerBlock
-  TRY(layernorm(c, h0, (int)M, C, t.s_ln1, tt));
+  CTRLV_TRY(layernorm(c, h0, (int)M, C, t.s_ln1, tt));
   el_t* qkv = c.rows(M, 3 * C);
   {
-    ctrlv_gemm_desc d = gd(tt, C, t.s_qkv, qkv, 3 * C, (int)M, 3 * C, C, 3 * C);
+    ctrlv_gemm_desc d = ctrlv_linear_desc(tt, C, t.s_qkv, qkv, 3 * C, (int)M, 3 * C, C, 3 * C);
     d.n_scale2 = C; d.s_acc2 = 0.125f * 1.44269504088896340736f;      // q block pre-scaled: (1/sqrt(64)) log2(e)
-    TRY(gemm(c, d));
+    CTRLV_TRY(gemm(c, d));
   }
   el_t* a = c.rows(M, C);
   if (!c.dry) {
     ProfScope ps(c, CTRLV_FAM_ATTENTION_SPATIAL, 4.0 * N * (C / 64) * (double)S * S * 64, 2.0 * 4 * N * (double)S * C, N, S, C);
-    TRY(ctrlv_attention_spatial_prescaled(qkv, a, N, S, C, c.st));
+    CTRLV_TRY(ctrlv_attention_spatial_prescaled(qkv, a, N, S, C, c.st));
   }
   const Trk h1 = c.trunk(M, C);
   {   // attn2 with one key == to_out(to_v(ehs[b])) for every query: a per-clip row vector
-    ctrlv_gemm_desc d = gd(a, C, t.s_o, h1.hi, C, (int)M, C, C, C);
+    ctrlv_gemm_desc d = ctrlv_linear_desc(a, C, t.s_o, h1.hi, C, (int)M, C, C, C);
     set_out(d, h1);
     set_r1(d, h0, C);
     d.V = c.xattn + t.xattn_off[0]; d.ldv = c.ldx; d.vmode = 1; d.vdiv = F * S;
-    TRY(gemm(c, d));
+    CTRLV_TRY(gemm(c, d));
   }
   el_t* u = nullptr;  // 4C-wide GEGLU output of the two-launch path: allocated by ff_pair on first need
   const Trk h2 = h0;  // h0 is dead from here on
   {
-    ctrlv_gemm_desc dp = gd(tt, C, t.s_ff.proj, u, 4 * C, (int)M, 8 * C, C, 4 * C);
+    ctrlv_gemm_desc dp = ctrlv_linear_desc(tt, C, t.s_ff.proj, u, 4 * C, (int)M, 8 * C, C, 4 * C);
     dp.geglu = 1;
-    ctrlv_gemm_desc d = gd(u, 4 * C, t.s_ff.out, h2.hi, C, (int)M, C, 4 * C, C);
+    ctrlv_gemm_desc d = ctrlv_linear_desc(u, 4 * C, t.s_ff.out, h2.hi, C, (int)M, C, 4 * C, C);
     set_out(d, h2);
     set_r1(d, h1, C);
     d.S = S;                              // (S: rows per image, the split plan's shape key for a mode-0 launch)
-    TRY(ln_ff(c, t.s_ff, t.s_ln3, h1, nullptr, 1, 1 << 30, 0, tt, dp, d, C, &u));
+    CTRLV_TRY(ln_ff(c, t.s_ff, t.s_ln3, h1, nullptr, 1, 1 << 30, 0, tt, dp, d, C, &u));
   }
   // ---- temporal block on tokens (b, s) x frames; rows stay ordered (b, f, s)
   const Trk g0 = h1;  // h1 is dead
   {
-    ctrlv_gemm_desc dp = gd(tt, C, t.t_ffin.proj, u, 4 * C, (int)M, 8 * C, C, 4 * C);
+    ctrlv_gemm_desc dp = ctrlv_linear_desc(tt, C, t.t_ffin.proj, u, 4 * C, (int)M, 8 * C, C, 4 * C);
     dp.geglu = 1;
-    ctrlv_gemm_desc d = gd(u, 4 * C, t.t_ffin.out, g0.hi, C, (int)M, C, 4 * C, C);
+    ctrlv_gemm_desc d = ctrlv_linear_desc(u, 4 * C, t.t_ffin.out, g0.hi, C, (int)M, C, 4 * C, C);
     set_out(d, g0);
     set_r1(d, h2, C);
     d.S = S;
     d.V = emb; d.ldv = C; d.vmode = 1; d.vdiv = S; d.vmod = F;
-    TRY(ln_ff(c, t.t_ffin, t.t_lnin, h2, emb, S, F, C, tt, dp, d, C, &u));
+    CTRLV_TRY(ln_ff(c, t.t_ffin, t.t_lnin, h2, emb, S, F, C, tt, dp, d, C, &u));
   }
   const Trk g1 = c.trunk(M, C);
   {
@@ -890,46 +700,46 @@ int run_tr(Ctx& c, const Transformer& t, const Trk& x, int H, int W, Trk* out_) 
     const bool fused = fuse && ctrlv_temporal_fused_serves(&fd);
     if (!fused || !ln_in) {
       if (ln_in) { ln_in = false; fd.x = tt; fd.ln_gamma = fd.ln_beta = nullptr; }
-      TRY(layernorm(c, t.t_wf ? Trk{g0.hi, nullptr} : g0, (int)M, C, t.t_ln1, tt));   // (C = 320: hi, as the prologue)
+      CTRLV_TRY(layernorm(c, t.t_wf ? Trk{g0.hi, nullptr} : g0, (int)M, C, t.t_ln1, tt));   // (C = 320: hi, as the prologue)
     }
     if (fused) {
       if (!c.dry) {
         if (c.overflow) { ctrlv_set_error("plan forward: workspace too small (need >= %zu bytes)", c.peak); return CTRLV_E_BAD_ARG; }
         ProfScope ps(c, CTRLV_FAM_GEMM_TEMPORAL_BLOCK, 2.0 * M * C * 4.0 * C + 4.0 * B * S * (C / 64) * (double)F * F * 64,
                      (double)M * C * (2 * (ln_in ? 2 : 3) + (g0.lo ? 1 : 0) + (g1.lo ? 1 : 0)), (int)M, 4 * C, C, ln_in ? 1 : 0);
-        TRY(ctrlv_temporal_fused(&fd, c.st));
+        CTRLV_TRY(ctrlv_temporal_fused(&fd, c.st));
       }
     } else {
-      TRY(gemm(c, gd(tt, C, t.t_qkv, qkv, 3 * C, (int)M, 3 * C, C, 3 * C)));
+      CTRLV_TRY(gemm(c, ctrlv_linear_desc(tt, C, t.t_qkv, qkv, 3 * C, (int)M, 3 * C, C, 3 * C)));
       if (!c.dry) {
         ProfScope ps(c, CTRLV_FAM_ATTENTION_TEMPORAL, 4.0 * B * S * (C / 64) * (double)F * F * 64, 2.0 * 4 * B * F * (double)S * C, B * S,
                      F, C);
-        TRY(ctrlv_attention_temporal(qkv, a, B, F, S, C, c.st));
+        CTRLV_TRY(ctrlv_attention_temporal(qkv, a, B, F, S, C, c.st));
       }
-      ctrlv_gemm_desc d = gd(a, C, t.t_o, g1.hi, C, (int)M, C, C, C);
+      ctrlv_gemm_desc d = ctrlv_linear_desc(a, C, t.t_o, g1.hi, C, (int)M, C, C, C);
       set_out(d, g1);
       set_r1(d, g0, C);
       d.V = fd.V; d.ldv = fd.ldv; d.vdiv = fd.vdiv; d.vmode = fd.vmode;
       if (fd.vmode == 2) { d.vS = S; d.vmod = B; }
-      TRY(gemm(c, d));
+      CTRLV_TRY(gemm(c, d));
     }
   }
   const Trk h3 = g0;
   {   // AlphaBlender folded: h3 = a*h2 + (1-a)*(g1 + ff)
-    ctrlv_gemm_desc dp = gd(tt, C, t.t_ff.proj, u, 4 * C, (int)M, 8 * C, C, 4 * C);
+    ctrlv_gemm_desc dp = ctrlv_linear_desc(tt, C, t.t_ff.proj, u, 4 * C, (int)M, 8 * C, C, 4 * C);
     dp.geglu = 1;
-    ctrlv_gemm_desc d = gd(u, 4 * C, t.t_ff.out, h3.hi, C, (int)M, C, 4 * C, C);
+    ctrlv_gemm_desc d = ctrlv_linear_desc(u, 4 * C, t.t_ff.out, h3.hi, C, (int)M, C, 4 * C, C);
     set_out(d, h3);
     d.s_acc = (float)(1.0 - t.alpha); d.s1 = (float)(1.0 - t.alpha); d.s2 = (float)t.alpha; d.S = S;
     set_r1(d, g1, C);
     set_r2(d, h2, C);
-    TRY(ln_ff(c, t.t_ff, t.t_ln3, g1, nullptr, 1, 1 << 30, 0, tt, dp, d, C, &u));
+    CTRLV_TRY(ln_ff(c, t.t_ff, t.t_ln3, g1, nullptr, 1, 1 << 30, 0, tt, dp, d, C, &u));
   }
   {
-    ctrlv_gemm_desc d = gd(h3.hi, C, t.pout, out.hi, C, (int)M, C, C, C);
+    ctrlv_gemm_desc d = ctrlv_linear_desc(h3.hi, C, t.pout, out.hi, C, (int)M, C, C, C);
     set_out(d, out);
     set_r1(d, x, C);
-    TRY(gemm(c, d));
+    CTRLV_TRY(gemm(c, d));
   }
   c.release(mk);
   *out_ = out;
@@ -941,12 +751,12 @@ int run_resample(Ctx& c, const Resample& r, const Trk& x, int H, int W, bool up,
   const int Ho = up ? 2 * H : (H + 2 - 3) / 2 + 1, Wo = up ? 2 * W : (W + 2 - 3) / 2 + 1;
   const long M = (long)N * Ho * Wo;
   const Trk out = c.trunk(M, r.C);
-  ctrlv_gemm_desc d = gd(x.hi, r.C, r.conv, out.hi, r.C, (int)M, r.C, r.C, r.C);
+  ctrlv_gemm_desc d = ctrlv_linear_desc(x.hi, r.C, r.conv, out.hi, r.C, (int)M, r.C, r.C, r.C);
   set_out(d, out);
   d.taps = 9; d.mode = 1; d.H = H; d.Wd = W; d.Ho = Ho; d.Wo = Wo; d.stride = up ? 1 : 2; d.up = up ? 1 : 0;
   // the up-sampler in phase form (four 2x2 convs, 4/9 of the multiply-adds) where the LAYER's shape is served
   if (up && r.wph && ctrlv_gemm_up_phase_serves(&d)) { d.up = 2; d.W = r.wph; }
-  TRY(gemm(c, d));
+  CTRLV_TRY(gemm(c, d));
   *out_ = out; *Ho_ = Ho; *Wo_ = Wo;
   return CTRLV_OK;
 }
@@ -980,33 +790,33 @@ int run_context(Ctx& c, int dtype, const float* timestep, int n_t, const void* e
     CTRLV_LAUNCH_CHECK();
     if (kt != boc0) {
       CTRLV_HIP_TRY(hipMemsetAsync(te, 0, (size_t)B * kt * 2, c.st));
-      TRY(ctrlv_timestep_embedding(t32, B, boc0, te_tmp, c.st));
+      CTRLV_TRY(ctrlv_timestep_embedding(t32, B, boc0, te_tmp, c.st));
       CTRLV_HIP_TRY(hipMemcpy2DAsync(te, (size_t)kt * 2, te_tmp, (size_t)boc0 * 2, (size_t)boc0 * 2, B, hipMemcpyDeviceToDevice, c.st));
     } else {
-      TRY(ctrlv_timestep_embedding(t32, B, boc0, te, c.st));
+      CTRLV_TRY(ctrlv_timestep_embedding(t32, B, boc0, te, c.st));
     }
     // added ids: sinusoid of every id -> [B*n_ids, add_dim] == [B, n_ids*add_dim]
     if (ka != n_ids * add_dim) {
       CTRLV_HIP_TRY(hipMemsetAsync(ae, 0, (size_t)B * ka * 2, c.st));
-      TRY(ctrlv_timestep_embedding(ids32, B * n_ids, add_dim, ae_tmp, c.st));
+      CTRLV_TRY(ctrlv_timestep_embedding(ids32, B * n_ids, add_dim, ae_tmp, c.st));
       CTRLV_HIP_TRY(hipMemcpy2DAsync(ae, (size_t)ka * 2, ae_tmp, (size_t)n_ids * add_dim * 2, (size_t)n_ids * add_dim * 2, B,
                                      hipMemcpyDeviceToDevice, c.st));
     } else {
-      TRY(ctrlv_timestep_embedding(ids32, B * n_ids, add_dim, ae, c.st));
+      CTRLV_TRY(ctrlv_timestep_embedding(ids32, B * n_ids, add_dim, ae, c.st));
     }
   }
   // (tile 11: per-clip rows -- one kernel for these launches whatever B is, so a clip's conditioning vectors have the same
   //  bits alone and in any batch: csrc/gemm.hip gemv_small_kernel)
   constexpr int kClipRows = 11;
-  { ctrlv_gemm_desc d = gd(te, kt, p->te1, h, ted, B, ted, kt, ted); d.act = 1; d.tile = kClipRows; TRY(gemm(c, d)); }
-  { ctrlv_gemm_desc d = gd(h, ted, p->te2, emb_t, ted, B, ted, ted, ted); d.tile = kClipRows; TRY(gemm(c, d)); }
-  { ctrlv_gemm_desc d = gd(ae, ka, p->ae1, h, ted, B, ted, ka, ted); d.act = 1; d.tile = kClipRows; TRY(gemm(c, d)); }
+  { ctrlv_gemm_desc d = ctrlv_linear_desc(te, kt, p->te1, h, ted, B, ted, kt, ted); d.act = 1; d.tile = kClipRows; CTRLV_TRY(gemm(c, d)); }
+  { ctrlv_gemm_desc d = ctrlv_linear_desc(h, ted, p->te2, emb_t, ted, B, ted, ted, ted); d.tile = kClipRows; CTRLV_TRY(gemm(c, d)); }
+  { ctrlv_gemm_desc d = ctrlv_linear_desc(ae, ka, p->ae1, h, ted, B, ted, ka, ted); d.act = 1; d.tile = kClipRows; CTRLV_TRY(gemm(c, d)); }
   {   // silu(emb + aug_emb): the SiLU in front of every time_emb_proj
-    ctrlv_gemm_desc d = gd(h, ted, p->ae2, emb_s, ted, B, ted, ted, ted);
+    ctrlv_gemm_desc d = ctrlv_linear_desc(h, ted, p->ae2, emb_s, ted, B, ted, ted, ted);
     d.R1 = emb_t; d.ldr1 = ted; d.act = 1; d.tile = kClipRows;
-    TRY(gemm(c, d));
+    CTRLV_TRY(gemm(c, d));
   }
-  { ctrlv_gemm_desc d = gd(emb_s, ted, p->temb, c.temb, c.ldtemb, B, p->temb.n, ted, c.ldtemb); d.out_f32 = 1; d.tile = kClipRows; TRY(gemm(c, d)); }
+  { ctrlv_gemm_desc d = ctrlv_linear_desc(emb_s, ted, p->temb, c.temb, c.ldtemb, B, p->temb.n, ted, c.ldtemb); d.out_f32 = 1; d.tile = kClipRows; CTRLV_TRY(gemm(c, d)); }
   if (p->xattn_n) {
     const int dc = cfg.cross_attention_dim, nx = p->xv.n;
     el_t* e = c.rows(B, kx);
@@ -1016,13 +826,13 @@ int run_context(Ctx& c, int dtype, const float* timestep, int n_t, const void* e
     if (!c.dry) {
       if (c.overflow) { ctrlv_set_error("plan forward: workspace too small (need >= %zu bytes)", c.peak); return CTRLV_E_BAD_ARG; }
       if (kx != dc) CTRLV_HIP_TRY(hipMemsetAsync(e, 0, (size_t)B * kx * 2, c.st));
-      TRY(ctrlv_nchw_to_rows(ehs, dtype, B, dc, 1, e, kx, 0, c.st));      // (B, 1, dc) any dtype -> bf16 rows [B, kx]
+      CTRLV_TRY(ctrlv_nchw_to_rows(ehs, dtype, B, dc, 1, e, kx, 0, c.st));      // (B, 1, dc) any dtype -> bf16 rows [B, kx]
     }
-    { ctrlv_gemm_desc d = gd(e, kx, p->xv, v_all, nx, B, nx, kx, nx); d.tile = kClipRows; TRY(gemm(c, d)); }
+    { ctrlv_gemm_desc d = ctrlv_linear_desc(e, kx, p->xv, v_all, nx, B, nx, kx, nx); d.tile = kClipRows; CTRLV_TRY(gemm(c, d)); }
     for (const CrossOut& xo : p->xouts) {
-      ctrlv_gemm_desc d = gd(v_all + xo.off, nx, xo.to_out, c.xattn + xo.off, nx, B, xo.c, xo.c, xo.c);
+      ctrlv_gemm_desc d = ctrlv_linear_desc(v_all + xo.off, nx, xo.to_out, c.xattn + xo.off, nx, B, xo.c, xo.c, xo.c);
       d.out_f32 = 1; d.tile = kClipRows;
-      TRY(gemm(c, d));
+      CTRLV_TRY(gemm(c, d));
     }
   }
   c.quirk = cfg.time_context_order == 0;
@@ -1040,14 +850,14 @@ int run_input(Ctx& c, int dtype, const void* sample, const void* control, int h,
   if (!c.dry) {
     if (c.overflow) { ctrlv_set_error("plan forward: workspace too small (need >= %zu bytes)", c.peak); return CTRLV_E_BAD_ARG; }
     CTRLV_HIP_TRY(hipMemsetAsync(x16, 0, (size_t)M * p->cin_cp * 2, c.st));
-    TRY(ctrlv_nchw_to_rows(sample, dtype, N, cin, h * w, x16, p->cin_cp, 0, c.st));
-    if (control) TRY(ctrlv_nchw_to_rows(control, dtype, N, cin / 2, h * w, x16, p->cin_cp, cin, c.st));
-    TRY(ctrlv_im2col3x3(x16, N, h, w, p->cin_cp, col, p->cin_kp, c.st));
+    CTRLV_TRY(ctrlv_nchw_to_rows(sample, dtype, N, cin, h * w, x16, p->cin_cp, 0, c.st));
+    if (control) CTRLV_TRY(ctrlv_nchw_to_rows(control, dtype, N, cin / 2, h * w, x16, p->cin_cp, cin, c.st));
+    CTRLV_TRY(ctrlv_im2col3x3(x16, N, h, w, p->cin_cp, col, p->cin_kp, c.st));
   }
   {
-    ctrlv_gemm_desc d = gd(col, p->cin_kp, p->cin, x.hi, c0, (int)M, p->cin.n, p->cin_kp, c0);
+    ctrlv_gemm_desc d = ctrlv_linear_desc(col, p->cin_kp, p->cin, x.hi, c0, (int)M, p->cin.n, p->cin_kp, c0);
     set_out(d, x);
-    TRY(gemm(c, d));
+    CTRLV_TRY(gemm(c, d));
   }
   *out_ = x;
   return CTRLV_OK;
@@ -1060,22 +870,22 @@ int run_down_mid(Ctx& c, Trk x, int h, int w, std::vector<Tap>& taps, Trk* mid_,
   for (auto& b : p->down) {
     for (size_t j = 0; j < b.res.size(); ++j) {
       Trk y;
-      TRY(run_res(c, b.res[j], x, Trk{}, 0, H, W, &y, !b.attn.empty()));
+      CTRLV_TRY(run_res(c, b.res[j], x, Trk{}, 0, H, W, &y, !b.attn.empty()));
       x = y;
-      if (!b.attn.empty()) { TRY(run_tr(c, b.attn[j], x, H, W, &y)); x = y; }
+      if (!b.attn.empty()) { CTRLV_TRY(run_tr(c, b.attn[j], x, H, W, &y)); x = y; }
       taps.push_back({x, H, W, b.res[j].cout});
     }
     if (b.down.present) {
       Trk y; int Ho, Wo;
-      TRY(run_resample(c, b.down, x, H, W, false, &y, &Ho, &Wo));
+      CTRLV_TRY(run_resample(c, b.down, x, H, W, false, &y, &Ho, &Wo));
       x = y; H = Ho; W = Wo;
       taps.push_back({x, H, W, b.down.C});
     }
   }
   Trk y;
-  TRY(run_res(c, p->mid_r0, x, Trk{}, 0, H, W, &y, true)); x = y;
-  TRY(run_tr(c, p->mid_attn, x, H, W, &y)); x = y;
-  TRY(run_res(c, p->mid_r1, x, Trk{}, 0, H, W, &y)); x = y;
+  CTRLV_TRY(run_res(c, p->mid_r0, x, Trk{}, 0, H, W, &y, true)); x = y;
+  CTRLV_TRY(run_tr(c, p->mid_attn, x, H, W, &y)); x = y;
+  CTRLV_TRY(run_res(c, p->mid_r1, x, Trk{}, 0, H, W, &y)); x = y;
   *mid_ = x; *H_ = H; *W_ = W;
   return CTRLV_OK;
 }
@@ -1093,12 +903,12 @@ int unet_forward(ctrlv_plan* p, Ctx& c, const void* sample, int dtype, const flo
                  const float* ids, int n_ids, const void* const* down_res, const void* mid_res, void* res_event, void* out,
                  int h, int w) {
   const int N = c.B * c.F;
-  TRY(run_context(c, dtype, timestep, n_t, ehs, ids, n_ids));
+  CTRLV_TRY(run_context(c, dtype, timestep, n_t, ehs, ids, n_ids));
   Trk x;
-  TRY(run_input(c, dtype, sample, nullptr, h, w, &x));
+  CTRLV_TRY(run_input(c, dtype, sample, nullptr, h, w, &x));
   std::vector<Tap> taps;
   int H, W;
-  TRY(run_down_mid(c, x, h, w, taps, &x, &H, &W));
+  CTRLV_TRY(run_down_mid(c, x, h, w, taps, &x, &H, &W));
   // the ControlNet residual add on a trunk tensor: in place; in trunk mode 1 the sum is split again
   auto add_res = [&](const Trk& t, const void* r, size_t n) -> int {
     if (t.lo) return ctrlv_axpby_split(t.hi, t.lo, r, 1.0f, 1.0f, t.hi, t.lo, n, c.st);
@@ -1111,11 +921,11 @@ int unet_forward(ctrlv_plan* p, Ctx& c, const void* sample, int dtype, const flo
         CTRLV_CHECK_ARG(down_res[i] != nullptr, "unet_forward: down_res[%zu] is null", i);
         const size_t n = (size_t)N * taps[i].H * taps[i].W * taps[i].C;
         ProfScope ps(c, CTRLV_FAM_RESIDUAL_ADD, 0.0, 2.0 * 3 * (double)n, (int)(n / taps[i].C), taps[i].C);
-        TRY(add_res(taps[i].x, down_res[i], n));
+        CTRLV_TRY(add_res(taps[i].x, down_res[i], n));
       }
       const size_t nm_ = (size_t)N * H * W * p->cfg.block_out_channels[p->cfg.n_blocks - 1];
       ProfScope ps(c, CTRLV_FAM_RESIDUAL_ADD, 0.0, 2.0 * 3 * (double)nm_, N * H * W, p->cfg.block_out_channels[p->cfg.n_blocks - 1]);
-      TRY(add_res(x, mid_res, nm_));
+      CTRLV_TRY(add_res(x, mid_res, nm_));
     }
   }
   for (auto& b : p->up) {           // :140-158 -- torch.cat([hidden, skip], dim=1) is read in place (x | x2)
@@ -1123,27 +933,27 @@ int unet_forward(ctrlv_plan* p, Ctx& c, const void* sample, int dtype, const flo
       const Tap skip = taps.back();
       taps.pop_back();
       Trk y;
-      TRY(run_res(c, b.res[j], x, skip.x, b.res[j].cin - skip.C, H, W, &y, !b.attn.empty()));
+      CTRLV_TRY(run_res(c, b.res[j], x, skip.x, b.res[j].cin - skip.C, H, W, &y, !b.attn.empty()));
       x = y;
-      if (!b.attn.empty()) { TRY(run_tr(c, b.attn[j], x, H, W, &y)); x = y; }
+      if (!b.attn.empty()) { CTRLV_TRY(run_tr(c, b.attn[j], x, H, W, &y)); x = y; }
     }
     if (b.up.present) {
       Trk y; int Ho, Wo;
-      TRY(run_resample(c, b.up, x, H, W, true, &y, &Ho, &Wo));
+      CTRLV_TRY(run_resample(c, b.up, x, H, W, true, &y, &Ho, &Wo));
       x = y; H = Ho; W = Wo;
     }
   }
   const int c0 = p->cfg.block_out_channels[0], co = p->cfg.out_channels, co_p = pad_to(co, 4);
   const long M = (long)N * H * W;
   el_t* xn = c.rows(M, c0);
-  TRY(groupnorm(c, x, Trk{}, 0, N, H * W, c0, 1, p->gno, 1e-5f, 1, xn));         // :161-163
+  CTRLV_TRY(groupnorm(c, x, Trk{}, 0, N, H * W, c0, 1, p->gno, 1e-5f, 1, xn));         // :161-163
   el_t* y = c.rows(M, co_p);
   {
-    ctrlv_gemm_desc d = gd(xn, c0, p->cout, y, co_p, (int)M, p->cout.n, c0, co_p);
+    ctrlv_gemm_desc d = ctrlv_linear_desc(xn, c0, p->cout, y, co_p, (int)M, p->cout.n, c0, co_p);
     d.taps = 9; d.mode = 1; d.H = H; d.Wd = W; d.Ho = H; d.Wo = W; d.stride = 1;
-    TRY(gemm(c, d));
+    CTRLV_TRY(gemm(c, d));
   }
-  if (!c.dry) TRY(ctrlv_rows_to_nchw(y, co_p, N, co, H * W, out, dtype, c.st));  // :166
+  if (!c.dry) CTRLV_TRY(ctrlv_rows_to_nchw(y, co_p, N, co, H * W, out, dtype, c.st));  // :166
   return CTRLV_OK;
 }
 
@@ -1151,26 +961,26 @@ int controlnet_forward(ctrlv_plan* p, Ctx& c, const void* sample, const void* co
                        int n_t, const void* ehs, const float* ids, int n_ids, float scale, void* const* out_down,
                        void* out_mid, int h, int w) {
   const int N = c.B * c.F;
-  TRY(run_context(c, dtype, timestep, n_t, ehs, ids, n_ids));
+  CTRLV_TRY(run_context(c, dtype, timestep, n_t, ehs, ids, n_ids));
   Trk x;
-  TRY(run_input(c, dtype, sample, control, h, w, &x));
+  CTRLV_TRY(run_input(c, dtype, sample, control, h, w, &x));
   std::vector<Tap> taps;
   int H, W;
-  TRY(run_down_mid(c, x, h, w, taps, &x, &H, &W));
+  CTRLV_TRY(run_down_mid(c, x, h, w, taps, &x, &H, &W));
   CTRLV_CHECK_ARG(taps.size() == p->zc.size(), "controlnet_forward: %zu taps but %zu zero-convs", taps.size(), p->zc.size());
   for (size_t i = 0; i < taps.size(); ++i) {       // controlnet.py:331-344: zero-conv * conditioning_scale, one GEMM
     const long M = (long)N * taps[i].H * taps[i].W;
     const int C = taps[i].C;
     if (!c.dry) CTRLV_CHECK_ARG(out_down && out_down[i], "controlnet_forward: out_down[%zu] is null", i);
-    ctrlv_gemm_desc d = gd(taps[i].x.hi, C, p->zc[i], c.dry ? nullptr : out_down[i], C, (int)M, p->zc[i].n, C, C);
+    ctrlv_gemm_desc d = ctrlv_linear_desc(taps[i].x.hi, C, p->zc[i], c.dry ? nullptr : out_down[i], C, (int)M, p->zc[i].n, C, C);
     d.s_acc = scale;
-    TRY(gemm(c, d));
+    CTRLV_TRY(gemm(c, d));
   }
   {
     const int C = p->cfg.block_out_channels[p->cfg.n_blocks - 1];
-    ctrlv_gemm_desc d = gd(x.hi, C, p->zc_mid, out_mid, C, (int)((long)N * H * W), p->zc_mid.n, C, C);
+    ctrlv_gemm_desc d = ctrlv_linear_desc(x.hi, C, p->zc_mid, out_mid, C, (int)((long)N * H * W), p->zc_mid.n, C, C);
     d.s_acc = scale;
-    TRY(gemm(c, d));
+    CTRLV_TRY(gemm(c, d));
   }
   return CTRLV_OK;
 }
@@ -1219,25 +1029,6 @@ void free_owned(ctrlv_plan* p) {
 }  // namespace
 
 // ================================================================================================== C entry points
-extern "C" int ctrlv_pack_weight(const void* src, int src_dtype, int N, int C, int taps, int form, int geglu, void* dst,
-                                 int ld_dst, ctrlv_stream_t stream) {
-  CTRLV_CHECK_ARG(src && dst, "pack_weight: null pointer");
-  CTRLV_CHECK_ARG(src_dtype >= 0 && src_dtype <= 2 && (form == 0 || form == 1), "pack_weight: bad dtype / form");
-  CTRLV_CHECK_SHAPE(N > 0 && C > 0 && taps > 0 && N <= 65535 && C <= 65535, "pack_weight: bad shape");
-  if (form == 0) {
-    CTRLV_CHECK_SHAPE(ld_dst >= taps * C && (!geglu || N % 32 == 0), "pack_weight: ld_dst < taps * C (or odd GEGLU rows)");
-    hipLaunchKernelGGL(pack_weight_rows_kernel, dim3((taps * C + 255) / 256, N), dim3(256), 0, (hipStream_t)stream, src,
-                       src_dtype, N, C, taps, (el_t*)dst, ld_dst, geglu);
-  } else {
-    CTRLV_CHECK_SHAPE(ld_dst % taps == 0 && ld_dst / taps >= N && !geglu, "pack_weight: ld_dst must be taps * Np, Np >= N");
-    const int Np = ld_dst / taps;
-    hipLaunchKernelGGL(pack_weight_swapped_kernel, dim3((taps * C + 63) / 64, (Np + 31) / 32), dim3(256), 0,
-                       (hipStream_t)stream, src, src_dtype, N, C, taps, Np, (el_t*)dst, ld_dst);
-  }
-  CTRLV_LAUNCH_CHECK();
-  return CTRLV_OK;
-}
-
 extern "C" int ctrlv_plan_create(const ctrlv_model_config* cfg, int device, ctrlv_plan** out) {
   CTRLV_CHECK_ARG(cfg && out, "plan_create: null argument");
   ctrlv_plan* p = new ctrlv_plan();
@@ -1263,61 +1054,54 @@ extern "C" int ctrlv_plan_destroy(ctrlv_plan* p) {
 
 extern "C" int ctrlv_plan_load_weights(ctrlv_plan* p, const ctrlv_tensor_desc* tensors, size_t n) {
   CTRLV_CHECK_ARG(p && tensors, "plan_load_weights: null argument");
-  CTRLV_HIP_TRY(hipSetDevice(p->device));
-  free_owned(p);
-  Loader L;
-  L.p = p;
-  for (size_t i = 0; i < n; ++i) {
-    CTRLV_CHECK_ARG(tensors[i].name && tensors[i].data && tensors[i].dtype >= 0 && tensors[i].dtype <= 2,
-                    "plan_load_weights: bad tensor descriptor %zu", i);
-    L.map[tensors[i].name] = &tensors[i];
-  }
+  WeightLoader L("plan_load_weights", &p->owned);
   const ctrlv_model_config& c = p->cfg;
   const int nb = c.n_blocks, c0 = c.block_out_channels[0], ted = 4 * c0;
   auto body = [&]() -> int {
+    free_owned(p);
+    for (size_t i = 0; i < n; ++i)
+      CTRLV_CHECK_ARG(tensors[i].name && tensors[i].data && tensors[i].dtype >= 0 && tensors[i].dtype <= 2,
+                      "plan_load_weights: bad tensor descriptor %zu", i);
+    L.add(tensors, n);
     // input convs: slots [conv_in channels | control_conv_in channels | pad], biases summed (controlnet.py:297-299)
     const int cin_tot = c.in_channels + (c.kind == 1 ? c.in_channels / 2 : 0);
-    p->cin_cp = pad_to(cin_tot, 8);
-    p->cin_kp = pad_to(9 * p->cin_cp, 64);
-    TRY(L.new_linear(p->cin, c0, p->cin_kp, true));
-    TRY(L.pack_w("conv_in.weight", c0, c.in_channels, 9, p->cin, p->cin_cp, 0, 0, 0));
-    TRY(L.pack_v("conv_in.bias", c0, p->cin.b, 0, 0, 0));
+    CTRLV_TRY(L.conv_in("conv_in", c0, c.in_channels, cin_tot, p->cin, &p->cin_cp, &p->cin_kp));
     if (c.kind == 1) {
-      TRY(L.pack_w("control_conv_in.weight", c0, c.in_channels / 2, 9, p->cin, p->cin_cp, c.in_channels, 0, 0));
-      TRY(L.pack_v("control_conv_in.bias", c0, p->cin.b, 0, 0, 1));
+      CTRLV_TRY(L.pack_w("control_conv_in.weight", c0, c.in_channels / 2, 9, p->cin, p->cin_cp, c.in_channels, 0, 0));
+      CTRLV_TRY(L.pack_v("control_conv_in.bias", c0, p->cin.b, 0, 0, 1));
     }
-    TRY(L.linear("time_embedding.linear_1", ted, c0, p->te1));
-    TRY(L.linear("time_embedding.linear_2", ted, ted, p->te2));
-    TRY(L.linear("add_embedding.linear_1", ted, c.projection_class_embeddings_input_dim, p->ae1));
-    TRY(L.linear("add_embedding.linear_2", ted, ted, p->ae2));
+    CTRLV_TRY(L.linear("time_embedding.linear_1", ted, c0, p->te1));
+    CTRLV_TRY(L.linear("time_embedding.linear_2", ted, ted, p->te2));
+    CTRLV_TRY(L.linear("add_embedding.linear_1", ted, c.projection_class_embeddings_input_dim, p->ae1));
+    CTRLV_TRY(L.linear("add_embedding.linear_2", ted, ted, p->ae2));
     // model-wide row-vector GEMMs: offsets first, then storage, then the blocks fill their rows
     int off = 0;
     for_each_res(p, [&](ResBlock& r) { r.temb_off[0] = off; off += r.cout; r.temb_off[1] = off; off += r.cout; });
     p->temb_n = off;
-    TRY(L.new_linear(p->temb, off, pad_to(ted, 64), true));
+    CTRLV_TRY(L.new_linear(p->temb, off, pad_to(ted, 64), true));
     off = 0;
     for_each_tr(p, [&](Transformer& t) { t.xattn_off[0] = off; off += t.C; t.xattn_off[1] = off; off += t.C; });
     p->xattn_n = off;
-    if (off) TRY(L.new_linear(p->xv, off, pad_to(c.cross_attention_dim, 64), false));
+    if (off) CTRLV_TRY(L.new_linear(p->xv, off, pad_to(c.cross_attention_dim, 64), false));
     int rc = CTRLV_OK;
-    for_each_res(p, [&](ResBlock& r) { if (rc == CTRLV_OK) rc = load_res(L, r, ted); });
-    TRY(rc);
-    for_each_tr(p, [&](Transformer& t) { if (rc == CTRLV_OK) rc = load_tr(L, t, c.cross_attention_dim); });
-    TRY(rc);
+    for_each_res(p, [&](ResBlock& r) { if (rc == CTRLV_OK) rc = load_res(L, p, r, ted); });
+    CTRLV_TRY(rc);
+    for_each_tr(p, [&](Transformer& t) { if (rc == CTRLV_OK) rc = load_tr(L, p, t, c.cross_attention_dim); });
+    CTRLV_TRY(rc);
     for (int i = 0; i < nb; ++i) {
       if (p->down[i].down.present)
-        TRY(L.conv3x3("down_blocks." + std::to_string(i) + ".downsamplers.0.conv", p->down[i].down.C, p->down[i].down.C,
+        CTRLV_TRY(L.conv3x3("down_blocks." + std::to_string(i) + ".downsamplers.0.conv", p->down[i].down.C, p->down[i].down.C,
                       p->down[i].down.conv));
       if (c.kind == 0 && p->up[i].up.present) {
         Resample& u = p->up[i].up;
         const std::string mod = "up_blocks." + std::to_string(i) + ".upsamplers.0.conv";
-        TRY(L.conv3x3(mod, u.C, u.C, u.conv));
-        if (u.conv.n == u.C) TRY(L.up_phase(mod, u.C, u.C, &u.wph));      // (no padded weight rows: the panels are [C][4 C])
+        CTRLV_TRY(L.conv3x3(mod, u.C, u.C, u.conv));
+        if (u.conv.n == u.C) CTRLV_TRY(up_phase(L, mod, u.C, u.C, &u.wph));      // (no padded weight rows: the panels are [C][4 C])
       }
     }
     if (c.kind == 0) {
-      TRY(L.norm("conv_norm_out", c0, p->gno));
-      TRY(L.conv3x3("conv_out", c.out_channels, c0, p->cout));
+      CTRLV_TRY(L.norm("conv_norm_out", c0, p->gno));
+      CTRLV_TRY(L.conv3x3("conv_out", c.out_channels, c0, p->cout));
     } else {
       // controlnet.py:148-185: one zero-conv per encoder tap (conv_in, every layer, every downsampler) + the mid block
       std::vector<int> ch;
@@ -1327,8 +1111,8 @@ extern "C" int ctrlv_plan_load_weights(ctrlv_plan* p, const ctrlv_tensor_desc* t
         if (i != nb - 1) ch.push_back(c.block_out_channels[i]);
       }
       p->zc.resize(ch.size());
-      for (size_t i = 0; i < ch.size(); ++i) TRY(L.linear("controlnet_down_blocks." + std::to_string(i), ch[i], ch[i], p->zc[i]));
-      TRY(L.linear("controlnet_mid_block", c.block_out_channels[nb - 1], c.block_out_channels[nb - 1], p->zc_mid));
+      for (size_t i = 0; i < ch.size(); ++i) CTRLV_TRY(L.linear("controlnet_down_blocks." + std::to_string(i), ch[i], ch[i], p->zc[i]));
+      CTRLV_TRY(L.linear("controlnet_mid_block", c.block_out_channels[nb - 1], c.block_out_channels[nb - 1], p->zc_mid));
     }
     // frame positional embedding tables for cfg.num_frames (weights-only constants)
     if (c.num_frames > 0) {
@@ -1349,20 +1133,13 @@ extern "C" int ctrlv_plan_load_weights(ctrlv_plan* p, const ctrlv_tensor_desc* t
         cx.B = 1; cx.F = c.num_frames;
         rc = frame_embedding(cx, t, c.num_frames, t.frame_emb);
       });
-      TRY(rc);
+      CTRLV_TRY(rc);
     }
-    if (p->ff_precision == 1) TRY(make_f8(p, L.st));
+    if (p->ff_precision == 1) CTRLV_TRY(make_f8(p, L.st));
     return CTRLV_OK;
   };
-  const int rc = body();
-  const hipError_t e = hipDeviceSynchronize();
-  for (void* d : L.staged) (void)hipFree(d);
+  const int rc = ctrlv_load::run_load(L, p->device, false, body);       // (the plan's device stays current)
   if (rc != CTRLV_OK) { free_owned(p); return rc; }
-  if (e != hipSuccess) {
-    ctrlv_set_error("plan_load_weights: %s", hipGetErrorString(e));
-    free_owned(p);
-    return CTRLV_E_HIP;
-  }
   p->loaded = true;
   return CTRLV_OK;
 }
@@ -1466,12 +1243,12 @@ extern "C" int ctrlv_unet_forward(ctrlv_plan* p, const void* sample, int dtype, 
                                   const void* ehs, const float* added_time_ids, int n_ids, const void* const* down_res,
                                   const void* mid_res, void* residual_event, void* out, int B, int F, int H, int W,
                                   void* workspace, size_t workspace_bytes, ctrlv_stream_t stream) {
-  TRY(check_common(p, B, F, H, W));
+  CTRLV_TRY(check_common(p, B, F, H, W));
   CTRLV_CHECK_ARG(p->cfg.kind == 0, "unet_forward: the plan is a ControlNet");
   CTRLV_CHECK_ARG(sample && timestep && ehs && added_time_ids && out && workspace, "unet_forward: null pointer");
   if (dtype < 0 || dtype > 2) { ctrlv_set_error("unet_forward: dtype must be 0 (fp32), 1 (fp16) or 2 (bf16)"); return CTRLV_E_BAD_DTYPE; }
   CTRLV_CHECK_ARG((down_res == nullptr) == (mid_res == nullptr), "unet_forward: pass both down_res and mid_res or neither");
-  TRY(check_workspace(p, "unet_forward", B, F, H, W, workspace_bytes));
+  CTRLV_TRY(check_workspace(p, "unet_forward", B, F, H, W, workspace_bytes));
   char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
   Ctx c{p, (hipStream_t)stream, false, base, workspace_bytes - (size_t)(base - (char*)workspace)};
   c.B = B; c.F = F;
@@ -1486,18 +1263,18 @@ extern "C" int ctrlv_unet_forward(ctrlv_plan* p, const void* sample, int dtype, 
 static int unet_encoder(ctrlv_plan* p, Ctx& c, const void* sample, int dtype, const float* timestep, int n_t, const void* ehs,
                         const float* ids, int n_ids, void* const* out_taps, void* out_mid, int h, int w) {
   const int N = c.B * c.F;
-  TRY(run_context(c, dtype, timestep, n_t, ehs, ids, n_ids));
+  CTRLV_TRY(run_context(c, dtype, timestep, n_t, ehs, ids, n_ids));
   Trk x;
-  TRY(run_input(c, dtype, sample, nullptr, h, w, &x));
+  CTRLV_TRY(run_input(c, dtype, sample, nullptr, h, w, &x));
   std::vector<Tap> taps;
   int H, W;
-  TRY(run_down_mid(c, x, h, w, taps, &x, &H, &W));
+  CTRLV_TRY(run_down_mid(c, x, h, w, taps, &x, &H, &W));
   if (!c.dry) {     // (the training step's tensors are plain element rows: the hi planes)
     for (size_t i = 0; i < taps.size(); ++i) {
       CTRLV_CHECK_ARG(out_taps[i] != nullptr, "unet_encoder_forward: out_taps[%zu] is null", i);
-      TRY(ctrlv_axpby(taps[i].x.hi, taps[i].x.hi, 1.0f, 0.0f, out_taps[i], (size_t)N * taps[i].H * taps[i].W * taps[i].C, c.st));
+      CTRLV_TRY(ctrlv_axpby(taps[i].x.hi, taps[i].x.hi, 1.0f, 0.0f, out_taps[i], (size_t)N * taps[i].H * taps[i].W * taps[i].C, c.st));
     }
-    TRY(ctrlv_axpby(x.hi, x.hi, 1.0f, 0.0f, out_mid, (size_t)N * H * W * p->cfg.block_out_channels[p->cfg.n_blocks - 1], c.st));
+    CTRLV_TRY(ctrlv_axpby(x.hi, x.hi, 1.0f, 0.0f, out_mid, (size_t)N * H * W * p->cfg.block_out_channels[p->cfg.n_blocks - 1], c.st));
   }
   return CTRLV_OK;
 }
@@ -1506,12 +1283,12 @@ extern "C" int ctrlv_unet_encoder_forward(ctrlv_plan* p, const void* sample, int
                                           const void* ehs, const float* added_time_ids, int n_ids, void* const* out_taps,
                                           void* out_mid, int B, int F, int H, int W, void* workspace,
                                           size_t workspace_bytes, ctrlv_stream_t stream) {
-  TRY(check_common(p, B, F, H, W));
+  CTRLV_TRY(check_common(p, B, F, H, W));
   CTRLV_CHECK_ARG(p->cfg.kind == 0, "unet_encoder_forward: the plan is a ControlNet");
   CTRLV_CHECK_ARG(sample && timestep && ehs && added_time_ids && out_taps && out_mid && workspace,
                   "unet_encoder_forward: null pointer");
   if (dtype < 0 || dtype > 2) { ctrlv_set_error("unet_encoder_forward: dtype must be 0 (fp32), 1 (fp16) or 2 (bf16)"); return CTRLV_E_BAD_DTYPE; }
-  TRY(check_workspace(p, "unet_encoder_forward", B, F, H, W, workspace_bytes));     // (sized for the whole forward)
+  CTRLV_TRY(check_workspace(p, "unet_encoder_forward", B, F, H, W, workspace_bytes));     // (sized for the whole forward)
   char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
   Ctx c{p, (hipStream_t)stream, false, base, workspace_bytes - (size_t)(base - (char*)workspace)};
   c.B = B; c.F = F;
@@ -1525,12 +1302,12 @@ extern "C" int ctrlv_controlnet_forward(ctrlv_plan* p, const void* sample, const
                                         const float* added_time_ids, int n_ids, float conditioning_scale,
                                         void* const* out_down, void* out_mid, int B, int F, int H, int W, void* workspace,
                                         size_t workspace_bytes, ctrlv_stream_t stream) {
-  TRY(check_common(p, B, F, H, W));
+  CTRLV_TRY(check_common(p, B, F, H, W));
   CTRLV_CHECK_ARG(p->cfg.kind == 1, "controlnet_forward: the plan is a UNet");
   CTRLV_CHECK_ARG(sample && control_cond && timestep && ehs && added_time_ids && out_down && out_mid && workspace,
                   "controlnet_forward: null pointer (control_cond is required, controlnet.py:289)");
   if (dtype < 0 || dtype > 2) { ctrlv_set_error("controlnet_forward: dtype must be 0 (fp32), 1 (fp16) or 2 (bf16)"); return CTRLV_E_BAD_DTYPE; }
-  TRY(check_workspace(p, "controlnet_forward", B, F, H, W, workspace_bytes));
+  CTRLV_TRY(check_workspace(p, "controlnet_forward", B, F, H, W, workspace_bytes));
   char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
   Ctx c{p, (hipStream_t)stream, false, base, workspace_bytes - (size_t)(base - (char*)workspace)};
   c.B = B; c.F = F;

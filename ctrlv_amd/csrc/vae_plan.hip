@@ -12,21 +12,15 @@
 #include <math.h>
 
 #include <string>
-#include <unordered_map>
 #include <vector>
 
-#include "common.h"
-
-#define TRY(expr)                      \
-  do {                                 \
-    const int rc__ = (expr);           \
-    if (rc__ != CTRLV_OK) return rc__; \
-  } while (0)
+#include "weight_loader.h"
 
 namespace {
 
-struct VConv { el_t* w = nullptr; float* b = nullptr; int n = 0, k = 0; };      // packed [n (rows, x32), k] + fp32 bias [n]
-struct VNorm { float* g = nullptr; float* b = nullptr; };
+using ctrlv_load::WeightLoader;
+using VConv = ctrlv_load::PackedLinear;        // packed [n (rows, x32), k] + fp32 bias [n]
+using VNorm = ctrlv_load::NormParams;
 struct VRes {
   int cin = 0, cout = 0;
   bool temporal = false, shortcut = false;
@@ -75,182 +69,48 @@ const ctrlv_vae_config* ctrlv_vae_plan_info(const ctrlv_vae_plan* p, int* device
 
 namespace {
 
-__device__ __forceinline__ float vld_any(const void* p, int dtype, long i) {
-  if (dtype == 0) return ((const float*)p)[i];
-  if (dtype == 1) return (float)((const _Float16*)p)[i];
-  return bf16_to_f32(((const bf16_t*)p)[i]);
+int res2d(WeightLoader& L, const std::string& mod, int cin, int cout, VRes& r) {
+  r.cin = cin; r.cout = cout;
+  CTRLV_TRY(L.norm(mod + ".norm1", cin, r.n1));
+  CTRLV_TRY(L.conv3x3(mod + ".conv1", cout, cin, r.c1));
+  CTRLV_TRY(L.norm(mod + ".norm2", cout, r.n2));
+  CTRLV_TRY(L.conv3x3(mod + ".conv2", cout, cout, r.c2));
+  r.shortcut = cin != cout;
+  if (r.shortcut) CTRLV_TRY(L.linear(mod + ".conv_shortcut", cout, cin, r.sc));
+  return CTRLV_OK;
 }
-// PyTorch conv / linear parameter [N, C, taps] -> dst[n * ldk + t * cslot + c] (dst pre-zeroed: row, slot and K padding):
-// packing.pack_linear (taps 1), pack_conv3x3 (9), pack_conv_temporal (3), pack_conv_in (9, cslot = padded channel slot)
-__global__ void vae_pack_kernel(const void* __restrict__ src, int dtype, long total, int C, int taps, el_t* __restrict__ dst,
-                                int ldk, int cslot) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const long nc = i / taps;
-    const int t = (int)(i - nc * taps), c = (int)(nc % C);
-    dst[(nc / C) * ldk + (long)t * cslot + c] = f32_to_el(vld_any(src, dtype, i));
-  }
+int res_st(WeightLoader& L, const std::string& mod, int cin, int cout, VRes& r) {
+  CTRLV_TRY(res2d(L, mod + ".spatial_res_block", cin, cout, r));
+  r.temporal = true;
+  const std::string t = mod + ".temporal_res_block";
+  CTRLV_TRY(L.norm(t + ".norm1", cout, r.tn1));
+  CTRLV_TRY(L.conv_t(t + ".conv1", cout, cout, r.tc1));
+  CTRLV_TRY(L.norm(t + ".norm2", cout, r.tn2));
+  CTRLV_TRY(L.conv_t(t + ".conv2", cout, cout, r.tc2));
+  double alpha;
+  CTRLV_TRY(L.mix_alpha(mod + ".time_mixer.mix_factor", &alpha));
+  r.mix = (float)alpha;
+  return CTRLV_OK;
 }
-__global__ void vae_pack_f32_kernel(const void* __restrict__ src, int dtype, long total, float* __restrict__ dst) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x)
-    dst[i] = vld_any(src, dtype, i);
+int attn(WeightLoader& L, const std::string& mod, int C, VAttn& a) {
+  CTRLV_TRY(L.norm(mod + ".group_norm", C, a.gn));
+  CTRLV_TRY(L.linear(mod + ".to_q", C, C, a.q));
+  CTRLV_TRY(L.linear(mod + ".to_k", C, C, a.k));
+  CTRLV_TRY(L.linear(mod + ".to_v", C, C, a.v_rows, false));
+  CTRLV_TRY(L.linear(mod + ".to_out.0", C, C, a.o, false));
+  // folded output bias b_o + W_o . b_v (rows of P sum to one): fp64 on the host from the fp32 values, rounded once
+  std::vector<float> wo, bo, bv;
+  CTRLV_TRY(L.host_f32(mod + ".to_out.0.weight", (long)C * C, wo));
+  CTRLV_TRY(L.host_f32(mod + ".to_out.0.bias", C, bo));
+  CTRLV_TRY(L.host_f32(mod + ".to_v.bias", C, bv));
+  std::vector<float> fold(C);
+  for (int o = 0; o < C; ++o) {
+    double s = (double)bo[o];
+    for (int c = 0; c < C; ++c) s += (double)wo[(size_t)o * C + c] * (double)bv[c];
+    fold[o] = (float)s;
+  }
+  return L.upload(fold, &a.o.b);
 }
-inline unsigned vblocks(long total) { return (unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096); }
-
-float host_to_f32(const void* p, int dtype, long i) {
-  if (dtype == 0) return ((const float*)p)[i];
-  const uint16_t h = ((const uint16_t*)p)[i];
-  uint32_t u;
-  if (dtype == 2) {
-    u = (uint32_t)h << 16;
-  } else {                                 // IEEE half -> float
-    const uint32_t s = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 0x3ffu;
-    if (e == 0) {
-      if (m == 0) u = s;
-      else { int sh = 0; uint32_t mm = m; while (!(mm & 0x400u)) { mm <<= 1; ++sh; } u = s | ((uint32_t)(113 - sh) << 23) | ((mm & 0x3ffu) << 13); }
-    } else if (e == 31) u = s | 0x7f800000u | (m << 13);
-    else u = s | ((e + 112u) << 23) | (m << 13);
-  }
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-}
-
-struct VLoader {
-  ctrlv_vae_plan* p;
-  std::unordered_map<std::string, const ctrlv_tensor_desc*> map;
-  std::vector<void*> staged;
-
-  int desc(const std::string& name, long numel, const ctrlv_tensor_desc** out) {
-    auto it = map.find(name);
-    if (it == map.end()) { ctrlv_set_error("vae_plan_load_weights: missing tensor '%s'", name.c_str()); return CTRLV_E_BAD_ARG; }
-    const ctrlv_tensor_desc* t = it->second;
-    if (t->numel != numel) {
-      ctrlv_set_error("vae_plan_load_weights: '%s' has %ld elements, expected %ld", name.c_str(), (long)t->numel, numel);
-      return CTRLV_E_BAD_SHAPE;
-    }
-    if (t->dtype < 0 || t->dtype > 2 || !t->data) {
-      ctrlv_set_error("vae_plan_load_weights: '%s': dtype code %d / null data", name.c_str(), t->dtype);
-      return CTRLV_E_BAD_DTYPE;
-    }
-    *out = t;
-    return CTRLV_OK;
-  }
-  int find(const std::string& name, long numel, const void** src, int* dtype) {       // device pointer of the tensor
-    const ctrlv_tensor_desc* t;
-    TRY(desc(name, numel, &t));
-    *dtype = t->dtype;
-    if (t->on_device) { *src = t->data; return CTRLV_OK; }
-    const size_t bytes = (size_t)t->numel * (t->dtype == 0 ? 4 : 2);
-    void* d = nullptr;
-    CTRLV_HIP_TRY(hipMalloc(&d, bytes));
-    staged.push_back(d);
-    CTRLV_HIP_TRY(hipMemcpy(d, t->data, bytes, hipMemcpyHostToDevice));
-    *src = d;
-    return CTRLV_OK;
-  }
-  int host(const std::string& name, long numel, std::vector<float>& out) {            // fp32 host copy of the tensor
-    const ctrlv_tensor_desc* t;
-    TRY(desc(name, numel, &t));
-    const size_t bytes = (size_t)numel * (t->dtype == 0 ? 4 : 2);
-    std::vector<char> raw(bytes);
-    if (t->on_device) CTRLV_HIP_TRY(hipMemcpy(raw.data(), t->data, bytes, hipMemcpyDeviceToHost));
-    else memcpy(raw.data(), t->data, bytes);
-    out.resize(numel);
-    for (long i = 0; i < numel; ++i) out[i] = host_to_f32(raw.data(), t->dtype, i);
-    return CTRLV_OK;
-  }
-  int alloc(size_t bytes, void** out, bool zero) {
-    void* d = nullptr;
-    CTRLV_HIP_TRY(hipMalloc(&d, bytes ? bytes : 256));
-    p->owned.push_back(d);
-    if (zero) CTRLV_HIP_TRY(hipMemsetAsync(d, 0, bytes ? bytes : 256, nullptr));
-    *out = d;
-    return CTRLV_OK;
-  }
-  int vec(const std::string& name, long n, float** dst, long n_pad = 0) {
-    TRY(alloc((size_t)(n_pad > n ? n_pad : n) * 4, (void**)dst, n_pad > n));
-    const void* src;
-    int dt;
-    TRY(find(name, n, &src, &dt));
-    vae_pack_f32_kernel<<<vblocks(n), 256, 0, nullptr>>>(src, dt, n, *dst);
-    CTRLV_LAUNCH_CHECK();
-    return CTRLV_OK;
-  }
-  int upload(const std::vector<float>& v, float** dst) {
-    TRY(alloc(v.size() * 4, (void**)dst, false));
-    CTRLV_HIP_TRY(hipMemcpy(*dst, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-    return CTRLV_OK;
-  }
-  // weight [N, C, taps] -> rows padded to 32, K = taps * cslot padded to kp (0: no K padding beyond the slots)
-  int weight(const std::string& name, int N, int C, int taps, int cslot, int kp, VConv& cv) {
-    cv.n = (N + 31) / 32 * 32;
-    cv.k = kp ? kp : taps * cslot;
-    TRY(alloc((size_t)cv.n * cv.k * 2, (void**)&cv.w, true));
-    const void* src;
-    int dt;
-    const long total = (long)N * C * taps;
-    TRY(find(name, total, &src, &dt));
-    vae_pack_kernel<<<vblocks(total), 256, 0, nullptr>>>(src, dt, total, C, taps, cv.w, cv.k, cslot);
-    CTRLV_LAUNCH_CHECK();
-    return CTRLV_OK;
-  }
-  int conv(const std::string& mod, int N, int C, int taps, VConv& cv, bool pad_b = false) {
-    TRY(weight(mod + ".weight", N, C, taps, C, taps == 1 ? (C + 63) / 64 * 64 : 0, cv));
-    return vec(mod + ".bias", N, &cv.b, pad_b ? cv.n : 0);
-  }
-  int conv_in(const std::string& mod, int N, int C, VConv& cv, int* cp, int* kp) {       // packing.pack_conv_in + pad_bias
-    *cp = (C + 7) / 8 * 8;
-    *kp = (9 * *cp + 63) / 64 * 64;
-    TRY(weight(mod + ".weight", N, C, 9, *cp, *kp, cv));
-    return vec(mod + ".bias", N, &cv.b, cv.n);
-  }
-  int norm(const std::string& mod, int C, VNorm& nm) {
-    TRY(vec(mod + ".weight", C, &nm.g));
-    return vec(mod + ".bias", C, &nm.b);
-  }
-  int res2d(const std::string& mod, int cin, int cout, VRes& r) {
-    r.cin = cin; r.cout = cout;
-    TRY(norm(mod + ".norm1", cin, r.n1));
-    TRY(conv(mod + ".conv1", cout, cin, 9, r.c1));
-    TRY(norm(mod + ".norm2", cout, r.n2));
-    TRY(conv(mod + ".conv2", cout, cout, 9, r.c2));
-    r.shortcut = cin != cout;
-    if (r.shortcut) TRY(conv(mod + ".conv_shortcut", cout, cin, 1, r.sc));
-    return CTRLV_OK;
-  }
-  int res_st(const std::string& mod, int cin, int cout, VRes& r) {
-    TRY(res2d(mod + ".spatial_res_block", cin, cout, r));
-    r.temporal = true;
-    const std::string t = mod + ".temporal_res_block";
-    TRY(norm(t + ".norm1", cout, r.tn1));
-    TRY(conv(t + ".conv1", cout, cout, 3, r.tc1));
-    TRY(norm(t + ".norm2", cout, r.tn2));
-    TRY(conv(t + ".conv2", cout, cout, 3, r.tc2));
-    std::vector<float> m;
-    TRY(host(mod + ".time_mixer.mix_factor", 1, m));
-    r.mix = (float)(1.0 / (1.0 + exp(-(double)m[0])));
-    return CTRLV_OK;
-  }
-  int attn(const std::string& mod, int C, VAttn& a) {
-    TRY(norm(mod + ".group_norm", C, a.gn));
-    TRY(conv(mod + ".to_q", C, C, 1, a.q));
-    TRY(conv(mod + ".to_k", C, C, 1, a.k));
-    TRY(weight(mod + ".to_v.weight", C, C, 1, C, 0, a.v_rows));
-    TRY(weight(mod + ".to_out.0.weight", C, C, 1, C, 0, a.o));
-    // folded output bias b_o + W_o . b_v (rows of P sum to one): fp64 on the host from the fp32 values, rounded once
-    std::vector<float> wo, bo, bv;
-    TRY(host(mod + ".to_out.0.weight", (long)C * C, wo));
-    TRY(host(mod + ".to_out.0.bias", C, bo));
-    TRY(host(mod + ".to_v.bias", C, bv));
-    std::vector<float> fold(C);
-    for (int o = 0; o < C; ++o) {
-      double s = (double)bo[o];
-      for (int c = 0; c < C; ++c) s += (double)wo[(size_t)o * C + c] * (double)bv[c];
-      fold[o] = (float)s;
-    }
-    return upload(fold, &a.o.b);
-  }
-};
 
 void free_owned(ctrlv_vae_plan* p) {
   for (void* d : p->owned) (void)hipFree(d);
@@ -259,13 +119,12 @@ void free_owned(ctrlv_vae_plan* p) {
   p->loaded = false;
 }
 
-int load_all(VLoader& L) {
-  ctrlv_vae_plan* p = L.p;
+int load_all(WeightLoader& L, ctrlv_vae_plan* p) {
   const ctrlv_vae_config& c = p->cfg;
   const int nb = c.n_blocks, top = c.block_out_channels[nb - 1], L2 = 2 * c.latent_channels;
   auto S = [](int i) { return std::to_string(i); };
   // ---- encoder
-  TRY(L.conv_in("encoder.conv_in", c.block_out_channels[0], c.in_channels, p->e_cin, &p->e_cp, &p->e_kp));
+  CTRLV_TRY(L.conv_in("encoder.conv_in", c.block_out_channels[0], c.in_channels, c.in_channels, p->e_cin, &p->e_cp, &p->e_kp));
   p->e_down.resize(nb);
   int prev = c.block_out_channels[0];
   for (int i = 0; i < nb; ++i) {
@@ -273,22 +132,22 @@ int load_all(VLoader& L) {
     VLevel& lv = p->e_down[i];
     lv.res.resize(c.layers_per_block);
     for (int j = 0; j < c.layers_per_block; ++j)
-      TRY(L.res2d("encoder.down_blocks." + S(i) + ".resnets." + S(j), j == 0 ? prev : ch, ch, lv.res[j]));
+      CTRLV_TRY(res2d(L, "encoder.down_blocks." + S(i) + ".resnets." + S(j), j == 0 ? prev : ch, ch, lv.res[j]));
     lv.has_resample = i != nb - 1;
-    if (lv.has_resample) TRY(L.conv("encoder.down_blocks." + S(i) + ".downsamplers.0.conv", ch, ch, 9, lv.resample));
+    if (lv.has_resample) CTRLV_TRY(L.conv3x3("encoder.down_blocks." + S(i) + ".downsamplers.0.conv", ch, ch, lv.resample));
     prev = ch;
   }
-  for (int j = 0; j < 2; ++j) TRY(L.res2d("encoder.mid_block.resnets." + S(j), top, top, p->e_mid[j]));
-  TRY(L.attn("encoder.mid_block.attentions.0", top, p->e_attn));
-  TRY(L.norm("encoder.conv_norm_out", top, p->e_gno));
-  TRY(L.conv("encoder.conv_out", L2, top, 9, p->e_cout, true));
-  TRY(L.vec("quant_conv.weight", (long)L2 * L2, &p->qw));
-  TRY(L.vec("quant_conv.bias", L2, &p->qb));
+  for (int j = 0; j < 2; ++j) CTRLV_TRY(res2d(L, "encoder.mid_block.resnets." + S(j), top, top, p->e_mid[j]));
+  CTRLV_TRY(attn(L, "encoder.mid_block.attentions.0", top, p->e_attn));
+  CTRLV_TRY(L.norm("encoder.conv_norm_out", top, p->e_gno));
+  CTRLV_TRY(L.conv3x3("encoder.conv_out", L2, top, p->e_cout));
+  CTRLV_TRY(L.vec("quant_conv.weight", (long)L2 * L2, &p->qw));
+  CTRLV_TRY(L.vec("quant_conv.bias", L2, &p->qb));
   // ---- decoder
-  TRY(L.conv_in("decoder.conv_in", top, c.latent_channels, p->d_cin, &p->d_cp, &p->d_kp));
+  CTRLV_TRY(L.conv_in("decoder.conv_in", top, c.latent_channels, c.latent_channels, p->d_cin, &p->d_cp, &p->d_kp));
   p->d_mid.resize(c.layers_per_block);
-  for (int j = 0; j < c.layers_per_block; ++j) TRY(L.res_st("decoder.mid_block.resnets." + S(j), top, top, p->d_mid[j]));
-  TRY(L.attn("decoder.mid_block.attentions.0", top, p->d_attn));
+  for (int j = 0; j < c.layers_per_block; ++j) CTRLV_TRY(res_st(L, "decoder.mid_block.resnets." + S(j), top, top, p->d_mid[j]));
+  CTRLV_TRY(attn(L, "decoder.mid_block.attentions.0", top, p->d_attn));
   p->d_up.resize(nb);
   prev = top;
   for (int i = 0; i < nb; ++i) {
@@ -296,20 +155,18 @@ int load_all(VLoader& L) {
     VLevel& lv = p->d_up[i];
     lv.res.resize(c.layers_per_block + 1);
     for (int j = 0; j <= c.layers_per_block; ++j)
-      TRY(L.res_st("decoder.up_blocks." + S(i) + ".resnets." + S(j), j == 0 ? prev : ch, ch, lv.res[j]));
+      CTRLV_TRY(res_st(L, "decoder.up_blocks." + S(i) + ".resnets." + S(j), j == 0 ? prev : ch, ch, lv.res[j]));
     lv.has_resample = i != nb - 1;
-    if (lv.has_resample) TRY(L.conv("decoder.up_blocks." + S(i) + ".upsamplers.0.conv", ch, ch, 9, lv.resample));
+    if (lv.has_resample) CTRLV_TRY(L.conv3x3("decoder.up_blocks." + S(i) + ".upsamplers.0.conv", ch, ch, lv.resample));
     prev = ch;
   }
-  TRY(L.norm("decoder.conv_norm_out", c.block_out_channels[0], p->d_gno));
-  TRY(L.conv("decoder.conv_out", c.out_channels, c.block_out_channels[0], 9, p->d_cout, true));
-  TRY(L.vec("decoder.time_conv_out.weight", (long)c.out_channels * c.out_channels * 3, &p->tco_w));
+  CTRLV_TRY(L.norm("decoder.conv_norm_out", c.block_out_channels[0], p->d_gno));
+  CTRLV_TRY(L.conv3x3("decoder.conv_out", c.out_channels, c.block_out_channels[0], p->d_cout));
+  CTRLV_TRY(L.vec("decoder.time_conv_out.weight", (long)c.out_channels * c.out_channels * 3, &p->tco_w));
   return L.vec("decoder.time_conv_out.bias", c.out_channels, &p->tco_b);
 }
 
 // ---- the walk: one function for the dry run (layout, peak) and the forward
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
 struct Arena {                             // first-fit free list over workspace offsets
   struct Blk { size_t off, size; bool free; };
   std::vector<Blk> blks;
@@ -357,16 +214,6 @@ struct Ctx {
   void drop(const void* q) { a.give((size_t)((const char*)q - base)); }
 };
 
-ctrlv_gemm_desc gd(const void* A, int lda, const VConv& w, void* out, int ldo, long M, int N, int cin, int n_store) {
-  ctrlv_gemm_desc d;
-  memset(&d, 0, sizeof d);
-  d.A = A; d.W = w.w; d.out = out; d.bias = w.b;
-  d.M = (int)M; d.N = N; d.Cin = cin; d.taps = 1;
-  d.lda = lda; d.ldo = ldo; d.n_store = n_store;
-  d.s_acc = 1.0f; d.s1 = 1.0f; d.s2 = 1.0f;
-  d.vdiv = 1; d.vmod = 1 << 30; d.vS = 1;
-  return d;
-}
 void conv2d(ctrlv_gemm_desc& d, int H, int W, int Ho, int Wo, int stride, int up) {
   d.taps = 9; d.mode = 1; d.H = H; d.Wd = W; d.Ho = Ho; d.Wo = Wo; d.stride = stride; d.up = up;
 }
@@ -412,12 +259,12 @@ int conv_in(Ctx& c, const void* src, int dtype, int n, int C, int H, int W, cons
   el_t* x16 = c.rows(M, cp);
   if (!c.dry) {
     CTRLV_HIP_TRY(hipMemsetAsync(x16, 0, (size_t)M * cp * 2, c.st));
-    TRY(ctrlv_nchw_to_rows(src, dtype, n, C, H * W, x16, cp, 0, c.st));
+    CTRLV_TRY(ctrlv_nchw_to_rows(src, dtype, n, C, H * W, x16, cp, 0, c.st));
   }
   el_t* col = c.rows(M, kp);
-  if (!c.dry) TRY(ctrlv_im2col3x3(x16, n, H, W, cp, col, kp, c.st));
+  if (!c.dry) CTRLV_TRY(ctrlv_im2col3x3(x16, n, H, W, cp, col, kp, c.st));
   el_t* x = c.rows(M, cv.n);
-  TRY(gemm(c, gd(col, kp, cv, x, cv.n, M, cv.n, kp, cv.n)));
+  CTRLV_TRY(gemm(c, ctrlv_linear_desc(col, kp, cv, x, cv.n, M, cv.n, kp, cv.n)));
   c.drop(col);
   c.drop(x16);
   *out = x;
@@ -430,20 +277,20 @@ int enc_res(Ctx& c, const VRes& r, const el_t* x, int n, int H, int W, el_t** ou
   const long M = (long)n * S;
   const float eps = 1e-6f;
   el_t* xn = c.rows(M, cin);
-  TRY(groupnorm(c, x, n, S, cin, 1, r.n1, eps, 1, xn));
+  CTRLV_TRY(groupnorm(c, x, n, S, cin, 1, r.n1, eps, 1, xn));
   el_t* h = c.rows(M, cout);
-  { ctrlv_gemm_desc d = gd(xn, cin, r.c1, h, cout, M, cout, cin, cout); conv2d(d, H, W, H, W, 1, 0); TRY(gemm(c, d)); }
+  { ctrlv_gemm_desc d = ctrlv_linear_desc(xn, cin, r.c1, h, cout, M, cout, cin, cout); conv2d(d, H, W, H, W, 1, 0); CTRLV_TRY(gemm(c, d)); }
   c.drop(xn);
   el_t* hn = c.rows(M, cout);
-  TRY(groupnorm(c, h, n, S, cout, 1, r.n2, eps, 1, hn));
+  CTRLV_TRY(groupnorm(c, h, n, S, cout, 1, r.n2, eps, 1, hn));
   const el_t* res = x;
   el_t* rs = nullptr;
   if (r.shortcut) {
     rs = c.rows(M, cout);
-    TRY(gemm(c, gd(x, cin, r.sc, rs, cout, M, cout, cin, cout)));
+    CTRLV_TRY(gemm(c, ctrlv_linear_desc(x, cin, r.sc, rs, cout, M, cout, cin, cout)));
     res = rs;
   }
-  { ctrlv_gemm_desc d = gd(hn, cout, r.c2, h, cout, M, cout, cout, cout); conv2d(d, H, W, H, W, 1, 0); resid(d, res, cout); TRY(gemm(c, d)); }
+  { ctrlv_gemm_desc d = ctrlv_linear_desc(hn, cout, r.c2, h, cout, M, cout, cout, cout); conv2d(d, H, W, H, W, 1, 0); resid(d, res, cout); CTRLV_TRY(gemm(c, d)); }
   c.drop(hn);
   if (rs) c.drop(rs);
   *out = h;
@@ -464,20 +311,20 @@ int dec_res(Ctx& c, const VRes& r, const el_t* x, int n, int H, int W, el_t** ou
   for (int f0 = 0; f0 < n; f0 += per) {
     const int k = (f0 + per < n ? f0 + per : n) - f0;
     const long r0 = (long)f0 * S, Mk = (long)k * S;
-    TRY(groupnorm(c, x + r0 * cin, k, S, cin, 1, r.n1, 1e-6f, 1, xn + r0 * cin));
-    { ctrlv_gemm_desc d = gd(xn + r0 * cin, cin, r.c1, h + r0 * cout, cout, Mk, cout, cin, cout); conv2d(d, H, W, H, W, 1, 0); TRY(gemm(c, d)); }
-    TRY(groupnorm(c, h + r0 * cout, k, S, cout, 1, r.n2, 1e-6f, 1, hn + r0 * cout));
-    if (r.shortcut) TRY(gemm(c, gd(x + r0 * cin, cin, r.sc, rs + r0 * cout, cout, Mk, cout, cin, cout)));
-    { ctrlv_gemm_desc d = gd(hn + r0 * cout, cout, r.c2, xs + r0 * cout, cout, Mk, cout, cout, cout); conv2d(d, H, W, H, W, 1, 0);
-      resid(d, res + r0 * cout, cout); TRY(gemm(c, d)); }
+    CTRLV_TRY(groupnorm(c, x + r0 * cin, k, S, cin, 1, r.n1, 1e-6f, 1, xn + r0 * cin));
+    { ctrlv_gemm_desc d = ctrlv_linear_desc(xn + r0 * cin, cin, r.c1, h + r0 * cout, cout, Mk, cout, cin, cout); conv2d(d, H, W, H, W, 1, 0); CTRLV_TRY(gemm(c, d)); }
+    CTRLV_TRY(groupnorm(c, h + r0 * cout, k, S, cout, 1, r.n2, 1e-6f, 1, hn + r0 * cout));
+    if (r.shortcut) CTRLV_TRY(gemm(c, ctrlv_linear_desc(x + r0 * cin, cin, r.sc, rs + r0 * cout, cout, Mk, cout, cin, cout)));
+    { ctrlv_gemm_desc d = ctrlv_linear_desc(hn + r0 * cout, cout, r.c2, xs + r0 * cout, cout, Mk, cout, cout, cout); conv2d(d, H, W, H, W, 1, 0);
+      resid(d, res + r0 * cout, cout); CTRLV_TRY(gemm(c, d)); }
   }
   c.drop(xn);
   if (rs) c.drop(rs);
   // temporal res block on (1, C, n, H, W): statistics over the whole clip, conv along the frames, blend in the epilogue
-  TRY(groupnorm(c, xs, n, S, cout, n, r.tn1, 1e-5f, 1, hn));
-  { ctrlv_gemm_desc d = gd(hn, cout, r.tc1, h, cout, M, cout, cout, cout); conv_t(d, n, S); TRY(gemm(c, d)); }
-  TRY(groupnorm(c, h, n, S, cout, n, r.tn2, 1e-5f, 1, hn));
-  { ctrlv_gemm_desc d = gd(hn, cout, r.tc2, h, cout, M, cout, cout, cout); conv_t(d, n, S); d.s_acc = r.mix; resid(d, xs, cout); TRY(gemm(c, d)); }
+  CTRLV_TRY(groupnorm(c, xs, n, S, cout, n, r.tn1, 1e-5f, 1, hn));
+  { ctrlv_gemm_desc d = ctrlv_linear_desc(hn, cout, r.tc1, h, cout, M, cout, cout, cout); conv_t(d, n, S); CTRLV_TRY(gemm(c, d)); }
+  CTRLV_TRY(groupnorm(c, h, n, S, cout, n, r.tn2, 1e-5f, 1, hn));
+  { ctrlv_gemm_desc d = ctrlv_linear_desc(hn, cout, r.tc2, h, cout, M, cout, cout, cout); conv_t(d, n, S); d.s_acc = r.mix; resid(d, xs, cout); CTRLV_TRY(gemm(c, d)); }
   c.drop(hn);
   c.drop(xs);
   *out = h;
@@ -489,11 +336,11 @@ int attn(Ctx& c, const VAttn& a, const el_t* x, int n, int H, int W, int C, el_t
   const int S = H * W;
   const long M = (long)n * S;
   el_t* t = c.rows(M, C);
-  TRY(groupnorm(c, x, n, S, C, 1, a.gn, 1e-6f, 0, t));
+  CTRLV_TRY(groupnorm(c, x, n, S, C, 1, a.gn, 1e-6f, 0, t));
   el_t* q = c.rows(M, C);
   el_t* k = c.rows(M, C);
-  TRY(gemm(c, gd(t, C, a.q, q, C, M, C, C, C)));
-  TRY(gemm(c, gd(t, C, a.k, k, C, M, C, C, C)));
+  CTRLV_TRY(gemm(c, ctrlv_linear_desc(t, C, a.q, q, C, M, C, C, C)));
+  CTRLV_TRY(gemm(c, ctrlv_linear_desc(t, C, a.k, k, C, M, C, C, C)));
   el_t* o = c.rows(M, C);
   float* scores = (float*)c.bytes((size_t)S * S * 4);
   el_t* probs = c.rows(S, S);
@@ -502,16 +349,16 @@ int attn(Ctx& c, const VAttn& a, const el_t* x, int n, int H, int W, int C, el_t
   for (int f = 0; f < n; ++f) {
     const long r0 = (long)f * S * C;
     VConv kw; kw.w = k + r0; kw.b = nullptr;
-    { ctrlv_gemm_desc d = gd(q + r0, C, kw, scores, S, S, S, C, S); d.s_acc = scale; d.out_f32 = 1; TRY(gemm(c, d)); }
-    if (!c.dry) TRY(ctrlv_softmax_rows(scores, S, S, S, probs, S, c.st));
+    { ctrlv_gemm_desc d = ctrlv_linear_desc(q + r0, C, kw, scores, S, S, S, C, S); d.s_acc = scale; d.out_f32 = 1; CTRLV_TRY(gemm(c, d)); }
+    if (!c.dry) CTRLV_TRY(ctrlv_softmax_rows(scores, S, S, S, probs, S, c.st));
     VConv tw; tw.w = t + r0; tw.b = nullptr;
-    TRY(gemm(c, gd(a.v_rows.w, C, tw, vt, S, C, S, C, S)));
+    CTRLV_TRY(gemm(c, ctrlv_linear_desc(a.v_rows.w, C, tw, vt, S, C, S, C, S)));
     VConv vw; vw.w = vt; vw.b = nullptr;
-    TRY(gemm(c, gd(probs, S, vw, o + r0, C, S, C, S, C)));
+    CTRLV_TRY(gemm(c, ctrlv_linear_desc(probs, S, vw, o + r0, C, S, C, S, C)));
   }
   c.drop(scores); c.drop(probs); c.drop(vt); c.drop(q); c.drop(k);
   el_t* y = c.rows(M, C);
-  { ctrlv_gemm_desc d = gd(o, C, a.o, y, C, M, C, C, C); resid(d, x, C); TRY(gemm(c, d)); }
+  { ctrlv_gemm_desc d = ctrlv_linear_desc(o, C, a.o, y, C, M, C, C, C); resid(d, x, C); CTRLV_TRY(gemm(c, d)); }
   c.drop(t);
   c.drop(o);
   *out = y;
@@ -523,21 +370,21 @@ int encode_walk(Ctx& c, const void* px, int dtype, int n, int H, int W, const fl
   const ctrlv_vae_plan* p = c.p;
   const ctrlv_vae_config& cf = p->cfg;
   el_t* h;
-  TRY(conv_in(c, px, dtype, n, cf.in_channels, H, W, p->e_cin, p->e_cp, p->e_kp, &h));
+  CTRLV_TRY(conv_in(c, px, dtype, n, cf.in_channels, H, W, p->e_cin, p->e_cp, p->e_kp, &h));
   for (const VLevel& lv : p->e_down) {
     for (const VRes& r : lv.res) {
       el_t* y;
-      TRY(enc_res(c, r, h, n, H, W, &y));
+      CTRLV_TRY(enc_res(c, r, h, n, H, W, &y));
       c.drop(h);
       h = y;
     }
     if (lv.has_resample) {               // F.pad(x, (0, 1, 0, 1)) + stride 2: ONE launch (pad_br)
       const int C = lv.res.back().cout;
       el_t* half = c.rows((long)n * (H / 2) * (W / 2), C);
-      ctrlv_gemm_desc d = gd(h, C, lv.resample, half, C, (long)n * (H / 2) * (W / 2), C, C, C);
+      ctrlv_gemm_desc d = ctrlv_linear_desc(h, C, lv.resample, half, C, (long)n * (H / 2) * (W / 2), C, C, C);
       conv2d(d, H, W, H / 2, W / 2, 2, 0);
       d.pad_br = 1;
-      TRY(gemm(c, d));
+      CTRLV_TRY(gemm(c, d));
       c.drop(h);
       h = half;
       H /= 2; W /= 2;
@@ -545,17 +392,17 @@ int encode_walk(Ctx& c, const void* px, int dtype, int n, int H, int W, const fl
   }
   const int C = cf.block_out_channels[cf.n_blocks - 1];
   el_t* y;
-  TRY(enc_res(c, p->e_mid[0], h, n, H, W, &y)); c.drop(h); h = y;
-  TRY(attn(c, p->e_attn, h, n, H, W, C, &y)); c.drop(h); h = y;
-  TRY(enc_res(c, p->e_mid[1], h, n, H, W, &y)); c.drop(h); h = y;
+  CTRLV_TRY(enc_res(c, p->e_mid[0], h, n, H, W, &y)); c.drop(h); h = y;
+  CTRLV_TRY(attn(c, p->e_attn, h, n, H, W, C, &y)); c.drop(h); h = y;
+  CTRLV_TRY(enc_res(c, p->e_mid[1], h, n, H, W, &y)); c.drop(h); h = y;
   const long M = (long)n * H * W;
   el_t* hn = c.rows(M, C);
-  TRY(groupnorm(c, h, n, H * W, C, 1, p->e_gno, 1e-6f, 1, hn));
+  CTRLV_TRY(groupnorm(c, h, n, H * W, C, 1, p->e_gno, 1e-6f, 1, hn));
   const int co = 2 * cf.latent_channels, co_p = (co + 3) / 4 * 4;
   el_t* rows = c.rows(M, co_p);
-  { ctrlv_gemm_desc d = gd(hn, C, p->e_cout, rows, co_p, M, p->e_cout.n, C, co_p); conv2d(d, H, W, H, W, 1, 0); TRY(gemm(c, d)); }
+  { ctrlv_gemm_desc d = ctrlv_linear_desc(hn, C, p->e_cout, rows, co_p, M, p->e_cout.n, C, co_p); conv2d(d, H, W, H, W, 1, 0); CTRLV_TRY(gemm(c, d)); }
   if (!c.dry)
-    TRY(ctrlv_vae_posterior(rows, co_p, n, cf.latent_channels, H * W, p->qw, p->qb, noise, scale, moments, latents, out_dtype, c.st));
+    CTRLV_TRY(ctrlv_vae_posterior(rows, co_p, n, cf.latent_channels, H * W, p->qw, p->qb, noise, scale, moments, latents, out_dtype, c.st));
   c.drop(rows); c.drop(hn); c.drop(h);
   return CTRLV_OK;
 }
@@ -565,15 +412,15 @@ int decode_clip(Ctx& c, const void* z, int dtype, int n, int H, int W, void* fra
   const ctrlv_vae_config& cf = p->cfg;
   el_t* x;
   el_t* y;
-  TRY(conv_in(c, z, dtype, n, cf.latent_channels, H, W, p->d_cin, p->d_cp, p->d_kp, &x));
+  CTRLV_TRY(conv_in(c, z, dtype, n, cf.latent_channels, H, W, p->d_cin, p->d_cp, p->d_kp, &x));
   const int top = cf.block_out_channels[cf.n_blocks - 1];
-  TRY(dec_res(c, p->d_mid[0], x, n, H, W, &y)); c.drop(x); x = y;
+  CTRLV_TRY(dec_res(c, p->d_mid[0], x, n, H, W, &y)); c.drop(x); x = y;
   for (size_t j = 1; j < p->d_mid.size(); ++j) {
-    TRY(attn(c, p->d_attn, x, n, H, W, top, &y)); c.drop(x); x = y;
-    TRY(dec_res(c, p->d_mid[j], x, n, H, W, &y)); c.drop(x); x = y;
+    CTRLV_TRY(attn(c, p->d_attn, x, n, H, W, top, &y)); c.drop(x); x = y;
+    CTRLV_TRY(dec_res(c, p->d_mid[j], x, n, H, W, &y)); c.drop(x); x = y;
   }
   for (const VLevel& lv : p->d_up) {
-    for (const VRes& r : lv.res) { TRY(dec_res(c, r, x, n, H, W, &y)); c.drop(x); x = y; }
+    for (const VRes& r : lv.res) { CTRLV_TRY(dec_res(c, r, x, n, H, W, &y)); c.drop(x); x = y; }
     if (lv.has_resample) {               // nearest x2 fused into the conv's gather; per-frame op: frame ranges
       const int C = lv.res.back().cout;
       const long S = (long)H * W;
@@ -581,9 +428,9 @@ int decode_clip(Ctx& c, const void* z, int dtype, int n, int H, int W, void* fra
       const int per = frames_per(p->limit, n, 4 * S, C);
       for (int f0 = 0; f0 < n; f0 += per) {
         const int k = (f0 + per < n ? f0 + per : n) - f0;
-        ctrlv_gemm_desc d = gd(x + (long)f0 * S * C, C, lv.resample, up + (long)f0 * 4 * S * C, C, (long)k * 4 * S, C, C, C);
+        ctrlv_gemm_desc d = ctrlv_linear_desc(x + (long)f0 * S * C, C, lv.resample, up + (long)f0 * 4 * S * C, C, (long)k * 4 * S, C, C, C);
         conv2d(d, H, W, 2 * H, 2 * W, 1, 1);
-        TRY(gemm(c, d));
+        CTRLV_TRY(gemm(c, d));
       }
       c.drop(x);
       x = up;
@@ -593,12 +440,12 @@ int decode_clip(Ctx& c, const void* z, int dtype, int n, int H, int W, void* fra
   const int C = cf.block_out_channels[0], co = cf.out_channels, co_p = (co + 3) / 4 * 4;
   const long M = (long)n * H * W;
   el_t* xn = c.rows(M, C);
-  TRY(groupnorm(c, x, n, H * W, C, 1, p->d_gno, 1e-6f, 1, xn));
+  CTRLV_TRY(groupnorm(c, x, n, H * W, C, 1, p->d_gno, 1e-6f, 1, xn));
   c.drop(x);
   el_t* rows = c.rows(M, co_p);
-  { ctrlv_gemm_desc d = gd(xn, C, p->d_cout, rows, co_p, M, p->d_cout.n, C, co_p); conv2d(d, H, W, H, W, 1, 0); TRY(gemm(c, d)); }
+  { ctrlv_gemm_desc d = ctrlv_linear_desc(xn, C, p->d_cout, rows, co_p, M, p->d_cout.n, C, co_p); conv2d(d, H, W, H, W, 1, 0); CTRLV_TRY(gemm(c, d)); }
   c.drop(xn);
-  if (!c.dry) TRY(ctrlv_time_conv_rows_to_nchw(rows, co_p, n, co, H * W, p->tco_w, p->tco_b, frames, out_dtype, c.st));
+  if (!c.dry) CTRLV_TRY(ctrlv_time_conv_rows_to_nchw(rows, co_p, n, co, H * W, p->tco_w, p->tco_b, frames, out_dtype, c.st));
   c.drop(rows);
   return CTRLV_OK;
 }
@@ -679,24 +526,13 @@ extern "C" int ctrlv_vae_plan_destroy(ctrlv_vae_plan* p) {
 
 extern "C" int ctrlv_vae_plan_load_weights(ctrlv_vae_plan* p, const ctrlv_tensor_desc* tensors, size_t n) {
   CTRLV_CHECK_ARG(p && tensors, "vae_plan_load_weights: null argument");
-  int prev = 0;
-  const bool sw = hipGetDevice(&prev) == hipSuccess && prev != p->device;
-  CTRLV_HIP_TRY(hipSetDevice(p->device));
-  free_owned(p);
-  VLoader L;
-  L.p = p;
-  for (size_t i = 0; i < n; ++i)
-    if (tensors[i].name) L.map[tensors[i].name] = &tensors[i];
-  const int rc = load_all(L);
-  const hipError_t e = hipDeviceSynchronize();
-  for (void* d : L.staged) (void)hipFree(d);
-  if (sw) (void)hipSetDevice(prev);
-  if (rc != CTRLV_OK) { free_owned(p); return rc; }
-  if (e != hipSuccess) {
+  WeightLoader L("vae_plan_load_weights", &p->owned);
+  const int rc = ctrlv_load::run_load(L, p->device, true, [&]() -> int {
     free_owned(p);
-    ctrlv_set_error("vae_plan_load_weights: %s", hipGetErrorString(e));
-    return CTRLV_E_HIP;
-  }
+    L.add(tensors, n);
+    return load_all(L, p);
+  });
+  if (rc != CTRLV_OK) { free_owned(p); return rc; }
   p->loaded = true;
   return CTRLV_OK;
 }
@@ -718,7 +554,7 @@ extern "C" int ctrlv_vae_encode(ctrlv_vae_plan* p, const void* pixels, int dtype
     ctrlv_set_error("vae_encode: dtype codes %d / %d (0 fp32, 1 fp16, 2 bf16)", dtype, out_dtype);
     return CTRLV_E_BAD_DTYPE;
   }
-  TRY(check_encode_shape(p, n, Hpx, Wpx));
+  CTRLV_TRY(check_encode_shape(p, n, Hpx, Wpx));
   CTRLV_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "vae_encode: workspace must be 256-byte aligned");
   const size_t need = dry_bytes(p, 0, n, 0, Hpx, Wpx);
   if (workspace_bytes < need) {
@@ -737,7 +573,7 @@ extern "C" int ctrlv_vae_decode(ctrlv_vae_plan* p, const void* z, int dtype, int
     ctrlv_set_error("vae_decode: dtype codes %d / %d (0 fp32, 1 fp16, 2 bf16)", dtype, out_dtype);
     return CTRLV_E_BAD_DTYPE;
   }
-  TRY(check_decode_shape(p, n, num_frames, h, w));
+  CTRLV_TRY(check_decode_shape(p, n, num_frames, h, w));
   CTRLV_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "vae_decode: workspace must be 256-byte aligned");
   const size_t need = dry_bytes(p, 1, n, num_frames, h, w);
   if (workspace_bytes < need) {
@@ -748,7 +584,7 @@ extern "C" int ctrlv_vae_decode(ctrlv_vae_plan* p, const void* z, int dtype, int
   const size_t in_el = dtype == 0 ? 4 : 2, out_el = out_dtype == 0 ? 4 : 2;
   for (int c0 = 0; c0 < n; c0 += num_frames) {       // independent clips, one after the other in the same workspace
     Ctx c{p, false, (char*)workspace, (hipStream_t)stream, {}};
-    TRY(decode_clip(c, (const char*)z + (size_t)c0 * cf.latent_channels * h * w * in_el, dtype, num_frames, h, w,
+    CTRLV_TRY(decode_clip(c, (const char*)z + (size_t)c0 * cf.latent_channels * h * w * in_el, dtype, num_frames, h, w,
                     (char*)frames + (size_t)c0 * cf.out_channels * 64 * h * w * out_el, out_dtype));
   }
   return CTRLV_OK;

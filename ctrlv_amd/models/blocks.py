@@ -499,7 +499,7 @@ class Upsample2D(nn.Module):
 
     def pack(self):
         self._pk = (packing.pack_conv3x3(self.conv.weight), _f32(self.conv.bias))
-        # the four 2x2 phase panels (ops.pack_up_phase_weight; csrc/plan.hip Loader::up_phase), from the parameter itself
+        # the four 2x2 phase panels (ops.pack_up_phase_weight; csrc/plan.hip up_phase), from the parameter itself
         w = self.conv.weight
         self._pk_up = ops.pack_up_phase_weight(w, self._pk[0].dtype) if w.is_cuda else None      # (else: at the first run)
 

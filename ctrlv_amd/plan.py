@@ -51,6 +51,26 @@ def config_struct(kind, cfg, time_context_order="sb"):
     return c
 
 
+def _tensor_descs(state_dict, floating_only):
+    """(TensorDesc array, the tensors it points into) of a state dict: every tensor, or the floating-point ones only.
+    Keep the second value alive until the library has read the array."""
+    items = [(k, v.detach()) for k, v in state_dict.items()
+             if torch.is_tensor(v) and (v.is_floating_point() or not floating_only)]
+    keep = []
+    arr = (TensorDesc * len(items))()
+    for i, (k, v) in enumerate(items):
+        if v.dtype not in _DT:
+            v = v.float()
+        v = v.contiguous()
+        keep.append(v)
+        arr[i].name = k.encode()
+        arr[i].data = v.data_ptr()
+        arr[i].dtype = _DT[v.dtype]
+        arr[i].on_device = 1 if v.is_cuda else 0
+        arr[i].numel = v.numel()
+    return arr, keep
+
+
 class Plan:
     """Owns one `ctrlv_plan` (module graph + packed weights in library-owned device memory)."""
 
@@ -81,22 +101,10 @@ class Plan:
 
     def load_state_dict(self, state_dict):
         """Hand every parameter to the library by its diffusers key; packing happens on the device in C++."""
-        items = [(k, v.detach()) for k, v in state_dict.items() if torch.is_tensor(v)]
-        keep = []
-        arr = (TensorDesc * len(items))()
-        for i, (k, v) in enumerate(items):
-            if v.dtype not in _DT:
-                v = v.float()
-            v = v.contiguous()
-            keep.append(v)
-            arr[i].name = k.encode()
-            arr[i].data = v.data_ptr()
-            arr[i].dtype = _DT[v.dtype]
-            arr[i].on_device = 1 if v.is_cuda else 0
-            arr[i].numel = v.numel()
+        arr, keep = _tensor_descs(state_dict, floating_only=False)
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)          # parameters may still be in flight on torch's streams
-        check(self._lib.ctrlv_plan_load_weights(self._h, arr, len(items)), "ctrlv_plan_load_weights")
+        check(self._lib.ctrlv_plan_load_weights(self._h, arr, len(arr)), "ctrlv_plan_load_weights")
         del keep
 
     def profile(self, enable=True):
@@ -232,22 +240,10 @@ class ClipPlan:
 
     def load_state_dict(self, state_dict):
         """Hand every parameter to the library by its transformers key; packing happens on the device in C++."""
-        items = [(k, v.detach()) for k, v in state_dict.items() if torch.is_tensor(v) and v.is_floating_point()]
-        keep = []
-        arr = (TensorDesc * len(items))()
-        for i, (k, v) in enumerate(items):
-            if v.dtype not in _DT:
-                v = v.float()
-            v = v.contiguous()
-            keep.append(v)
-            arr[i].name = k.encode()
-            arr[i].data = v.data_ptr()
-            arr[i].dtype = _DT[v.dtype]
-            arr[i].on_device = 1 if v.is_cuda else 0
-            arr[i].numel = v.numel()
+        arr, keep = _tensor_descs(state_dict, floating_only=True)
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
-        check(self._lib.ctrlv_clip_plan_load_weights(self._h, arr, len(items)), "ctrlv_clip_plan_load_weights")
+        check(self._lib.ctrlv_clip_plan_load_weights(self._h, arr, len(arr)), "ctrlv_clip_plan_load_weights")
         del keep
 
     def workspace_bytes(self, n_img):
@@ -323,22 +319,10 @@ class VaePlan:
 
     def load_state_dict(self, state_dict):
         """Hand every parameter to the library by its diffusers key; packing happens on the device in C++."""
-        items = [(k, v.detach()) for k, v in state_dict.items() if torch.is_tensor(v) and v.is_floating_point()]
-        keep = []
-        arr = (TensorDesc * len(items))()
-        for i, (k, v) in enumerate(items):
-            if v.dtype not in _DT:
-                v = v.float()
-            v = v.contiguous()
-            keep.append(v)
-            arr[i].name = k.encode()
-            arr[i].data = v.data_ptr()
-            arr[i].dtype = _DT[v.dtype]
-            arr[i].on_device = 1 if v.is_cuda else 0
-            arr[i].numel = v.numel()
+        arr, keep = _tensor_descs(state_dict, floating_only=True)
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
-        check(self._lib.ctrlv_vae_plan_load_weights(self._h, arr, len(items)), "ctrlv_vae_plan_load_weights")
+        check(self._lib.ctrlv_vae_plan_load_weights(self._h, arr, len(arr)), "ctrlv_vae_plan_load_weights")
         del keep
 
     def workspace_bytes(self, what, n, num_frames, H, W):
