@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "plan_walk.h"
 #include "weight_loader.h"
 
 namespace {
@@ -235,11 +236,8 @@ extern "C" int ctrlv_clip_plan_create(const ctrlv_clip_config* cfg, int device, 
 extern "C" int ctrlv_clip_plan_destroy(ctrlv_clip_plan* p) {
   if (!p) return CTRLV_OK;
   if (!p->owned.empty()) {
-    int dev = 0;
-    const bool sw = hipGetDevice(&dev) == hipSuccess && dev != p->device;
-    if (sw) (void)hipSetDevice(p->device);
+    ctrlv_walk::DeviceScope on(p->device);
     free_owned(p);
-    if (sw) (void)hipSetDevice(dev);
   }
   delete p;
   return CTRLV_OK;
@@ -268,10 +266,7 @@ extern "C" int ctrlv_clip_forward(ctrlv_clip_plan* p, const void* pixel_values, 
                                   void* last_hidden_state, void* workspace, size_t workspace_bytes, ctrlv_stream_t stream) {
   CTRLV_CHECK_ARG(p && p->loaded, "clip_forward: plan not loaded");
   CTRLV_CHECK_ARG(pixel_values && image_embeds && workspace, "clip_forward: null pointer");
-  if (dtype < 0 || dtype > 2) {
-    ctrlv_set_error("clip_forward: dtype code %d (0 fp32, 1 fp16, 2 bf16)", dtype);
-    return CTRLV_E_BAD_DTYPE;
-  }
+  CTRLV_CHECK_DTYPE(dtype >= 0 && dtype <= 2, "clip_forward: dtype code %d (0 fp32, 1 fp16, 2 bf16)", dtype);
   CTRLV_CHECK_SHAPE(n_img >= 1 && n_img <= 65535, "clip_forward: n_img=%d must be in [1, 65535]", n_img);
   CTRLV_CHECK_ARG(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)image_embeds & 15) == 0 && ((uintptr_t)last_hidden_state & 15) == 0,
                   "clip_forward: workspace must be 256-byte aligned, outputs 16-byte aligned");

@@ -379,6 +379,13 @@ const ctrlv_vae_config* ctrlv_vae_plan_info(const ctrlv_vae_plan* p, int* device
       return CTRLV_E_BAD_SHAPE;                     \
     }                                               \
   } while (0)
+#define CTRLV_CHECK_DTYPE(cond, ...)                \
+  do {                                              \
+    if (!(cond)) {                                  \
+      ctrlv_set_error(__VA_ARGS__);                 \
+      return CTRLV_E_BAD_DTYPE;                     \
+    }                                               \
+  } while (0)
 #define CTRLV_HIP_TRY(expr)                                                             \
   do {                                                                                  \
     hipError_t e__ = (expr);                                                            \

@@ -84,10 +84,7 @@ int validate(const ctrlv_pipeline* p, const ctrlv_clip_request* r, Geo* g) {
   if (r->cond) {
     CTRLV_CHECK_SHAPE(r->cond_channels == 3 || r->cond_channels == vc->latent_channels,
                       "pipeline: cond_channels=%d must be 3 (pixels) or %d (latents)", r->cond_channels, vc->latent_channels);
-    if (r->cond_dtype < 0 || r->cond_dtype > 2) {
-      ctrlv_set_error("pipeline: cond_dtype code %d (0 fp32, 1 fp16, 2 bf16)", r->cond_dtype);
-      return CTRLV_E_BAD_DTYPE;
-    }
+    CTRLV_CHECK_DTYPE(r->cond_dtype >= 0 && r->cond_dtype <= 2, "pipeline: cond_dtype code %d (0 fp32, 1 fp16, 2 bf16)", r->cond_dtype);
   }
   CTRLV_CHECK_SHAPE(r->num_steps >= 1 && r->num_steps <= kMaxSteps, "pipeline: num_steps=%d must be in [1, %d]", r->num_steps,
                     kMaxSteps);

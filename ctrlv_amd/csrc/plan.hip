@@ -14,11 +14,16 @@
 #include <string>
 #include <vector>
 
+#include "plan_walk.h"
 #include "weight_loader.h"
 
 namespace {
 
 using ctrlv_load::WeightLoader;
+using ctrlv_walk::conv2d;
+using ctrlv_walk::conv_t;
+using ctrlv_walk::DeviceScope;
+using ctrlv_walk::resid;
 using Linear = ctrlv_load::PackedLinear;
 using Norm = ctrlv_load::NormParams;
 
@@ -285,14 +290,37 @@ struct Trk {
   el_t* hi = nullptr;
   lo_t* lo = nullptr;        // one byte per element (e5m2: common.h lo_t)
 };
-struct Ctx {
-  ctrlv_plan* p;
+// The profile record of one launch (or launch group) of the walk: its family and algorithmic work.  family < 0: none (the
+// layout kernels and copies around the model's inputs and outputs).
+struct Prof { int family = -1; double flops = 0, bytes = 0; int M = 0, N = 0, K = 0, flags = 0; };
+// While the plan is profiling: events on the launch stream before / after what runs in this scope.
+struct ProfScope {
+  ctrlv_plan* p = nullptr;
   hipStream_t st;
-  bool dry;                  // measuring pass for ctrlv_plan_workspace_bytes: no launches, no dereferences
+  size_t idx = 0;
+  ProfScope(ctrlv_plan* plan, hipStream_t st_, const Prof& w) : st(st_) {
+    if (w.family < 0 || !plan->profiling) return;
+    ctrlv_plan::ProfRec pr;
+    memset(&pr.r, 0, sizeof(pr.r));
+    pr.r.family = w.family; pr.r.M = w.M; pr.r.N = w.N; pr.r.K = w.K; pr.r.flags = w.flags; pr.r.flops = w.flops; pr.r.bytes = w.bytes;
+    if (hipEventCreate(&pr.e0) != hipSuccess || hipEventCreate(&pr.e1) != hipSuccess) return;
+    (void)hipEventRecord(pr.e0, st);
+    p = plan;
+    idx = p->prof.size();
+    p->prof.push_back(pr);
+  }
+  ~ProfScope() {
+    if (p) (void)hipEventRecord(p->prof[idx].e1, st);
+  }
+};
+struct Ctx : ctrlv_walk::LaunchGate {      // dry: the measuring pass of ctrlv_plan_workspace_bytes (no launches, no dereferences)
+  ctrlv_plan* p;
   char* base;
   size_t cap, off = 0, peak = 0;
   bool overflow = false;
   int B, F;
+  Ctx(ctrlv_plan* p_, hipStream_t st_, bool dry_, char* base_, size_t cap_, int B_, int F_)
+      : LaunchGate{st_, dry_}, p(p_), base(base_), cap(cap_), B(B_), F(F_) {}
   float* temb = nullptr; int ldtemb = 0;
   float* xattn = nullptr; int ldx = 0;
   bool quirk = false;
@@ -305,8 +333,22 @@ struct Ctx {
     const size_t o = off;
     off += a;
     if (off > peak) peak = off;
-    if (!dry && off > cap) overflow = true;
+    if (off > cap) overflow = true;
     return base + o;
+  }
+  // EVERY launch of the walk goes through here.  Measuring walk: nothing happens.  Live walk: `fn` runs between the events of
+  // its profile record.  The refusal is a second line of defence that no entry point can reach: check_workspace has sized
+  // the workspace with this same walk, whose peak bounds the live walk's, before anything was launched.
+  template <class Fn>
+  int launch(const Prof& work, Fn&& fn) {
+    return run([&]() -> int {
+      if (overflow) {
+        ctrlv_set_error("plan forward: workspace too small (need >= %zu bytes)", peak);
+        return CTRLV_E_WORKSPACE;
+      }
+      ProfScope ps(p, st, work);
+      return fn();
+    });
   }
   el_t* rows(long m, int c) { return (el_t*)alloc((size_t)m * c * 2); }
   Trk trunk(long m, int c) {          // a trunk tensor: one plane, or hi + lo in trunk mode 1
@@ -319,41 +361,30 @@ struct Ctx {
   void release(size_t m) { off = m; }
 };
 
-// One launch (or launch group) of the walk under the profiler: events on the launch stream before / after it.
-struct ProfScope {
-  ctrlv_plan* p = nullptr;
-  hipStream_t st;
-  size_t idx = 0;
-  ProfScope(Ctx& c, int family, double flops, double bytes, int M = 0, int N = 0, int K = 0, int flags = 0) : st(c.st) {
-    if (c.dry || !c.p->profiling) return;
-    ctrlv_plan::ProfRec pr;
-    memset(&pr.r, 0, sizeof(pr.r));
-    pr.r.family = family; pr.r.M = M; pr.r.N = N; pr.r.K = K; pr.r.flags = flags; pr.r.flops = flops; pr.r.bytes = bytes;
-    if (hipEventCreate(&pr.e0) != hipSuccess || hipEventCreate(&pr.e1) != hipSuccess) return;
-    (void)hipEventRecord(pr.e0, st);
-    p = c.p;
-    idx = p->prof.size();
-    p->prof.push_back(pr);
-  }
-  ~ProfScope() {
-    if (p) (void)hipEventRecord(p->prof[idx].e1, st);
-  }
-};
 // algorithmic work of a gather-GEMM launch (the accounting of ops.py: 2 MAC per output element and K step; operands once)
-void gemm_work(const ctrlv_gemm_desc& d, int* fam, double* flops, double* bytes) {
-  *fam = d.mode == 1 ? CTRLV_FAM_GEMM_CONV3X3 : (d.mode == 2 ? CTRLV_FAM_GEMM_CONV_TEMPORAL : CTRLV_FAM_GEMM_LINEAR);
+Prof gemm_work(const ctrlv_gemm_desc& d) {
+  Prof w;
+  w.family = d.mode == 1 ? CTRLV_FAM_GEMM_CONV3X3 : (d.mode == 2 ? CTRLV_FAM_GEMM_CONV_TEMPORAL : CTRLV_FAM_GEMM_LINEAR);
   const double n_alg = d.geglu ? d.N : (d.N < d.n_store ? d.N : d.n_store);
   const double n_out = d.geglu ? (d.n_store < d.N / 2 ? d.n_store : d.N / 2) : d.n_store;
-  const double K = (double)(d.mode == 1 && d.up == 2 ? 4 : d.taps) * d.Cin;       // (phase form: 2x2 taps per output pixel)
-  *flops = 2.0 * d.M * n_alg * K;
-  *bytes = (double)d.M * d.Cin * 2 + (double)d.M * n_out * ((d.out_f32 & 1) ? 4 : 2) + (double)d.N * K * 2 * (d.mode == 1 && d.up == 2 ? 4 : 1) +
-           (d.R1 ? (double)d.M * n_out * 2 : 0) + (d.R2 ? (double)d.M * n_out * 2 : 0) +
-           ((d.R1_lo ? 1 : 0) + (d.R2_lo ? 1 : 0) + (d.out_lo ? 1 : 0)) * (double)d.M * n_out;       // (lo planes: 1 byte)
+  w.K = (d.mode == 1 && d.up == 2 ? 4 : d.taps) * d.Cin;                          // (phase form: 2x2 taps per output pixel)
+  const double K = w.K;
+  w.flops = 2.0 * d.M * n_alg * K;
+  w.bytes = (double)d.M * d.Cin * 2 + (double)d.M * n_out * ((d.out_f32 & 1) ? 4 : 2) + (double)d.N * K * 2 * (d.mode == 1 && d.up == 2 ? 4 : 1) +
+            (d.R1 ? (double)d.M * n_out * 2 : 0) + (d.R2 ? (double)d.M * n_out * 2 : 0) +
+            ((d.R1_lo ? 1 : 0) + (d.R2_lo ? 1 : 0) + (d.out_lo ? 1 : 0)) * (double)d.M * n_out;       // (lo planes: 1 byte)
+  w.M = d.M; w.N = d.N;
+  w.flags = (d.geglu ? 1 : 0) | ((d.R1 ? 1 : 0) + (d.R2 ? 1 : 0)) << 1 | d.vmode << 3;
+  return w;
 }
 // residual operand / output of a GEMM from a trunk tensor
 inline void set_r1(ctrlv_gemm_desc& d, const Trk& t, int ld) { d.R1 = t.hi; d.R1_lo = t.lo; d.ldr1 = ld; }
 inline void set_r2(ctrlv_gemm_desc& d, const Trk& t, int ld) { d.R2 = t.hi; d.R2_lo = t.lo; d.ldr2 = ld; }
 inline void set_out(ctrlv_gemm_desc& d, const Trk& t) { d.out = t.hi; d.out_lo = t.lo; }
+// a GroupNorm's record (algorithmic: 1 read + 1 write); flags 1: its statistics came from the producing GEMM's epilogue
+inline Prof gn_work(int n_img, int S, int C, int flags) {
+  return {CTRLV_FAM_GROUPNORM, 0.0, 2.0 * 2 * n_img * (double)S * C, n_img * S, C, 0, flags};
+}
 
 int gemm(Ctx& c, const ctrlv_gemm_desc& d0) {
   // split contraction of the small-image long-K convs (gemm.hip splitk_plan): its scratch comes from the arena for the
@@ -362,14 +393,7 @@ int gemm(Ctx& c, const ctrlv_gemm_desc& d0) {
   const size_t mk = c.mark();
   const size_t ws = ctrlv_gemm_splitk_ws_bytes(&d);
   if (ws) d.splitk_ws = c.alloc(ws);
-  int rc = CTRLV_OK;
-  if (!c.dry) {
-    if (c.overflow) { ctrlv_set_error("plan forward: workspace too small (need >= %zu bytes)", c.peak); return CTRLV_E_BAD_ARG; }
-    int fam; double fl, by;
-    gemm_work(d, &fam, &fl, &by);
-    ProfScope ps(c, fam, fl, by, d.M, d.N, (d.mode == 1 && d.up == 2 ? 4 : d.taps) * d.Cin, (d.geglu ? 1 : 0) | ((d.R1 ? 1 : 0) + (d.R2 ? 1 : 0)) << 1 | d.vmode << 3);
-    rc = ctrlv_gemm(&d, c.st);
-  }
+  const int rc = c.launch(gemm_work(d), [&] { return ctrlv_gemm(&d, c.st); });
   c.release(mk);
   return rc;
 }
@@ -379,14 +403,10 @@ int groupnorm(Ctx& c, const Trk& x, const Trk& x2, int c_split, int n_img, int S
   if (chunks < 0) return chunks;
   const size_t m = c.mark();
   float* part = (float*)c.alloc(((size_t)n_img * chunks + n_img / ips) * 64 * 4);
-  int rc = CTRLV_OK;
-  if (!c.dry) {
-    if (c.overflow) { ctrlv_set_error("plan forward: workspace too small (need >= %zu bytes)", c.peak); return CTRLV_E_BAD_ARG; }
-    ProfScope ps(c, CTRLV_FAM_GROUPNORM, 0.0, 2.0 * 2 * n_img * (double)S * C, n_img * S, C);   // algorithmic: 1 read + 1 write
-    rc = ctrlv_groupnorm_stats_split(x.hi, x.lo, x2.hi, x2.lo, c_split, n_img, S, C, ips, eps, part, c.st);
-    if (rc == CTRLV_OK)
-      rc = ctrlv_groupnorm_apply_split(x.hi, x.lo, x2.hi, x2.lo, c_split, n_img, S, C, ips, part, nm.g, nm.b, silu, y, c.st);
-  }
+  const int rc = c.launch(gn_work(n_img, S, C, 0), [&]() -> int {
+    CTRLV_TRY(ctrlv_groupnorm_stats_split(x.hi, x.lo, x2.hi, x2.lo, c_split, n_img, S, C, ips, eps, part, c.st));
+    return ctrlv_groupnorm_apply_split(x.hi, x.lo, x2.hi, x2.lo, c_split, n_img, S, C, ips, part, nm.g, nm.b, silu, y, c.st);
+  });
   c.release(m);          // stream order keeps the scratch alive until the apply pass has read it
   return rc;
 }
@@ -402,14 +422,13 @@ int gemm_groupnorm(Ctx& c, ctrlv_gemm_desc d, int n_img, int S, int C, int ips, 
   }
   const size_t m = c.mark();
   float* part = (float*)c.alloc(((size_t)n_img * (S / 64) + n_img / ips) * 64 * 4);
-  int rc = CTRLV_OK;
-  if (!c.dry && ctrlv_gemm_gn_partials_serves(&d)) {
+  if (!c.dry && ctrlv_gemm_gn_partials_serves(&d)) {      // (the predicate reads the operand pointers: live walk only)
     d.gn_partials = part;
-    rc = gemm(c, d);
-    if (rc == CTRLV_OK) {
-      ProfScope ps(c, CTRLV_FAM_GROUPNORM, 0.0, 2.0 * 2 * n_img * (double)S * C, n_img * S, C, 1);   // flags 1: fused statistics
-      rc = ctrlv_groupnorm_from_partials_split(d.out, d.out_lo, n_img, S, C, ips, eps, part, nm.g, nm.b, silu, y, c.st);
-    }
+    int rc = gemm(c, d);
+    if (rc == CTRLV_OK)
+      rc = c.launch(gn_work(n_img, S, C, 1), [&] {
+        return ctrlv_groupnorm_from_partials_split(d.out, d.out_lo, n_img, S, C, ips, eps, part, nm.g, nm.b, silu, y, c.st);
+      });
     c.release(m);
     return rc;
   }
@@ -419,9 +438,8 @@ int gemm_groupnorm(Ctx& c, ctrlv_gemm_desc d, int n_img, int S, int C, int ips, 
 }
 int layernorm(Ctx& c, const Trk& x, int M, int C, const Norm& nm, el_t* y, const float* V = nullptr, int vdiv = 1,
               int vmod = 1 << 30, int ldv = 0) {
-  if (c.dry) return CTRLV_OK;
-  ProfScope ps(c, CTRLV_FAM_LAYERNORM, 0.0, 2.0 * 2 * (double)M * C, M, C);
-  return ctrlv_layernorm_split(x.hi, x.lo, M, C, nm.g, nm.b, 1e-5f, V, vdiv, vmod, ldv, y, c.st);
+  return c.launch({CTRLV_FAM_LAYERNORM, 0.0, 2.0 * 2 * (double)M * C, M, C},
+                  [&] { return ctrlv_layernorm_split(x.hi, x.lo, M, C, nm.g, nm.b, 1e-5f, V, vdiv, vmod, ldv, y, c.st); });
 }
 
 // ---- SpatioTemporalResBlock (blocks.py::SpatioTemporalResBlock.run)
@@ -444,7 +462,7 @@ int run_res(Ctx& c, const ResBlock& r, const Trk& x, const Trk& x2, int c1, int 
   el_t* hn = nullptr;
   {
     ctrlv_gemm_desc d = ctrlv_linear_desc(xn, cin, r.c1, h, cout, (int)M, cout, cin, cout);
-    d.taps = 9; d.mode = 1; d.H = H; d.Wd = W; d.Ho = H; d.Wo = W; d.stride = 1; d.up = 0;
+    conv2d(d, H, W, H, W);
     d.V = c.temb + r.temb_off[0]; d.ldv = c.ldtemb; d.vmode = 1; d.vdiv = F * S;
     hn = c.rows(M, cout);
     CTRLV_TRY(gemm_groupnorm(c, d, N, S, cout, 1, r.n2, r.eps, 1, hn));
@@ -463,23 +481,24 @@ int run_res(Ctx& c, const ResBlock& r, const Trk& x, const Trk& x2, int c1, int 
   const Trk xs = c.trunk(M, cout);
   {
     ctrlv_gemm_desc d = ctrlv_linear_desc(hn, cout, r.c2, xs.hi, cout, (int)M, cout, cout, cout);
-    d.taps = 9; d.mode = 1; d.H = H; d.Wd = W; d.Ho = H; d.Wo = W; d.stride = 1;
+    conv2d(d, H, W, H, W);
     set_out(d, xs);
     set_r1(d, res, ldres);
     CTRLV_TRY(gemm_groupnorm(c, d, N, S, cout, F, r.tn1, r.eps, 1, hn));
   }
   {
     ctrlv_gemm_desc d = ctrlv_linear_desc(hn, cout, r.tc1, h, cout, (int)M, cout, cout, cout);
-    d.taps = 3; d.mode = 2; d.F = F; d.S = S;
+    conv_t(d, F, S);
     d.V = c.temb + r.temb_off[1]; d.ldv = c.ldtemb; d.vmode = 1; d.vdiv = F * S;
     CTRLV_TRY(gemm_groupnorm(c, d, N, S, cout, F, r.tn2, r.eps, 1, hn));
   }
   {   // AlphaBlender: a*xs + (1-a)*(xs + conv2) = xs + (1-a)*conv2
     ctrlv_gemm_desc d = ctrlv_linear_desc(hn, cout, r.tc2, out.hi, cout, (int)M, cout, cout, cout);
-    d.taps = 3; d.mode = 2; d.F = F; d.S = S;
+    conv_t(d, F, S);
     d.s_acc = (float)(1.0 - r.alpha);
     set_out(d, out);
     set_r1(d, xs, cout);
+    // (live walk only: the predicate reads the operand pointers, so gn_cross_valid is never set on the measuring walk)
     if (feeds_norm && S % 64 == 0 && !c.dry && ctrlv_gemm_gn_partials_serves(&d)) {
       d.gn_partials = c.gn_cross;       // the transformer behind this block opens with a GroupNorm of `out`
       c.gn_cross_valid = true;
@@ -499,18 +518,16 @@ int frame_embedding(Ctx& c, const Transformer& t, int F, float* e) {
   el_t* te = c.rows(F, kp);
   el_t* hh = c.rows(F, 4 * C);
   el_t* tmp = kp != C ? c.rows(F, C) : nullptr;
-  if (!c.dry) {
-    if (c.overflow) { ctrlv_set_error("plan forward: workspace too small"); return CTRLV_E_BAD_ARG; }
+  CTRLV_TRY(c.launch({}, [&]() -> int {
     hipLaunchKernelGGL(arange_kernel, dim3((F + 63) / 64), dim3(64), 0, c.st, ar, F);
     CTRLV_LAUNCH_CHECK();
-    if (kp != C) {       // K zero padding (tiny configs only): sinusoid into a compact buffer, then strided copy
-      CTRLV_HIP_TRY(hipMemsetAsync(te, 0, (size_t)F * kp * 2, c.st));
-      CTRLV_TRY(ctrlv_timestep_embedding(ar, F, C, tmp, c.st));
-      CTRLV_HIP_TRY(hipMemcpy2DAsync(te, (size_t)kp * 2, tmp, (size_t)C * 2, (size_t)C * 2, F, hipMemcpyDeviceToDevice, c.st));
-    } else {
-      CTRLV_TRY(ctrlv_timestep_embedding(ar, F, C, te, c.st));
-    }
-  }
+    if (kp == C) return ctrlv_timestep_embedding(ar, F, C, te, c.st);
+    // K zero padding (tiny configs only): sinusoid into a compact buffer, then strided copy
+    CTRLV_HIP_TRY(hipMemsetAsync(te, 0, (size_t)F * kp * 2, c.st));
+    CTRLV_TRY(ctrlv_timestep_embedding(ar, F, C, tmp, c.st));
+    CTRLV_HIP_TRY(hipMemcpy2DAsync(te, (size_t)kp * 2, tmp, (size_t)C * 2, (size_t)C * 2, F, hipMemcpyDeviceToDevice, c.st));
+    return CTRLV_OK;
+  }));
   {
     ctrlv_gemm_desc d = ctrlv_linear_desc(te, kp, t.tpe1, hh, 4 * C, F, t.tpe1.n, kp, 4 * C);
     d.act = 1;
@@ -531,12 +548,10 @@ int ff_pair(Ctx& c, const FeedFwd& f, ctrlv_gemm_desc proj, ctrlv_gemm_desc outd
   // C = 320: one fused launch, the 4C-wide intermediate stays on chip (ff_fused.hip): 234.5 -> 231.3 ms per step (three
   // alternations on one device).  CTRLV_FF_FUSED=0: the two launches.
   if (ctrlv_debug().ff_fused && f.w1f && ctrlv_ff_fused_serves(&outd, proj.lda)) {
-    if (c.dry) return CTRLV_OK;
-    if (c.overflow) { ctrlv_set_error("plan forward: workspace too small (need >= %zu bytes)", c.peak); return CTRLV_E_BAD_ARG; }
-    ProfScope ps(c, CTRLV_FAM_GEMM_LINEAR, 2.0 * outd.M * 320.0 * (2560 + 1280),
-                 (double)outd.M * 320 * (2 * (2 + (outd.R1 ? 1 : 0) + (outd.R2 ? 1 : 0)) + (outd.R1_lo ? 1 : 0) + (outd.R2_lo ? 1 : 0) +
-                                         (outd.out_lo ? 1 : 0)), outd.M, 320, 320, 0x100);
-    return ctrlv_ff_fused(proj.A, proj.lda, f.w1f, f.w2f, &outd, c.st);
+    return c.launch({CTRLV_FAM_GEMM_LINEAR, 2.0 * outd.M * 320.0 * (2560 + 1280),
+                     (double)outd.M * 320 * (2 * (2 + (outd.R1 ? 1 : 0) + (outd.R2 ? 1 : 0)) + (outd.R1_lo ? 1 : 0) + (outd.R2_lo ? 1 : 0) +
+                                             (outd.out_lo ? 1 : 0)), outd.M, 320, 320, 0x100},
+                    [&] { return ctrlv_ff_fused(proj.A, proj.lda, f.w1f, f.w2f, &outd, c.st); });
   }
   if (*u == nullptr) *u = c.rows(proj.M, 4 * C);
   proj.out = *u;
@@ -553,11 +568,10 @@ int ff_pair(Ctx& c, const FeedFwd& f, ctrlv_gemm_desc proj, ctrlv_gemm_desc outd
 int ln_ff(Ctx& c, const FeedFwd& f, const Norm& nm, const Trk& xraw, const float* lnV, int lnvdiv, int lnvmod, int lnldv,
           el_t* tt, const ctrlv_gemm_desc& proj, const ctrlv_gemm_desc& outd, int C, el_t** u) {
   if (ctrlv_debug().ff_fused && ctrlv_debug().ff_ln && f.w1f && !xraw.lo && ctrlv_ff_fused_serves(&outd, C)) {
-    if (c.dry) return CTRLV_OK;
-    if (c.overflow) { ctrlv_set_error("plan forward: workspace too small (need >= %zu bytes)", c.peak); return CTRLV_E_BAD_ARG; }
-    ProfScope ps(c, CTRLV_FAM_GEMM_LINEAR, 2.0 * outd.M * 320.0 * (2560 + 1280),
-                 (double)outd.M * 320 * 2 * (2 + (outd.R1 ? 1 : 0) + (outd.R2 ? 1 : 0)), outd.M, 320, 320, 0x300);
-    return ctrlv_ff_fused_ln(xraw.hi, C, nm.g, nm.b, 1e-5f, lnV, lnvdiv, lnvmod, lnldv, f.w1f, f.w2f, &outd, c.st);
+    return c.launch({CTRLV_FAM_GEMM_LINEAR, 2.0 * outd.M * 320.0 * (2560 + 1280),
+                     (double)outd.M * 320 * 2 * (2 + (outd.R1 ? 1 : 0) + (outd.R2 ? 1 : 0)), outd.M, 320, 320, 0x300}, [&] {
+      return ctrlv_ff_fused_ln(xraw.hi, C, nm.g, nm.b, 1e-5f, lnV, lnvdiv, lnvmod, lnldv, f.w1f, f.w2f, &outd, c.st);
+    });
   }
   if (c.p->ff_precision == 1 && f.proj8 && f.out8 && !xraw.lo) {
     // FF precision 1: LayerNorm + row quantisation in one pass, the GEGLU projection on e4m3 operands, the
@@ -571,30 +585,23 @@ int ln_ff(Ctx& c, const FeedFwd& f, const Norm& nm, const Trk& xraw, const float
       const long M = proj.M;
       uint8_t* q = (uint8_t*)c.alloc((size_t)M * 4 * C);       // codes of the normalised rows (C wide), then of u (4C wide)
       float* qs = (float*)c.alloc((size_t)M * 4);
-      int rc = CTRLV_OK;
-      if (!c.dry) {
-        if (c.overflow) { ctrlv_set_error("plan forward: workspace too small (need >= %zu bytes)", c.peak); return CTRLV_E_BAD_ARG; }
-        p8.A = q; p8.lda = C; p8.out = *u;
-        o8.A = q; o8.lda = 4 * C;
-        {
-          ProfScope ps(c, CTRLV_FAM_LAYERNORM, 0.0, 3.0 * (double)M * C, (int)M, C, 0, 0x400);
-          rc = ctrlv_quant_rows_f8(xraw.hi, (int)M, C, C, nm.g, nm.b, 1e-5f, lnV, lnvdiv, lnvmod, lnldv, q, C, qs, c.st);
-        }
-        if (rc == CTRLV_OK) {
-          ProfScope ps(c, CTRLV_FAM_GEMM_LINEAR, 2.0 * M * 8.0 * C * C, (double)M * C + (double)M * 4 * C * 2 + 8.0 * C * C, (int)M, 8 * C, C, 0x401);
-          rc = ctrlv_gemm_f8(&p8, qs, f.proj8_s, c.st);
-        }
-        if (rc == CTRLV_OK) {
-          ProfScope ps(c, CTRLV_FAM_LAYERNORM, 0.0, 3.0 * (double)M * 4 * C, (int)M, 4 * C, 0, 0x400);
-          rc = ctrlv_quant_rows_f8(*u, (int)M, 4 * C, 4 * C, nullptr, nullptr, 0.f, nullptr, 1, 1, 0, q, 4 * C, qs, c.st);
-        }
-        if (rc == CTRLV_OK) {
-          ProfScope ps(c, CTRLV_FAM_GEMM_LINEAR, 2.0 * M * 4.0 * C * C,
+      p8.A = q; p8.lda = C; p8.out = *u;
+      o8.A = q; o8.lda = 4 * C;
+      int rc = c.launch({CTRLV_FAM_LAYERNORM, 0.0, 3.0 * (double)M * C, (int)M, C, 0, 0x400}, [&] {
+        return ctrlv_quant_rows_f8(xraw.hi, (int)M, C, C, nm.g, nm.b, 1e-5f, lnV, lnvdiv, lnvmod, lnldv, q, C, qs, c.st);
+      });
+      if (rc == CTRLV_OK)
+        rc = c.launch({CTRLV_FAM_GEMM_LINEAR, 2.0 * M * 8.0 * C * C, (double)M * C + (double)M * 4 * C * 2 + 8.0 * C * C, (int)M, 8 * C, C, 0x401},
+                      [&] { return ctrlv_gemm_f8(&p8, qs, f.proj8_s, c.st); });
+      if (rc == CTRLV_OK)
+        rc = c.launch({CTRLV_FAM_LAYERNORM, 0.0, 3.0 * (double)M * 4 * C, (int)M, 4 * C, 0, 0x400}, [&] {
+          return ctrlv_quant_rows_f8(*u, (int)M, 4 * C, 4 * C, nullptr, nullptr, 0.f, nullptr, 1, 1, 0, q, 4 * C, qs, c.st);
+        });
+      if (rc == CTRLV_OK)
+        rc = c.launch({CTRLV_FAM_GEMM_LINEAR, 2.0 * M * 4.0 * C * C,
                        (double)M * 4 * C + (double)M * C * 2 * (1 + (o8.R1 ? 1 : 0) + (o8.R2 ? 1 : 0)) + 4.0 * C * C, (int)M, C, 4 * C,
-                       0x400 | ((o8.R1 ? 1 : 0) + (o8.R2 ? 1 : 0)) << 1 | o8.vmode << 3);
-          rc = ctrlv_gemm_f8(&o8, qs, f.out8_s, c.st);
-        }
-      }
+                       0x400 | ((o8.R1 ? 1 : 0) + (o8.R2 ? 1 : 0)) << 1 | o8.vmode << 3},
+                      [&] { return ctrlv_gemm_f8(&o8, qs, f.out8_s, c.st); });
       c.release(mk);
       return rc;
     }
@@ -616,10 +623,11 @@ int run_tr(Ctx& c, const Transformer& t, const Trk& x, int H, int W, Trk* out_) 
     emb = e;
   }
   el_t* tt = c.rows(M, C);
-  if (c.gn_cross_valid && !c.dry) {     // statistics from the res block's last GEMM (run_res, feeds_norm)
+  if (c.gn_cross_valid) {     // statistics from the res block's last GEMM (run_res, feeds_norm: set on the live walk only)
     c.gn_cross_valid = false;
-    ProfScope ps(c, CTRLV_FAM_GROUPNORM, 0.0, 2.0 * 2 * N * (double)S * C, N * S, C, 1);
-    CTRLV_TRY(ctrlv_groupnorm_from_partials_split(x.hi, x.lo, N, S, C, 1, 1e-6f, c.gn_cross, t.gn.g, t.gn.b, 0, tt, c.st));
+    CTRLV_TRY(c.launch(gn_work(N, S, C, 1), [&] {
+      return ctrlv_groupnorm_from_partials_split(x.hi, x.lo, N, S, C, 1, 1e-6f, c.gn_cross, t.gn.g, t.gn.b, 0, tt, c.st);
+    }));
   } else {
     CTRLV_TRY(groupnorm(c, x, Trk{}, 0, N, S, C, 1, t.gn, 1e-6f, 0, tt));
   }
@@ -638,10 +646,8 @@ int run_tr(Ctx& c, const Transformer& t, const Trk& x, int H, int W, Trk* out_) 
     CTRLV_TRY(gemm(c, d));
   }
   el_t* a = c.rows(M, C);
-  if (!c.dry) {
-    ProfScope ps(c, CTRLV_FAM_ATTENTION_SPATIAL, 4.0 * N * (C / 64) * (double)S * S * 64, 2.0 * 4 * N * (double)S * C, N, S, C);
-    CTRLV_TRY(ctrlv_attention_spatial_prescaled(qkv, a, N, S, C, c.st));
-  }
+  CTRLV_TRY(c.launch({CTRLV_FAM_ATTENTION_SPATIAL, 4.0 * N * (C / 64) * (double)S * S * 64, 2.0 * 4 * N * (double)S * C, N, S, C},
+                     [&] { return ctrlv_attention_spatial_prescaled(qkv, a, N, S, C, c.st); }));
   const Trk h1 = c.trunk(M, C);
   {   // attn2 with one key == to_out(to_v(ehs[b])) for every query: a per-clip row vector
     ctrlv_gemm_desc d = ctrlv_linear_desc(a, C, t.s_o, h1.hi, C, (int)M, C, C, C);
@@ -703,19 +709,13 @@ int run_tr(Ctx& c, const Transformer& t, const Trk& x, int H, int W, Trk* out_) 
       CTRLV_TRY(layernorm(c, t.t_wf ? Trk{g0.hi, nullptr} : g0, (int)M, C, t.t_ln1, tt));   // (C = 320: hi, as the prologue)
     }
     if (fused) {
-      if (!c.dry) {
-        if (c.overflow) { ctrlv_set_error("plan forward: workspace too small (need >= %zu bytes)", c.peak); return CTRLV_E_BAD_ARG; }
-        ProfScope ps(c, CTRLV_FAM_GEMM_TEMPORAL_BLOCK, 2.0 * M * C * 4.0 * C + 4.0 * B * S * (C / 64) * (double)F * F * 64,
-                     (double)M * C * (2 * (ln_in ? 2 : 3) + (g0.lo ? 1 : 0) + (g1.lo ? 1 : 0)), (int)M, 4 * C, C, ln_in ? 1 : 0);
-        CTRLV_TRY(ctrlv_temporal_fused(&fd, c.st));
-      }
+      CTRLV_TRY(c.launch({CTRLV_FAM_GEMM_TEMPORAL_BLOCK, 2.0 * M * C * 4.0 * C + 4.0 * B * S * (C / 64) * (double)F * F * 64,
+                          (double)M * C * (2 * (ln_in ? 2 : 3) + (g0.lo ? 1 : 0) + (g1.lo ? 1 : 0)), (int)M, 4 * C, C, ln_in ? 1 : 0},
+                         [&] { return ctrlv_temporal_fused(&fd, c.st); }));
     } else {
       CTRLV_TRY(gemm(c, ctrlv_linear_desc(tt, C, t.t_qkv, qkv, 3 * C, (int)M, 3 * C, C, 3 * C)));
-      if (!c.dry) {
-        ProfScope ps(c, CTRLV_FAM_ATTENTION_TEMPORAL, 4.0 * B * S * (C / 64) * (double)F * F * 64, 2.0 * 4 * B * F * (double)S * C, B * S,
-                     F, C);
-        CTRLV_TRY(ctrlv_attention_temporal(qkv, a, B, F, S, C, c.st));
-      }
+      CTRLV_TRY(c.launch({CTRLV_FAM_ATTENTION_TEMPORAL, 4.0 * B * S * (C / 64) * (double)F * F * 64, 2.0 * 4 * B * F * (double)S * C, B * S, F, C},
+                         [&] { return ctrlv_attention_temporal(qkv, a, B, F, S, C, c.st); }));
       ctrlv_gemm_desc d = ctrlv_linear_desc(a, C, t.t_o, g1.hi, C, (int)M, C, C, C);
       set_out(d, g1);
       set_r1(d, g0, C);
@@ -753,7 +753,7 @@ int run_resample(Ctx& c, const Resample& r, const Trk& x, int H, int W, bool up,
   const Trk out = c.trunk(M, r.C);
   ctrlv_gemm_desc d = ctrlv_linear_desc(x.hi, r.C, r.conv, out.hi, r.C, (int)M, r.C, r.C, r.C);
   set_out(d, out);
-  d.taps = 9; d.mode = 1; d.H = H; d.Wd = W; d.Ho = Ho; d.Wo = Wo; d.stride = up ? 1 : 2; d.up = up ? 1 : 0;
+  conv2d(d, H, W, Ho, Wo, up ? 1 : 2, up ? 1 : 0);
   // the up-sampler in phase form (four 2x2 convs, 4/9 of the multiply-adds) where the LAYER's shape is served
   if (up && r.wph && ctrlv_gemm_up_phase_serves(&d)) { d.up = 2; d.W = r.wph; }
   CTRLV_TRY(gemm(c, d));
@@ -784,8 +784,7 @@ int run_context(Ctx& c, int dtype, const float* timestep, int n_t, const void* e
   el_t* emb_s = c.rows(B, ted);
   c.ldtemb = p->temb.n;
   c.temb = (float*)c.alloc((size_t)B * c.ldtemb * 4);
-  if (!c.dry) {
-    if (c.overflow) { ctrlv_set_error("plan forward: workspace too small (need >= %zu bytes)", c.peak); return CTRLV_E_BAD_ARG; }
+  CTRLV_TRY(c.launch({}, [&]() -> int {
     hipLaunchKernelGGL(expand_f32_kernel, dim3((B + 63) / 64), dim3(64), 0, c.st, timestep, n_t, t32, B);
     CTRLV_LAUNCH_CHECK();
     if (kt != boc0) {
@@ -804,7 +803,8 @@ int run_context(Ctx& c, int dtype, const float* timestep, int n_t, const void* e
     } else {
       CTRLV_TRY(ctrlv_timestep_embedding(ids32, B * n_ids, add_dim, ae, c.st));
     }
-  }
+    return CTRLV_OK;
+  }));
   // (tile 11: per-clip rows -- one kernel for these launches whatever B is, so a clip's conditioning vectors have the same
   //  bits alone and in any batch: csrc/gemm.hip gemv_small_kernel)
   constexpr int kClipRows = 11;
@@ -813,7 +813,7 @@ int run_context(Ctx& c, int dtype, const float* timestep, int n_t, const void* e
   { ctrlv_gemm_desc d = ctrlv_linear_desc(ae, ka, p->ae1, h, ted, B, ted, ka, ted); d.act = 1; d.tile = kClipRows; CTRLV_TRY(gemm(c, d)); }
   {   // silu(emb + aug_emb): the SiLU in front of every time_emb_proj
     ctrlv_gemm_desc d = ctrlv_linear_desc(h, ted, p->ae2, emb_s, ted, B, ted, ted, ted);
-    d.R1 = emb_t; d.ldr1 = ted; d.act = 1; d.tile = kClipRows;
+    resid(d, emb_t, ted); d.act = 1; d.tile = kClipRows;
     CTRLV_TRY(gemm(c, d));
   }
   { ctrlv_gemm_desc d = ctrlv_linear_desc(emb_s, ted, p->temb, c.temb, c.ldtemb, B, p->temb.n, ted, c.ldtemb); d.out_f32 = 1; d.tile = kClipRows; CTRLV_TRY(gemm(c, d)); }
@@ -823,11 +823,10 @@ int run_context(Ctx& c, int dtype, const float* timestep, int n_t, const void* e
     el_t* v_all = c.rows(B, nx);
     c.ldx = nx;
     c.xattn = (float*)c.alloc((size_t)B * nx * 4);
-    if (!c.dry) {
-      if (c.overflow) { ctrlv_set_error("plan forward: workspace too small (need >= %zu bytes)", c.peak); return CTRLV_E_BAD_ARG; }
+    CTRLV_TRY(c.launch({}, [&]() -> int {
       if (kx != dc) CTRLV_HIP_TRY(hipMemsetAsync(e, 0, (size_t)B * kx * 2, c.st));
-      CTRLV_TRY(ctrlv_nchw_to_rows(ehs, dtype, B, dc, 1, e, kx, 0, c.st));      // (B, 1, dc) any dtype -> bf16 rows [B, kx]
-    }
+      return ctrlv_nchw_to_rows(ehs, dtype, B, dc, 1, e, kx, 0, c.st);      // (B, 1, dc) any dtype -> bf16 rows [B, kx]
+    }));
     { ctrlv_gemm_desc d = ctrlv_linear_desc(e, kx, p->xv, v_all, nx, B, nx, kx, nx); d.tile = kClipRows; CTRLV_TRY(gemm(c, d)); }
     for (const CrossOut& xo : p->xouts) {
       ctrlv_gemm_desc d = ctrlv_linear_desc(v_all + xo.off, nx, xo.to_out, c.xattn + xo.off, nx, B, xo.c, xo.c, xo.c);
@@ -847,13 +846,12 @@ int run_input(Ctx& c, int dtype, const void* sample, const void* control, int h,
   el_t* x16 = c.rows(M, p->cin_cp);
   el_t* col = c.rows(M, p->cin_kp);
   const Trk x = c.trunk(M, c0);
-  if (!c.dry) {
-    if (c.overflow) { ctrlv_set_error("plan forward: workspace too small (need >= %zu bytes)", c.peak); return CTRLV_E_BAD_ARG; }
+  CTRLV_TRY(c.launch({}, [&]() -> int {
     CTRLV_HIP_TRY(hipMemsetAsync(x16, 0, (size_t)M * p->cin_cp * 2, c.st));
     CTRLV_TRY(ctrlv_nchw_to_rows(sample, dtype, N, cin, h * w, x16, p->cin_cp, 0, c.st));
     if (control) CTRLV_TRY(ctrlv_nchw_to_rows(control, dtype, N, cin / 2, h * w, x16, p->cin_cp, cin, c.st));
-    CTRLV_TRY(ctrlv_im2col3x3(x16, N, h, w, p->cin_cp, col, p->cin_kp, c.st));
-  }
+    return ctrlv_im2col3x3(x16, N, h, w, p->cin_cp, col, p->cin_kp, c.st);
+  }));
   {
     ctrlv_gemm_desc d = ctrlv_linear_desc(col, p->cin_kp, p->cin, x.hi, c0, (int)M, p->cin.n, p->cin_kp, c0);
     set_out(d, x);
@@ -914,19 +912,18 @@ int unet_forward(ctrlv_plan* p, Ctx& c, const void* sample, int dtype, const flo
     if (t.lo) return ctrlv_axpby_split(t.hi, t.lo, r, 1.0f, 1.0f, t.hi, t.lo, n, c.st);
     return ctrlv_axpby(t.hi, r, 1.0f, 1.0f, t.hi, n, c.st);
   };
+  // (the measuring walk comes without residuals: they need no workspace)
   if (down_res && mid_res) {        // unet_spatio_temporal_condition.py:61,119-127,136-137
-    if (!c.dry) {
-      if (res_event) CTRLV_HIP_TRY(hipStreamWaitEvent(c.st, (hipEvent_t)res_event, 0));
-      for (size_t i = 0; i < taps.size(); ++i) {
-        CTRLV_CHECK_ARG(down_res[i] != nullptr, "unet_forward: down_res[%zu] is null", i);
-        const size_t n = (size_t)N * taps[i].H * taps[i].W * taps[i].C;
-        ProfScope ps(c, CTRLV_FAM_RESIDUAL_ADD, 0.0, 2.0 * 3 * (double)n, (int)(n / taps[i].C), taps[i].C);
-        CTRLV_TRY(add_res(taps[i].x, down_res[i], n));
-      }
-      const size_t nm_ = (size_t)N * H * W * p->cfg.block_out_channels[p->cfg.n_blocks - 1];
-      ProfScope ps(c, CTRLV_FAM_RESIDUAL_ADD, 0.0, 2.0 * 3 * (double)nm_, N * H * W, p->cfg.block_out_channels[p->cfg.n_blocks - 1]);
-      CTRLV_TRY(add_res(x, mid_res, nm_));
+    if (res_event) CTRLV_TRY(c.launch({}, [&]() -> int { CTRLV_HIP_TRY(hipStreamWaitEvent(c.st, (hipEvent_t)res_event, 0)); return CTRLV_OK; }));
+    taps.push_back({x, H, W, p->cfg.block_out_channels[p->cfg.n_blocks - 1]});      // (the mid residual, like the others)
+    for (size_t i = 0; i < taps.size(); ++i) {
+      const void* r = i + 1 < taps.size() ? down_res[i] : mid_res;
+      CTRLV_CHECK_ARG(r != nullptr, "unet_forward: down_res[%zu] is null", i);
+      const size_t n = (size_t)N * taps[i].H * taps[i].W * taps[i].C;
+      CTRLV_TRY(c.launch({CTRLV_FAM_RESIDUAL_ADD, 0.0, 2.0 * 3 * (double)n, (int)(n / taps[i].C), taps[i].C},
+                         [&] { return add_res(taps[i].x, r, n); }));
     }
+    taps.pop_back();
   }
   for (auto& b : p->up) {           // :140-158 -- torch.cat([hidden, skip], dim=1) is read in place (x | x2)
     for (size_t j = 0; j < b.res.size(); ++j) {
@@ -950,11 +947,10 @@ int unet_forward(ctrlv_plan* p, Ctx& c, const void* sample, int dtype, const flo
   el_t* y = c.rows(M, co_p);
   {
     ctrlv_gemm_desc d = ctrlv_linear_desc(xn, c0, p->cout, y, co_p, (int)M, p->cout.n, c0, co_p);
-    d.taps = 9; d.mode = 1; d.H = H; d.Wd = W; d.Ho = H; d.Wo = W; d.stride = 1;
+    conv2d(d, H, W, H, W);
     CTRLV_TRY(gemm(c, d));
   }
-  if (!c.dry) CTRLV_TRY(ctrlv_rows_to_nchw(y, co_p, N, co, H * W, out, dtype, c.st));  // :166
-  return CTRLV_OK;
+  return c.launch({}, [&] { return ctrlv_rows_to_nchw(y, co_p, N, co, H * W, out, dtype, c.st); });  // :166
 }
 
 int controlnet_forward(ctrlv_plan* p, Ctx& c, const void* sample, const void* control, int dtype, const float* timestep,
@@ -971,6 +967,7 @@ int controlnet_forward(ctrlv_plan* p, Ctx& c, const void* sample, const void* co
   for (size_t i = 0; i < taps.size(); ++i) {       // controlnet.py:331-344: zero-conv * conditioning_scale, one GEMM
     const long M = (long)N * taps[i].H * taps[i].W;
     const int C = taps[i].C;
+    // (the measuring walk has no output list to read the pointer from)
     if (!c.dry) CTRLV_CHECK_ARG(out_down && out_down[i], "controlnet_forward: out_down[%zu] is null", i);
     ctrlv_gemm_desc d = ctrlv_linear_desc(taps[i].x.hi, C, p->zc[i], c.dry ? nullptr : out_down[i], C, (int)M, p->zc[i].n, C, C);
     d.s_acc = scale;
@@ -1042,12 +1039,11 @@ extern "C" int ctrlv_plan_create(const ctrlv_model_config* cfg, int device, ctrl
 
 extern "C" int ctrlv_plan_destroy(ctrlv_plan* p) {
   if (!p) return CTRLV_OK;
-  int dev = 0;
-  const bool sw = hipGetDevice(&dev) == hipSuccess && dev != p->device;
-  if (sw) (void)hipSetDevice(p->device);
-  free_owned(p);
-  for (auto& r : p->prof) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
-  if (sw) (void)hipSetDevice(dev);
+  {
+    DeviceScope on(p->device);
+    free_owned(p);
+    for (auto& r : p->prof) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
+  }
   delete p;
   return CTRLV_OK;
 }
@@ -1129,8 +1125,7 @@ extern "C" int ctrlv_plan_load_weights(ctrlv_plan* p, const ctrlv_tensor_desc* t
         if (rc != CTRLV_OK) return;
         rc = L.alloc((size_t)c.num_frames * t.C * 4, (void**)&t.frame_emb, false);
         if (rc != CTRLV_OK) return;
-        Ctx cx{p, L.st, false, (char*)scratch, need + 1024};
-        cx.B = 1; cx.F = c.num_frames;
+        Ctx cx(p, L.st, false, (char*)scratch, need + 1024, 1, c.num_frames);
         rc = frame_embedding(cx, t, c.num_frames, t.frame_emb);
       });
       CTRLV_TRY(rc);
@@ -1168,14 +1163,11 @@ extern "C" int ctrlv_plan_set_ff_precision(ctrlv_plan* p, int mode) {
   if (p->ff_precision == mode) return CTRLV_OK;
   p->ws_cache.clear();                                  // the workspace grows with the codes and scales
   if (mode == 1 && p->loaded) {                         // (not loaded yet: ctrlv_plan_load_weights makes them)
-    int dev = 0;
-    const bool sw = hipGetDevice(&dev) == hipSuccess && dev != p->device;
-    if (sw) CTRLV_HIP_TRY(hipSetDevice(p->device));
+    DeviceScope on(p->device);
+    CTRLV_TRY(on.status());
     int rc = make_f8(p, nullptr);
     if (rc == CTRLV_OK && hipDeviceSynchronize() != hipSuccess) { ctrlv_set_error("plan_set_ff_precision: quantising the weights failed"); rc = CTRLV_E_HIP; }
-    if (rc != CTRLV_OK) free_f8(p);
-    if (sw) (void)hipSetDevice(dev);
-    if (rc != CTRLV_OK) return rc;
+    if (rc != CTRLV_OK) { free_f8(p); return rc; }
   }
   if (mode == 0) free_f8(p);
   p->ff_precision = mode;
@@ -1207,8 +1199,7 @@ extern "C" int ctrlv_plan_residual_shape(ctrlv_plan* p, int idx, int B, int F, i
 
 extern "C" size_t ctrlv_plan_workspace_bytes(ctrlv_plan* p, int B, int F, int H, int W) {
   if (check_common(p, B, F, H, W) != CTRLV_OK) return 0;
-  Ctx c{p, nullptr, true, nullptr, 0};
-  c.B = B; c.F = F;
+  Ctx c(p, nullptr, true, nullptr, 0, B, F);
   const int n_ids = p->cfg.projection_class_embeddings_input_dim / (p->cfg.addition_time_embed_dim > 0 ? p->cfg.addition_time_embed_dim : 1);
   int rc;
   if (p->cfg.kind == 0) {
@@ -1220,8 +1211,10 @@ extern "C" size_t ctrlv_plan_workspace_bytes(ctrlv_plan* p, int B, int F, int H,
   return rc == CTRLV_OK ? c.peak + 256 : 0;
 }
 
-// A too-small workspace is refused BEFORE anything is launched (the walk's own overflow flags are a second line of
-// defence: not every launch helper tests them).  The dry walk's result is cached per (B, F, H, W).
+// A workspace below the measuring walk's answer is refused BEFORE anything is launched.  That answer is an upper bound of
+// what the live walk takes, so the refusal inside Ctx::launch, which every launch passes, never fires behind this one
+// (tests/test_plan_entries_gpu.py runs the forwards in exactly this many bytes).  The dry walk's result is cached per
+// (B, F, H, W).
 static int check_workspace(ctrlv_plan* p, const char* who, int B, int F, int H, int W, size_t have) {
   size_t need = 0;
   for (const auto& e : p->ws_cache)
@@ -1239,23 +1232,32 @@ static int check_workspace(ctrlv_plan* p, const char* who, int B, int F, int H, 
   return CTRLV_OK;
 }
 
+// The common shape of the three forward entries, in the order their refusals always had: the plan and the shape, the plan's
+// kind, the entry's own pointer list (`null_msg`: its refusal, or null), the dtype code, what else the entry refuses
+// (`arg_msg`), the workspace size; then the live walk over the 256-aligned workspace.
+template <class Walk>
+static int forward_entry(ctrlv_plan* p, const char* who, int kind, const char* null_msg, int dtype, const char* arg_msg, int B,
+                         int F, int H, int W, void* workspace, size_t workspace_bytes, ctrlv_stream_t stream, Walk&& walk) {
+  CTRLV_TRY(check_common(p, B, F, H, W));
+  CTRLV_CHECK_ARG(p->cfg.kind == kind, "%s: the plan is a %s", who, kind == 0 ? "ControlNet" : "UNet");
+  CTRLV_CHECK_ARG(null_msg == nullptr, "%s: %s", who, null_msg);
+  CTRLV_CHECK_DTYPE(dtype >= 0 && dtype <= 2, "%s: dtype must be 0 (fp32), 1 (fp16) or 2 (bf16)", who);
+  CTRLV_CHECK_ARG(arg_msg == nullptr, "%s: %s", who, arg_msg);
+  CTRLV_TRY(check_workspace(p, who, B, F, H, W, workspace_bytes));
+  char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  Ctx c(p, (hipStream_t)stream, false, base, workspace_bytes - (size_t)(base - (char*)workspace), B, F);
+  return walk(c);
+}
+
 extern "C" int ctrlv_unet_forward(ctrlv_plan* p, const void* sample, int dtype, const float* timestep, int n_timestep,
                                   const void* ehs, const float* added_time_ids, int n_ids, const void* const* down_res,
                                   const void* mid_res, void* residual_event, void* out, int B, int F, int H, int W,
                                   void* workspace, size_t workspace_bytes, ctrlv_stream_t stream) {
-  CTRLV_TRY(check_common(p, B, F, H, W));
-  CTRLV_CHECK_ARG(p->cfg.kind == 0, "unet_forward: the plan is a ControlNet");
-  CTRLV_CHECK_ARG(sample && timestep && ehs && added_time_ids && out && workspace, "unet_forward: null pointer");
-  if (dtype < 0 || dtype > 2) { ctrlv_set_error("unet_forward: dtype must be 0 (fp32), 1 (fp16) or 2 (bf16)"); return CTRLV_E_BAD_DTYPE; }
-  CTRLV_CHECK_ARG((down_res == nullptr) == (mid_res == nullptr), "unet_forward: pass both down_res and mid_res or neither");
-  CTRLV_TRY(check_workspace(p, "unet_forward", B, F, H, W, workspace_bytes));
-  char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  Ctx c{p, (hipStream_t)stream, false, base, workspace_bytes - (size_t)(base - (char*)workspace)};
-  c.B = B; c.F = F;
-  const int rc = unet_forward(p, c, sample, dtype, timestep, n_timestep, ehs, added_time_ids, n_ids, down_res, mid_res,
-                              residual_event, out, H, W);
-  if (rc == CTRLV_OK && c.overflow) { ctrlv_set_error("unet_forward: workspace too small (need >= %zu bytes)", c.peak + 256); return CTRLV_E_WORKSPACE; }
-  return rc;
+  return forward_entry(p, "unet_forward", 0, sample && timestep && ehs && added_time_ids && out && workspace ? nullptr : "null pointer",
+                       dtype, (down_res == nullptr) == (mid_res == nullptr) ? nullptr : "pass both down_res and mid_res or neither",
+                       B, F, H, W, workspace, workspace_bytes, stream, [&](Ctx& c) {
+    return unet_forward(p, c, sample, dtype, timestep, n_timestep, ehs, added_time_ids, n_ids, down_res, mid_res, residual_event, out, H, W);
+  });
 }
 
 // Down + mid path of the UNet only (the frozen-UNet half of the training step): the skip tensors and the mid output are
@@ -1269,32 +1271,24 @@ static int unet_encoder(ctrlv_plan* p, Ctx& c, const void* sample, int dtype, co
   std::vector<Tap> taps;
   int H, W;
   CTRLV_TRY(run_down_mid(c, x, h, w, taps, &x, &H, &W));
-  if (!c.dry) {     // (the training step's tensors are plain element rows: the hi planes)
-    for (size_t i = 0; i < taps.size(); ++i) {
-      CTRLV_CHECK_ARG(out_taps[i] != nullptr, "unet_encoder_forward: out_taps[%zu] is null", i);
-      CTRLV_TRY(ctrlv_axpby(taps[i].x.hi, taps[i].x.hi, 1.0f, 0.0f, out_taps[i], (size_t)N * taps[i].H * taps[i].W * taps[i].C, c.st));
-    }
-    CTRLV_TRY(ctrlv_axpby(x.hi, x.hi, 1.0f, 0.0f, out_mid, (size_t)N * H * W * p->cfg.block_out_channels[p->cfg.n_blocks - 1], c.st));
+  // (live walk only -- the size query measures the whole forward; the training step's tensors are plain element rows: the hi planes)
+  auto copy = [&](const el_t* src, void* dst, size_t n) { return c.launch({}, [&] { return ctrlv_axpby(src, src, 1.0f, 0.0f, dst, n, c.st); }); };
+  for (size_t i = 0; i < taps.size(); ++i) {
+    CTRLV_CHECK_ARG(out_taps[i] != nullptr, "unet_encoder_forward: out_taps[%zu] is null", i);
+    CTRLV_TRY(copy(taps[i].x.hi, out_taps[i], (size_t)N * taps[i].H * taps[i].W * taps[i].C));
   }
-  return CTRLV_OK;
+  return copy(x.hi, out_mid, (size_t)N * H * W * p->cfg.block_out_channels[p->cfg.n_blocks - 1]);
 }
 
 extern "C" int ctrlv_unet_encoder_forward(ctrlv_plan* p, const void* sample, int dtype, const float* timestep, int n_timestep,
                                           const void* ehs, const float* added_time_ids, int n_ids, void* const* out_taps,
                                           void* out_mid, int B, int F, int H, int W, void* workspace,
                                           size_t workspace_bytes, ctrlv_stream_t stream) {
-  CTRLV_TRY(check_common(p, B, F, H, W));
-  CTRLV_CHECK_ARG(p->cfg.kind == 0, "unet_encoder_forward: the plan is a ControlNet");
-  CTRLV_CHECK_ARG(sample && timestep && ehs && added_time_ids && out_taps && out_mid && workspace,
-                  "unet_encoder_forward: null pointer");
-  if (dtype < 0 || dtype > 2) { ctrlv_set_error("unet_encoder_forward: dtype must be 0 (fp32), 1 (fp16) or 2 (bf16)"); return CTRLV_E_BAD_DTYPE; }
-  CTRLV_TRY(check_workspace(p, "unet_encoder_forward", B, F, H, W, workspace_bytes));     // (sized for the whole forward)
-  char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  Ctx c{p, (hipStream_t)stream, false, base, workspace_bytes - (size_t)(base - (char*)workspace)};
-  c.B = B; c.F = F;
-  const int rc = unet_encoder(p, c, sample, dtype, timestep, n_timestep, ehs, added_time_ids, n_ids, out_taps, out_mid, H, W);
-  if (rc == CTRLV_OK && c.overflow) { ctrlv_set_error("unet_encoder_forward: workspace too small"); return CTRLV_E_WORKSPACE; }
-  return rc;
+  return forward_entry(p, "unet_encoder_forward", 0,
+                       sample && timestep && ehs && added_time_ids && out_taps && out_mid && workspace ? nullptr : "null pointer", dtype,
+                       nullptr, B, F, H, W, workspace, workspace_bytes, stream, [&](Ctx& c) {      // (workspace: sized for the whole forward)
+    return unet_encoder(p, c, sample, dtype, timestep, n_timestep, ehs, added_time_ids, n_ids, out_taps, out_mid, H, W);
+  });
 }
 
 extern "C" int ctrlv_controlnet_forward(ctrlv_plan* p, const void* sample, const void* control_cond, int dtype,
@@ -1302,19 +1296,13 @@ extern "C" int ctrlv_controlnet_forward(ctrlv_plan* p, const void* sample, const
                                         const float* added_time_ids, int n_ids, float conditioning_scale,
                                         void* const* out_down, void* out_mid, int B, int F, int H, int W, void* workspace,
                                         size_t workspace_bytes, ctrlv_stream_t stream) {
-  CTRLV_TRY(check_common(p, B, F, H, W));
-  CTRLV_CHECK_ARG(p->cfg.kind == 1, "controlnet_forward: the plan is a UNet");
-  CTRLV_CHECK_ARG(sample && control_cond && timestep && ehs && added_time_ids && out_down && out_mid && workspace,
-                  "controlnet_forward: null pointer (control_cond is required, controlnet.py:289)");
-  if (dtype < 0 || dtype > 2) { ctrlv_set_error("controlnet_forward: dtype must be 0 (fp32), 1 (fp16) or 2 (bf16)"); return CTRLV_E_BAD_DTYPE; }
-  CTRLV_TRY(check_workspace(p, "controlnet_forward", B, F, H, W, workspace_bytes));
-  char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  Ctx c{p, (hipStream_t)stream, false, base, workspace_bytes - (size_t)(base - (char*)workspace)};
-  c.B = B; c.F = F;
-  const int rc = controlnet_forward(p, c, sample, control_cond, dtype, timestep, n_timestep, ehs, added_time_ids, n_ids,
-                                    conditioning_scale, out_down, out_mid, H, W);
-  if (rc == CTRLV_OK && c.overflow) { ctrlv_set_error("controlnet_forward: workspace too small (need >= %zu bytes)", c.peak + 256); return CTRLV_E_WORKSPACE; }
-  return rc;
+  return forward_entry(p, "controlnet_forward", 1,
+                       sample && control_cond && timestep && ehs && added_time_ids && out_down && out_mid && workspace
+                           ? nullptr : "null pointer (control_cond is required, controlnet.py:289)",
+                       dtype, nullptr, B, F, H, W, workspace, workspace_bytes, stream, [&](Ctx& c) {
+    return controlnet_forward(p, c, sample, control_cond, dtype, timestep, n_timestep, ehs, added_time_ids, n_ids,
+                              conditioning_scale, out_down, out_mid, H, W);
+  });
 }
 
 // ---- per-launch profile of the plan's own launches (include/ctrlv_hip.h)

@@ -14,11 +14,15 @@
 #include <string>
 #include <vector>
 
+#include "plan_walk.h"
 #include "weight_loader.h"
 
 namespace {
 
 using ctrlv_load::WeightLoader;
+using ctrlv_walk::conv2d;
+using ctrlv_walk::conv_t;
+using ctrlv_walk::resid;
 using VConv = ctrlv_load::PackedLinear;        // packed [n (rows, x32), k] + fp32 bias [n]
 using VNorm = ctrlv_load::NormParams;
 struct VRes {
@@ -203,32 +207,21 @@ struct Arena {                             // first-fit free list over workspace
   }
 };
 
-struct Ctx {
+struct Ctx : ctrlv_walk::LaunchGate {      // dry: lay out only (base is a fake, never dereferenced address)
   const ctrlv_vae_plan* p;
-  bool dry;                                // true: lay out only (base is a fake, never dereferenced address)
   char* base;
-  hipStream_t st;
   Arena a;
   el_t* rows(long M, long C) { return (el_t*)(base + a.take((size_t)M * C * 2)); }
   void* bytes(size_t n) { return base + a.take(n); }
   void drop(const void* q) { a.give((size_t)((const char*)q - base)); }
 };
 
-void conv2d(ctrlv_gemm_desc& d, int H, int W, int Ho, int Wo, int stride, int up) {
-  d.taps = 9; d.mode = 1; d.H = H; d.Wd = W; d.Ho = Ho; d.Wo = Wo; d.stride = stride; d.up = up;
-}
-void conv_t(ctrlv_gemm_desc& d, int F, int S) { d.taps = 3; d.mode = 2; d.F = F; d.S = S; }
-void resid(ctrlv_gemm_desc& d, const void* R1, int ld) { d.R1 = R1; d.ldr1 = ld; }
-
 // ops.gemm: the K-split scratch is offered to every launch whose layer shape asks for it (a function of the shape only)
 int gemm(Ctx& c, ctrlv_gemm_desc d) {
   const size_t need = ctrlv_gemm_splitk_ws_bytes(&d);
   void* ws = need ? c.bytes(need) : nullptr;
-  int rc = CTRLV_OK;
-  if (!c.dry) {
-    d.splitk_ws = ws;
-    rc = ctrlv_gemm(&d, c.st);
-  }
+  d.splitk_ws = ws;
+  const int rc = c.run([&] { return ctrlv_gemm(&d, c.st); });
   if (ws) c.drop(ws);                      // (stream order: the next launch that reuses it runs behind this one)
   return rc;
 }
@@ -236,12 +229,10 @@ int gemm(Ctx& c, ctrlv_gemm_desc d) {
 int groupnorm(Ctx& c, const el_t* x, int n_img, int S, int C, int ips, const VNorm& nm, float eps, int silu, el_t* y) {
   const size_t fl = ((size_t)n_img * ctrlv_groupnorm_chunks(n_img, S, C, ips) + n_img / ips) * 64;
   float* part = (float*)c.bytes(fl * 4);
-  int rc = CTRLV_OK;
-  if (!c.dry) {
-    rc = ctrlv_groupnorm_stats_split(x, nullptr, nullptr, nullptr, 0, n_img, S, C, ips, eps, part, c.st);
-    if (rc == CTRLV_OK)
-      rc = ctrlv_groupnorm_apply_split(x, nullptr, nullptr, nullptr, 0, n_img, S, C, ips, part, nm.g, nm.b, silu, y, c.st);
-  }
+  const int rc = c.run([&]() -> int {
+    CTRLV_TRY(ctrlv_groupnorm_stats_split(x, nullptr, nullptr, nullptr, 0, n_img, S, C, ips, eps, part, c.st));
+    return ctrlv_groupnorm_apply_split(x, nullptr, nullptr, nullptr, 0, n_img, S, C, ips, part, nm.g, nm.b, silu, y, c.st);
+  });
   c.drop(part);
   return rc;
 }
@@ -257,12 +248,12 @@ inline int frames_per(long limit, int n, long S, int C) {
 int conv_in(Ctx& c, const void* src, int dtype, int n, int C, int H, int W, const VConv& cv, int cp, int kp, el_t** out) {
   const long M = (long)n * H * W;
   el_t* x16 = c.rows(M, cp);
-  if (!c.dry) {
+  CTRLV_TRY(c.run([&]() -> int {
     CTRLV_HIP_TRY(hipMemsetAsync(x16, 0, (size_t)M * cp * 2, c.st));
-    CTRLV_TRY(ctrlv_nchw_to_rows(src, dtype, n, C, H * W, x16, cp, 0, c.st));
-  }
+    return ctrlv_nchw_to_rows(src, dtype, n, C, H * W, x16, cp, 0, c.st);
+  }));
   el_t* col = c.rows(M, kp);
-  if (!c.dry) CTRLV_TRY(ctrlv_im2col3x3(x16, n, H, W, cp, col, kp, c.st));
+  CTRLV_TRY(c.run([&] { return ctrlv_im2col3x3(x16, n, H, W, cp, col, kp, c.st); }));
   el_t* x = c.rows(M, cv.n);
   CTRLV_TRY(gemm(c, ctrlv_linear_desc(col, kp, cv, x, cv.n, M, cv.n, kp, cv.n)));
   c.drop(col);
@@ -279,7 +270,7 @@ int enc_res(Ctx& c, const VRes& r, const el_t* x, int n, int H, int W, el_t** ou
   el_t* xn = c.rows(M, cin);
   CTRLV_TRY(groupnorm(c, x, n, S, cin, 1, r.n1, eps, 1, xn));
   el_t* h = c.rows(M, cout);
-  { ctrlv_gemm_desc d = ctrlv_linear_desc(xn, cin, r.c1, h, cout, M, cout, cin, cout); conv2d(d, H, W, H, W, 1, 0); CTRLV_TRY(gemm(c, d)); }
+  { ctrlv_gemm_desc d = ctrlv_linear_desc(xn, cin, r.c1, h, cout, M, cout, cin, cout); conv2d(d, H, W, H, W); CTRLV_TRY(gemm(c, d)); }
   c.drop(xn);
   el_t* hn = c.rows(M, cout);
   CTRLV_TRY(groupnorm(c, h, n, S, cout, 1, r.n2, eps, 1, hn));
@@ -290,7 +281,7 @@ int enc_res(Ctx& c, const VRes& r, const el_t* x, int n, int H, int W, el_t** ou
     CTRLV_TRY(gemm(c, ctrlv_linear_desc(x, cin, r.sc, rs, cout, M, cout, cin, cout)));
     res = rs;
   }
-  { ctrlv_gemm_desc d = ctrlv_linear_desc(hn, cout, r.c2, h, cout, M, cout, cout, cout); conv2d(d, H, W, H, W, 1, 0); resid(d, res, cout); CTRLV_TRY(gemm(c, d)); }
+  { ctrlv_gemm_desc d = ctrlv_linear_desc(hn, cout, r.c2, h, cout, M, cout, cout, cout); conv2d(d, H, W, H, W); resid(d, res, cout); CTRLV_TRY(gemm(c, d)); }
   c.drop(hn);
   if (rs) c.drop(rs);
   *out = h;
@@ -312,10 +303,10 @@ int dec_res(Ctx& c, const VRes& r, const el_t* x, int n, int H, int W, el_t** ou
     const int k = (f0 + per < n ? f0 + per : n) - f0;
     const long r0 = (long)f0 * S, Mk = (long)k * S;
     CTRLV_TRY(groupnorm(c, x + r0 * cin, k, S, cin, 1, r.n1, 1e-6f, 1, xn + r0 * cin));
-    { ctrlv_gemm_desc d = ctrlv_linear_desc(xn + r0 * cin, cin, r.c1, h + r0 * cout, cout, Mk, cout, cin, cout); conv2d(d, H, W, H, W, 1, 0); CTRLV_TRY(gemm(c, d)); }
+    { ctrlv_gemm_desc d = ctrlv_linear_desc(xn + r0 * cin, cin, r.c1, h + r0 * cout, cout, Mk, cout, cin, cout); conv2d(d, H, W, H, W); CTRLV_TRY(gemm(c, d)); }
     CTRLV_TRY(groupnorm(c, h + r0 * cout, k, S, cout, 1, r.n2, 1e-6f, 1, hn + r0 * cout));
     if (r.shortcut) CTRLV_TRY(gemm(c, ctrlv_linear_desc(x + r0 * cin, cin, r.sc, rs + r0 * cout, cout, Mk, cout, cin, cout)));
-    { ctrlv_gemm_desc d = ctrlv_linear_desc(hn + r0 * cout, cout, r.c2, xs + r0 * cout, cout, Mk, cout, cout, cout); conv2d(d, H, W, H, W, 1, 0);
+    { ctrlv_gemm_desc d = ctrlv_linear_desc(hn + r0 * cout, cout, r.c2, xs + r0 * cout, cout, Mk, cout, cout, cout); conv2d(d, H, W, H, W);
       resid(d, res + r0 * cout, cout); CTRLV_TRY(gemm(c, d)); }
   }
   c.drop(xn);
@@ -350,7 +341,7 @@ int attn(Ctx& c, const VAttn& a, const el_t* x, int n, int H, int W, int C, el_t
     const long r0 = (long)f * S * C;
     VConv kw; kw.w = k + r0; kw.b = nullptr;
     { ctrlv_gemm_desc d = ctrlv_linear_desc(q + r0, C, kw, scores, S, S, S, C, S); d.s_acc = scale; d.out_f32 = 1; CTRLV_TRY(gemm(c, d)); }
-    if (!c.dry) CTRLV_TRY(ctrlv_softmax_rows(scores, S, S, S, probs, S, c.st));
+    CTRLV_TRY(c.run([&] { return ctrlv_softmax_rows(scores, S, S, S, probs, S, c.st); }));
     VConv tw; tw.w = t + r0; tw.b = nullptr;
     CTRLV_TRY(gemm(c, ctrlv_linear_desc(a.v_rows.w, C, tw, vt, S, C, S, C, S)));
     VConv vw; vw.w = vt; vw.b = nullptr;
@@ -400,9 +391,10 @@ int encode_walk(Ctx& c, const void* px, int dtype, int n, int H, int W, const fl
   CTRLV_TRY(groupnorm(c, h, n, H * W, C, 1, p->e_gno, 1e-6f, 1, hn));
   const int co = 2 * cf.latent_channels, co_p = (co + 3) / 4 * 4;
   el_t* rows = c.rows(M, co_p);
-  { ctrlv_gemm_desc d = ctrlv_linear_desc(hn, C, p->e_cout, rows, co_p, M, p->e_cout.n, C, co_p); conv2d(d, H, W, H, W, 1, 0); CTRLV_TRY(gemm(c, d)); }
-  if (!c.dry)
-    CTRLV_TRY(ctrlv_vae_posterior(rows, co_p, n, cf.latent_channels, H * W, p->qw, p->qb, noise, scale, moments, latents, out_dtype, c.st));
+  { ctrlv_gemm_desc d = ctrlv_linear_desc(hn, C, p->e_cout, rows, co_p, M, p->e_cout.n, C, co_p); conv2d(d, H, W, H, W); CTRLV_TRY(gemm(c, d)); }
+  CTRLV_TRY(c.run([&] {
+    return ctrlv_vae_posterior(rows, co_p, n, cf.latent_channels, H * W, p->qw, p->qb, noise, scale, moments, latents, out_dtype, c.st);
+  }));
   c.drop(rows); c.drop(hn); c.drop(h);
   return CTRLV_OK;
 }
@@ -443,9 +435,9 @@ int decode_clip(Ctx& c, const void* z, int dtype, int n, int H, int W, void* fra
   CTRLV_TRY(groupnorm(c, x, n, H * W, C, 1, p->d_gno, 1e-6f, 1, xn));
   c.drop(x);
   el_t* rows = c.rows(M, co_p);
-  { ctrlv_gemm_desc d = ctrlv_linear_desc(xn, C, p->d_cout, rows, co_p, M, p->d_cout.n, C, co_p); conv2d(d, H, W, H, W, 1, 0); CTRLV_TRY(gemm(c, d)); }
+  { ctrlv_gemm_desc d = ctrlv_linear_desc(xn, C, p->d_cout, rows, co_p, M, p->d_cout.n, C, co_p); conv2d(d, H, W, H, W); CTRLV_TRY(gemm(c, d)); }
   c.drop(xn);
-  if (!c.dry) CTRLV_TRY(ctrlv_time_conv_rows_to_nchw(rows, co_p, n, co, H * W, p->tco_w, p->tco_b, frames, out_dtype, c.st));
+  CTRLV_TRY(c.run([&] { return ctrlv_time_conv_rows_to_nchw(rows, co_p, n, co, H * W, p->tco_w, p->tco_b, frames, out_dtype, c.st); }));
   c.drop(rows);
   return CTRLV_OK;
 }
@@ -478,7 +470,7 @@ int check_decode_shape(const ctrlv_vae_plan* p, int n, int nf, int h, int w) {
 char* const kFakeBase = (char*)(uintptr_t)0x10000000;       // dry runs: pointers are compared with NULL, never dereferenced
 
 size_t dry_bytes(ctrlv_vae_plan* p, int what, int n, int nf, int H, int W) {
-  Ctx c{p, true, kFakeBase, nullptr, {}};
+  Ctx c{{nullptr, true}, p, kFakeBase};
   const int rc = what == 0 ? encode_walk(c, kFakeBase, 0, n, H, W, nullptr, 1.f, kFakeBase, kFakeBase, 0)
                            : decode_clip(c, kFakeBase, 0, nf, H, W, kFakeBase, 0);
   return rc == CTRLV_OK ? c.a.peak : 0;
@@ -514,11 +506,8 @@ extern "C" int ctrlv_vae_plan_create(const ctrlv_vae_config* cfg, int device, ct
 extern "C" int ctrlv_vae_plan_destroy(ctrlv_vae_plan* p) {
   if (!p) return CTRLV_OK;
   if (!p->owned.empty()) {
-    int dev = 0;
-    const bool sw = hipGetDevice(&dev) == hipSuccess && dev != p->device;
-    if (sw) (void)hipSetDevice(p->device);
+    ctrlv_walk::DeviceScope on(p->device);
     free_owned(p);
-    if (sw) (void)hipSetDevice(dev);
   }
   delete p;
   return CTRLV_OK;
@@ -550,10 +539,8 @@ extern "C" int ctrlv_vae_encode(ctrlv_vae_plan* p, const void* pixels, int dtype
   CTRLV_CHECK_ARG(p && p->loaded, "vae_encode: plan not loaded");
   CTRLV_CHECK_ARG(pixels && workspace && (latents || moments), "vae_encode: null pointer (pixels, workspace, and at least one of "
                   "latents / moments)");
-  if (dtype < 0 || dtype > 2 || out_dtype < 0 || out_dtype > 2) {
-    ctrlv_set_error("vae_encode: dtype codes %d / %d (0 fp32, 1 fp16, 2 bf16)", dtype, out_dtype);
-    return CTRLV_E_BAD_DTYPE;
-  }
+  CTRLV_CHECK_DTYPE(dtype >= 0 && dtype <= 2 && out_dtype >= 0 && out_dtype <= 2, "vae_encode: dtype codes %d / %d (0 fp32, 1 fp16, 2 bf16)",
+                    dtype, out_dtype);
   CTRLV_TRY(check_encode_shape(p, n, Hpx, Wpx));
   CTRLV_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "vae_encode: workspace must be 256-byte aligned");
   const size_t need = dry_bytes(p, 0, n, 0, Hpx, Wpx);
@@ -561,7 +548,7 @@ extern "C" int ctrlv_vae_encode(ctrlv_vae_plan* p, const void* pixels, int dtype
     ctrlv_set_error("vae_encode: workspace of %zu bytes, %zu needed (ctrlv_vae_plan_workspace_bytes)", workspace_bytes, need);
     return CTRLV_E_WORKSPACE;
   }
-  Ctx c{p, false, (char*)workspace, (hipStream_t)stream, {}};
+  Ctx c{{(hipStream_t)stream, false}, p, (char*)workspace};
   return encode_walk(c, pixels, dtype, n, Hpx, Wpx, noise, scale, latents, moments, out_dtype);
 }
 
@@ -569,10 +556,8 @@ extern "C" int ctrlv_vae_decode(ctrlv_vae_plan* p, const void* z, int dtype, int
                                 int out_dtype, void* workspace, size_t workspace_bytes, ctrlv_stream_t stream) {
   CTRLV_CHECK_ARG(p && p->loaded, "vae_decode: plan not loaded");
   CTRLV_CHECK_ARG(z && frames && workspace, "vae_decode: null pointer");
-  if (dtype < 0 || dtype > 2 || out_dtype < 0 || out_dtype > 2) {
-    ctrlv_set_error("vae_decode: dtype codes %d / %d (0 fp32, 1 fp16, 2 bf16)", dtype, out_dtype);
-    return CTRLV_E_BAD_DTYPE;
-  }
+  CTRLV_CHECK_DTYPE(dtype >= 0 && dtype <= 2 && out_dtype >= 0 && out_dtype <= 2, "vae_decode: dtype codes %d / %d (0 fp32, 1 fp16, 2 bf16)",
+                    dtype, out_dtype);
   CTRLV_TRY(check_decode_shape(p, n, num_frames, h, w));
   CTRLV_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "vae_decode: workspace must be 256-byte aligned");
   const size_t need = dry_bytes(p, 1, n, num_frames, h, w);
@@ -583,7 +568,7 @@ extern "C" int ctrlv_vae_decode(ctrlv_vae_plan* p, const void* z, int dtype, int
   const ctrlv_vae_config& cf = p->cfg;
   const size_t in_el = dtype == 0 ? 4 : 2, out_el = out_dtype == 0 ? 4 : 2;
   for (int c0 = 0; c0 < n; c0 += num_frames) {       // independent clips, one after the other in the same workspace
-    Ctx c{p, false, (char*)workspace, (hipStream_t)stream, {}};
+    Ctx c{{(hipStream_t)stream, false}, p, (char*)workspace};
     CTRLV_TRY(decode_clip(c, (const char*)z + (size_t)c0 * cf.latent_channels * h * w * in_el, dtype, num_frames, h, w,
                     (char*)frames + (size_t)c0 * cf.out_channels * 64 * h * w * out_el, out_dtype));
   }

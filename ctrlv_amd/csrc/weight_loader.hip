@@ -2,6 +2,7 @@
 // packed ON THE DEVICE into the layouts the kernels consume (include/ctrlv_hip.h: ctrlv_gemm_desc).
 #include <math.h>
 
+#include "plan_walk.h"
 #include "weight_loader.h"
 
 namespace {
@@ -91,10 +92,7 @@ int WeightLoader::find(const std::string& name, long numel, const ctrlv_tensor_d
     ctrlv_set_error("%s: '%s' has %ld elements, expected %ld", who, name.c_str(), (long)t->numel, numel);
     return CTRLV_E_BAD_SHAPE;
   }
-  if (t->dtype < 0 || t->dtype > 2 || !t->data) {
-    ctrlv_set_error("%s: '%s': dtype code %d / null data", who, name.c_str(), t->dtype);
-    return CTRLV_E_BAD_DTYPE;
-  }
+  CTRLV_CHECK_DTYPE(t->dtype >= 0 && t->dtype <= 2 && t->data, "%s: '%s': dtype code %d / null data", who, name.c_str(), t->dtype);
   *out = t;
   return CTRLV_OK;
 }
@@ -221,14 +219,12 @@ int WeightLoader::norm(const std::string& mod, int C, NormParams& nm) {
 }
 
 int run_load(WeightLoader& L, int device, bool restore_device, const std::function<int()>& body) {
-  int prev = 0;
-  const bool sw = restore_device && hipGetDevice(&prev) == hipSuccess && prev != device;
-  CTRLV_HIP_TRY(hipSetDevice(device));
+  ctrlv_walk::DeviceScope on(device, restore_device);
+  CTRLV_TRY(on.status());
   int rc = body();
   const hipError_t e = hipDeviceSynchronize();
   for (void* d : L.staged) (void)hipFree(d);
   L.staged.clear();
-  if (sw) (void)hipSetDevice(prev);
   if (rc == CTRLV_OK && e != hipSuccess) {
     ctrlv_set_error("%s: %s", L.who, hipGetErrorString(e));
     rc = CTRLV_E_HIP;

@@ -71,17 +71,60 @@ def _tensor_descs(state_dict, floating_only):
     return arr, keep
 
 
-class Plan:
+class _Handle:
+    """What the plan objects share: the library and the C handle with its destroy symbol, the hand-over of a state dict, the
+    current stream, the "a size query answered 0" idiom and one workspace per stream."""
+    _destroy = None          # name of the library's destroy call for this kind of handle
+
+    def _open(self, device, dtype):
+        self.device = torch.device(device)
+        self.dtype = dtype
+        self._lib = _lib.load(dtype)
+        self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                getattr(self._lib, self._destroy)(h)
+            except Exception:       # noqa: BLE001  (interpreter shutdown)
+                pass
+
+    def _load(self, symbol, state_dict, floating_only):
+        """Hand every (floating-point) parameter to the library by its key; packing happens on the device in C++."""
+        arr, keep = _tensor_descs(state_dict, floating_only)
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)          # parameters may still be in flight on torch's streams
+        check(getattr(self._lib, symbol)(self._h, arr, len(arr)), symbol)
+        del keep
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _nonzero(self, n, symbol):
+        """The answer of a size query; 0 means refused: raise the library's message."""
+        if n == 0:
+            check(-2, symbol, lib=self._lib)
+        return n
+
+    def _stream_workspace(self, need):
+        """A uint8 tensor of at least `need` bytes, one per stream (self._ws: stream -> tensor)."""
+        key = torch.cuda.current_stream(self.device).cuda_stream
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < need:
+            ws = self._ws[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return ws
+
+
+class Plan(_Handle):
     """Owns one `ctrlv_plan` (module graph + packed weights in library-owned device memory)."""
+    _destroy = "ctrlv_plan_destroy"
 
     def __init__(self, kind, config, device, time_context_order="sb", dtype=torch.bfloat16):
         """dtype: the ELEMENT type of the plan's activations and packed weights -- torch.bfloat16 (libctrlv_hip.so) or
         torch.float16 (libctrlv_hip_f16.so)."""
         self.kind = kind
-        self.device = torch.device(device)
-        self.dtype = dtype
-        self._lib = _lib.load(dtype)
-        self._h = ctypes.c_void_p()
+        self._open(device, dtype)
         self._cfg = config_struct(kind, config, time_context_order)
         check(self._lib.ctrlv_plan_create(ctypes.byref(self._cfg), self.device.index or 0, ctypes.byref(self._h)),
               "ctrlv_plan_create")
@@ -91,21 +134,9 @@ class Plan:
         self._ws_bytes = {}      # (B, F, H, W) -> bytes
         self.n_down = self._lib.ctrlv_plan_num_down_residuals(self._h)
 
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                self._lib.ctrlv_plan_destroy(h)
-            except Exception:       # noqa: BLE001  (interpreter shutdown)
-                pass
-
     def load_state_dict(self, state_dict):
         """Hand every parameter to the library by its diffusers key; packing happens on the device in C++."""
-        arr, keep = _tensor_descs(state_dict, floating_only=False)
-        if self.device.type == "cuda":
-            torch.cuda.synchronize(self.device)          # parameters may still be in flight on torch's streams
-        check(self._lib.ctrlv_plan_load_weights(self._h, arr, len(arr)), "ctrlv_plan_load_weights")
-        del keep
+        self._load("ctrlv_plan_load_weights", state_dict, floating_only=False)
 
     def profile(self, enable=True):
         """Bracket every kernel the plan issues with HIP events (eager forwards only; not under graph capture)."""
@@ -147,10 +178,8 @@ class Plan:
     def workspace_bytes(self, B, F, H, W):
         key = (B, F, H, W)
         if key not in self._ws_bytes:
-            n = self._lib.ctrlv_plan_workspace_bytes(self._h, B, F, H, W)
-            if n == 0:
-                check(-2, "ctrlv_plan_workspace_bytes", lib=self._lib)
-            self._ws_bytes[key] = n
+            self._ws_bytes[key] = self._nonzero(self._lib.ctrlv_plan_workspace_bytes(self._h, B, F, H, W),
+                                                "ctrlv_plan_workspace_bytes")
         return self._ws_bytes[key]
 
     def workspace(self, B, F, H, W, lane=0):
@@ -165,10 +194,6 @@ class Plan:
         check(self._lib.ctrlv_plan_residual_shape(self._h, i, B, F, H, W, ctypes.byref(rows), ctypes.byref(ch)),
               "ctrlv_plan_residual_shape")
         return rows.value, ch.value
-
-    @staticmethod
-    def _stream():
-        return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
     def unet_forward(self, sample, t32, ehs, ids32, down_rows, mid_rows, out, residual_event=None, lane=0):
         B, F, _, H, W = sample.shape
@@ -206,16 +231,14 @@ class Plan:
 CLIP_ACTS = {"gelu": 0, "quick_gelu": 1}
 
 
-class ClipPlan:
+class ClipPlan(_Handle):
     """Owns one `ctrlv_clip_plan`: the CLIP vision tower (transformers' CLIPVisionModelWithProjection) as one C call --
     create, `load_state_dict` (transformers' keys), workspace, `forward` (include/ctrlv_hip.h)."""
+    _destroy = "ctrlv_clip_plan_destroy"
 
     def __init__(self, config, device, dtype=torch.bfloat16):
         """config: transformers' CLIPVisionConfig fields (a dict); dtype: the element type, as for `Plan`."""
-        self.device = torch.device(device)
-        self.dtype = dtype
-        self._lib = _lib.load(dtype)
-        self._h = ctypes.c_void_p()
+        self._open(device, dtype)
         act = config["hidden_act"]
         if act not in CLIP_ACTS:
             raise ValueError(f"ClipPlan: hidden_act {act!r} (gelu or quick_gelu)")
@@ -230,35 +253,15 @@ class ClipPlan:
         self.tokens = (c.image_size // c.patch_size) ** 2 + 1
         self._ws = {}            # stream -> uint8 workspace tensor
 
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                self._lib.ctrlv_clip_plan_destroy(h)
-            except Exception:       # noqa: BLE001  (interpreter shutdown)
-                pass
-
     def load_state_dict(self, state_dict):
         """Hand every parameter to the library by its transformers key; packing happens on the device in C++."""
-        arr, keep = _tensor_descs(state_dict, floating_only=True)
-        if self.device.type == "cuda":
-            torch.cuda.synchronize(self.device)
-        check(self._lib.ctrlv_clip_plan_load_weights(self._h, arr, len(arr)), "ctrlv_clip_plan_load_weights")
-        del keep
+        self._load("ctrlv_clip_plan_load_weights", state_dict, floating_only=True)
 
     def workspace_bytes(self, n_img):
-        n = self._lib.ctrlv_clip_plan_workspace_bytes(self._h, n_img)
-        if n == 0:
-            check(-2, "ctrlv_clip_plan_workspace_bytes", lib=self._lib)
-        return n
+        return self._nonzero(self._lib.ctrlv_clip_plan_workspace_bytes(self._h, n_img), "ctrlv_clip_plan_workspace_bytes")
 
     def workspace(self, n_img):
-        need = self.workspace_bytes(n_img)
-        key = torch.cuda.current_stream(self.device).cuda_stream
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            ws = self._ws[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return ws
+        return self._stream_workspace(self.workspace_bytes(n_img))
 
     def forward(self, pixel_values, return_hidden=False, workspace=None):
         """image_embeds [n, projection_dim] (and last_hidden_state [n, tokens, hidden]) in the plan's element type, enqueued on
@@ -275,26 +278,23 @@ class ClipPlan:
         ws = self.workspace(n) if workspace is None else workspace
         embeds = torch.empty(n, c.projection_dim, dtype=self.dtype, device=self.device)
         hidden = torch.empty(n, self.tokens, c.hidden_size, dtype=self.dtype, device=self.device) if return_hidden else None
-        st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         check(self._lib.ctrlv_clip_forward(self._h, px.data_ptr(), _DT[px.dtype], n, embeds.data_ptr(),
-                                           hidden.data_ptr() if return_hidden else None, ws.data_ptr(), ws.numel(), st),
-              "ctrlv_clip_forward")
+                                           hidden.data_ptr() if return_hidden else None, ws.data_ptr(), ws.numel(),
+                                           self._stream()), "ctrlv_clip_forward")
         return (embeds, hidden) if return_hidden else embeds
 
 
-class VaePlan:
+class VaePlan(_Handle):
     """Owns one `ctrlv_vae_plan`: the SVD VAE (AutoencoderKLTemporalDecoder) as one C call each way -- create,
     `load_state_dict` (diffusers keys: encoder.*, decoder.*, quant_conv.*), workspace, `encode` / `decode`
     (include/ctrlv_hip.h).  The plan runs in bf16 elements: the Python layer routes the VAE to libctrlv_hip.so."""
+    _destroy = "ctrlv_vae_plan_destroy"
 
     def __init__(self, config, device, offset_limit_bytes=0, dtype=torch.bfloat16):
         """config: the fields of AutoencoderKLTemporalDecoder's config (a dict or its config object).  dtype: the element type;
         torch.float16 selects libctrlv_hip_f16.so's build of the same walk (what a PipelinePlan of fp16 models borrows)."""
         get = config.get if isinstance(config, dict) else (lambda k, d=None: getattr(config, k, d))
-        self.device = torch.device(device)
-        self.dtype = dtype
-        self._lib = _lib.load(dtype)
-        self._h = ctypes.c_void_p()
+        self._open(device, dtype)
         c = self._cfg = _lib.VaeConfig()
         boc = tuple(get("block_out_channels"))
         if len(boc) > _lib.CTRLV_MAX_BLOCKS:
@@ -309,45 +309,23 @@ class VaePlan:
               "ctrlv_vae_plan_create")
         self._ws = {}            # stream -> uint8 workspace tensor
 
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                self._lib.ctrlv_vae_plan_destroy(h)
-            except Exception:       # noqa: BLE001  (interpreter shutdown)
-                pass
-
     def load_state_dict(self, state_dict):
         """Hand every parameter to the library by its diffusers key; packing happens on the device in C++."""
-        arr, keep = _tensor_descs(state_dict, floating_only=True)
-        if self.device.type == "cuda":
-            torch.cuda.synchronize(self.device)
-        check(self._lib.ctrlv_vae_plan_load_weights(self._h, arr, len(arr)), "ctrlv_vae_plan_load_weights")
-        del keep
+        self._load("ctrlv_vae_plan_load_weights", state_dict, floating_only=True)
 
     def workspace_bytes(self, what, n, num_frames, H, W):
         """what: "encode" (n images of H x W pixels) or "decode" (n latent frames of H x W latent pixels, clips of num_frames)."""
-        nb = self._lib.ctrlv_vae_plan_workspace_bytes(self._h, {"encode": 0, "decode": 1}[what], n, num_frames, H, W)
-        if nb == 0:
-            check(-2, "ctrlv_vae_plan_workspace_bytes", lib=self._lib)
-        return nb
+        return self._nonzero(self._lib.ctrlv_vae_plan_workspace_bytes(self._h, {"encode": 0, "decode": 1}[what], n, num_frames, H, W),
+                             "ctrlv_vae_plan_workspace_bytes")
 
     def workspace(self, what, n, num_frames, H, W):
-        need = self.workspace_bytes(what, n, num_frames, H, W)
-        key = torch.cuda.current_stream(self.device).cuda_stream
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            ws = self._ws[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return ws
+        return self._stream_workspace(self.workspace_bytes(what, n, num_frames, H, W))
 
     def _check(self, t, what):
         if t.dim() != 4 or t.dtype not in _DT or not t.is_cuda:
             raise ValueError(f"VaePlan.{what}: a 4-D fp32 / fp16 / bf16 tensor on the HIP device")
         if (t.device.index or 0) != (self.device.index or 0):
             raise ValueError(f"VaePlan.{what}: input on {t.device}, the plan's weights on {self.device}")
-
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def encode(self, x, noise=None, scale=1.0, moments=True, workspace=None):
         """x (n, 3, H, W) in [-1, 1] -> (latents, moments): latents (n, L, H/8, W/8) = scale * (mean + std * noise) -- noise
@@ -383,9 +361,10 @@ class VaePlan:
         return out
 
 
-class PipelinePlan:
+class PipelinePlan(_Handle):
     """Owns one `ctrlv_pipeline`: a whole clip as one C call (include/ctrlv_hip.h: ctrlv_pipeline_generate) on four borrowed
     plans of ONE library -- `Plan("unet")`, `Plan("controlnet")` or None, `VaePlan`, `ClipPlan`.  The object keeps them alive."""
+    _destroy = "ctrlv_pipeline_destroy"
 
     def __init__(self, unet_plan, controlnet_plan, vae_plan, clip_plan):
         self.unet, self.controlnet, self.vae, self.clip = unet_plan, controlnet_plan, vae_plan, clip_plan
@@ -400,14 +379,6 @@ class PipelinePlan:
                                               vae_plan._h, clip_plan._h, self.device.index or 0, ctypes.byref(self._h)),
               "ctrlv_pipeline_create")
         self._ws = None
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                self._lib.ctrlv_pipeline_destroy(h)
-            except Exception:       # noqa: BLE001  (interpreter shutdown)
-                pass
 
     def set_overlap(self, on):
         check(self._lib.ctrlv_pipeline_set_overlap(self._h, 1 if on else 0), "ctrlv_pipeline_set_overlap")
@@ -444,10 +415,8 @@ class PipelinePlan:
         return r, (sig, ts, image_u8, latents, cond, aug_noise, out_latents, out_frames, out_frames_u8)
 
     def workspace_bytes(self, request):
-        n = self._lib.ctrlv_pipeline_workspace_bytes(self._h, ctypes.byref(request))
-        if n == 0:
-            check(-2, "ctrlv_pipeline_workspace_bytes", lib=self._lib)
-        return n
+        return self._nonzero(self._lib.ctrlv_pipeline_workspace_bytes(self._h, ctypes.byref(request)),
+                             "ctrlv_pipeline_workspace_bytes")
 
     def generate(self, image_u8, latents, sigmas, timesteps, *, cond=None, aug_noise=None, frames=True, frames_u8=True, **kw):
         """image_u8 (n, H, W, 3) uint8 at the working size; latents fp32 (n, F, L, h, w) already multiplied by
@@ -485,8 +454,7 @@ class PipelinePlan:
         need = self.workspace_bytes(r)
         if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
             self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        check(self._lib.ctrlv_pipeline_generate(self._h, ctypes.byref(r), self._ws.data_ptr(), self._ws.numel(), st),
+        check(self._lib.ctrlv_pipeline_generate(self._h, ctypes.byref(r), self._ws.data_ptr(), self._ws.numel(), self._stream()),
               "ctrlv_pipeline_generate")
         del keep
         return out_lat, out_fr, out_u8
