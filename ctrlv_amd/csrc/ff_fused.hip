@@ -522,6 +522,8 @@ static int ff_check(const ctrlv_gemm_desc& d, int ldx, bool report, bool* fold) 
          "ctrlv_ff_fused: plain element-type output only");
   FF_REQ(d.n_store == kC && d.ldo % 8 == 0 && (!d.R1 || d.ldr1 % 8 == 0) && (!d.R2 || d.ldr2 % 8 == 0), CTRLV_E_BAD_SHAPE,
          "ctrlv_ff_fused: n_store must be 320 and the row pitches multiples of 8");
+  FF_REQ(d.ldo >= kC && (!d.R1 || d.ldr1 >= kC) && (!d.R2 || d.ldr2 >= kC), CTRLV_E_BAD_SHAPE,
+         "ctrlv_ff_fused: a row pitch is smaller than the 320 stored columns (ldo=%d ldr1=%d ldr2=%d)", d.ldo, d.ldr1, d.ldr2);
   const long lim = 0xFFFFFFF0L;
   FF_REQ((long)d.M * d.ldo * 2 <= lim && (long)d.M * ldx * 2 <= lim && (!d.R1 || (long)d.M * d.ldr1 * 2 <= lim) &&
              (!d.R2 || (long)d.M * d.ldr2 * 2 <= lim),

@@ -412,6 +412,17 @@ extern "C" int ctrlv_gemm(const ctrlv_gemm_desc* dp, ctrlv_stream_t stream_) {
   CTRLV_CHECK_SHAPE(d.lda % 8 == 0 && (d.A2 == nullptr || (d.lda2 % 8 == 0 && d.c_split % 64 == 0)),
                     "ctrlv_gemm: lda/lda2 must be multiples of 8 and c_split a multiple of 64");
   CTRLV_CHECK_SHAPE(d.ldo % 4 == 0 && d.n_store % 4 == 0, "ctrlv_gemm: ldo and n_store must be multiples of 4");
+  {   // a row pitch covers its row (include/ctrlv_hip.h): rows that overlap would race, or read their neighbour
+    const int a_cols = d.A2 ? d.c_split : d.Cin, n_st = d.geglu ? (d.n_store < d.N / 2 ? d.n_store : d.N / 2) : d.n_store;
+    CTRLV_CHECK_SHAPE(d.lda >= a_cols, "ctrlv_gemm: row pitch lda=%d is smaller than A's %d channels", d.lda, a_cols);
+    CTRLV_CHECK_SHAPE(!d.A2 || d.lda2 >= d.Cin - d.c_split, "ctrlv_gemm: row pitch lda2=%d is smaller than A2's %d channels",
+                      d.lda2, d.Cin - d.c_split);
+    CTRLV_CHECK_SHAPE(d.ldo >= n_st, "ctrlv_gemm: row pitch ldo=%d is smaller than the %d stored columns", d.ldo, n_st);
+    CTRLV_CHECK_SHAPE(!d.R1 || d.ldr1 >= n_st, "ctrlv_gemm: row pitch ldr1=%d is smaller than the %d stored columns", d.ldr1, n_st);
+    CTRLV_CHECK_SHAPE(!d.R2 || d.ldr2 >= n_st, "ctrlv_gemm: row pitch ldr2=%d is smaller than the %d stored columns", d.ldr2, n_st);
+    CTRLV_CHECK_SHAPE(!(d.vmode && d.V) || d.ldv >= n_st, "ctrlv_gemm: row pitch ldv=%d is smaller than the %d stored columns",
+                      d.ldv, n_st);
+  }
   CTRLV_CHECK_ARG(d.pad_br == 0 || (d.pad_br == 1 && d.mode == 1 && d.stride == 2 && d.up == 0),
                   "ctrlv_gemm: pad_br=%d is the 3x3 conv of stride 2 without upsampling (mode %d, stride %d, up %d)", d.pad_br,
                   d.mode, d.stride, d.up);

@@ -175,6 +175,12 @@ const char* f8_unserved(const ctrlv_gemm_desc& d) {
   if (d.vmode < 0 || d.vmode > 2) return "bad vmode";
   if (d.vmode && !(d.V && d.vdiv > 0 && d.vmod > 0 && d.ldv % 4 == 0 && (d.vmode == 1 || d.vS > 0))) return "bad row-vector table";
   if (d.geglu && (d.R1 || d.R2 || d.vmode || d.out_f32)) return "GEGLU takes a bias-only epilogue";
+  {   // a row pitch covers its row (include/ctrlv_hip.h)
+    const int n_st = d.geglu ? (d.n_store < d.N / 2 ? d.n_store : d.N / 2) : d.n_store;
+    if (d.ldo < n_st) return "row pitch ldo is smaller than the stored columns";
+    if ((d.R1 && d.ldr1 < n_st) || (d.R2 && d.ldr2 < n_st)) return "row pitch ldr1 / ldr2 is smaller than the stored columns";
+    if (d.vmode && d.ldv < n_st) return "row pitch ldv is smaller than the stored columns";
+  }
   if (((uintptr_t)d.A & 15) || ((uintptr_t)d.W & 15) || ((uintptr_t)d.out & (d.out_f32 ? 15 : 7)) || ((uintptr_t)d.bias & 15) ||
       ((uintptr_t)d.R1 & 7) || ((uintptr_t)d.R2 & 7) || ((uintptr_t)d.V & 15))
     return "operands must be aligned (A, W, bias, V 16 bytes; R1, R2, out 8 bytes; out 16 with out_f32)";

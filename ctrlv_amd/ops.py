@@ -31,6 +31,22 @@ def _need_gpu(t, name="tensor"):
         raise _lib.CtrlvHipError(f"ctrlv_amd: {name} must live on a HIP device (got {t.device}); there is no CPU path")
 
 
+def _need_dense(fn, **named):
+    """The kernel behind `fn` takes no row pitch for these tensors: a view that is not contiguous (a column slice of a wider
+    buffer) would be read as if it were, so it is refused by name."""
+    for name, t in named.items():
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"{fn}: {name} must be contiguous -- the kernel takes no row pitch for it (shape {tuple(t.shape)}, "
+                             f"strides {tuple(t.stride())})")
+
+
+def _need_rows(fn, **named):
+    """Pitched operands: the row pitch is passed (stride(0)), the column stride must be 1."""
+    for name, t in named.items():
+        if t is not None and t.dim() >= 1 and t.stride(-1) != 1:
+            raise ValueError(f"{fn}: {name} must have unit column stride (shape {tuple(t.shape)}, strides {tuple(t.stride())})")
+
+
 # Parameter-gradient reductions of the training step (wgrad, bias / row-vector column sums, the mixing-weight dot product):
 # True = ordered sums through scratch buffers (bit-reproducible gradients; VERDICT r04 item 6), False = fp32 atomics.
 DETERMINISTIC = __import__("os").environ.get("CTRLV_DETERMINISTIC", "1") != "0"
@@ -54,6 +70,8 @@ def gemm_wgrad(A, dY, dW, *, N, cin, taps=1, mode=0, A2=None, c_split=0, conv=No
     geometry; dbias[N] (fp32, optional) += scale * column sums of dY.  torch_layout: dW is [N, cin, taps] (the conv
     parameter's own layout) instead of the packed [N, taps*cin].  assign (deterministic form only): dW / dbias are
     written, not accumulated into -- they need no zero fill."""
+    _need_rows("gemm_wgrad", A=A, A2=A2, dY=dY)
+    _need_dense("gemm_wgrad", dW=dW, dbias=dbias)
     _need_gpu(A, "A")
     d = GemmDesc()
     d.A, d.A2 = _p(A), _p(A2)
@@ -147,6 +165,7 @@ def lora_merge(W, A, B, scale, out=None):
 
 def colsum(x, out, vmode=0, vdiv=1, vmod=1, scale=1.0):
     """out[idx(m), :N] += scale * sum_m x[m, :]  (fp32, atomics): bias gradients (vmode 0) / per-clip row-vector gradients."""
+    _need_rows("colsum", x=x, out=out)
     _need_gpu(x, "x")
     lib = _L(x)
     scratch = None
@@ -170,6 +189,8 @@ def dot_diff(dy, p, q, out, scale=1.0):
 def groupnorm_bwd(x, dy, n_img, S, C, imgs_per_stat, fwd_partials, gamma, beta, silu, dx, dgamma, dbeta, add=None):
     """add (rows like dy, optional): dx = (norm backward) + add -- the gradient of the skip connection around the branch the norm
     opens, summed in the same pass (ctrlv_groupnorm_bwd_add)."""
+    _need_dense("groupnorm_bwd", x=x, dy=dy, add=add, fwd_partials=fwd_partials, gamma=gamma, beta=beta, dx=dx, dgamma=dgamma,
+                dbeta=dbeta)
     _need_gpu(x, "x")
     lib = _L(x)
     n = lib.ctrlv_groupnorm_bwd_scratch_floats(n_img, S, C, imgs_per_stat)
@@ -183,6 +204,8 @@ def groupnorm_bwd(x, dy, n_img, S, C, imgs_per_stat, fwd_partials, gamma, beta, 
 
 
 def layernorm_bwd(x, dy, gamma, eps, dx, dgamma, dbeta, V=None, vdiv=1, vmod=1 << 30, add=None):
+    _need_dense("layernorm_bwd", x=x, dy=dy, add=add, gamma=gamma, dx=dx, dgamma=dgamma, dbeta=dbeta)
+    _need_rows("layernorm_bwd", V=V)
     _need_gpu(x, "x")
     M, C = x.shape
     lib = _L(x)
@@ -194,6 +217,7 @@ def layernorm_bwd(x, dy, gamma, eps, dx, dgamma, dbeta, V=None, vdiv=1, vmod=1 <
 
 
 def geglu_bwd(raw, du, draw):
+    _need_dense("geglu_bwd", raw=raw, du=du, draw=draw)
     _need_gpu(raw, "raw")
     check(_L(raw).ctrlv_geglu_bwd(_p(raw), _p(du), du.shape[0], du.shape[1], _p(draw), _stream()), "ctrlv_geglu_bwd")
     return draw
@@ -203,6 +227,7 @@ def _gemm_desc(A, W, out, *, N, cin, taps=1, mode=0, bias=None, A2=None, c_split
                R1=None, s1=1.0, R2=None, s2=1.0, s_acc=1.0, V=None, vmode=0, vdiv=1, vmod=1 << 30, vS=1,
                act=0, geglu=0, out_f32=False, n_store=None, M=None, tile=0, raw_out=None, n_scale2=0, s_acc2=1.0, _dbg=0,
                gn_partials=None, splitk=True, rows_per_image=0, R1_lo=None, R2_lo=None, out_lo=None, pad_br=False):
+    _need_rows("gemm", A=A, A2=A2, out=out, R1=R1, R2=R2, V=V, raw_out=raw_out, R1_lo=R1_lo, R2_lo=R2_lo, out_lo=out_lo)
     d = GemmDesc()
     d.A, d.A2, d.W, d.out = _p(A), _p(A2), _p(W), _p(out)
     d.bias, d.R1, d.R2, d.V = _p(bias), _p(R1), _p(R2), _p(V)
@@ -273,8 +298,8 @@ def pack_up_phase_weight(weight, dtype=torch.bfloat16):
 def gemm(A, W, out, **kw):
     """out = epilogue(gather-GEMM(A[, A2], W)).  `conv` = (H, W, Ho, Wo, stride, up); `temporal` = (F, S).
     Keywords: see `_gemm_desc` (the fields of ctrlv_gemm_desc)."""
-    _need_gpu(A, "A")
     d = _gemm_desc(A, W, out, **kw)
+    _need_gpu(A, "A")
     lib = _L(A, W)
     if kw.get("splitk", True):
         # split contraction of the small-image long-K convs (csrc/gemm.hip splitk_plan): the scratch is what enables it, and
@@ -350,8 +375,8 @@ def gemm_f8(A, a_scale, W, w_scale, out, **kw):
     scales (quant_rows_f8), on the K = 64 block-scaled MFMA at twice the 16-bit rate; epilogue keywords as `gemm` (bias, geglu,
     R1 / R2 / s1 / s2 / s_acc, V with vmode 1 / 2, n_store, out_f32).  The element library is the one of `out` / R1 / R2; an
     fp32 output without residuals names it with el=torch.float16 / torch.bfloat16 (default bf16)."""
-    _need_gpu(A, "A")
     d, lib = _gemm_f8_desc(A, W, out, **kw)
+    _need_gpu(A, "A")
     ev = _prof.begin()
     check(lib.ctrlv_gemm_f8(ctypes.byref(d), _p(a_scale), _p(w_scale), _stream()), "ctrlv_gemm_f8")
     if ev is not None:
@@ -381,6 +406,7 @@ def ff_fused_pack(w1_packed, b1, w2_packed):
 def _ff_out_desc(out, bias=None, R1=None, s1=1.0, R2=None, s2=1.0, s_acc=1.0, V=None, vmode=0, vdiv=1, vmod=1 << 30, vS=1,
                  R1_lo=None, R2_lo=None, out_lo=None):
     """The second projection's descriptor of a C = 320 feed-forward (what ctrlv_ff_fused / ctrlv_ff_fused_serves take)."""
+    _need_rows("ff_fused", out=out, R1=R1, R2=R2, V=V, R1_lo=R1_lo, R2_lo=R2_lo, out_lo=out_lo)
     d = GemmDesc()
     d.out, d.bias, d.R1, d.R2, d.V = _p(out), _p(bias), _p(R1), _p(R2), _p(V)
     d.R1_lo, d.R2_lo, d.out_lo = _p(R1_lo), _p(R2_lo), _p(out_lo)
@@ -406,8 +432,9 @@ def ff_fused(x, w1f, w2f, out, *, bias=None, R1=None, s1=1.0, R2=None, s2=1.0, s
              vmod=1 << 30, vS=1, ln=None, ln_V=None, ln_vdiv=1, ln_vmod=1 << 30, R1_lo=None, R2_lo=None, out_lo=None):
     """out = s_acc * (GEGLU(x W1^T + b1) W2^T + bias) + s1 R1 + s2 R2 + V[idx(m)] for a C = 320 feed-forward, the 4C-wide
     intermediate kept on chip (csrc/ff_fused.hip).  The epilogue operands are those of `gemm`."""
-    _need_gpu(x, "x")
+    _need_rows("ff_fused", x=x, ln_V=ln_V)
     d = _ff_out_desc(out, bias, R1, s1, R2, s2, s_acc, V, vmode, vdiv, vmod, vS, R1_lo, R2_lo, out_lo)
+    _need_gpu(x, "x")
     ev = _prof.begin()
     if ln is None:        # ln = (gamma, beta, eps): the LayerNorm in front of the feed-forward, folded into the kernel
         check(_L(x).ctrlv_ff_fused(_p(x), x.stride(0), _p(w1f), _p(w2f), ctypes.byref(d), _stream()),
@@ -444,6 +471,7 @@ def groupnorm_fused_scratch_floats(n_img, S, imgs_per_stat):
 def groupnorm_from_partials(x, n_img, S, C, imgs_per_stat, gamma, beta, eps, silu, y, partials, x_lo=None):
     """GroupNorm(+SiLU) of a tensor whose producing `gemm` wrote the chunk partials: finalize + apply.  x_lo: the lo plane of
     a SPLIT tensor (the launch wrote out_lo and gn_partials together; the normalised value is x + x_lo)."""
+    _need_dense("groupnorm_from_partials", x=x, x_lo=x_lo, y=y, partials=partials, gamma=gamma, beta=beta)
     _need_gpu(x, "x")
     assert partials.numel() >= groupnorm_fused_scratch_floats(n_img, S, imgs_per_stat)
     ev = _prof.begin()
@@ -457,6 +485,7 @@ def groupnorm_from_partials(x, n_img, S, C, imgs_per_stat, gamma, beta, eps, sil
 def groupnorm(x, x2, n_img, S, C, imgs_per_stat, gamma, beta, eps, silu, y, partials, x_lo=None, x2_lo=None):
     """Two-pass GroupNorm(32)(+SiLU) over channels-last rows; (x | x2) is a channel concat when x2 is given.  x_lo / x2_lo:
     the lo planes of a SPLIT input (the normalised value is x + x_lo)."""
+    _need_dense("groupnorm", x=x, x2=x2, x_lo=x_lo, x2_lo=x2_lo, y=y, partials=partials, gamma=gamma, beta=beta)
     _need_gpu(x, "x")
     lib = _L(x)
     c_split = x.shape[1] if x2 is not None else 0
@@ -472,6 +501,8 @@ def groupnorm(x, x2, n_img, S, C, imgs_per_stat, gamma, beta, eps, silu, y, part
 
 
 def layernorm(x, gamma, beta, eps, y, V=None, vdiv=1, vmod=1 << 30, x_lo=None):
+    _need_dense("layernorm", x=x, x_lo=x_lo, y=y, gamma=gamma, beta=beta)
+    _need_rows("layernorm", V=V)
     _need_gpu(x, "x")
     M, C = x.shape
     ev = _prof.begin()
@@ -486,6 +517,7 @@ Q_PRESCALE = 0.125 * 1.44269504088896340736      # (1/sqrt(64)) * log2(e): the q
 
 def attention_spatial(qkv, out, n_img, S, C, prescaled=False):
     """prescaled: the q columns already carry Q_PRESCALE (gemm(..., n_scale2=C, s_acc2=Q_PRESCALE))."""
+    _need_dense("attention_spatial", qkv=qkv, out=out)
     _need_gpu(qkv, "qkv")
     ev = _prof.begin()
     fn = _L(qkv).ctrlv_attention_spatial_prescaled if prescaled else _L(qkv).ctrlv_attention_spatial
@@ -496,6 +528,7 @@ def attention_spatial(qkv, out, n_img, S, C, prescaled=False):
 
 def attention_spatial_lse(qkv, out, lse, n_img, S, C):
     """Training forward: also writes lse [n_img, C/64, S] fp32 (log2-domain log-sum-exp of the scaled scores)."""
+    _need_dense("attention_spatial_lse", qkv=qkv, out=out, lse=lse)
     _need_gpu(qkv, "qkv")
     ev = _prof.begin()
     check(_L(qkv).ctrlv_attention_spatial_lse(_p(qkv), _p(out), _p(lse), n_img, S, C, _stream()),
@@ -505,6 +538,7 @@ def attention_spatial_lse(qkv, out, lse, n_img, S, C):
 
 
 def attention_spatial_bwd(qkv, out, dout, lse, dqkv, n_img, S, C):
+    _need_dense("attention_spatial_bwd", qkv=qkv, out=out, dout=dout, lse=lse, dqkv=dqkv)
     _need_gpu(qkv, "qkv")
     delta = torch.empty(_L(qkv).ctrlv_attention_bwd_scratch_floats(n_img, S, C), dtype=torch.float32, device=qkv.device)
     ev = _prof.begin()
@@ -515,6 +549,7 @@ def attention_spatial_bwd(qkv, out, dout, lse, dqkv, n_img, S, C):
 
 
 def attention_temporal_bwd(qkv, out, dout, dqkv, B, F, S, C):
+    _need_dense("attention_temporal_bwd", qkv=qkv, out=out, dout=dout, dqkv=dqkv)
     _need_gpu(qkv, "qkv")
     ev = _prof.begin()
     check(_L(qkv).ctrlv_attention_temporal_bwd(_p(qkv), _p(out), _p(dout), _p(dqkv), B, F, S, C, _stream()),
@@ -524,6 +559,7 @@ def attention_temporal_bwd(qkv, out, dout, dqkv, B, F, S, C):
 
 
 def attention_temporal(qkv, out, B, F, S, C):
+    _need_dense("attention_temporal", qkv=qkv, out=out)
     _need_gpu(qkv, "qkv")
     ev = _prof.begin()
     check(_L(qkv).ctrlv_attention_temporal(_p(qkv), _p(out), B, F, S, C, _stream()), "ctrlv_attention_temporal")
@@ -651,6 +687,7 @@ def temporal_fused_pack(wqkv_packed, wo_packed):
 def _temporal_fused_desc(x, wf, out, B, F, S, bias=None, R1=None, V=None, vmode=0, vdiv=1, vmod=1 << 30, vS=1, R1_lo=None,
                          out_lo=None, ln=None):
     from ._lib import TemporalFusedDesc
+    _need_rows("temporal_fused", x=x, out=out, R1=R1, V=V, R1_lo=R1_lo, out_lo=out_lo)
     d = TemporalFusedDesc()
     d.x, d.ldx, d.wf, d.bias = _p(x), x.stride(0), _p(wf), _p(bias)
     d.R1, d.R1_lo, d.ldr1 = _p(R1), _p(R1_lo), (R1.stride(0) if R1 is not None else 0)
@@ -670,8 +707,8 @@ def temporal_fused_serves(x, wf, out, B, F, S, **kw):
 def temporal_fused(x, wf, out, B, F, S, **kw):
     """out = R1 + to_out(softmax_f(q k^T / 8) v) + bias + V[clip], (q|k|v) = x W_qkv^T, over the F frames of every pixel:
     the temporal self-attention block at C = 320 in one launch (csrc/temporal_fused.hip)."""
-    _need_gpu(x, "x")
     d = _temporal_fused_desc(x, wf, out, B, F, S, **kw)
+    _need_gpu(x, "x")
     ev = _prof.begin()
     check(_L(x).ctrlv_temporal_fused(ctypes.byref(d), _stream()), "ctrlv_temporal_fused")
     M, C = B * F * S, x.shape[1]
@@ -682,6 +719,8 @@ def temporal_fused(x, wf, out, B, F, S, **kw):
 
 def nchw_to_rows(src, dst, c_off=0):
     """src: contiguous (n_img, C, H, W) fp32/fp16/bf16 -> dst rows [n_img*H*W, ldc] bf16, channels [c_off, c_off+C)."""
+    _need_dense("nchw_to_rows", src=src)
+    _need_rows("nchw_to_rows", dst=dst)
     _need_gpu(src, "src")
     n_img, C = src.shape[0], src.shape[1]
     HW = src.shape[2] * src.shape[3]
@@ -692,6 +731,8 @@ def nchw_to_rows(src, dst, c_off=0):
 
 def rows_to_nchw(src, dst, C=None):
     """src rows [n_img*H*W, ldc] bf16 -> dst contiguous (n_img, C, H, W) of dst.dtype."""
+    _need_rows("rows_to_nchw", src=src)
+    _need_dense("rows_to_nchw", dst=dst)
     _need_gpu(src, "src")
     n_img, Cd = dst.shape[0], dst.shape[1]
     HW = dst.shape[2] * dst.shape[3]
@@ -765,6 +806,8 @@ def cfg_euler_step(latents, noise_pred, guidance, sigma, sigma_next, scaled_next
 def time_conv_rows_to_nchw(rows, n_frames, C, HW, weight, bias, out):
     """Conv3d(C, C, (3,1,1)) over the frames of one clip on channels-last rows, written as NCHW `out` (the VAE decoder's
     time_conv_out)."""
+    _need_rows("time_conv_rows_to_nchw", rows=rows)
+    _need_dense("time_conv_rows_to_nchw", weight=weight, bias=bias, out=out)
     _need_gpu(rows, "rows")
     check(_L(rows).ctrlv_time_conv_rows_to_nchw(_p(rows), rows.stride(0), n_frames, C, HW, _p(weight), _p(bias), _p(out),
                                                    _DT[out.dtype], _stream()), "ctrlv_time_conv_rows_to_nchw")
@@ -773,6 +816,7 @@ def time_conv_rows_to_nchw(rows, n_frames, C, HW, weight, bias, out):
 
 def softmax_rows(scores, probs):
     """probs (bf16) = row softmax of fp32 `scores` (both 2-D, unit inner stride)."""
+    _need_rows("softmax_rows", scores=scores, probs=probs)
     _need_gpu(scores, "scores")
     check(_L(probs).ctrlv_softmax_rows(_p(scores), scores.shape[0], scores.shape[1], scores.stride(0), _p(probs),
                                          probs.stride(0), _stream()), "ctrlv_softmax_rows")

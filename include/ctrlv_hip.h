@@ -89,7 +89,12 @@ typedef struct ctrlv_gemm_desc {
   const void* R2;     /* [M, ldr2] bf16 or NULL */
   const float* V;     /* [*, ldv] fp32 row-vector table or NULL */
   int32_t M, N, Cin, taps;
-  int32_t lda, lda2, c_split;
+  int32_t lda, lda2, c_split;         /* ROW PITCHES (lda, lda2, ldo, ldr1, ldr2, ldv, ld_raw), in elements of their tensor: a
+                                         pitch covers its row -- rows may be views into wider buffers, they never overlap.
+                                         lda >= Cin (>= c_split with A2), lda2 >= Cin - c_split; ldo, ldr1, ldr2 and ldv >=
+                                         the stored columns = n_store (GEGLU: min(n_store, N / 2)); ld_raw >= N.  Checked for
+                                         the operands that are present, before any launch (CTRLV_E_BAD_SHAPE); the same rule
+                                         holds for ctrlv_gemm_f8 and the out / R1 / R2 pitches of ctrlv_ff_fused (>= 320) */
   int32_t mode;                       /* 0 plain, 1 conv2d 3x3, 2 temporal (3,1,1) */
   int32_t H, Wd, Ho, Wo, stride, up;  /* mode 1: input H x Wd (before upsample), output Ho x Wo.  up = 1: nearest-x2 upsample
                                          fused into the 3x3 gather (source pixel (y >> 1, x >> 1)), W = [N][9 Cin].
