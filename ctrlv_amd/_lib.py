@@ -127,6 +127,17 @@ class ClipRequest(ctypes.Structure):
     ]
 
 
+class BoxCondition(ctypes.Structure):
+    """Mirror of `ctrlv_box_condition`."""
+    _fields_ = [("frames", c_void_p), ("channels", c_int), ("dtype", c_int), ("num_cond_frames", c_int), ("reserved", c_int)]
+
+
+class TwoStageRequest(ctypes.Structure):
+    """Mirror of `ctrlv_two_stage_request`."""
+    _fields_ = [("boxes", ClipRequest), ("box_cond", BoxCondition), ("video", ClipRequest), ("out_box_frames_u8", c_void_p),
+                ("clean_threshold", c_float), ("reserved", c_int)]
+
+
 # name -> (restype, argtypes); lists every symbol include/ctrlv_hip.h declares (tests/test_abi.py checks this)
 SIGNATURES = {
     "ctrlv_abi_version": (c_int, []),
@@ -266,6 +277,15 @@ SIGNATURES = {
     "ctrlv_pipeline_workspace_bytes": (c_size_t, [c_void_p, ctypes.POINTER(ClipRequest)]),
     "ctrlv_pipeline_generate": (c_int, [c_void_p, ctypes.POINTER(ClipRequest), c_void_p, c_size_t, c_void_p]),
     "ctrlv_pipeline_destroy": (c_int, [c_void_p]),
+    "ctrlv_pipeline_boxes_workspace_bytes": (c_size_t, [c_void_p, ctypes.POINTER(ClipRequest), ctypes.POINTER(BoxCondition)]),
+    "ctrlv_pipeline_predict_boxes": (c_int, [c_void_p, ctypes.POINTER(ClipRequest), ctypes.POINTER(BoxCondition), c_void_p,
+                                             c_size_t, c_void_p]),
+    "ctrlv_box_frames_post_ws_bytes": (c_size_t, [c_int, c_int]),
+    "ctrlv_box_frames_post": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_size_t, c_void_p]),
+    "ctrlv_mask_counts": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ctrlv_pipeline_chain_workspace_bytes": (c_size_t, [c_void_p, c_void_p, ctypes.POINTER(TwoStageRequest)]),
+    "ctrlv_pipeline_boxes_to_video": (c_int, [c_void_p, c_void_p, ctypes.POINTER(TwoStageRequest), c_void_p, c_size_t, c_void_p]),
 }
 
 _libs = {}                # element dtype code (2 bf16 / 1 fp16) -> CDLL
@@ -276,7 +296,8 @@ _NO_STATUS = {"ctrlv_abi_version", "ctrlv_elem_dtype", "ctrlv_build_id", "ctrlv_
               "ctrlv_temporal_fused_serves", "ctrlv_gemm_f8_serves",
               # size queries (size_t: never wrapped, listed with their kin for the reader)
               "ctrlv_gemm_tokens_ws_bytes", "ctrlv_clip_plan_workspace_bytes", "ctrlv_vae_plan_workspace_bytes",
-              "ctrlv_pipeline_workspace_bytes"}
+              "ctrlv_pipeline_workspace_bytes", "ctrlv_pipeline_boxes_workspace_bytes", "ctrlv_box_frames_post_ws_bytes",
+              "ctrlv_pipeline_chain_workspace_bytes"}
 
 
 def _status_recorder(lib, fn):

@@ -1,14 +1,19 @@
 // A whole clip as one C call: the driver behind ctrlv_pipeline_generate (include/ctrlv_hip.h).  It owns nothing but a side
 // stream and two events; the four plans are borrowed, every buffer is carved out of the caller's workspace.  What it enqueues is
 // what prepare_clip -> DenoiseStepper (eager) -> finish_clip of ctrlv_amd/pipelines/pipeline_utils.py enqueue, call for call:
-// the plan-level entry points plus the glue kernels of csrc/pipeline_io.hip.
+// the plan-level entry points plus the glue kernels of csrc/pipeline_io.hip.  ctrlv_pipeline_predict_boxes is the same clip with
+// the box frames written over the conditioning channels and the decoded frames clamped (VideoDiffusionPipeline.__call__ with
+// bbox_images); ctrlv_pipeline_boxes_to_video chains it, the kernels of csrc/box_frames.hip and generate.
 #include <math.h>
 
 #include <vector>
 
 #include "pipeline_io.h"
 
+constexpr uint32_t kPipelineTag = 0x43564c00u | CTRLV_ELEM_DTYPE;      // "CVL" + the element code of the library that made it
+
 struct ctrlv_pipeline {
+  uint32_t tag = kPipelineTag;           // first member: ctrlv_pipeline_boxes_to_video tells a handle of the other library by it
   ctrlv_plan* unet = nullptr;
   ctrlv_plan* cn = nullptr;
   ctrlv_vae_plan* vae = nullptr;
@@ -44,6 +49,11 @@ float round_el(float v) {
 struct Geo {                 // a validated request's derived sizes
   int B, F, H, W, h, w, hw, L, nb, cfg, D, S;      // nb = model batch (2 B with cfg), D = embedding width, S = CLIP image size
   bool decode;
+};
+
+struct BoxGeo {              // a validated ctrlv_box_condition
+  int K, take;               // take = min(K + 1, F): the frames [0, K) and F - 1
+  bool encode;               // 3-channel pixels: the taken frames go through the VAE encoder first
 };
 
 struct Layout {              // byte offsets into the workspace
@@ -119,7 +129,33 @@ int validate(const ctrlv_pipeline* p, const ctrlv_clip_request* r, Geo* g) {
   return CTRLV_OK;
 }
 
-int layout(ctrlv_pipeline* p, const ctrlv_clip_request* r, const Geo& g, Layout* L) {
+// The box condition of ctrlv_pipeline_predict_boxes against a validated request: the refusals that name the box predictor come
+// first (a ControlNet pipeline would otherwise be refused for its missing cond), then the request as generate validates it.
+int validate_boxes(const ctrlv_pipeline* p, const ctrlv_clip_request* r, const ctrlv_box_condition* bc, Geo* g, BoxGeo* bg) {
+  CTRLV_CHECK_ARG(p != nullptr, "predict_boxes: null pipeline");
+  CTRLV_CHECK_ARG(r != nullptr, "predict_boxes: null request");
+  CTRLV_CHECK_ARG(bc != nullptr, "predict_boxes: null box condition");
+  CTRLV_CHECK_ARG(p->cn == nullptr, "predict_boxes: the pipeline has a ControlNet; the box predictor is a UNet-only pipeline "
+                  "(ctrlv_pipeline_create with controlnet = NULL)");
+  CTRLV_CHECK_ARG(r->cond == nullptr, "predict_boxes: cond is set; the box predictor takes its box frames through "
+                  "ctrlv_box_condition, not the ControlNet condition");
+  CTRLV_TRY(validate(p, r, g));
+  CTRLV_CHECK_ARG(bc->reserved == 0, "predict_boxes: box condition reserved=%d must be 0", bc->reserved);
+  CTRLV_CHECK_ARG(bc->frames != nullptr, "predict_boxes: box condition frames is null");
+  CTRLV_CHECK_SHAPE(bc->channels == 3 || bc->channels == g->L, "predict_boxes: box condition channels=%d must be 3 (pixels) or "
+                    "%d (latents)", bc->channels, g->L);
+  CTRLV_CHECK_DTYPE(bc->dtype >= 0 && bc->dtype <= 2, "predict_boxes: box condition dtype code %d (0 fp32, 1 fp16, 2 bf16)",
+                    bc->dtype);
+  CTRLV_CHECK_SHAPE(bc->num_cond_frames >= 0 && bc->num_cond_frames <= g->F, "predict_boxes: num_cond_frames=%d must be in "
+                    "[0, %d] (num_frames)", bc->num_cond_frames, g->F);
+  bg->K = bc->num_cond_frames;
+  bg->take = bg->K + 1 < g->F ? bg->K + 1 : g->F;
+  bg->encode = bc->channels == 3;
+  return CTRLV_OK;
+}
+
+// bx: the box condition of predict_boxes (its encoder call and the latents of the taken frames join the VAE-encode phase)
+int layout(ctrlv_pipeline* p, const ctrlv_clip_request* r, const Geo& g, const BoxGeo* bx, Layout* L) {
   int lu = 0, lv = 0, lc = 0, ln = 1;
   ctrlv_plan_info(p->unet, nullptr, &lu);
   ctrlv_vae_plan_info(p->vae, nullptr, &lv);
@@ -182,9 +218,20 @@ int layout(ctrlv_pipeline* p, const ctrlv_clip_request* r, const Geo& g, Layout*
     if (b2 == 0) return CTRLV_E_BAD_SHAPE;
     L->enc_bytes = b2 > L->enc_bytes ? b2 : L->enc_bytes;
   }
+  size_t box_lat = 0;
+  if (bx && bx->encode) {      // one call over all the clips' frames when every frame is taken, else [0, K) and F - 1 per clip
+    const int calls[2] = {bx->take == g.F ? g.B * g.F : bx->K, bx->take == g.F ? 0 : 1};
+    for (int n : calls) {
+      if (n == 0) continue;
+      const size_t b2 = ctrlv_vae_plan_workspace_bytes(p->vae, 0, n, 1, g.H, g.W);
+      if (b2 == 0) return CTRLV_E_BAD_SHAPE;
+      L->enc_bytes = b2 > L->enc_bytes ? b2 : L->enc_bytes;
+    }
+    box_lat = (size_t)g.B * bx->take * g.L * g.hw * el;
+  }
   o = L->phase;
   L->enc_px = take((size_t)g.B * 3 * g.H * g.W * el);
-  L->enc_lat = take(enc_cond ? lat * el : 0);
+  L->enc_lat = take(enc_cond ? lat * el : box_lat);
   L->enc_ws = take(L->enc_bytes);
   end = o > end ? o : end;
   // decode: the scaled latents, the frames (unless the caller takes them), the decoder's workspace
@@ -261,27 +308,22 @@ extern "C" int ctrlv_pipeline_destroy(ctrlv_pipeline* p) {
   return CTRLV_OK;
 }
 
-extern "C" size_t ctrlv_pipeline_workspace_bytes(ctrlv_pipeline* p, const ctrlv_clip_request* r) {
-  Geo g;
-  Layout L;
-  if (validate(p, r, &g) != CTRLV_OK) return 0;
-  if (layout(p, r, g, &L) != CTRLV_OK) return 0;
-  return L.total;
-}
+namespace {
 
-extern "C" int ctrlv_pipeline_generate(ctrlv_pipeline* p, const ctrlv_clip_request* r, void* ws, size_t ws_bytes,
-                                       ctrlv_stream_t stream) {
-  Geo g;
-  Layout L;
-  CTRLV_TRY(validate(p, r, &g));
-  CTRLV_TRY(layout(p, r, g, &L));
-  CTRLV_CHECK_ARG(ws != nullptr && ((uintptr_t)ws & (kAlign - 1)) == 0, "pipeline_generate: the workspace must be non-null and "
-                  "256-byte aligned");
-  if (ws_bytes < L.total) {
-    ctrlv_set_error("pipeline_generate: ws_bytes=%zu is smaller than the %zu bytes this request needs "
-                    "(ctrlv_pipeline_workspace_bytes)", ws_bytes, L.total);
+int check_workspace(const char* who, const char* query, const void* ws, size_t ws_bytes, size_t need) {
+  CTRLV_CHECK_ARG(ws != nullptr && ((uintptr_t)ws & (kAlign - 1)) == 0, "%s: the workspace must be non-null and 256-byte aligned",
+                  who);
+  if (ws_bytes < need) {
+    ctrlv_set_error("%s: ws_bytes=%zu is smaller than the %zu bytes this request needs (%s)", who, ws_bytes, need, query);
     return CTRLV_E_WORKSPACE;
   }
+  return CTRLV_OK;
+}
+
+// The clip of a validated request in a workspace of L.total bytes: ctrlv_pipeline_generate (bc = NULL), or
+// ctrlv_pipeline_predict_boxes (bc / bx: the box frames overwrite the conditioning channels, the decoded frames are clamped).
+int run_clip(ctrlv_pipeline* p, const ctrlv_clip_request* r, const ctrlv_box_condition* bc, const Geo& g, const BoxGeo* bx,
+             const Layout& L, void* ws, ctrlv_stream_t stream) {
   const hipStream_t s = (hipStream_t)stream;
   char* base = (char*)ws;
   const bool overlap = p->cn && p->overlap;
@@ -330,6 +372,30 @@ extern "C" int ctrlv_pipeline_generate(ctrlv_pipeline* p, const ctrlv_clip_reque
   CTRLV_TRY(ctrlv_vae_encode(p->vae, base + L.enc_px, CTRLV_ELEM_DTYPE, B, g.H, g.W, nullptr, 1.0f, base + L.first, nullptr,
                        CTRLV_ELEM_DTYPE, base + L.enc_ws, L.enc_bytes, stream));
   CTRLV_TRY(ctrlv_pio_lmi_cond(base + L.first, base + L.lmi, B, F, Lc, hw, g.cfg, s));
+  if (bx) {
+    // the box frames [0, K) and F - 1 of every clip replace the image's latent there.  Only those are encoded: the encoder
+    // treats every image on its own, so a frame's latent does not depend on which frames share its call
+    if (bx->encode) {
+      const size_t px = (size_t)3 * g.H * g.W * (bc->dtype == 0 ? 4 : 2), lt = (size_t)Lc * hw * sizeof(el_t);
+      const char* src = (const char*)bc->frames;
+      char* dst = base + L.enc_lat;
+      auto encode = [&](const char* x, int n, char* out) {
+        return ctrlv_vae_encode(p->vae, x, bc->dtype, n, g.H, g.W, nullptr, 1.0f, out, nullptr, CTRLV_ELEM_DTYPE, base + L.enc_ws,
+                                L.enc_bytes, stream);
+      };
+      if (bx->take == F) {
+        CTRLV_TRY(encode(src, B * F, dst));
+      } else {
+        for (int b = 0; b < B; ++b) {
+          if (bx->K > 0) CTRLV_TRY(encode(src + (size_t)b * F * px, bx->K, dst + (size_t)b * bx->take * lt));
+          CTRLV_TRY(encode(src + ((size_t)b * F + F - 1) * px, 1, dst + ((size_t)b * bx->take + bx->K) * lt));
+        }
+      }
+      CTRLV_TRY(ctrlv_pio_lmi_boxes(dst, CTRLV_ELEM_DTYPE, bx->take, 1, base + L.lmi, B, F, bx->K, Lc, hw, g.cfg, s));
+    } else {
+      CTRLV_TRY(ctrlv_pio_lmi_boxes(bc->frames, bc->dtype, F, 0, base + L.lmi, B, F, bx->K, Lc, hw, g.cfg, s));
+    }
+  }
   if (p->cn) {
     if (r->cond_channels == 3) {
       CTRLV_TRY(ctrlv_vae_encode(p->vae, r->cond, r->cond_dtype, B * F, g.H, g.W, nullptr, 1.0f, base + L.enc_lat, nullptr,
@@ -384,6 +450,119 @@ extern "C" int ctrlv_pipeline_generate(ctrlv_pipeline* p, const ctrlv_clip_reque
                            stream));
     }
     if (r->out_frames_u8) CTRLV_TRY(ctrlv_frames_to_u8(frames, total, g.H, g.W, r->out_frames_u8, stream));
+    // (the bytes above are those of the clamped frames too: ctrlv_frames_to_u8 clamps x / 2 + 0.5 to [0, 1] itself)
+    if (bx && r->out_frames) CTRLV_TRY(ctrlv_pio_clamp_frames(r->out_frames, (long)total * 3 * g.H * g.W, s));
   }
   return CTRLV_OK;
+}
+
+struct Chain {               // ctrlv_pipeline_boxes_to_video: the two requests as the stages see them, and where things lie
+  ctrlv_clip_request boxes, video;
+  Geo gb, gv;
+  BoxGeo bx;
+  Layout Lb, Lv;
+  size_t frames, cond, post, post_bytes, stage, total;
+};
+
+int plan_chain(ctrlv_pipeline* pb, ctrlv_pipeline* pv, const ctrlv_two_stage_request* q, Chain* c) {
+  CTRLV_CHECK_ARG(pb != nullptr && pv != nullptr, "boxes_to_video: null pipeline");
+  CTRLV_CHECK_ARG(q != nullptr, "boxes_to_video: null request");
+  CTRLV_CHECK_ARG(pb->tag == kPipelineTag && pv->tag == kPipelineTag, "boxes_to_video: both pipelines must come from this library "
+                  "(element dtype code %d)", CTRLV_ELEM_DTYPE);
+  CTRLV_CHECK_ARG(pb->device == pv->device, "boxes_to_video: the pipelines live on different devices (%d and %d)", pb->device,
+                  pv->device);
+  CTRLV_CHECK_ARG(q->reserved == 0, "boxes_to_video: reserved=%d must be 0", q->reserved);
+  CTRLV_CHECK_ARG(pv->cn != nullptr, "boxes_to_video: the video pipeline has no ControlNet to take the box frames");
+  CTRLV_CHECK_ARG(q->video.cond == nullptr, "boxes_to_video: video.cond must be NULL on entry (the driver supplies stage 1's frames)");
+  CTRLV_CHECK_ARG(isfinite(q->clean_threshold), "boxes_to_video: clean_threshold=%g", (double)q->clean_threshold);
+  CTRLV_CHECK_SHAPE(q->boxes.n_clips == q->video.n_clips && q->boxes.num_frames == q->video.num_frames &&
+                    q->boxes.height == q->video.height && q->boxes.width == q->video.width,
+                    "boxes_to_video: the two requests differ in geometry (boxes %d x %d x %d x %d, video %d x %d x %d x %d)",
+                    q->boxes.n_clips, q->boxes.num_frames, q->boxes.height, q->boxes.width, q->video.n_clips, q->video.num_frames,
+                    q->video.height, q->video.width);
+  c->boxes = q->boxes;
+  c->video = q->video;
+  c->video.cond = (const void*)(uintptr_t)kAlign;     // (a placeholder until the workspace is known: validate asks for non-null)
+  c->video.cond_channels = 3;
+  c->video.cond_dtype = CTRLV_ELEM_DTYPE;
+  // stage 1 must decode: its frames are what stage 2 is conditioned on.  Without out_frames they go into the chain's workspace
+  const bool own_frames = c->boxes.out_frames == nullptr;
+  if (own_frames) c->boxes.out_frames = (void*)(uintptr_t)kAlign;
+  CTRLV_TRY(validate_boxes(pb, &c->boxes, &q->box_cond, &c->gb, &c->bx));
+  CTRLV_TRY(validate(pv, &c->video, &c->gv));
+  CTRLV_TRY(layout(pb, &c->boxes, c->gb, &c->bx, &c->Lb));
+  CTRLV_TRY(layout(pv, &c->video, c->gv, nullptr, &c->Lv));
+  const size_t fr = (size_t)c->gb.B * c->gb.F * 3 * c->gb.H * c->gb.W * sizeof(el_t);
+  size_t o = 0;
+  auto take = [&](size_t bytes) { const size_t at = o; o += up(bytes); return at; };
+  c->frames = take(own_frames ? fr : 0);
+  c->cond = take(fr);
+  c->post_bytes = ctrlv_box_frames_post_ws_bytes(c->gb.B, c->gb.F);
+  c->post = take(c->post_bytes);
+  c->stage = o;
+  c->total = o + (c->Lb.total > c->Lv.total ? c->Lb.total : c->Lv.total);
+  if (own_frames) c->boxes.out_frames = nullptr;      // (resolved against the workspace by the call)
+  return CTRLV_OK;
+}
+
+}  // namespace
+
+extern "C" size_t ctrlv_pipeline_workspace_bytes(ctrlv_pipeline* p, const ctrlv_clip_request* r) {
+  Geo g;
+  Layout L;
+  if (validate(p, r, &g) != CTRLV_OK) return 0;
+  if (layout(p, r, g, nullptr, &L) != CTRLV_OK) return 0;
+  return L.total;
+}
+
+extern "C" int ctrlv_pipeline_generate(ctrlv_pipeline* p, const ctrlv_clip_request* r, void* ws, size_t ws_bytes,
+                                       ctrlv_stream_t stream) {
+  Geo g;
+  Layout L;
+  CTRLV_TRY(validate(p, r, &g));
+  CTRLV_TRY(layout(p, r, g, nullptr, &L));
+  CTRLV_TRY(check_workspace("pipeline_generate", "ctrlv_pipeline_workspace_bytes", ws, ws_bytes, L.total));
+  return run_clip(p, r, nullptr, g, nullptr, L, ws, stream);
+}
+
+extern "C" size_t ctrlv_pipeline_boxes_workspace_bytes(ctrlv_pipeline* p, const ctrlv_clip_request* r,
+                                                       const ctrlv_box_condition* bc) {
+  Geo g;
+  BoxGeo bx;
+  Layout L;
+  if (validate_boxes(p, r, bc, &g, &bx) != CTRLV_OK) return 0;
+  if (layout(p, r, g, &bx, &L) != CTRLV_OK) return 0;
+  return L.total;
+}
+
+extern "C" int ctrlv_pipeline_predict_boxes(ctrlv_pipeline* p, const ctrlv_clip_request* r, const ctrlv_box_condition* bc, void* ws,
+                                            size_t ws_bytes, ctrlv_stream_t stream) {
+  Geo g;
+  BoxGeo bx;
+  Layout L;
+  CTRLV_TRY(validate_boxes(p, r, bc, &g, &bx));
+  CTRLV_TRY(layout(p, r, g, &bx, &L));
+  CTRLV_TRY(check_workspace("pipeline_predict_boxes", "ctrlv_pipeline_boxes_workspace_bytes", ws, ws_bytes, L.total));
+  return run_clip(p, r, bc, g, &bx, L, ws, stream);
+}
+
+extern "C" size_t ctrlv_pipeline_chain_workspace_bytes(ctrlv_pipeline* boxes, ctrlv_pipeline* video,
+                                                       const ctrlv_two_stage_request* q) {
+  Chain c;
+  return plan_chain(boxes, video, q, &c) == CTRLV_OK ? c.total : 0;
+}
+
+extern "C" int ctrlv_pipeline_boxes_to_video(ctrlv_pipeline* boxes, ctrlv_pipeline* video, const ctrlv_two_stage_request* q,
+                                             void* ws, size_t ws_bytes, ctrlv_stream_t stream) {
+  Chain c;
+  CTRLV_TRY(plan_chain(boxes, video, q, &c));
+  CTRLV_TRY(check_workspace("pipeline_boxes_to_video", "ctrlv_pipeline_chain_workspace_bytes", ws, ws_bytes, c.total));
+  char* base = (char*)ws;
+  if (!c.boxes.out_frames) c.boxes.out_frames = base + c.frames;
+  c.video.cond = base + c.cond;
+  // the three calls a host would make by hand; the two stages' own workspaces share one region
+  CTRLV_TRY(run_clip(boxes, &c.boxes, &q->box_cond, c.gb, &c.bx, c.Lb, base + c.stage, stream));
+  CTRLV_TRY(ctrlv_box_frames_post(c.boxes.out_frames, c.gb.B, c.gb.F, c.gb.H, c.gb.W, q->clean_threshold, nullptr, base + c.cond,
+                                  q->out_box_frames_u8, base + c.post, c.post_bytes, stream));
+  return run_clip(video, &c.video, nullptr, c.gv, nullptr, c.Lv, base + c.stage, stream);
 }

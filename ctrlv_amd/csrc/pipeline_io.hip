@@ -189,6 +189,48 @@ __global__ void lmi_cond_kernel(const el_t* __restrict__ first, el_t* __restrict
   lmi[bf * 2 * per + per + cs] = cond ? first[(long)b * per + cs] : (el_t)0;
 }
 
+// The box predictor's overwrite of the conditioning channels: the `take` frames j of every clip -- frame j for j < K, frame F - 1
+// for the one behind them -- come from src (dtype 0 / 1 / 2, src_frames frames per clip, the taken frames packed in front when
+// `compact`) and land in the conditional half only: the unconditional half keeps lmi_cond_kernel's zeros.
+__global__ void lmi_boxes_kernel(const void* __restrict__ src, int dtype, int src_frames, int compact, el_t* __restrict__ lmi,
+                                 int B, int F, int K, int take, int c_lat, int hw, int cfg) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;          // over (b, j, c, s)
+  const long per = (long)c_lat * hw, total = (long)B * take * per;
+  if (i >= total) return;
+  const long cs = i % per, bj = i / per;
+  const int j = (int)(bj % take), b = (int)(bj / take);
+  const int f = j < K ? j : F - 1;
+  const el_t v = f32_to_el(pio_load(src, dtype, ((long)b * src_frames + (compact ? j : f)) * per + cs));
+  const long bf = ((long)(cfg ? B : 0) + b) * F + f;
+  lmi[bf * 2 * per + per + cs] = v;
+}
+
+// x [n] elements clamped to [-1, 1] in place (torch.clamp: a NaN stays); eight elements per thread where the base is 16-byte
+// aligned, the last n % 8 -- or everything, from an unaligned base -- one by one
+__device__ __forceinline__ el_t clamp_unit(el_t e) {
+  const float v = el_to_f32(e);
+  return v < -1.0f ? f32_to_el(-1.0f) : (v > 1.0f ? f32_to_el(1.0f) : e);
+}
+
+__global__ void clamp_frames_kernel(el_t* __restrict__ x, long n, int vec) {
+  const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (vec) {
+    const long i0 = g * 8;
+    if (i0 + 8 <= n) {
+      uint4 q = *(const uint4*)(x + i0);
+      uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        w[k] = (uint32_t)clamp_unit((el_t)(w[k] & 0xffffu)) | ((uint32_t)clamp_unit((el_t)(w[k] >> 16)) << 16);
+      *(uint4*)(x + i0) = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {
+      for (long i = i0; i < n; ++i) x[i] = clamp_unit(x[i]);
+    }
+  } else if (g < n) {
+    x[g] = clamp_unit(x[g]);
+  }
+}
+
 __global__ void lmi_scatter_kernel(const el_t* __restrict__ scaled, el_t* __restrict__ lmi, long n_half, long per, int cfg) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;          // over (b, f, c, s) of `scaled`
   if (i >= n_half) return;
@@ -324,6 +366,23 @@ int ctrlv_pio_lmi_cond(const void* first, void* lmi, int B, int F, int c_lat, in
   const long total = (long)(cfg ? 2 : 1) * B * F * c_lat * hw;
   hipLaunchKernelGGL(lmi_cond_kernel, dim3(blocks_for(total)), dim3(256), 0, s, (const el_t*)first, (el_t*)lmi, B, F, c_lat, hw,
                      cfg);
+  CTRLV_LAUNCH_CHECK();
+  return CTRLV_OK;
+}
+
+int ctrlv_pio_lmi_boxes(const void* src, int src_dtype, int src_frames, int compact, void* lmi, int B, int F, int K, int c_lat,
+                        int hw, int cfg, hipStream_t s) {
+  const int take = K + 1 < F ? K + 1 : F;
+  const long total = (long)B * take * c_lat * hw;
+  hipLaunchKernelGGL(lmi_boxes_kernel, dim3(blocks_for(total)), dim3(256), 0, s, src, src_dtype, src_frames, compact, (el_t*)lmi,
+                     B, F, K, take, c_lat, hw, cfg);
+  CTRLV_LAUNCH_CHECK();
+  return CTRLV_OK;
+}
+
+int ctrlv_pio_clamp_frames(void* x, long n, hipStream_t s) {
+  const int vec = ((uintptr_t)x & 15) == 0 ? 1 : 0;
+  hipLaunchKernelGGL(clamp_frames_kernel, dim3(blocks_for(vec ? (n + 7) / 8 : n)), dim3(256), 0, s, (el_t*)x, n, vec);
   CTRLV_LAUNCH_CHECK();
   return CTRLV_OK;
 }

@@ -904,3 +904,56 @@ def frames_to_u8(frames):
     out = torch.empty(m, H, W, 3, dtype=torch.uint8, device=frames.device)
     check(_L(frames).ctrlv_frames_to_u8(_p(frames), m, H, W, _p(out), _stream()), "ctrlv_frames_to_u8")
     return out
+
+
+def _out_arg(arg, shape, dtype, device, fn, name):
+    """True: a fresh tensor; a tensor: that one (dense, of the shape and type); None / False: not asked for."""
+    if arg is None or arg is False:
+        return None
+    if arg is True:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if tuple(arg.shape) != tuple(shape) or arg.dtype != dtype or arg.device != device:
+        raise ValueError(f"{fn}: {name} must be {tuple(shape)} {dtype} on {device}")
+    _need_dense(fn, **{name: arg})
+    return arg
+
+
+def box_frames_post(frames, num_frames, threshold=50.0, pt=True, cond=True, u8=True):
+    """Decoded box frames (n F, 3, H, W) fp16 / bf16 -> (pt, cond, u8) (ctrlv_box_frames_post), each None unless asked for
+    (True, or a dense tensor to write into): pt = clamp(x / 2 + 0.5, 0, 1) and cond = 2 * (pt - 0.5), (n F, 3, H, W) in the
+    element type, every operation rounded; u8 (n, F, 3, H, W) uint8 = the cleaned frames of eval_overall.py:96-105 -- pixels
+    with channel sum < threshold and interior frames without such a pixel zeroed, the rest truncated.  No host sync."""
+    fn = "box_frames_post"
+    _need_gpu(frames, "frames")
+    if frames.dim() != 4 or frames.shape[1] != 3 or frames.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"{fn}: frames must be (n F, 3, H, W) fp16 / bf16")
+    F = int(num_frames)
+    m, _, H, W = frames.shape
+    if F < 1 or m % F:
+        raise ValueError(f"{fn}: {m} frames are not clips of {F}")
+    _need_dense(fn, frames=frames)
+    n, dev = m // F, frames.device
+    pt = _out_arg(pt, (m, 3, H, W), frames.dtype, dev, fn, "pt")
+    cond = _out_arg(cond, (m, 3, H, W), frames.dtype, dev, fn, "cond")
+    u8 = _out_arg(u8, (n, F, 3, H, W), torch.uint8, dev, fn, "u8")
+    lib = _L(frames)
+    ws = torch.empty(lib.ctrlv_box_frames_post_ws_bytes(n, F), dtype=torch.uint8, device=dev) if u8 is not None else None
+    check(lib.ctrlv_box_frames_post(_p(frames), n, F, H, W, float(threshold), _p(pt), _p(cond), _p(u8), _p(ws),
+                                    ws.numel() if ws is not None else 0, _stream()), "ctrlv_box_frames_post")
+    return pt, cond, u8
+
+
+def mask_counts(gt_u8, pred_u8, out=None):
+    """gt_u8, pred_u8 (n, F, 3, H, W) uint8 -> int64 (n, 2, 3) on the device (ctrlv_mask_counts): per clip {gt area, pred
+    area, intersection} of the any-channel-nonzero masks, over all frames and over the frames {0, F - 1}."""
+    fn = "mask_counts"
+    _need_gpu(gt_u8, "gt_u8")
+    if gt_u8.dim() != 5 or gt_u8.shape[2] != 3 or gt_u8.dtype != torch.uint8:
+        raise ValueError(f"{fn}: gt_u8 must be (n, F, 3, H, W) uint8")
+    if tuple(pred_u8.shape) != tuple(gt_u8.shape) or pred_u8.dtype != torch.uint8 or pred_u8.device != gt_u8.device:
+        raise ValueError(f"{fn}: pred_u8 must be uint8 {tuple(gt_u8.shape)} on {gt_u8.device}")
+    _need_dense(fn, gt_u8=gt_u8, pred_u8=pred_u8)
+    n, F, _, H, W = gt_u8.shape
+    out = _out_arg(True if out is None else out, (n, 2, 3), torch.int64, gt_u8.device, fn, "out")
+    check(_lib.load().ctrlv_mask_counts(_p(gt_u8), _p(pred_u8), n, F, H, W, _p(out), _stream()), "ctrlv_mask_counts")
+    return out

@@ -245,14 +245,16 @@ def resolve_pretrained_dir(name_or_path):
 PLAN_ROUTE_OUTPUTS = ("np", "pt", "pil", "latent")
 
 
-def pipeline_route(image, callback_on_step_end, output_type, plans_serve, env=None):
-    """Which route a pipeline call takes: "plan" (the whole clip as ONE C call, ctrlv_pipeline_generate through
-    plan.PipelinePlan) or "python" (prepare_clip -> _denoise -> finish_clip, the default).  Pure host logic.  "plan" is opt-in
-    -- CTRLV_PIPELINE=plan -- and taken only for a PIL image (or a non-empty list of PIL images), without a
-    callback_on_step_end, with output_type np / pt / pil / latent, and where the VAE, CLIP and model plans all serve the call
-    (`plans_serve`: a bool or a callable asked last)."""
+def pipeline_route(image, callback_on_step_end, output_type, plans_serve, env=None, bbox_images=None):
+    """Which route a pipeline call takes: "plan" (the whole clip as ONE C call, ctrlv_pipeline_generate -- with `bbox_images`
+    ctrlv_pipeline_predict_boxes -- through plan.PipelinePlan) or "python" (prepare_clip -> _denoise -> finish_clip, the
+    default).  Pure host logic.  "plan" is opt-in -- CTRLV_PIPELINE=plan -- and taken only for a PIL image (or a non-empty list
+    of PIL images), without a callback_on_step_end, with output_type np / pt / pil / latent, with box frames that are a tensor
+    (or none), and where the VAE, CLIP and model plans all serve the call (`plans_serve`: a bool or a callable asked last)."""
     env = os.environ if env is None else env
     if env.get("CTRLV_PIPELINE") != "plan":
+        return "python"
+    if bbox_images is not None and not torch.is_tensor(bbox_images):
         return "python"
     if PIL is None:
         return "python"
@@ -612,15 +614,17 @@ class SVDPipelineBase:
     def _generate_plan(self, image, cond_images, check, *, height, width, num_frames, decode_chunk_size, fps, motion_bucket_id,
                        noise_aug_strength, num_videos_per_prompt, generator, latents, latent_channels, min_guidance_scale,
                        max_guidance_scale, num_inference_steps, control_condition_scale, output_type, return_dict,
-                       callback_on_step_end):
-        """The call through ctrlv_pipeline_generate, or None where the route is not taken (nothing has been drawn or changed
+                       callback_on_step_end, bbox_images=None, num_cond_bbox_frames=3):
+        """The call through ctrlv_pipeline_generate -- with `bbox_images` (the box predictor: a pipeline without a ControlNet)
+        through ctrlv_pipeline_predict_boxes --, or None where the route is not taken (nothing has been drawn or changed
         then).  The PIL Lanczos resize to the working size and the two random draws stay here, in the reference's order
         (augmentation noise first, latents second); CLIP sees the working-size image."""
         if num_videos_per_prompt != 1 or (cond_images is not None and not torch.is_tensor(cond_images)):
             return None
-        if getattr(self, "controlnet", None) is not None and cond_images is None:
+        if getattr(self, "controlnet", None) is not None and (cond_images is None or bbox_images is not None):
             return None
-        if pipeline_route(image, callback_on_step_end, output_type, lambda: self._pipeline_plan() is not None) != "plan":
+        if pipeline_route(image, callback_on_step_end, output_type, lambda: self._pipeline_plan() is not None,
+                          bbox_images=bbox_images) != "plan":
             return None
         pp = self._pipeline_plan()
         unet_cfg = self.unet.config
@@ -636,6 +640,14 @@ class SVDPipelineBase:
             return None
         dev, el = pp.device, pp.dtype
         n = len(arr)
+        boxes = None
+        if bbox_images is not None:
+            K, lat_shape = num_cond_bbox_frames, (n, F, latent_channels // 2, height // 8, width // 8)
+            if tuple(bbox_images.shape) not in ((n, F, 3, height, width), lat_shape) or not 0 <= K <= F:
+                return None                              # (the Python route raises what the reference raises)
+            boxes = bbox_images.to(dev)
+            if boxes.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+                boxes = boxes.float()
         sched = self.scheduler                           # (from here on the route is taken: state changes and draws)
         sched.set_timesteps(num_inference_steps, device=dev)
         sigmas, timesteps = list(sched._sigmas_host), list(sched._timesteps_host)
@@ -652,7 +664,9 @@ class SVDPipelineBase:
         fe = self.feature_extractor
         mean, std = getattr(fe, "image_mean", None), getattr(fe, "image_std", None)
         want_frames = output_type != "latent"
-        out_lat, frames, u8 = pp.generate(
+        run = pp.generate if boxes is None else \
+            (lambda *a, cond, **kw: pp.predict_boxes(*a, boxes, num_cond_bbox_frames, **kw))
+        out_lat, frames, u8 = run(
             image_u8, lat.float(), sigmas, timesteps, cond=cond, aug_noise=aug, noise_aug_strength=noise_aug_strength, fps=fps,
             motion_bucket_id=motion_bucket_id, min_guidance=min_guidance_scale, max_guidance=max_guidance_scale,
             conditioning_scale=control_condition_scale, decode_chunk=chunk, clip_mean=mean, clip_std=std,

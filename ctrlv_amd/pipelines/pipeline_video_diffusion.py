@@ -55,15 +55,16 @@ class VideoDiffusionPipeline(SVDPipelineBase):
         return_dict: bool = True,
         num_cond_bbox_frames: int = 3,
     ):
-        # opt-in (CTRLV_PIPELINE=plan): the whole clip as one C call where the plans serve it (pipeline_utils.pipeline_route)
+        # opt-in (CTRLV_PIPELINE=plan): the whole clip as one C call where the plans serve it (pipeline_utils.pipeline_route);
+        # with tensor bbox_images that call is ctrlv_pipeline_predict_boxes
         done = self._generate_plan(
             image, None, lambda h, w: self.check_inputs(image, h, w), height=height, width=width, num_frames=num_frames,
             decode_chunk_size=decode_chunk_size, fps=fps, motion_bucket_id=motion_bucket_id,
             noise_aug_strength=noise_aug_strength, num_videos_per_prompt=num_videos_per_prompt, generator=generator,
             latents=latents, latent_channels=self.unet.config.in_channels, min_guidance_scale=min_guidance_scale,
             max_guidance_scale=max_guidance_scale, num_inference_steps=num_inference_steps, control_condition_scale=1.0,
-            output_type=output_type, return_dict=return_dict,
-            callback_on_step_end=callback_on_step_end) if bbox_images is None else None
+            output_type=output_type, return_dict=return_dict, callback_on_step_end=callback_on_step_end,
+            bbox_images=bbox_images, num_cond_bbox_frames=num_cond_bbox_frames)
         if done is not None:
             return done
         job = self.prepare_clip(

@@ -418,46 +418,116 @@ class PipelinePlan(_Handle):
         return self._nonzero(self._lib.ctrlv_pipeline_workspace_bytes(self._h, ctypes.byref(request)),
                              "ctrlv_pipeline_workspace_bytes")
 
+    def _checked_request(self, who, image_u8, latents, sigmas, timesteps, cond, cond_name, aug_noise, frames, frames_u8, **kw):
+        """Validate the tensors of a generate / predict_boxes call, allocate the outputs and build the request around them.
+        `cond` is the ControlNet condition of generate or the box frames of predict_boxes (which do not enter the request).
+        Returns (request, keep, cond, (out_latents, out_frames, out_frames_u8))."""
+        dev = self.device
+        for name, t in (("image_u8", image_u8), ("latents", latents), (cond_name, cond), ("aug_noise", aug_noise)):
+            if t is not None and (not t.is_cuda or (t.device.index or 0) != (dev.index or 0)):
+                raise ValueError(f"PipelinePlan.{who}: {name} on {t.device}, the plans' weights on {dev}")
+        if image_u8.dtype != torch.uint8 or image_u8.dim() != 4 or image_u8.shape[3] != 3:
+            raise ValueError(f"PipelinePlan.{who}: image_u8 must be (n, H, W, 3) uint8")
+        if latents.dtype != torch.float32 or latents.dim() != 5:
+            raise ValueError(f"PipelinePlan.{who}: latents must be fp32 (n, F, L, h, w)")
+        n, H, W, _ = image_u8.shape
+        F = latents.shape[1]
+        if tuple(latents.shape) != (n, F, latents.shape[2], H // 8, W // 8):
+            raise ValueError(f"PipelinePlan.{who}: latents {tuple(latents.shape)} do not match a {n} x {H} x {W} image")
+        if cond is not None:
+            want = (n, F, 3, H, W) if cond.dim() == 5 and cond.shape[2] == 3 else (n, F, latents.shape[2], H // 8, W // 8)
+            if tuple(cond.shape) != want or cond.dtype not in _DT:
+                raise ValueError(f"PipelinePlan.{who}: {cond_name} {tuple(cond.shape)} must be {want} in fp32 / fp16 / bf16")
+            cond = cond.contiguous()
+        if aug_noise is not None:
+            if aug_noise.dtype != torch.float32 or tuple(aug_noise.shape) != (n, 3, H, W):
+                raise ValueError(f"PipelinePlan.{who}: aug_noise must be fp32 {(n, 3, H, W)}")
+            aug_noise = aug_noise.contiguous()
+        image_u8, latents = image_u8.contiguous(), latents.contiguous()
+        out_lat = torch.empty_like(latents)
+        out_fr = torch.empty(n * F, 3, H, W, dtype=self.dtype, device=dev) if frames else None
+        out_u8 = torch.empty(n, F, H, W, 3, dtype=torch.uint8, device=dev) if frames_u8 else None
+        r, keep = self.request(image_u8, latents, sigmas, timesteps, cond=cond if cond_name == "cond" else None,
+                               aug_noise=aug_noise, out_latents=out_lat, out_frames=out_fr, out_frames_u8=out_u8, **kw)
+        return r, keep, cond, (out_lat, out_fr, out_u8)
+
+    def _workspace(self, need):
+        if self._ws is None or self._ws.numel() < need or self._ws.device != self.device:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws
+
     def generate(self, image_u8, latents, sigmas, timesteps, *, cond=None, aug_noise=None, frames=True, frames_u8=True, **kw):
         """image_u8 (n, H, W, 3) uint8 at the working size; latents fp32 (n, F, L, h, w) already multiplied by
         init_noise_sigma; sigmas [steps + 1] / timesteps [steps]: the scheduler's values (host floats); cond (n, F, 3, H, W)
         pixels or (n, F, L, h, w) latents; aug_noise fp32 (n, 3, H, W) or None; the other fields of `request` by keyword.
         Everything on the plan's device, enqueued on torch's current stream.  Returns (latents fp32, frames (n F, 3, H, W) in
         the element type or None, frames_u8 (n, F, H, W, 3) or None)."""
-        dev = self.device
-        for name, t in (("image_u8", image_u8), ("latents", latents), ("cond", cond), ("aug_noise", aug_noise)):
-            if t is not None and (not t.is_cuda or (t.device.index or 0) != (dev.index or 0)):
-                raise ValueError(f"PipelinePlan.generate: {name} on {t.device}, the plans' weights on {dev}")
-        if image_u8.dtype != torch.uint8 or image_u8.dim() != 4 or image_u8.shape[3] != 3:
-            raise ValueError("PipelinePlan.generate: image_u8 must be (n, H, W, 3) uint8")
-        if latents.dtype != torch.float32 or latents.dim() != 5:
-            raise ValueError("PipelinePlan.generate: latents must be fp32 (n, F, L, h, w)")
-        n, H, W, _ = image_u8.shape
-        F = latents.shape[1]
-        if tuple(latents.shape) != (n, F, latents.shape[2], H // 8, W // 8):
-            raise ValueError(f"PipelinePlan.generate: latents {tuple(latents.shape)} do not match a {n} x {H} x {W} image")
-        if cond is not None:
-            want = (n, F, 3, H, W) if cond.dim() == 5 and cond.shape[2] == 3 else (n, F, latents.shape[2], H // 8, W // 8)
-            if tuple(cond.shape) != want or cond.dtype not in _DT:
-                raise ValueError(f"PipelinePlan.generate: cond {tuple(cond.shape)} must be {want} in fp32 / fp16 / bf16")
-            cond = cond.contiguous()
-        if aug_noise is not None:
-            if aug_noise.dtype != torch.float32 or tuple(aug_noise.shape) != (n, 3, H, W):
-                raise ValueError(f"PipelinePlan.generate: aug_noise must be fp32 {(n, 3, H, W)}")
-            aug_noise = aug_noise.contiguous()
-        image_u8, latents = image_u8.contiguous(), latents.contiguous()
-        out_lat = torch.empty_like(latents)
-        out_fr = torch.empty(n * F, 3, H, W, dtype=self.dtype, device=dev) if frames else None
-        out_u8 = torch.empty(n, F, H, W, 3, dtype=torch.uint8, device=dev) if frames_u8 else None
-        r, keep = self.request(image_u8, latents, sigmas, timesteps, cond=cond, aug_noise=aug_noise, out_latents=out_lat,
-                               out_frames=out_fr, out_frames_u8=out_u8, **kw)
-        need = self.workspace_bytes(r)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        check(self._lib.ctrlv_pipeline_generate(self._h, ctypes.byref(r), self._ws.data_ptr(), self._ws.numel(), self._stream()),
+        r, keep, cond, out = self._checked_request("generate", image_u8, latents, sigmas, timesteps, cond, "cond", aug_noise,
+                                                   frames, frames_u8, **kw)
+        ws = self._workspace(self.workspace_bytes(r))
+        check(self._lib.ctrlv_pipeline_generate(self._h, ctypes.byref(r), ws.data_ptr(), ws.numel(), self._stream()),
               "ctrlv_pipeline_generate")
         del keep
-        return out_lat, out_fr, out_u8
+        return out
+
+    @staticmethod
+    def box_condition(bbox_frames, num_cond_frames):
+        """The `ctrlv_box_condition` of (n, F, 3, H, W) box pixels or (n, F, L, h, w) box latents (contiguous, fp32 / fp16 /
+        bf16); keep the tensor alive beside it."""
+        bc = _lib.BoxCondition()
+        bc.frames, bc.channels, bc.dtype = bbox_frames.data_ptr(), bbox_frames.shape[2], _DT[bbox_frames.dtype]
+        bc.num_cond_frames = int(num_cond_frames)
+        return bc
+
+    def predict_boxes(self, image_u8, latents, sigmas, timesteps, bbox_frames, num_cond_frames=3, *, aug_noise=None, frames=True,
+                      frames_u8=True, **kw):
+        """The box predictor (ctrlv_pipeline_predict_boxes; a plan without a ControlNet): `generate` with the conditioning
+        channels of frames [0, num_cond_frames) and F - 1 overwritten by bbox_frames -- (n, F, 3, H, W) pixels in [-1, 1], VAE
+        encoded, or (n, F, L, h, w) latents -- and the decoded frames clamped to [-1, 1].  Same returns as `generate`."""
+        if bbox_frames is None:
+            raise ValueError("PipelinePlan.predict_boxes: bbox_frames is None")
+        r, keep, boxes, out = self._checked_request("predict_boxes", image_u8, latents, sigmas, timesteps, bbox_frames,
+                                                    "bbox_frames", aug_noise, frames, frames_u8, **kw)
+        bc = self.box_condition(boxes, num_cond_frames)
+        need = self._nonzero(self._lib.ctrlv_pipeline_boxes_workspace_bytes(self._h, ctypes.byref(r), ctypes.byref(bc)),
+                             "ctrlv_pipeline_boxes_workspace_bytes")
+        ws = self._workspace(need)
+        check(self._lib.ctrlv_pipeline_predict_boxes(self._h, ctypes.byref(r), ctypes.byref(bc), ws.data_ptr(), ws.numel(),
+                                                     self._stream()), "ctrlv_pipeline_predict_boxes")
+        del keep, boxes
+        return out
+
+
+def boxes_to_video(boxes_plan, video_plan, image_u8, box_latents, video_latents, box_schedule, video_schedule, bbox_frames,
+                   num_cond_frames=3, *, box_aug_noise=None, video_aug_noise=None, clean_threshold=50.0, box_frames_u8=True,
+                   frames=True, frames_u8=True, box_kw=None, video_kw=None):
+    """The chain as one C call (ctrlv_pipeline_boxes_to_video): `boxes_plan.predict_boxes`, `ops.box_frames_post`, then
+    `video_plan.generate` conditioned on the predicted box frames.  box_schedule / video_schedule: (sigmas, timesteps) of the
+    two stages; box_kw / video_kw: the other request fields of each stage (see PipelinePlan.request).  Returns (video latents
+    fp32, video frames or None, video frames_u8 or None, cleaned box frames (n, F, 3, H, W) uint8 or None)."""
+    if boxes_plan._lib is not video_plan._lib:
+        raise ValueError("boxes_to_video: the two pipeline plans must come from one library (one element type)")
+    if bbox_frames is None:
+        raise ValueError("boxes_to_video: bbox_frames is None")
+    rb, keep_b, boxes, _ = boxes_plan._checked_request("boxes_to_video", image_u8, box_latents, *box_schedule, bbox_frames,
+                                                       "bbox_frames", box_aug_noise, False, False, **(box_kw or {}))
+    rv, keep_v, _, out = video_plan._checked_request("boxes_to_video", image_u8, video_latents, *video_schedule, None, "cond",
+                                                     video_aug_noise, frames, frames_u8, **(video_kw or {}))
+    n, F = box_latents.shape[0], box_latents.shape[1]
+    H, W = image_u8.shape[1], image_u8.shape[2]
+    clean = torch.empty(n, F, 3, H, W, dtype=torch.uint8, device=video_plan.device) if box_frames_u8 else None
+    q = _lib.TwoStageRequest()
+    q.boxes, q.video, q.box_cond = rb, rv, boxes_plan.box_condition(boxes, num_cond_frames)
+    q.out_box_frames_u8 = clean.data_ptr() if clean is not None else None
+    q.clean_threshold = float(clean_threshold)
+    lib = video_plan._lib
+    need = video_plan._nonzero(lib.ctrlv_pipeline_chain_workspace_bytes(boxes_plan._h, video_plan._h, ctypes.byref(q)),
+                               "ctrlv_pipeline_chain_workspace_bytes")
+    ws = video_plan._workspace(need)
+    check(lib.ctrlv_pipeline_boxes_to_video(boxes_plan._h, video_plan._h, ctypes.byref(q), ws.data_ptr(), ws.numel(),
+                                            video_plan._stream()), "ctrlv_pipeline_boxes_to_video")
+    del keep_b, keep_v, boxes
+    return out + (clean,)
 
 
 _VAE_PLANS = {}

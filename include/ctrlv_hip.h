@@ -880,6 +880,73 @@ size_t ctrlv_pipeline_workspace_bytes(ctrlv_pipeline* p, const ctrlv_clip_reques
 int ctrlv_pipeline_generate(ctrlv_pipeline* p, const ctrlv_clip_request* r, void* ws, size_t ws_bytes, ctrlv_stream_t stream);
 int ctrlv_pipeline_destroy(ctrlv_pipeline* p);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * The box predictor and the boxes-to-video chain (tools/eval_overall.py:74-163 of the reference): stage 1 is an SVD UNet that
+ * sees the conditioning image plus the first few and the last bounding-box frames and generates the box frames in between
+ * (pipeline_video_diffusion.py:197-206, 297); the frames are cleaned and remapped; stage 2 is ctrlv_pipeline_generate on a
+ * pipeline with a ControlNet.  Additive entry points: the ABI number does not change, ctrlv_clip_request keeps its layout.
+ * ------------------------------------------------------------------------------------------------------------------ */
+/* The box frames of one predict_boxes call.  Clear the struct before setting fields. */
+typedef struct ctrlv_box_condition {
+  const void* frames;        /* channels 3: (n, F, 3, H, W) pixels in [-1, 1]; channels L: latents (n, F, L, h, w) */
+  int32_t channels, dtype;   /* dtype code as cond_dtype (0 fp32, 1 fp16, 2 bf16) */
+  int32_t num_cond_frames;   /* K in [0, F]: frames [0, K) and frame F-1 are taken */
+  int32_t reserved;          /* must be 0 */
+} ctrlv_box_condition;
+/* Bytes of workspace ctrlv_pipeline_predict_boxes needs; 0 for a request it would refuse (ctrlv_last_error). */
+size_t ctrlv_pipeline_boxes_workspace_bytes(ctrlv_pipeline* p, const ctrlv_clip_request* r, const ctrlv_box_condition* bc);
+/* ctrlv_pipeline_generate on a pipeline WITHOUT a ControlNet and a request WITHOUT cond (either is CTRLV_E_BAD_ARG, named, before
+ * any launch; the request is otherwise validated as generate validates it), with two differences:
+ *   - after the image's latent has been repeated over the frames as the conditioning channels (step 2), those channels of frames
+ *     [0, K) and F - 1 of every clip are overwritten in the conditional half: with the VAE mode latents (scale 1) of the 3-channel
+ *     box frames, or with the latents as given, rounded to the element type.  With guidance on the unconditional half stays
+ *     zero (the reference writes cat[zeros, cond] there).  Only the min(K + 1, F) taken frames are encoded; the encoder treats
+ *     every image on its own, so the bits are those of encoding all F;
+ *   - out_frames, when asked for, is clamped to [-1, 1].  out_frames_u8 is unchanged by the clamp: ctrlv_frames_to_u8 already
+ *     clamps x / 2 + 0.5 to [0, 1], which is the same function of x.
+ * CTRLV_E_BAD_ARG: reserved != 0, frames NULL; CTRLV_E_BAD_SHAPE: channels not 3 / L, K outside [0, F]; CTRLV_E_BAD_DTYPE. */
+int ctrlv_pipeline_predict_boxes(ctrlv_pipeline* p, const ctrlv_clip_request* r, const ctrlv_box_condition* bc, void* ws,
+                                 size_t ws_bytes, ctrlv_stream_t stream);
+
+/* Between the stages (csrc/box_frames.hip; eval_overall.py:96-105, 154 and tensor2vid(..., "pt")).  frames (n F, 3, H, W)
+ * elements as decoded; any of the three outputs may be NULL (all three: CTRLV_E_BAD_ARG).  One pass over the frames; every
+ * value stays on the device and nothing synchronises with the host, so the call can be captured into a graph.
+ *   out_pt   (n F, 3, H, W) elements: y = clamp(x / 2 + 0.5, 0, 1), each operation rounded to the element type
+ *   out_cond (n F, 3, H, W) elements: 2 * (y - 0.5), each operation rounded (not the identity on x in fp16)
+ *   out_u8   (n, F, 3, H, W) uint8: v = (float) y * 255 in fp32; a pixel whose channel sum (v0 + v1) + v2 is < threshold is
+ *            zeroed; an interior frame 1 .. F-2 of a clip whose MINIMUM channel sum over all pixels is > threshold is zeroed
+ *            whole (frames 0 and F-1 never are); the rest is truncated to uint8 as numpy's astype does.
+ * ws: ctrlv_box_frames_post_ws_bytes(n, F) bytes, 4-byte aligned, needed with out_u8 only: the per-frame minimum (an atomic
+ * minimum on the bits of the non-negative sums).  16-byte accesses where H W is a multiple of 16 and the pointers are aligned. */
+size_t ctrlv_box_frames_post_ws_bytes(int n, int F);
+int ctrlv_box_frames_post(const void* frames, int n, int F, int H, int W, float threshold, void* out_pt, void* out_cond,
+                          void* out_u8, void* ws, size_t ws_bytes, ctrlv_stream_t stream);
+/* binary_mask_iou's counts (src/ctrlv/metrics/FandJ.py:11-23) of gt_u8 and pred_u8, both (n, F, 3, H, W) uint8: a pixel is in a
+ * mask when any of its channels is nonzero.  counts: DEVICE (n, 2, 3) 64-bit -- per clip {gt area, pred area, intersection}
+ * over all F frames, then over the frames {0, F-1} (a one-frame clip counts its frame once).  Integers: the metric formed from
+ * them on the host is exact. */
+int ctrlv_mask_counts(const void* gt_u8, const void* pred_u8, int n, int F, int H, int W, unsigned long long* counts,
+                      ctrlv_stream_t stream);
+
+/* The chain as one call.  Clear the struct before setting fields. */
+typedef struct ctrlv_two_stage_request {
+  ctrlv_clip_request boxes;          /* stage 1 (no cond); out_frames may be NULL: the frames then live in the workspace */
+  ctrlv_box_condition box_cond;
+  ctrlv_clip_request video;          /* cond must be NULL on entry: the driver supplies stage 1's frames (3 channels, element dtype) */
+  void* out_box_frames_u8;           /* cleaned (n, F, 3, H, W), or NULL */
+  float clean_threshold;             /* the reference's 50 */
+  int32_t reserved;                  /* must be 0 */
+} ctrlv_two_stage_request;
+/* 0 for a request the call would refuse (ctrlv_last_error). */
+size_t ctrlv_pipeline_chain_workspace_bytes(ctrlv_pipeline* boxes, ctrlv_pipeline* video, const ctrlv_two_stage_request* q);
+/* In order: ctrlv_pipeline_predict_boxes on `boxes` (no ControlNet), ctrlv_box_frames_post (out_cond -> stage 2's condition,
+ * out_u8 -> out_box_frames_u8), ctrlv_pipeline_generate on `video` (with a ControlNet).  Nothing else: the bits are those of the
+ * three calls made by hand.  Stage 1's frames and the condition live in `ws`, the stages' own workspaces alias.  Refused by
+ * name before any launch: pipelines of another library or on different devices, requests of different geometry, video.cond
+ * set, a video pipeline without a ControlNet, and whatever the two stages refuse. */
+int ctrlv_pipeline_boxes_to_video(ctrlv_pipeline* boxes, ctrlv_pipeline* video, const ctrlv_two_stage_request* q, void* ws,
+                                  size_t ws_bytes, ctrlv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

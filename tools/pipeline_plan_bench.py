@@ -11,6 +11,11 @@ the step counts (what a step adds, without the per-clip work around the loop).  
 tool under one `timeout`.
 
     timeout -k 10 900 python tools/pipeline_plan_bench.py [--steps 25 --steps-lo 5 --rounds 3]
+
+`--boxes` times the two-stage chain instead (boxes_main below): image + first / last box frames -> video as ONE C call against
+the two Python pipeline calls with host numpy in between; the record goes to profiles/box_chain_bench.jsonl.
+
+    timeout -k 10 900 python tools/pipeline_plan_bench.py --boxes [--height 320 --width 512 --steps 25 --rounds 3]
 """
 import argparse
 import json
@@ -56,9 +61,105 @@ def build_pipe(frames, clip_layers):
     return pipe
 
 
+def host_between(bbox_im, threshold):
+    """What a Python host does between the two pipeline calls (the reference's eval_overall.py:96-105, 154): the [0, 1] box
+    frames (F, 3, H, W) come to the host, dark pixels and box-less interior frames are zeroed in numpy and the result is
+    truncated to bytes; the condition of stage 2 is formed on the device."""
+    v = bbox_im.detach().float().cpu().numpy() * 255
+    total = v.sum(axis=1)
+    v[np.repeat((total < threshold)[:, None], 3, axis=1)] = 0
+    for f in range(1, v.shape[0] - 1):
+        if v[f].sum(axis=0).min() > threshold:
+            v[f] = 0
+    return v.astype(np.uint8), 2 * (bbox_im - 0.5).unsqueeze(0)
+
+
+def boxes_main(args):
+    """--boxes: image + first / last box frames -> video.  `chain`: ONE C call (plan.boxes_to_video: box predictor, the
+    kernels between the stages, Box2Video) against `python`: VideoDiffusionPipeline, host numpy, StableVideoControlPipeline --
+    two Python pipeline calls with their HIP graphs.  Same device, one process, alternated `--rounds` times after one warm
+    call each; host clock around synchronised calls that end with the video's and the cleaned box frames' bytes on the host."""
+    import __graft_entry__ as g
+    g.build()
+    from PIL import Image
+    from ctrlv_amd import plan as plan_mod
+    from ctrlv_amd.models import UNetSpatioTemporalConditionModel
+    from ctrlv_amd.pipelines import VideoDiffusionPipeline
+    from ctrlv_amd.pipelines.pipeline_utils import randn_tensor
+    from ctrlv_amd.utils import build_on_device, random_init_
+    os.environ["CTRLV_VAE_HIP"] = "plan"
+    os.environ["CTRLV_CLIP_HIP"] = "plan"
+    os.environ.pop("CTRLV_PIPELINE", None)
+    H, W, F, K, steps, thr = args.height, args.width, args.frames, args.cond_frames, args.steps, 50.0
+    video = build_pipe(F, args.clip_layers)
+    box_unet = build_on_device(UNetSpatioTemporalConditionModel, DEV, num_frames=F)
+    random_init_(box_unet, seed=2)
+    boxes_pipe = VideoDiffusionPipeline(video.vae, video.image_encoder, box_unet.eval(), video.scheduler, video.feature_extractor)
+    boxes_pipe.set_progress_bar_config(disable=True)
+    gen = torch.Generator().manual_seed(3)
+    image = Image.fromarray(torch.randint(0, 256, (H, W, 3), generator=gen, dtype=torch.uint8).numpy())
+    bbox = (torch.rand(1, F, 3, H, W, generator=gen) * 2 - 1).to(DEV)
+    common = dict(height=H, width=W, num_frames=F, num_inference_steps=steps, decode_chunk_size=F)
+
+    def python_route():
+        bbox_im = boxes_pipe(image, bbox_images=bbox, generator=torch.Generator().manual_seed(7), output_type="pt",
+                             num_cond_bbox_frames=K, **common).frames[0]
+        clean, cond = host_between(bbox_im, thr)
+        frames = video(image, cond_images=cond, generator=torch.Generator().manual_seed(8), output_type="pil", **common).frames
+        return np.stack([np.asarray(im) for im in frames[0]]), clean
+
+    def chain_route():
+        pb, pv = boxes_pipe._pipeline_plan(), video._pipeline_plan()
+        assert pb is not None and pv is not None, "the plans do not serve these pipelines"
+        image_u8 = torch.from_numpy(np.array(image)[None]).to(DEV)
+        sched = video.scheduler
+        sched.set_timesteps(steps, device=DEV)
+        schedule = (list(sched._sigmas_host), list(sched._timesteps_host))
+        draws = []
+        for pipe, seed in ((boxes_pipe, 7), (video, 8)):          # the pipelines' own two draws, in their order
+            gn = torch.Generator().manual_seed(seed)
+            aug = randn_tensor((1, 3, H, W), generator=gn, device=DEV, dtype=torch.float32)
+            draws.append((aug, pipe.prepare_latents(1, F, 8, H, W, pb.dtype, DEV, gn, None).float()))
+        kw = dict(noise_aug_strength=0.02, fps=7, motion_bucket_id=127, min_guidance=1.0, max_guidance=3.0, decode_chunk=F)
+        out = plan_mod.boxes_to_video(pb, pv, image_u8, draws[0][1], draws[1][1], schedule, schedule, bbox, K,
+                                      box_aug_noise=draws[0][0], video_aug_noise=draws[1][0], clean_threshold=thr, box_kw=kw,
+                                      video_kw=dict(kw, conditioning_scale=1.0), frames=False)
+        return out[2][0].cpu().numpy(), out[3][0].cpu().numpy()
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    routes = {"python": python_route, "chain": chain_route}
+    with torch.no_grad():
+        ref = {name: timed(fn)[1] for name, fn in routes.items()}                     # warm
+        times = {name: [] for name in routes}
+        for _ in range(args.rounds):
+            for name, fn in routes.items():
+                times[name].append(timed(fn)[0])
+    diff = float(np.abs(ref["chain"][0].astype(np.float32) - ref["python"][0].astype(np.float32)).mean())
+    clean_diff = float((ref["chain"][1] != ref["python"][1]).mean())
+    rec = dict(tool="pipeline_plan_bench --boxes", size=f"{H}x{W}", frames=F, steps=steps, cond_frames=K, rounds=args.rounds,
+               clip_layers=args.clip_layers, device=torch.cuda.get_device_name(0), mean_abs_byte_difference_video=round(diff, 3),
+               cleaned_box_bytes_that_differ=round(clean_diff, 5))
+    for name in routes:
+        rec[name] = dict(chain_s=round(statistics.median(times[name]), 4), all_chain_s=[round(v, 4) for v in times[name]])
+    rec["chain_over_python"] = round(rec["chain"]["chain_s"] / rec["python"]["chain_s"], 4)
+    print(json.dumps(rec), flush=True)
+    out_path = args.out or os.path.join(ROOT, "profiles", "box_chain_bench.jsonl")
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    with open(out_path, "a") as f:
+        f.write(json.dumps(rec) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pipeline_plan_bench.jsonl"))
+    ap.add_argument("--boxes", action="store_true", help="time the boxes-to-video chain (appends to profiles/box_chain_bench.jsonl)")
+    ap.add_argument("--cond-frames", type=int, default=3, help="--boxes: num_cond_bbox_frames")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--height", type=int, default=576)
     ap.add_argument("--width", type=int, default=1024)
     ap.add_argument("--frames", type=int, default=25)
@@ -67,6 +168,9 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--clip-layers", type=int, default=32)
     args = ap.parse_args()
+    if args.boxes:
+        return boxes_main(args)
+    args.out = args.out or os.path.join(ROOT, "profiles", "pipeline_plan_bench.jsonl")
     if not 2 <= args.steps_lo < args.steps:
         ap.error("2 <= --steps-lo < --steps (the Python loop captures its graph in the second step)")
     import __graft_entry__ as g
