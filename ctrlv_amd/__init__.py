@@ -12,3 +12,5 @@ ctypes; PyTorch only owns device memory, streams and `torch.distributed`.  There
 shared library is missing every forward raises.
 """
 __version__ = "0.1.0"
+
+from .seed import DeviceSeed  # noqa: E402,F401

@@ -138,6 +138,14 @@ class TwoStageRequest(ctypes.Structure):
                 ("clean_threshold", c_float), ("reserved", c_int)]
 
 
+class SeedRequest(ctypes.Structure):
+    """Mirror of `ctrlv_seed_request`."""
+    _fields_ = [("seed", ctypes.c_uint64), ("clip_index0", ctypes.c_uint32), ("call", ctypes.c_uint32),
+                ("src_image_u8", c_void_p), ("src_height", c_int), ("src_width", c_int),
+                ("sigma_min", c_float), ("sigma_max", c_float),
+                ("sigmas_host", ctypes.POINTER(c_float)), ("timesteps_host", ctypes.POINTER(c_float)), ("reserved", c_int)]
+
+
 # name -> (restype, argtypes); lists every symbol include/ctrlv_hip.h declares (tests/test_abi.py checks this)
 SIGNATURES = {
     "ctrlv_abi_version": (c_int, []),
@@ -286,6 +294,18 @@ SIGNATURES = {
     "ctrlv_mask_counts": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "ctrlv_pipeline_chain_workspace_bytes": (c_size_t, [c_void_p, c_void_p, ctypes.POINTER(TwoStageRequest)]),
     "ctrlv_pipeline_boxes_to_video": (c_int, [c_void_p, c_void_p, ctypes.POINTER(TwoStageRequest), c_void_p, c_size_t, c_void_p]),
+    "ctrlv_randn": (c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, c_int, c_size_t, c_float, c_int,
+                            c_void_p, c_int, c_void_p]),
+    "ctrlv_euler_schedule": (c_int, [c_int, c_float, c_float, ctypes.POINTER(c_float), ctypes.POINTER(c_float),
+                                     ctypes.POINTER(ctypes.c_double)]),
+    "ctrlv_resize_lanczos_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "ctrlv_resize_lanczos_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "ctrlv_pipeline_prepare_bytes": (c_size_t, [c_void_p, ctypes.POINTER(ClipRequest), ctypes.POINTER(SeedRequest)]),
+    "ctrlv_pipeline_prepare": (c_int, [c_void_p, ctypes.POINTER(ClipRequest), ctypes.POINTER(SeedRequest),
+                                       ctypes.POINTER(ClipRequest), c_void_p, c_size_t, c_void_p]),
+    "ctrlv_pipeline_seeded_workspace_bytes": (c_size_t, [c_void_p, ctypes.POINTER(ClipRequest), ctypes.POINTER(SeedRequest)]),
+    "ctrlv_pipeline_generate_seeded": (c_int, [c_void_p, ctypes.POINTER(ClipRequest), ctypes.POINTER(SeedRequest), c_void_p,
+                                               c_size_t, c_void_p]),
 }
 
 _libs = {}                # element dtype code (2 bf16 / 1 fp16) -> CDLL
@@ -297,7 +317,8 @@ _NO_STATUS = {"ctrlv_abi_version", "ctrlv_elem_dtype", "ctrlv_build_id", "ctrlv_
               # size queries (size_t: never wrapped, listed with their kin for the reader)
               "ctrlv_gemm_tokens_ws_bytes", "ctrlv_clip_plan_workspace_bytes", "ctrlv_vae_plan_workspace_bytes",
               "ctrlv_pipeline_workspace_bytes", "ctrlv_pipeline_boxes_workspace_bytes", "ctrlv_box_frames_post_ws_bytes",
-              "ctrlv_pipeline_chain_workspace_bytes"}
+              "ctrlv_pipeline_chain_workspace_bytes", "ctrlv_resize_lanczos_ws_bytes", "ctrlv_pipeline_prepare_bytes",
+              "ctrlv_pipeline_seeded_workspace_bytes"}
 
 
 def _status_recorder(lib, fn):

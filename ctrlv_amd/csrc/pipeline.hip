@@ -23,6 +23,7 @@ struct ctrlv_pipeline {
   hipStream_t side = nullptr;            // created by the first generate that overlaps
   hipEvent_t ev_fork = nullptr, ev_res = nullptr;
   std::vector<float> consts;             // host staging of the one upload (timesteps | guidance | added time ids)
+  std::vector<float> sched;              // sigmas | timesteps of a generate_seeded call whose host gave no arrays
 };
 
 namespace {
@@ -523,6 +524,179 @@ extern "C" int ctrlv_pipeline_generate(ctrlv_pipeline* p, const ctrlv_clip_reque
   CTRLV_TRY(layout(p, r, g, nullptr, &L));
   CTRLV_TRY(check_workspace("pipeline_generate", "ctrlv_pipeline_workspace_bytes", ws, ws_bytes, L.total));
   return run_clip(p, r, nullptr, g, nullptr, L, ws, stream);
+}
+
+namespace {
+
+struct Prep {                // ctrlv_pipeline_prepare: the filled request (pointers into prep_ws as offsets from 0) and the layout
+  ctrlv_clip_request filled;
+  size_t resize_ws, resize_bytes, image, aug, lat, total;
+  bool resize, draw_aug, draw_lat, schedule;
+  double init_noise_sigma;
+  Geo g;
+};
+
+// Everything prepare decides on the host.  sig / ts: where a schedule the request asks for is written (the caller's arrays, the
+// pipeline's, or a size query's scratch).  The filled request is validated as generate validates it; what prepare would place
+// in prep_ws stands in as the placeholder `kAlign + offset` until the workspace is known.
+int plan_prepare(const ctrlv_pipeline* p, const ctrlv_clip_request* in, const ctrlv_seed_request* s, float* sig, float* ts, Prep* q) {
+  CTRLV_CHECK_ARG(p != nullptr, "pipeline_prepare: null pipeline");
+  CTRLV_CHECK_ARG(in != nullptr, "pipeline_prepare: null request");
+  CTRLV_CHECK_ARG(s != nullptr, "pipeline_prepare: null seed request");
+  CTRLV_CHECK_ARG(s->reserved == 0, "pipeline_prepare: seed request reserved=%d must be 0", s->reserved);
+  ctrlv_clip_request& f = q->filled;
+  f = *in;
+  q->schedule = in->sigmas == nullptr || in->timesteps == nullptr;
+  if (q->schedule) {
+    CTRLV_CHECK_SHAPE(in->num_steps >= 1 && in->num_steps <= kMaxSteps, "pipeline_prepare: num_steps=%d must be in [1, %d]",
+                      in->num_steps, kMaxSteps);
+    CTRLV_CHECK_ARG(sig != nullptr && ts != nullptr, "pipeline_prepare: the request leaves sigmas / timesteps NULL, and "
+                    "sigmas_host / timesteps_host of the seed request are null (host arrays of num_steps + 1 and num_steps floats)");
+    // into scratch first: a table the caller did set is kept
+    std::vector<float> tmp((size_t)2 * in->num_steps + 1);
+    CTRLV_TRY(ctrlv_euler_schedule(in->num_steps, s->sigma_min, s->sigma_max, tmp.data(), tmp.data() + in->num_steps + 1, nullptr));
+    if (!in->sigmas) {
+      memcpy(sig, tmp.data(), ((size_t)in->num_steps + 1) * sizeof(float));
+      f.sigmas = sig;
+    }
+    if (!in->timesteps) {
+      memcpy(ts, tmp.data() + in->num_steps + 1, (size_t)in->num_steps * sizeof(float));
+      f.timesteps = ts;
+    }
+  }
+  q->init_noise_sigma = sqrt((double)f.sigmas[0] * (double)f.sigmas[0] + 1.0);
+  size_t o = 0;
+  auto take = [&](size_t bytes) { const size_t at = o; o += up(bytes); return at; };
+  auto hold = [](size_t at) { return (const void*)((uintptr_t)kAlign + at); };
+  q->resize = false;
+  q->resize_ws = q->resize_bytes = q->image = q->aug = q->lat = 0;
+  if (s->src_image_u8) {
+    CTRLV_CHECK_ARG(in->image_u8 == nullptr, "pipeline_prepare: image_u8 and src_image_u8 are both set");
+    CTRLV_CHECK_SHAPE(s->src_height > 0 && s->src_width > 0, "pipeline_prepare: src_image_u8 without sizes (src_height=%d, "
+                      "src_width=%d)", s->src_height, s->src_width);
+    if (s->src_height == in->height && s->src_width == in->width) {
+      f.image_u8 = s->src_image_u8;
+    } else {
+      CTRLV_CHECK_SHAPE(in->n_clips >= 1 && in->height > 0 && in->width > 0, "pipeline_prepare: n_clips=%d, height=%d, width=%d "
+                        "must be positive", in->n_clips, in->height, in->width);
+      CTRLV_TRY(ctrlv_resize_lanczos_check(in->n_clips, s->src_height, s->src_width, in->height, in->width));
+      q->resize = true;
+      q->resize_bytes = ctrlv_resize_lanczos_ws_bytes(in->n_clips, s->src_height, s->src_width, in->height, in->width);
+      q->resize_ws = take(q->resize_bytes);
+      q->image = take((size_t)in->n_clips * in->height * in->width * 3);
+      f.image_u8 = hold(q->image);
+    }
+  }
+  q->draw_aug = in->aug_noise == nullptr;
+  q->draw_lat = in->latents == nullptr;
+  if (q->draw_aug) f.aug_noise = (const float*)hold(0);
+  if (q->draw_lat) f.latents = (const float*)hold(0);
+  // (a ControlNet pipeline's request may still lack its cond here: stage 2 of a ctrlv_two_stage_request receives it from the
+  // chain.  The consuming call validates the request it is given)
+  ctrlv_clip_request v = f;
+  if (p->cn && !v.cond) {
+    v.cond = hold(0);
+    v.cond_channels = 3;
+    v.cond_dtype = CTRLV_ELEM_DTYPE;
+  }
+  Geo& g = q->g;
+  CTRLV_TRY(validate(p, &v, &g));
+  if (q->draw_aug) {
+    q->aug = take((size_t)g.B * 3 * g.H * g.W * sizeof(float));
+    f.aug_noise = (const float*)hold(q->aug);
+  }
+  if (q->draw_lat) {
+    q->lat = take((size_t)g.B * g.F * g.L * g.hw * sizeof(float));
+    f.latents = (const float*)hold(q->lat);
+  }
+  q->total = o;
+  return CTRLV_OK;
+}
+
+// the placeholders of plan_prepare against the workspace
+void resolve_prepare(Prep* q, void* prep_ws) {
+  char* base = (char*)prep_ws;
+  if (q->resize) q->filled.image_u8 = base + q->image;
+  if (q->draw_aug) q->filled.aug_noise = (const float*)(base + q->aug);
+  if (q->draw_lat) q->filled.latents = (const float*)(base + q->lat);
+}
+
+int run_prepare(const Prep& q, const ctrlv_seed_request* s, void* prep_ws, ctrlv_stream_t stream) {
+  char* base = (char*)prep_ws;
+  const ctrlv_clip_request& f = q.filled;
+  if (q.resize)
+    CTRLV_TRY(ctrlv_resize_lanczos_u8(s->src_image_u8, f.n_clips, s->src_height, s->src_width, base + q.image, f.height, f.width,
+                                      base + q.resize_ws, q.resize_bytes, stream));
+  if (q.draw_aug)
+    CTRLV_TRY(ctrlv_randn(s->seed, s->clip_index0, s->call, 0, f.n_clips, (size_t)3 * f.height * f.width, 1.0f, 0, base + q.aug, 0,
+                          stream));
+  if (q.draw_lat)
+    CTRLV_TRY(ctrlv_randn(s->seed, s->clip_index0, s->call, 1, f.n_clips,
+                          (size_t)q.g.F * q.g.L * q.g.hw, (float)q.init_noise_sigma, 1, base + q.lat,
+                          0, stream));
+  return CTRLV_OK;
+}
+
+// the schedule's home of a size query or of a generate_seeded call without host arrays
+float* sched_store(std::vector<float>* v, const ctrlv_clip_request* r) {
+  const int n = r && r->num_steps >= 1 && r->num_steps <= kMaxSteps ? r->num_steps : 1;
+  v->assign((size_t)2 * n + 1, 0.f);
+  return v->data();
+}
+
+}  // namespace
+
+extern "C" size_t ctrlv_pipeline_prepare_bytes(ctrlv_pipeline* p, const ctrlv_clip_request* r, const ctrlv_seed_request* s) {
+  Prep q;
+  std::vector<float> tmp;
+  float* sig = sched_store(&tmp, r);
+  if (plan_prepare(p, r, s, sig, sig + (tmp.size() + 1) / 2, &q) != CTRLV_OK) return 0;
+  return q.total > 0 ? q.total : kAlign;
+}
+
+extern "C" int ctrlv_pipeline_prepare(ctrlv_pipeline* p, const ctrlv_clip_request* in, const ctrlv_seed_request* s,
+                                      ctrlv_clip_request* out, void* prep_ws, size_t prep_bytes, ctrlv_stream_t stream) {
+  CTRLV_CHECK_ARG(out != nullptr, "pipeline_prepare: null output request");
+  Prep q;
+  CTRLV_TRY(plan_prepare(p, in, s, s ? s->sigmas_host : nullptr, s ? s->timesteps_host : nullptr, &q));
+  CTRLV_TRY(check_workspace("pipeline_prepare", "ctrlv_pipeline_prepare_bytes", prep_ws, prep_bytes, q.total > 0 ? q.total : kAlign));
+  resolve_prepare(&q, prep_ws);
+  CTRLV_TRY(run_prepare(q, s, prep_ws, stream));
+  *out = q.filled;
+  return CTRLV_OK;
+}
+
+extern "C" size_t ctrlv_pipeline_seeded_workspace_bytes(ctrlv_pipeline* p, const ctrlv_clip_request* r,
+                                                        const ctrlv_seed_request* s) {
+  Prep q;
+  std::vector<float> tmp;
+  float* sig = sched_store(&tmp, r);
+  if (plan_prepare(p, r, s, sig, sig + (tmp.size() + 1) / 2, &q) != CTRLV_OK) return 0;
+  const size_t rest = ctrlv_pipeline_workspace_bytes(p, &q.filled);
+  return rest ? (q.total > 0 ? q.total : kAlign) + rest : 0;
+}
+
+extern "C" int ctrlv_pipeline_generate_seeded(ctrlv_pipeline* p, const ctrlv_clip_request* r, const ctrlv_seed_request* s, void* ws,
+                                              size_t ws_bytes, ctrlv_stream_t stream) {
+  CTRLV_CHECK_ARG(p != nullptr, "pipeline_generate_seeded: null pipeline");
+  CTRLV_CHECK_ARG(s != nullptr, "pipeline_generate_seeded: null seed request");
+  Prep q;
+  float* sig = s->sigmas_host;
+  float* ts = s->timesteps_host;
+  if (!sig || !ts) {
+    float* own = sched_store(&p->sched, r);
+    if (!sig) sig = own;
+    if (!ts) ts = own + (p->sched.size() + 1) / 2;
+  }
+  CTRLV_TRY(plan_prepare(p, r, s, sig, ts, &q));
+  Layout L;
+  CTRLV_TRY(validate(p, &q.filled, &q.g));
+  CTRLV_TRY(layout(p, &q.filled, q.g, nullptr, &L));
+  const size_t front = q.total > 0 ? q.total : kAlign;
+  CTRLV_TRY(check_workspace("pipeline_generate_seeded", "ctrlv_pipeline_seeded_workspace_bytes", ws, ws_bytes, front + L.total));
+  resolve_prepare(&q, ws);
+  CTRLV_TRY(run_prepare(q, s, ws, stream));
+  return run_clip(p, &q.filled, nullptr, q.g, nullptr, L, (char*)ws + front, stream);
 }
 
 extern "C" size_t ctrlv_pipeline_boxes_workspace_bytes(ctrlv_pipeline* p, const ctrlv_clip_request* r,

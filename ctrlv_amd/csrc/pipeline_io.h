@@ -25,3 +25,5 @@ int ctrlv_pio_scale_latents(const float* x, float* out, void* scaled, long n, fl
 int ctrlv_pio_decode_input(const float* x, void* z, long n, float inv, hipStream_t s);
 // Host-side validation of one ctrlv_resize_antialias call (the driver refuses a request before its first launch).
 int ctrlv_resize_check(int n, int H, int W, int h, int w);
+// Host-side validation of one ctrlv_resize_lanczos_u8 call (ctrlv_pipeline_prepare refuses a request before its first launch).
+int ctrlv_resize_lanczos_check(int n, int H, int W, int h, int w);

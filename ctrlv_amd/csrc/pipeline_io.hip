@@ -4,10 +4,15 @@
 //                            around it: uint8 -> [-1, 1] in front, the CLIP normalisation behind
 //   ctrlv_pixels_prepare     VaeImageProcessor.preprocess + the noise augmentation of prepare_clip
 //   ctrlv_frames_to_u8       VaeImageProcessor.postprocess + numpy_to_pil's (x * 255).round()
+//   ctrlv_randn              counter-based Gaussian noise: Philox4x32-10, fp32 uniforms, Box-Muller (keyed per clip)
+//   ctrlv_euler_schedule     EulerDiscreteScheduler.set_timesteps' tables (host arithmetic)
+//   ctrlv_resize_lanczos_u8  PIL's 8-bit Lanczos resize, byte for byte (integer arithmetic on host-built tables)
 //   ctrlv_pio_*              the doubling / repeating / scattering of the loop's inputs (pipeline_io.h; csrc/pipeline.hip)
 // All arithmetic is fp32.  Where the Python expression is a multiply followed by an add that a test compares bit for bit the two
 // roundings are kept (__fmul_rn / __fadd_rn: never contracted into an fma).  Once per clip, HBM-bound, no atomics.
 #include <math.h>
+
+#include <vector>
 
 #include "pipeline_io.h"
 
@@ -255,6 +260,152 @@ __global__ void decode_input_kernel(const float* __restrict__ x, el_t* __restric
   z[i] = round_to_el(__fmul_rn(el_to_f32(round_to_el(x[i])), inv));
 }
 
+// ---- ctrlv_randn: Philox4x32-10 -> fp32 uniforms -> Box-Muller (the arithmetic is stated in include/ctrlv_hip.h)
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                              uint32_t* x) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {           // the key is bumped between rounds (the bump behind the last one is dead)
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  x[0] = c0; x[1] = c1; x[2] = c2; x[3] = c3;
+}
+
+// (x + 0.5) / 2^32 rounded ONCE: the 33-bit odd integer 2 x + 1 converted to fp32 (nearest even), times 2^-33 (exact)
+__device__ __forceinline__ float philox_uniform(uint32_t x) { return (float)(2ull * x + 1ull) * 0x1p-33f; }
+
+__device__ __forceinline__ void box_muller(float ua, float ub, float* z) {
+  const float r = sqrtf(-2.0f * logf(ua));
+  float s, c;
+  sincospif(2.0f * ub, &s, &c);
+  z[0] = __fmul_rn(r, c);
+  z[1] = __fmul_rn(r, s);
+}
+
+// One Philox block (four normals) per thread and iteration over (clip, block) pairs.  A block's four elements go out as one
+// 16-byte (fp32) / 8-byte (elements) store where their address allows it -- decided per block from the address, so the values
+// never depend on the alignment --, one by one elsewhere and in the tail block of a per_clip that is no multiple of 4.
+__global__ __launch_bounds__(256) void randn_kernel(uint32_t k0, uint32_t k1, uint32_t clip0, uint32_t call, uint32_t stream_id,
+                                                    unsigned long long per_clip, unsigned long long nblk,
+                                                    unsigned long long total, float scale, int round_el, void* __restrict__ out,
+                                                    int out_el) {
+  for (unsigned long long g = (unsigned long long)blockIdx.x * 256 + threadIdx.x; g < total;
+       g += (unsigned long long)gridDim.x * 256) {
+    const unsigned long long i = g / nblk, j = g % nblk;
+    uint32_t x[4];
+    philox4x32_10((uint32_t)j, call, stream_id, clip0 + (uint32_t)i, k0, k1, x);
+    float z[4];
+    box_muller(philox_uniform(x[0]), philox_uniform(x[1]), z);
+    box_muller(philox_uniform(x[2]), philox_uniform(x[3]), z + 2);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      z[k] = round_el ? el_to_f32(round_to_el(__fmul_rn(el_to_f32(round_to_el(z[k])), scale))) : __fmul_rn(scale, z[k]);
+    const unsigned long long e0 = 4 * j;
+    const int left = per_clip - e0 < 4 ? (int)(per_clip - e0) : 4;
+    if (out_el) {
+      el_t* o = (el_t*)out + i * per_clip + e0;
+      el_t e[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) e[k] = round_to_el(z[k]);
+      if (left == 4 && ((uintptr_t)o & 7) == 0) {
+        *(uint2*)o = make_uint2((uint32_t)e[0] | ((uint32_t)e[1] << 16), (uint32_t)e[2] | ((uint32_t)e[3] << 16));
+      } else {
+        for (int k = 0; k < left; ++k) o[k] = e[k];
+      }
+    } else {
+      float* o = (float*)out + i * per_clip + e0;
+      if (left == 4 && ((uintptr_t)o & 15) == 0) {
+        *(float4*)o = make_float4(z[0], z[1], z[2], z[3]);
+      } else {
+        for (int k = 0; k < left; ++k) o[k] = z[k];
+      }
+    }
+  }
+}
+
+// ---- ctrlv_resize_lanczos_u8: one pass of PIL's 8-bit resample along `axis` (0: columns, 1: rows)
+constexpr int kLzTx = 64, kLzTy = 4;     // a workgroup's tile of output pixels
+constexpr int kLzMaxScale = 16;          // per-axis down-scale: at most 2 * 48 + 1 = 97 taps, 64 rows of them in 24.3 KiB of LDS
+
+// src (n, Hi, Wi, 3) -> dst (n, Ho, Wo, 3); the axis that is not resampled has the same size on both sides.  bounds[o] = (first
+// tap, taps) and weights[o][ksize] (22-bit fixed point) of output index o along the axis.  The workgroup stages the weight rows
+// of its tile -- 64 along x, 4 along y -- in LDS (ksize is odd: the 64 rows of the horizontal pass fall on different banks).
+__global__ __launch_bounds__(256) void lanczos_pass_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                           const int2* __restrict__ bounds, const int* __restrict__ weights,
+                                                           int ksize, int axis, int Hi, int Wi, int Ho, int Wo) {
+  extern __shared__ int kw[];
+  const int tx = threadIdx.x, ty = threadIdx.y, tid = ty * kLzTx + tx;
+  const int x = blockIdx.x * kLzTx + tx, y = blockIdx.y * kLzTy + ty, img = blockIdx.z;
+  const int o0 = axis == 0 ? blockIdx.x * kLzTx : blockIdx.y * kLzTy;
+  const int rows = min(axis == 0 ? kLzTx : kLzTy, (axis == 0 ? Wo : Ho) - o0);
+  for (int i = tid; i < rows * ksize; i += kLzTx * kLzTy) kw[i] = weights[(long)o0 * ksize + i];
+  __syncthreads();
+  if (x >= Wo || y >= Ho) return;
+  const int lo = axis == 0 ? tx : ty;
+  const int2 b = bounds[o0 + lo];
+  const int* k = kw + lo * ksize;
+  const uint8_t* p = axis == 0 ? src + (((long)img * Hi + y) * Wi + b.x) * 3 : src + (((long)img * Hi + b.x) * Wi + x) * 3;
+  const long step = axis == 0 ? 3 : (long)Wi * 3;
+  int s0 = 1 << 21, s1 = 1 << 21, s2 = 1 << 21;
+  for (int t = 0; t < b.y; ++t) {
+    const int w = k[t];
+    s0 += (int)p[0] * w;
+    s1 += (int)p[1] * w;
+    s2 += (int)p[2] * w;
+    p += step;
+  }
+  uint8_t* o = dst + (((long)img * Ho + y) * Wo + x) * 3;
+  o[0] = (uint8_t)clampi(s0 >> 22, 0, 255);
+  o[1] = (uint8_t)clampi(s1 >> 22, 0, 255);
+  o[2] = (uint8_t)clampi(s2 >> 22, 0, 255);
+}
+
+int lanczos_ksize(int in, int out) {
+  const double scale = (double)in / (double)out, fs = scale < 1.0 ? 1.0 : scale;
+  return (int)ceil(3.0 * fs) * 2 + 1;
+}
+
+double lanczos_sinc(double v) {
+  if (v == 0.0) return 1.0;
+  v *= M_PI;
+  return sin(v) / v;
+}
+
+// bounds [out][2] and weights [out][ksize] of one axis, as PIL's precompute_coeffs + normalize_coeffs_8bpc form them
+void lanczos_tables(int in, int out, int ksize, int32_t* bounds, int32_t* weights) {
+  const double scale = (double)in / (double)out, fs = scale < 1.0 ? 1.0 : scale, support = 3.0 * fs;
+  std::vector<double> k((size_t)ksize);
+  for (int x = 0; x < out; ++x) {
+    const double center = (x + 0.5) * scale;
+    int xmin = (int)(center - support + 0.5), xmax = (int)(center + support + 0.5);
+    if (xmin < 0) xmin = 0;
+    if (xmax > in) xmax = in;
+    int cnt = xmax - xmin;
+    if (cnt > ksize) cnt = ksize;                     // (cannot happen: 2 support + 1 <= ksize; guards the table)
+    double sum = 0.0;
+    for (int t = 0; t < cnt; ++t) {
+      const double v = (t + xmin - center + 0.5) / fs;
+      k[t] = (-3.0 <= v && v < 3.0) ? lanczos_sinc(v) * lanczos_sinc(v / 3.0) : 0.0;
+      sum += k[t];
+    }
+    int32_t* w = weights + (size_t)x * ksize;
+    for (int t = 0; t < ksize; ++t) {
+      double q = t < cnt ? k[t] : 0.0;
+      if (t < cnt && sum != 0.0) q /= sum;
+      w[t] = q < 0.0 ? (int32_t)(-0.5 + q * 4194304.0) : (int32_t)(0.5 + q * 4194304.0);
+    }
+    bounds[2 * x] = xmin;
+    bounds[2 * x + 1] = cnt;
+  }
+}
+
+// the tables of one call in `ws`, in ints: bounds x [w][2] | bounds y [h][2] | weights x [w][ksx] | weights y [h][ksy]
+size_t lanczos_table_ints(int H, int W, int h, int w) {
+  return (size_t)w * (2 + lanczos_ksize(W, w)) + (size_t)h * (2 + lanczos_ksize(H, h));
+}
+
 inline unsigned blocks_for(long n) { return (unsigned)((n + 255) / 256); }
 constexpr long kMaxThreads = 0x7fffffffL * 256;      // one-dimensional grids: 2^31 - 1 workgroups of 256
 
@@ -403,6 +554,107 @@ int ctrlv_pio_scale_latents(const float* x, float* out, void* scaled, long n, fl
 
 int ctrlv_pio_decode_input(const float* x, void* z, long n, float inv, hipStream_t s) {
   hipLaunchKernelGGL(decode_input_kernel, dim3(blocks_for(n)), dim3(256), 0, s, x, (el_t*)z, n, inv);
+  CTRLV_LAUNCH_CHECK();
+  return CTRLV_OK;
+}
+
+extern "C" int ctrlv_randn(uint64_t seed, uint32_t clip0, uint32_t call, uint32_t stream_id, int n_clips, size_t per_clip,
+                           float scale, int round_dtype, void* out, int out_dtype, ctrlv_stream_t stream) {
+  CTRLV_CHECK_ARG(out != nullptr, "randn: null output");
+  CTRLV_CHECK_ARG(round_dtype == 0 || round_dtype == 1, "randn: round_dtype=%d must be 0 (fp32) or 1 (the element type)", round_dtype);
+  CTRLV_CHECK_ARG(isfinite(scale), "randn: scale=%g", (double)scale);
+  if (out_dtype != 0 && out_dtype != CTRLV_ELEM_DTYPE) {
+    ctrlv_set_error("randn: out dtype code %d (0 fp32 or %d, this library's element type)", out_dtype, CTRLV_ELEM_DTYPE);
+    return CTRLV_E_BAD_DTYPE;
+  }
+  CTRLV_CHECK_SHAPE(n_clips >= 1 && n_clips <= 65536 && per_clip >= 1, "randn: n_clips=%d must be in [1, 65536] and per_clip=%zu "
+                    "positive", n_clips, per_clip);
+  CTRLV_CHECK_SHAPE(per_clip <= ((size_t)1 << 34), "randn: per_clip=%zu is above the counter's range (2^32 blocks of 4 elements "
+                    "per clip)", per_clip);
+  CTRLV_CHECK_ARG(((uintptr_t)out & (out_dtype == 0 ? 3 : 1)) == 0, "randn: the output is not aligned to its element size");
+  const unsigned long long nblk = ((unsigned long long)per_clip + 3) / 4, total = nblk * (unsigned long long)n_clips;
+  const unsigned long long want = (total + 255) / 256;
+  const unsigned grid = (unsigned)(want < 16384 ? want : 16384);       // grid-stride: 64 workgroups per CU at the most
+  hipLaunchKernelGGL(randn_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (uint32_t)(seed & 0xffffffffu),
+                     (uint32_t)(seed >> 32), clip0, call, stream_id, (unsigned long long)per_clip, nblk, total, scale, round_dtype,
+                     out, out_dtype != 0 ? 1 : 0);
+  CTRLV_LAUNCH_CHECK();
+  return CTRLV_OK;
+}
+
+extern "C" int ctrlv_euler_schedule(int num_steps, float sigma_min, float sigma_max, float* sigmas, float* timesteps,
+                                    double* init_noise_sigma) {
+  CTRLV_CHECK_SHAPE(num_steps >= 1 && num_steps <= 1024, "euler_schedule: num_steps=%d must be in [1, 1024]", num_steps);
+  CTRLV_CHECK_ARG(sigmas != nullptr && timesteps != nullptr, "euler_schedule: sigmas / timesteps are null (host arrays of "
+                  "num_steps + 1 and num_steps floats)");
+  const bool svd = sigma_min == 0.f && sigma_max == 0.f;          // SVD's bounds as the doubles the Python scheduler holds
+  const double lo = svd ? 0.002 : (double)sigma_min, hi = svd ? 700.0 : (double)sigma_max;
+  CTRLV_CHECK_ARG(isfinite(lo) && isfinite(hi) && lo > 0.0 && lo < hi,
+                  "euler_schedule: sigma_min=%g / sigma_max=%g must be finite, positive and ordered (both 0: 0.002 and 700)", lo, hi);
+  const double a = pow(hi, 1.0 / 7.0), b = pow(lo, 1.0 / 7.0);
+  const double step = num_steps > 1 ? 1.0 / (double)(num_steps - 1) : 0.0;
+  for (int i = 0; i < num_steps; ++i) {
+    const double ramp = i == num_steps - 1 && num_steps > 1 ? 1.0 : (double)i * step;
+    sigmas[i] = (float)pow(a + ramp * (b - a), 7.0);
+    timesteps[i] = 0.25f * (float)log((double)sigmas[i]);
+  }
+  sigmas[num_steps] = 0.f;
+  if (init_noise_sigma) *init_noise_sigma = sqrt((double)sigmas[0] * (double)sigmas[0] + 1.0);
+  return CTRLV_OK;
+}
+
+// Host-side validation of one Lanczos resize (shared with ctrlv_pipeline_prepare, which refuses before its first launch).
+int ctrlv_resize_lanczos_check(int n, int H, int W, int h, int w) {
+  CTRLV_CHECK_SHAPE(n > 0 && H > 0 && W > 0 && h > 0 && w > 0, "resize_lanczos: an image with a zero dimension (n=%d, %dx%d -> "
+                    "%dx%d)", n, H, W, h, w);
+  CTRLV_CHECK_SHAPE(n <= 65535 && (h + kLzTy - 1) / kLzTy <= 65535 && (H + kLzTy - 1) / kLzTy <= 65535,
+                    "resize_lanczos: n=%d images of %d -> %d rows: at most 65535 images and 262140 rows", n, H, h);
+  CTRLV_CHECK_SHAPE((long)H <= (long)kLzMaxScale * h && (long)W <= (long)kLzMaxScale * w, "resize_lanczos: a down-scale above %d "
+                    "(%dx%d -> %dx%d)", kLzMaxScale, H, W, h, w);
+  return CTRLV_OK;
+}
+
+extern "C" size_t ctrlv_resize_lanczos_ws_bytes(int n, int H, int W, int h, int w) {
+  if (ctrlv_resize_lanczos_check(n, H, W, h, w) != CTRLV_OK) return 0;
+  return up256(lanczos_table_ints(H, W, h, w) * sizeof(int32_t)) + up256((size_t)n * H * w * 3);
+}
+
+extern "C" int ctrlv_resize_lanczos_u8(const void* src_u8, int n, int H, int W, void* dst_u8, int h, int w, void* ws,
+                                       size_t ws_bytes, ctrlv_stream_t stream) {
+  CTRLV_CHECK_ARG(src_u8 != nullptr && dst_u8 != nullptr, "resize_lanczos: null pointer");
+  CTRLV_TRY(ctrlv_resize_lanczos_check(n, H, W, h, w));
+  CTRLV_CHECK_ARG(ws != nullptr && ((uintptr_t)ws & 15) == 0, "resize_lanczos: the workspace must be non-null and 16-byte aligned");
+  const size_t need = ctrlv_resize_lanczos_ws_bytes(n, H, W, h, w);
+  if (ws_bytes < need) {
+    ctrlv_set_error("resize_lanczos: ws_bytes=%zu is smaller than the %zu bytes this resize needs (ctrlv_resize_lanczos_ws_bytes)",
+                    ws_bytes, need);
+    return CTRLV_E_WORKSPACE;
+  }
+  const int ksx = lanczos_ksize(W, w), ksy = lanczos_ksize(H, h);
+  const size_t ints = lanczos_table_ints(H, W, h, w);
+  // the host staging of the one upload: the copy of a pageable source is staged before hipMemcpyAsync returns, as with the
+  // driver's constants block (csrc/pipeline.hip)
+  static thread_local std::vector<int32_t> tab;
+  tab.assign(ints, 0);
+  int32_t* bx = tab.data();
+  int32_t* by = bx + 2 * (size_t)w;
+  int32_t* wx = by + 2 * (size_t)h;
+  int32_t* wy = wx + (size_t)w * ksx;
+  lanczos_tables(W, w, ksx, bx, wx);
+  lanczos_tables(H, h, ksy, by, wy);
+  const hipStream_t s = (hipStream_t)stream;
+  int32_t* d = (int32_t*)ws;
+  uint8_t* mid = (uint8_t*)ws + up256(ints * sizeof(int32_t));
+  CTRLV_HIP_TRY(hipMemcpyAsync(d, tab.data(), ints * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  const dim3 block(kLzTx, kLzTy);
+  hipLaunchKernelGGL(lanczos_pass_kernel, dim3((unsigned)((w + kLzTx - 1) / kLzTx), (unsigned)((H + kLzTy - 1) / kLzTy), (unsigned)n),
+                     block, (size_t)kLzTx * ksx * sizeof(int), s, (const uint8_t*)src_u8, mid, (const int2*)d,
+                     (const int*)(d + 2 * (size_t)w + 2 * (size_t)h), ksx, 0, H, W, H, w);
+  CTRLV_LAUNCH_CHECK();
+  hipLaunchKernelGGL(lanczos_pass_kernel, dim3((unsigned)((w + kLzTx - 1) / kLzTx), (unsigned)((h + kLzTy - 1) / kLzTy), (unsigned)n),
+                     block, (size_t)kLzTy * ksy * sizeof(int), s, (const uint8_t*)mid, (uint8_t*)dst_u8,
+                     (const int2*)(d + 2 * (size_t)w), (const int*)(d + 2 * (size_t)w + 2 * (size_t)h + (size_t)w * ksx), ksy, 1, H, w,
+                     h, w);
   CTRLV_LAUNCH_CHECK();
   return CTRLV_OK;
 }

@@ -957,3 +957,54 @@ def mask_counts(gt_u8, pred_u8, out=None):
     out = _out_arg(True if out is None else out, (n, 2, 3), torch.int64, gt_u8.device, fn, "out")
     check(_lib.load().ctrlv_mask_counts(_p(gt_u8), _p(pred_u8), n, F, H, W, _p(out), _stream()), "ctrlv_mask_counts")
     return out
+
+
+def randn(seed, shape, *, clip0=0, call=0, stream_id=0, scale=1.0, round_el=False, dtype=torch.float32, el=None, device=None,
+          out=None):
+    """Counter-based Gaussian noise (ctrlv_randn): shape (n_clips, ...) -- element e of row i is a pure function of (seed,
+    clip0 + i, call, stream_id, e): Philox4x32-10, fp32 uniforms, Box-Muller.  dtype: fp32 or an element type (bf16 / fp16).
+    round_el=False: scale * z in fp32; round_el=True: rne_el(rne_el(z) * scale) in the element type `el` (default: dtype when it
+    is an element type, else bf16) -- torch's element-typed randn times a Python scalar.  `out`: a dense tensor of the shape and
+    dtype to write into (any element alignment), else a fresh one on `device` (default: the current HIP device)."""
+    shape = tuple(int(v) for v in shape)
+    if len(shape) < 1 or any(v < 1 for v in shape):
+        raise ValueError(f"randn: shape {shape} must have positive sizes, clips first")
+    if dtype not in _DT:
+        raise ValueError(f"randn: dtype {dtype} (fp32, fp16 or bf16)")
+    if el is None:
+        el = dtype if dtype != torch.float32 else torch.bfloat16
+    if dtype != torch.float32 and el != dtype:
+        raise ValueError(f"randn: an output in {dtype} comes from the library of that element type, not {el}")
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=torch.device("cuda", torch.cuda.current_device()) if device is None else device)
+    elif tuple(out.shape) != shape or out.dtype != dtype:
+        raise ValueError(f"randn: out must be {shape} {dtype}")
+    _need_gpu(out, "out")
+    _need_dense("randn", out=out)
+    per = 1
+    for v in shape[1:]:
+        per *= v
+    check(_lib.load(el).ctrlv_randn(int(seed) & 0xFFFFFFFFFFFFFFFF, int(clip0), int(call), int(stream_id), shape[0], per,
+                                    float(scale), 1 if round_el else 0, _p(out), _DT[dtype], _stream()), "ctrlv_randn")
+    return out
+
+
+def resize_lanczos_u8(image_u8, h, w, out=None, workspace=None):
+    """(n, H, W, 3) uint8 -> (n, h, w, 3) uint8 = PIL.Image.resize((w, h), resample=LANCZOS) of every image, byte for byte
+    (ctrlv_resize_lanczos_u8: integer arithmetic on weight tables built on the host).  out / workspace: dense uint8 tensors to
+    use (the workspace 16-byte aligned, at least ctrlv_resize_lanczos_ws_bytes long), else fresh ones."""
+    _need_gpu(image_u8, "image_u8")
+    if image_u8.dtype != torch.uint8 or image_u8.dim() != 4 or image_u8.shape[3] != 3:
+        raise ValueError("resize_lanczos_u8: image_u8 must be (n, H, W, 3) uint8")
+    image_u8 = image_u8.contiguous()
+    n, H, W, _ = image_u8.shape
+    lib = _lib.load()
+    need = lib.ctrlv_resize_lanczos_ws_bytes(n, H, W, int(h), int(w))
+    if need == 0:
+        check(-2, "ctrlv_resize_lanczos_ws_bytes", lib=lib)
+    ws = torch.empty(need, dtype=torch.uint8, device=image_u8.device) if workspace is None else workspace
+    out = _out_arg(True if out is None else out, (n, int(h), int(w), 3), torch.uint8, image_u8.device, "resize_lanczos_u8", "out")
+    _need_dense("resize_lanczos_u8", workspace=ws)
+    check(lib.ctrlv_resize_lanczos_u8(_p(image_u8), n, H, W, _p(out), int(h), int(w), _p(ws), ws.numel(), _stream()),
+          "ctrlv_resize_lanczos_u8")
+    return out

@@ -18,6 +18,7 @@ import torch
 import torch.nn.functional as Fnn
 
 from .. import ops
+from ..seed import DeviceSeed
 
 # The VAE encoder / CLIP run through MIOpen.  Its default find mode benchmarks every solver the first time a conv shape is
 # seen -- minutes for the 576x1024 VAE shapes on this stack (tools/vae_decode_bench.py) -- for kernels that run once per
@@ -514,6 +515,10 @@ class SVDPipelineBase:
         pipeline_video_control.py:196-292 / pipeline_video_diffusion.py:131-228; in particular the two random draws happen
         in the reference's order (augmentation noise first, initial latents second), so a seeded generator gives the
         reference's sample.  Returns a ClipJob."""
+        if isinstance(generator, DeviceSeed):
+            raise ValueError("generator=DeviceSeed(...) is served on the CTRLV_PIPELINE=plan route only (a PIL image, no per-step "
+                             "callback, plans that serve the call); this call takes the default Python route: pass a "
+                             "torch.Generator or None")
         job = ClipJob()
         unet_cfg = self.unet.config
         job.height = height or unet_cfg.sample_size * self.vae_scale_factor
@@ -618,7 +623,8 @@ class SVDPipelineBase:
         """The call through ctrlv_pipeline_generate -- with `bbox_images` (the box predictor: a pipeline without a ControlNet)
         through ctrlv_pipeline_predict_boxes --, or None where the route is not taken (nothing has been drawn or changed
         then).  The PIL Lanczos resize to the working size and the two random draws stay here, in the reference's order
-        (augmentation noise first, latents second); CLIP sees the working-size image."""
+        (augmentation noise first, latents second); CLIP sees the working-size image.  With generator=DeviceSeed(...) all three
+        move into the library instead (PipelinePlan.generate(seed=...)): the image goes there at its own size."""
         if num_videos_per_prompt != 1 or (cond_images is not None and not torch.is_tensor(cond_images)):
             return None
         if getattr(self, "controlnet", None) is not None and (cond_images is None or bbox_images is not None):
@@ -634,7 +640,13 @@ class SVDPipelineBase:
         chunk = F if decode_chunk_size is None else decode_chunk_size
         check(height, width)
         images = image if isinstance(image, list) else [image]
-        images = [im if im.size == (width, height) else im.resize((width, height), resample=PIL.Image.LANCZOS) for im in images]
+        seeded = isinstance(generator, DeviceSeed)
+        if seeded:
+            if latents is not None or len({im.size for im in images}) != 1:
+                return None                              # (prepare_clip names the route in its refusal)
+        else:
+            images = [im if im.size == (width, height) else im.resize((width, height), resample=PIL.Image.LANCZOS)
+                      for im in images]
         arr = [np.asarray(im) for im in images]
         if any(a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 for a in arr):
             return None
@@ -659,15 +671,23 @@ class SVDPipelineBase:
         self._guidance_scale = max_guidance_scale
         self._num_timesteps = len(timesteps)
         image_u8 = torch.from_numpy(np.stack(arr)).to(dev)
-        aug = randn_tensor((n, 3, height, width), generator=generator, device=dev, dtype=torch.float32)       # random draw 1
-        lat = self.prepare_latents(n, F, latent_channels, height, width, el, dev, generator, latents)           # random draw 2
         fe = self.feature_extractor
         mean, std = getattr(fe, "image_mean", None), getattr(fe, "image_std", None)
         want_frames = output_type != "latent"
         run = pp.generate if boxes is None else \
             (lambda *a, cond, **kw: pp.predict_boxes(*a, boxes, num_cond_bbox_frames, **kw))
+        if seeded:                                       # the draws, the schedule and the resize happen in the library
+            c = sched.config
+            own = (float(c["sigma_min"]), float(c["sigma_max"])) != (0.002, 700.0)
+            first, extra = (image_u8, None, None, None), dict(
+                seed=generator.seed, clip_index0=generator.clip_index0, num_steps=num_inference_steps, num_frames=F,
+                height=height, width=width, sigma_min=c["sigma_min"] if own else 0.0, sigma_max=c["sigma_max"] if own else 0.0)
+        else:
+            aug = randn_tensor((n, 3, height, width), generator=generator, device=dev, dtype=torch.float32)    # random draw 1
+            lat = self.prepare_latents(n, F, latent_channels, height, width, el, dev, generator, latents)        # random draw 2
+            first, extra = (image_u8, lat.float(), sigmas, timesteps), dict(aug_noise=aug)
         out_lat, frames, u8 = run(
-            image_u8, lat.float(), sigmas, timesteps, cond=cond, aug_noise=aug, noise_aug_strength=noise_aug_strength, fps=fps,
+            *first, **extra, cond=cond, noise_aug_strength=noise_aug_strength, fps=fps,
             motion_bucket_id=motion_bucket_id, min_guidance=min_guidance_scale, max_guidance=max_guidance_scale,
             conditioning_scale=control_condition_scale, decode_chunk=chunk, clip_mean=mean, clip_std=std,
             frames=want_frames and output_type != "pil", frames_u8=output_type == "pil")

@@ -361,6 +361,18 @@ class VaePlan(_Handle):
         return out
 
 
+def euler_schedule(num_steps, sigma_min=0.0, sigma_max=0.0):
+    """EulerDiscreteScheduler.set_timesteps' tables from the library (ctrlv_euler_schedule: host arithmetic in double, no GPU):
+    (sigmas [num_steps + 1], timesteps [num_steps], init_noise_sigma) as Python floats holding the fp32 values.  Both bounds 0:
+    SVD's 0.002 and 700."""
+    n = int(num_steps)
+    room = min(max(n, 1), 1024)
+    sig, ts, ins = (ctypes.c_float * (room + 1))(), (ctypes.c_float * room)(), ctypes.c_double()
+    check(_lib.load().ctrlv_euler_schedule(n, float(sigma_min), float(sigma_max), sig, ts, ctypes.byref(ins)),
+          "ctrlv_euler_schedule")
+    return list(sig), list(ts), ins.value
+
+
 class PipelinePlan(_Handle):
     """Owns one `ctrlv_pipeline`: a whole clip as one C call (include/ctrlv_hip.h: ctrlv_pipeline_generate) on four borrowed
     plans of ONE library -- `Plan("unet")`, `Plan("controlnet")` or None, `VaePlan`, `ClipPlan`.  The object keeps them alive."""
@@ -394,25 +406,33 @@ class PipelinePlan(_Handle):
         r = _lib.ClipRequest()
         r.n_clips, r.num_frames, r.height, r.width = n, F, H, W
         r.image_u8 = image_u8.data_ptr()
+        r.num_steps = len(timesteps)
+        r.latents = latents.data_ptr()
+        r.sigmas, r.timesteps = sig, ts
+        self._request_fields(r, cond, aug_noise, noise_aug_strength, fps, motion_bucket_id, min_guidance, max_guidance,
+                             conditioning_scale, decode_chunk, clip_mean, clip_std, out_latents, out_frames, out_frames_u8)
+        return r, (sig, ts, image_u8, latents, cond, aug_noise, out_latents, out_frames, out_frames_u8)
+
+    @staticmethod
+    def _request_fields(r, cond=None, aug_noise=None, noise_aug_strength=0.02, fps=7, motion_bucket_id=127, min_guidance=1.0,
+                        max_guidance=3.0, conditioning_scale=1.0, decode_chunk=None, clip_mean=None, clip_std=None,
+                        out_latents=None, out_frames=None, out_frames_u8=None):
+        """The fields of a request beside its geometry, image, latents and schedule."""
         if cond is not None:
             r.cond, r.cond_channels, r.cond_dtype = cond.data_ptr(), cond.shape[2], _DT[cond.dtype]
         if aug_noise is not None:
             r.aug_noise = aug_noise.data_ptr()
         r.noise_aug_strength = float(noise_aug_strength)
-        r.num_steps = len(timesteps)
-        r.latents = latents.data_ptr()
-        r.sigmas, r.timesteps = sig, ts
         r.fps, r.motion_bucket_id = int(fps), int(motion_bucket_id)
         r.min_guidance, r.max_guidance = float(min_guidance), float(max_guidance)
         r.conditioning_scale = float(conditioning_scale)
-        r.decode_chunk = int(F if decode_chunk is None else decode_chunk)
+        r.decode_chunk = int(r.num_frames if decode_chunk is None else decode_chunk)
         if clip_mean is not None:
             for i in range(3):
                 r.clip_mean[i], r.clip_std[i] = float(clip_mean[i]), float(clip_std[i])
         for name, t in (("out_latents", out_latents), ("out_frames", out_frames), ("out_frames_u8", out_frames_u8)):
             if t is not None:
                 setattr(r, name, t.data_ptr())
-        return r, (sig, ts, image_u8, latents, cond, aug_noise, out_latents, out_frames, out_frames_u8)
 
     def workspace_bytes(self, request):
         return self._nonzero(self._lib.ctrlv_pipeline_workspace_bytes(self._h, ctypes.byref(request)),
@@ -456,12 +476,110 @@ class PipelinePlan(_Handle):
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._ws
 
-    def generate(self, image_u8, latents, sigmas, timesteps, *, cond=None, aug_noise=None, frames=True, frames_u8=True, **kw):
+    def seeded_request(self, who, image_u8, seed, *, num_steps=None, num_frames=None, height=None, width=None, clip_index0=0,
+                       call=0, sigma_min=0.0, sigma_max=0.0, latents=None, sigmas=None, timesteps=None, cond=None,
+                       cond_name="cond", aug_noise=None, frames=True, frames_u8=True, **kw):
+        """The (`ctrlv_clip_request`, `ctrlv_seed_request`) pair of a seeded call: image_u8 (n, Hs, Ws, 3) uint8 of ANY size --
+        the library resizes it to (height, width), default its own size --, and NULL for whatever of latents / aug_noise /
+        sigmas / timesteps is not given: ctrlv_pipeline_prepare fills those from (seed, clip_index0, call).  Returns
+        (request, seed request, keep, cond, (out_latents, out_frames, out_frames_u8)); keep the five together."""
+        dev = self.device
+        for name, t in (("image_u8", image_u8), ("latents", latents), (cond_name, cond), ("aug_noise", aug_noise)):
+            if t is not None and (not t.is_cuda or (t.device.index or 0) != (dev.index or 0)):
+                raise ValueError(f"PipelinePlan.{who}: {name} on {t.device}, the plans' weights on {dev}")
+        if image_u8.dtype != torch.uint8 or image_u8.dim() != 4 or image_u8.shape[3] != 3:
+            raise ValueError(f"PipelinePlan.{who}: image_u8 must be (n, H, W, 3) uint8")
+        n, Hs, Ws, _ = image_u8.shape
+        H, W = int(height or Hs), int(width or Ws)
+        L = self.vae._cfg.latent_channels
+        if latents is not None:
+            if latents.dtype != torch.float32 or latents.dim() != 5:
+                raise ValueError(f"PipelinePlan.{who}: latents must be fp32 (n, F, L, h, w)")
+            num_frames = latents.shape[1] if num_frames is None else num_frames
+            if tuple(latents.shape) != (n, num_frames, L, H // 8, W // 8):
+                raise ValueError(f"PipelinePlan.{who}: latents {tuple(latents.shape)} do not match {n} clips of {num_frames} x {H} x {W}")
+            latents = latents.contiguous()
+        if num_frames is None and cond is not None:
+            num_frames = cond.shape[1]
+        if num_frames is None:
+            raise ValueError(f"PipelinePlan.{who}: num_frames is needed with a seed")
+        F = int(num_frames)
+        if (sigmas is None) != (timesteps is None):
+            raise ValueError(f"PipelinePlan.{who}: sigmas and timesteps come together")
+        if sigmas is not None:
+            num_steps = len(timesteps)
+        if num_steps is None:
+            raise ValueError(f"PipelinePlan.{who}: num_steps is needed with a seed")
+        if cond is not None:
+            want = (n, F, 3, H, W) if cond.dim() == 5 and cond.shape[2] == 3 else (n, F, L, H // 8, W // 8)
+            if tuple(cond.shape) != want or cond.dtype not in _DT:
+                raise ValueError(f"PipelinePlan.{who}: {cond_name} {tuple(cond.shape)} must be {want} in fp32 / fp16 / bf16")
+            cond = cond.contiguous()
+        if aug_noise is not None:
+            if aug_noise.dtype != torch.float32 or tuple(aug_noise.shape) != (n, 3, H, W):
+                raise ValueError(f"PipelinePlan.{who}: aug_noise must be fp32 {(n, 3, H, W)}")
+            aug_noise = aug_noise.contiguous()
+        image_u8 = image_u8.contiguous()
+        out_lat = torch.empty(n, F, L, H // 8, W // 8, dtype=torch.float32, device=dev)
+        out_fr = torch.empty(n * F, 3, H, W, dtype=self.dtype, device=dev) if frames else None
+        out_u8 = torch.empty(n, F, H, W, 3, dtype=torch.uint8, device=dev) if frames_u8 else None
+        r = _lib.ClipRequest()                  # image_u8 stays NULL: the source goes through the seed request
+        r.n_clips, r.num_frames, r.height, r.width = n, F, H, W
+        r.num_steps = int(num_steps)
+        sig = ts = None
+        if sigmas is not None:
+            sig = (ctypes.c_float * len(sigmas))(*[float(v) for v in sigmas])
+            ts = (ctypes.c_float * len(timesteps))(*[float(v) for v in timesteps])
+            r.sigmas, r.timesteps = sig, ts
+        if latents is not None:
+            r.latents = latents.data_ptr()
+        self._request_fields(r, cond=cond if cond_name == "cond" else None, aug_noise=aug_noise, out_latents=out_lat,
+                             out_frames=out_fr, out_frames_u8=out_u8, **kw)
+        keep = (sig, ts, cond, aug_noise)
+        steps = min(max(r.num_steps, 1), 1024)
+        sig_host, ts_host = (ctypes.c_float * (steps + 1))(), (ctypes.c_float * steps)()
+        sr = _lib.SeedRequest()
+        sr.seed, sr.clip_index0, sr.call = int(seed) & 0xFFFFFFFFFFFFFFFF, int(clip_index0), int(call)
+        sr.src_image_u8, sr.src_height, sr.src_width = image_u8.data_ptr(), Hs, Ws
+        sr.sigma_min, sr.sigma_max = float(sigma_min), float(sigma_max)
+        sr.sigmas_host, sr.timesteps_host = sig_host, ts_host
+        return r, sr, (keep, image_u8, latents, sig_host, ts_host, out_lat, out_fr, out_u8), cond, (out_lat, out_fr, out_u8)
+
+    def prepare(self, request, seed_request):
+        """ctrlv_pipeline_prepare: the request with its NULL fields filled -- Lanczos resize, the two draws, the schedule -- and
+        the device buffer the filled request points into (fresh per call: keep it until the consuming call has finished)."""
+        need = self._nonzero(self._lib.ctrlv_pipeline_prepare_bytes(self._h, ctypes.byref(request), ctypes.byref(seed_request)),
+                             "ctrlv_pipeline_prepare_bytes")
+        ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        out = _lib.ClipRequest()
+        check(self._lib.ctrlv_pipeline_prepare(self._h, ctypes.byref(request), ctypes.byref(seed_request), ctypes.byref(out),
+                                               ws.data_ptr(), ws.numel(), self._stream()), "ctrlv_pipeline_prepare")
+        return out, ws
+
+    def generate(self, image_u8, latents=None, sigmas=None, timesteps=None, *, cond=None, aug_noise=None, frames=True,
+                 frames_u8=True, seed=None, **kw):
         """image_u8 (n, H, W, 3) uint8 at the working size; latents fp32 (n, F, L, h, w) already multiplied by
         init_noise_sigma; sigmas [steps + 1] / timesteps [steps]: the scheduler's values (host floats); cond (n, F, 3, H, W)
         pixels or (n, F, L, h, w) latents; aug_noise fp32 (n, 3, H, W) or None; the other fields of `request` by keyword.
         Everything on the plan's device, enqueued on torch's current stream.  Returns (latents fp32, frames (n F, 3, H, W) in
-        the element type or None, frames_u8 (n, F, H, W, 3) or None)."""
+        the element type or None, frames_u8 (n, F, H, W, 3) or None).
+
+        With `seed=` (ctrlv_pipeline_generate_seeded): latents, sigmas and timesteps may be omitted -- give num_steps= and
+        num_frames= --, image_u8 may have any size when height= and width= are given, and what is omitted comes from the
+        library: see `seeded_request` for the other keywords (clip_index0, call, sigma_min, sigma_max)."""
+        if seed is not None:
+            r, sr, keep, cond, out = self.seeded_request("generate", image_u8, seed, latents=latents, sigmas=sigmas,
+                                                         timesteps=timesteps, cond=cond, aug_noise=aug_noise, frames=frames,
+                                                         frames_u8=frames_u8, **kw)
+            need = self._nonzero(self._lib.ctrlv_pipeline_seeded_workspace_bytes(self._h, ctypes.byref(r), ctypes.byref(sr)),
+                                 "ctrlv_pipeline_seeded_workspace_bytes")
+            ws = self._workspace(need)
+            check(self._lib.ctrlv_pipeline_generate_seeded(self._h, ctypes.byref(r), ctypes.byref(sr), ws.data_ptr(), ws.numel(),
+                                                           self._stream()), "ctrlv_pipeline_generate_seeded")
+            del keep
+            return out
+        if latents is None or sigmas is None or timesteps is None:
+            raise ValueError("PipelinePlan.generate: latents, sigmas and timesteps are needed without seed=")
         r, keep, cond, out = self._checked_request("generate", image_u8, latents, sigmas, timesteps, cond, "cond", aug_noise,
                                                    frames, frames_u8, **kw)
         ws = self._workspace(self.workspace_bytes(r))
@@ -480,14 +598,21 @@ class PipelinePlan(_Handle):
         return bc
 
     def predict_boxes(self, image_u8, latents, sigmas, timesteps, bbox_frames, num_cond_frames=3, *, aug_noise=None, frames=True,
-                      frames_u8=True, **kw):
+                      frames_u8=True, seed=None, **kw):
         """The box predictor (ctrlv_pipeline_predict_boxes; a plan without a ControlNet): `generate` with the conditioning
         channels of frames [0, num_cond_frames) and F - 1 overwritten by bbox_frames -- (n, F, 3, H, W) pixels in [-1, 1], VAE
         encoded, or (n, F, L, h, w) latents -- and the decoded frames clamped to [-1, 1].  Same returns as `generate`."""
         if bbox_frames is None:
             raise ValueError("PipelinePlan.predict_boxes: bbox_frames is None")
-        r, keep, boxes, out = self._checked_request("predict_boxes", image_u8, latents, sigmas, timesteps, bbox_frames,
-                                                    "bbox_frames", aug_noise, frames, frames_u8, **kw)
+        if seed is not None:       # latents / sigmas / timesteps may be None: ctrlv_pipeline_prepare fills them (see `generate`)
+            r0, sr, keep0, boxes, out = self.seeded_request("predict_boxes", image_u8, seed, latents=latents, sigmas=sigmas,
+                                                            timesteps=timesteps, cond=bbox_frames, cond_name="bbox_frames",
+                                                            aug_noise=aug_noise, frames=frames, frames_u8=frames_u8, **kw)
+            r, prep = self.prepare(r0, sr)
+            keep = (keep0, r0, sr, prep)
+        else:
+            r, keep, boxes, out = self._checked_request("predict_boxes", image_u8, latents, sigmas, timesteps, bbox_frames,
+                                                        "bbox_frames", aug_noise, frames, frames_u8, **kw)
         bc = self.box_condition(boxes, num_cond_frames)
         need = self._nonzero(self._lib.ctrlv_pipeline_boxes_workspace_bytes(self._h, ctypes.byref(r), ctypes.byref(bc)),
                              "ctrlv_pipeline_boxes_workspace_bytes")
@@ -500,21 +625,41 @@ class PipelinePlan(_Handle):
 
 def boxes_to_video(boxes_plan, video_plan, image_u8, box_latents, video_latents, box_schedule, video_schedule, bbox_frames,
                    num_cond_frames=3, *, box_aug_noise=None, video_aug_noise=None, clean_threshold=50.0, box_frames_u8=True,
-                   frames=True, frames_u8=True, box_kw=None, video_kw=None):
+                   frames=True, frames_u8=True, box_kw=None, video_kw=None, seed=None, num_steps=None, clip_index0=0):
     """The chain as one C call (ctrlv_pipeline_boxes_to_video): `boxes_plan.predict_boxes`, `ops.box_frames_post`, then
     `video_plan.generate` conditioned on the predicted box frames.  box_schedule / video_schedule: (sigmas, timesteps) of the
     two stages; box_kw / video_kw: the other request fields of each stage (see PipelinePlan.request).  Returns (video latents
-    fp32, video frames or None, video frames_u8 or None, cleaned box frames (n, F, 3, H, W) uint8 or None)."""
+    fp32, video frames or None, video frames_u8 or None, cleaned box frames (n, F, 3, H, W) uint8 or None).
+
+    With `seed=`: the latents and schedules may be None (num_steps: one count or one per stage; image_u8 of any size with
+    height / width in box_kw and video_kw); each stage's request is filled by ctrlv_pipeline_prepare, stage 1 drawing with
+    call = 0 and stage 2 with call = 1, and the chain call itself is the same."""
     if boxes_plan._lib is not video_plan._lib:
         raise ValueError("boxes_to_video: the two pipeline plans must come from one library (one element type)")
     if bbox_frames is None:
         raise ValueError("boxes_to_video: bbox_frames is None")
-    rb, keep_b, boxes, _ = boxes_plan._checked_request("boxes_to_video", image_u8, box_latents, *box_schedule, bbox_frames,
-                                                       "bbox_frames", box_aug_noise, False, False, **(box_kw or {}))
-    rv, keep_v, _, out = video_plan._checked_request("boxes_to_video", image_u8, video_latents, *video_schedule, None, "cond",
-                                                     video_aug_noise, frames, frames_u8, **(video_kw or {}))
-    n, F = box_latents.shape[0], box_latents.shape[1]
-    H, W = image_u8.shape[1], image_u8.shape[2]
+    if seed is not None:
+        steps = tuple(num_steps) if isinstance(num_steps, (tuple, list)) else (num_steps, num_steps)
+        filled = []
+        for call, (pl, lat, schedule, aug, fr, u8, kw) in enumerate((
+                (boxes_plan, box_latents, box_schedule, box_aug_noise, False, False, box_kw),
+                (video_plan, video_latents, video_schedule, video_aug_noise, frames, frames_u8, video_kw))):
+            sig, ts = schedule if schedule is not None else (None, None)
+            r0, sr, keep0, cond, outs = pl.seeded_request(
+                "boxes_to_video", image_u8, seed, num_steps=steps[call], num_frames=bbox_frames.shape[1], clip_index0=clip_index0,
+                call=call, latents=lat, sigmas=sig, timesteps=ts, cond=bbox_frames if call == 0 else None,
+                cond_name="bbox_frames", aug_noise=aug, frames=fr, frames_u8=u8, **(kw or {}))
+            r, prep = pl.prepare(r0, sr)
+            filled.append((r, (keep0, r0, sr, prep), cond, outs))
+        (rb, keep_b, boxes, _), (rv, keep_v, _, out) = filled
+        n, F, H, W = rb.n_clips, rb.num_frames, rb.height, rb.width
+    else:
+        rb, keep_b, boxes, _ = boxes_plan._checked_request("boxes_to_video", image_u8, box_latents, *box_schedule, bbox_frames,
+                                                           "bbox_frames", box_aug_noise, False, False, **(box_kw or {}))
+        rv, keep_v, _, out = video_plan._checked_request("boxes_to_video", image_u8, video_latents, *video_schedule, None, "cond",
+                                                         video_aug_noise, frames, frames_u8, **(video_kw or {}))
+        n, F = box_latents.shape[0], box_latents.shape[1]
+        H, W = image_u8.shape[1], image_u8.shape[2]
     clean = torch.empty(n, F, 3, H, W, dtype=torch.uint8, device=video_plan.device) if box_frames_u8 else None
     q = _lib.TwoStageRequest()
     q.boxes, q.video, q.box_cond = rb, rv, boxes_plan.box_condition(boxes, num_cond_frames)

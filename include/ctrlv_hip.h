@@ -46,7 +46,8 @@ enum {
  * bump the number: a host built against 22 runs unchanged on a library that also exports the CLIP vision kernels
  * (ctrlv_attention_tokens, ctrlv_clip_patch_rows, ctrlv_clip_tokens, ctrlv_act_rows) or ctrlv_gemm_tokens and the CLIP plan
  * (ctrlv_clip_*) ctrlv_vae_posterior or the VAE plan (ctrlv_vae_*) or the whole-clip driver and its I/O kernels (ctrlv_pipeline_*,
- * ctrlv_resize_antialias, ctrlv_pixels_prepare, ctrlv_frames_to_u8), and a host that needs them fails at symbol lookup on a library without them.
+ * ctrlv_resize_antialias, ctrlv_pixels_prepare, ctrlv_frames_to_u8) or the seeded-clip entry points (ctrlv_randn,
+ * ctrlv_euler_schedule, ctrlv_resize_lanczos_u8, ctrlv_pipeline_prepare, ctrlv_pipeline_generate_seeded), and a host that needs them fails at symbol lookup on a library without them.
  * NOT neutral, although the number did not move: ctrlv_gemm_desc.pad_br gives meaning to four bytes that were alignment
  * padding, so descriptors must now be zero-initialised (see the field). */
 int ctrlv_abi_version(void);
@@ -946,6 +947,96 @@ size_t ctrlv_pipeline_chain_workspace_bytes(ctrlv_pipeline* boxes, ctrlv_pipelin
  * set, a video pipeline without a ControlNet, and whatever the two stages refuse. */
 int ctrlv_pipeline_boxes_to_video(ctrlv_pipeline* boxes, ctrlv_pipeline* video, const ctrlv_two_stage_request* q, void* ws,
                                   size_t ws_bytes, ctrlv_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Seeded clips: what a host without a numerics stack still had to bring to a ctrlv_clip_request -- the two Gaussian draws, the
+ * Karras schedule of EulerDiscreteScheduler and PIL's Lanczos resize to the working size (pipeline_utils.py: prepare_latents,
+ * prepare_clip; VaeImageProcessor.preprocess) -- as library calls (csrc/pipeline_io.hip, csrc/pipeline.hip).  Pixels of any size
+ * plus a 64-bit seed go in, video frames come out.  Additive entry points: the ABI number does not change, the three request
+ * structs keep their layouts, ctrlv_pipeline_generate / _predict_boxes / _boxes_to_video are untouched.  The arithmetic stated
+ * here is the contract: tests/seeded_ref.py restates it in numpy.
+ * ------------------------------------------------------------------------------------------------------------------ */
+/* Counter-based Gaussian noise.  out (n_clips, per_clip), out_dtype 0 fp32 or the library's element code.  Element e of clip i is
+ * a pure function of (seed, clip0 + i, call, stream_id, e): never of the grid, of n_clips or of the pointer's alignment.
+ *   block    j = e / 4 of a clip is Philox4x32-10 (Random123: multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 /
+ *            0xBB67AE85, the key bumped before rounds 2 .. 10) of the counter (j, call, stream_id, clip0 + i) under the key
+ *            (seed & 0xffffffff, seed >> 32) -> x0 .. x3.  j <= 2^32 - 1: per_clip > 2^34 is CTRLV_E_BAD_SHAPE.
+ *            Known answers: counter (0,0,0,0), key (0,0) -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8; all ones -> 408f276d 41c83b0e
+ *            a20bc7c6 6d5451fd; (243f6a88, 85a308d3, 13198a2e, 03707344), (a4093822, 299f31d0) -> d16cfe09 94fdcceb 5001e420
+ *            24126ea1.
+ *   uniform  u_k = the fp32 value nearest to (x_k + 0.5) / 2^32, ties to even, ONE rounding (the integer 2 x_k + 1 converted,
+ *            times 2^-33).  u_k lies in [2^-33, 1]: ln u is finite, |z| <= sqrt(66 ln 2) ~ 6.77, never an infinity or a NaN.
+ *   normal   Box-Muller in fp32 with the accurate device functions: r = sqrtf(-2 logf(u_a)), (c, s) = sincospif(2 u_b);
+ *            elements 4j, 4j+1 = (r c, r s) of (u_0, u_1), elements 4j+2, 4j+3 the same of (u_2, u_3).
+ *   output   round_dtype 0: out = scale * z in fp32; round_dtype 1: out = rne_el(rne_el(z) * scale) -- torch's element-typed
+ *            randn times a Python scalar (prepare_latents); then stored as out_dtype.
+ * One Philox block per thread and iteration, grid-stride; 16-byte stores (8 for 16-bit elements) where a block's four elements
+ * are aligned, scalar stores elsewhere and for the tail of a per_clip that is no multiple of 4. */
+int ctrlv_randn(uint64_t seed, uint32_t clip0, uint32_t call, uint32_t stream_id, int n_clips, size_t per_clip, float scale,
+                int round_dtype, void* out, int out_dtype, ctrlv_stream_t stream);
+/* The tables of EulerDiscreteScheduler.set_timesteps (Karras sigmas, "leading" spacing's init_noise_sigma): host arithmetic in
+ * double, needs no GPU.  sigma_min = sigma_max = 0: SVD's 0.002 and 700.  With a = pow(max, 1/7.), b = pow(min, 1/7.) and
+ * ramp_i = i * (1.0 / (num_steps - 1)) (0 for a single step):
+ *   sigmas[i] = (float) pow(a + ramp_i * (b - a), 7.), sigmas[num_steps] = 0;   timesteps[i] = 0.25f * (float) log((double) sigmas[i]);
+ *   *init_noise_sigma = sqrt((double) sigmas[0] * sigmas[0] + 1).
+ * Against the Python scheduler: the sigmas are bit-equal, a timestep may differ by one fp32 ulp (torch takes the logarithm in
+ * fp32).  CTRLV_E_BAD_SHAPE: num_steps outside 1 .. 1024; CTRLV_E_BAD_ARG: bounds not finite, positive and ordered (min < max),
+ * NULL outputs (init_noise_sigma may be NULL). */
+int ctrlv_euler_schedule(int num_steps, float sigma_min, float sigma_max, float* sigmas, float* timesteps,
+                         double* init_noise_sigma);
+/* PIL.Image.resize((w, h), resample=LANCZOS) of 8-bit RGB, every byte: src (n, H, W, 3) uint8 -> dst (n, h, w, 3) uint8.
+ * Per axis (in -> out), on the host in double: scale = in / out, fs = max(scale, 1), support = 3 fs; per output index x:
+ * center = (x + 0.5) scale, xmin = max((int) (center - support + 0.5), 0), xmax = min((int) (center + support + 0.5), in); tap
+ * t = 0 .. xmax - xmin - 1 weighs lanczos3((t + xmin - center + 0.5) / fs), lanczos3(v) = sinc(v) sinc(v / 3) for -3 <= v < 3,
+ * else 0, sinc(v) = sin(pi v) / (pi v), sinc(0) = 1; the weights are divided by their sum and become 22-bit fixed point:
+ * (int) (k 2^22 + 0.5) for k >= 0, (int) (k 2^22 - 0.5) for k < 0.  Two passes, horizontal into a uint8 intermediate (n, H, w, 3)
+ * in `ws`, then vertical; each output byte = clip8((2^21 + sum pixel k) >> 22), an arithmetic shift in int32 (255 times the sum
+ * of |k| stays below 2^31).  An axis whose size does not change runs its pass too: same bytes as PIL, which skips it.
+ * ws: ctrlv_resize_lanczos_ws_bytes bytes, 16-byte aligned: the tables (one upload per call) and the intermediate.  One thread
+ * per output pixel (three channels); a workgroup stages its rows of weights in LDS.  CTRLV_E_BAD_SHAPE (host, by name): a zero
+ * dimension, a down-scale above 16 per axis, n > 65535; ws_bytes too small: CTRLV_E_WORKSPACE.  The size query is 0 for a
+ * shape the call would refuse. */
+size_t ctrlv_resize_lanczos_ws_bytes(int n, int H, int W, int h, int w);
+int ctrlv_resize_lanczos_u8(const void* src_u8, int n, int H, int W, void* dst_u8, int h, int w, void* ws, size_t ws_bytes,
+                            ctrlv_stream_t stream);
+
+/* What ctrlv_pipeline_prepare adds to a clip request.  Clear the struct before setting fields. */
+typedef struct ctrlv_seed_request {
+  uint64_t seed;
+  uint32_t clip_index0;          /* clip i of the request draws as clip clip_index0 + i: the noise of a clip is a function of
+                                    (seed, its index), not of the batch or the rank that draws it */
+  uint32_t call;                 /* distinguishes the calls of one seed: stage 1 = 0, stage 2 = 1, ... */
+  const void* src_image_u8;      /* (n, src_height, src_width, 3) uint8 on the device, or NULL: the request's image_u8 is used */
+  int32_t src_height, src_width;
+  float sigma_min, sigma_max;    /* both 0: the SVD values */
+  float* sigmas_host;            /* caller's HOST arrays of num_steps + 1 and num_steps floats: they outlive the consuming call */
+  float* timesteps_host;
+  int32_t reserved;              /* must be 0 */
+} ctrlv_seed_request;
+/* Bytes of prep_ws for (r, s): what of {resized image, aug_noise, latents} the request leaves NULL, plus the resize's own
+ * workspace.  Host arithmetic on the plans' configurations (weights need not be loaded); 0 for a pair prepare would refuse. */
+size_t ctrlv_pipeline_prepare_bytes(ctrlv_pipeline* p, const ctrlv_clip_request* r, const ctrlv_seed_request* s);
+/* *out = *in with the fields `in` leaves NULL filled; a field the caller did set is kept:
+ *   sigmas, timesteps  ctrlv_euler_schedule(num_steps, sigma_min, sigma_max) written to sigmas_host / timesteps_host
+ *   image_u8           ctrlv_resize_lanczos_u8 of src_image_u8 to (height, width) in prep_ws; the source pointer itself when it
+ *                      already has that size (image_u8 and src_image_u8 both set: CTRLV_E_BAD_ARG)
+ *   aug_noise          ctrlv_randn(seed, clip_index0, call, stream 0), fp32, scale 1, (n, 3, H, W)
+ *   latents            ctrlv_randn(seed, clip_index0, call, stream 1), round_dtype 1, scale (float) init_noise_sigma -- of the
+ *                      schedule above, or sqrt(sigmas[0]^2 + 1) of the caller's --, stored as fp32 (n, F, L, h, w)
+ * `out` points into prep_ws (256-byte aligned), which stays alive until the consuming call -- ctrlv_pipeline_generate,
+ * ctrlv_pipeline_predict_boxes, or a ctrlv_two_stage_request (prepare twice, call = 0 and call = 1) -- has finished on the
+ * stream.  The filled request is validated as generate validates it; everything is refused by name on the host before the
+ * first launch: reserved != 0, NULL host arrays where the schedule is asked for, a source image without sizes, a resize
+ * ctrlv_resize_lanczos_u8 refuses, num_steps outside 1 .. 1024, prep_bytes too small (CTRLV_E_WORKSPACE). */
+int ctrlv_pipeline_prepare(ctrlv_pipeline* p, const ctrlv_clip_request* in, const ctrlv_seed_request* s, ctrlv_clip_request* out,
+                           void* prep_ws, size_t prep_bytes, ctrlv_stream_t stream);
+/* ctrlv_pipeline_prepare_bytes (a multiple of 256) + ctrlv_pipeline_workspace_bytes of the filled request; 0 on refusal. */
+size_t ctrlv_pipeline_seeded_workspace_bytes(ctrlv_pipeline* p, const ctrlv_clip_request* r, const ctrlv_seed_request* s);
+/* ctrlv_pipeline_prepare into the front of ws, then ctrlv_pipeline_generate on the rest: the bits of the two calls made by hand.
+ * sigmas_host / timesteps_host may be NULL here: the pipeline object then keeps the two arrays.  Not thread-safe on one
+ * pipeline. */
+int ctrlv_pipeline_generate_seeded(ctrlv_pipeline* p, const ctrlv_clip_request* r, const ctrlv_seed_request* s, void* ws,
+                                   size_t ws_bytes, ctrlv_stream_t stream);
 
 #ifdef __cplusplus
 }

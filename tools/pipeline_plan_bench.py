@@ -16,6 +16,13 @@ tool under one `timeout`.
 the two Python pipeline calls with host numpy in between; the record goes to profiles/box_chain_bench.jsonl.
 
     timeout -k 10 900 python tools/pipeline_plan_bench.py --boxes [--height 320 --width 512 --steps 25 --rounds 3]
+
+`--seeded` times what precedes a seeded clip instead (seeded_main below): the prepare phase as ONE C call
+(ctrlv_pipeline_prepare: Lanczos resize, the two Gaussian draws, the sigma schedule) against the same work on the host route
+(PIL's resize, two torch.randn, set_timesteps, the uploads), for 375 x 1242 -> 320 x 512 and 720 x 1280 -> 576 x 1024 at 25
+frames.  Needs no weights: prepare reads the plans' configurations only.
+
+    timeout -k 10 300 python tools/pipeline_plan_bench.py --seeded [--rounds 10]
 """
 import argparse
 import json
@@ -155,8 +162,79 @@ def boxes_main(args):
         f.write(json.dumps(rec) + "\n")
 
 
+SVD = dict(in_channels=8, out_channels=4, block_out_channels=(320, 640, 1280, 1280), layers_per_block=2,
+           down_block_types=("CrossAttnDownBlockSpatioTemporal",) * 3 + ("DownBlockSpatioTemporal",),
+           up_block_types=("UpBlockSpatioTemporal",) + ("CrossAttnUpBlockSpatioTemporal",) * 3,
+           num_attention_heads=(5, 10, 20, 20), cross_attention_dim=1024, addition_time_embed_dim=256,
+           projection_class_embeddings_input_dim=768, num_frames=25)
+VAE = dict(in_channels=3, out_channels=3, latent_channels=4, layers_per_block=2, block_out_channels=(128, 256, 512, 512),
+           scaling_factor=0.18215)
+SEEDED_SIZES = (((375, 1242), (320, 512)), ((720, 1280), (576, 1024)))
+
+
+def seeded_main(args):
+    """--seeded: what fills a clip request before the loop, per clip.  `prepare`: the source image's bytes go up and
+    ctrlv_pipeline_prepare resizes, draws and tabulates (PipelinePlan.seeded_request + prepare).  `host`: what the pipelines'
+    plan route does today -- PIL's Lanczos resize, the upload, randn_tensor twice with a CPU generator (augmentation noise
+    fp32, latents in bf16 times init_noise_sigma, widened), EulerDiscreteScheduler.set_timesteps.  Alternated `--rounds` times
+    after one warm call each; host clock around synchronised phases."""
+    import __graft_entry__ as g
+    g.build()
+    from PIL import Image
+    from ctrlv_amd.pipelines.pipeline_utils import randn_tensor
+    from ctrlv_amd.plan import ClipPlan, PipelinePlan, Plan, VaePlan
+    from ctrlv_amd.schedulers import EulerDiscreteScheduler
+    F, steps = args.frames, args.steps
+    pipe = PipelinePlan(Plan("unet", SVD, DEV), None, VaePlan(VAE, DEV), ClipPlan(VIT_H, DEV))      # configurations only
+    sched = EulerDiscreteScheduler()
+    for (SH, SW), (H, W) in SEEDED_SIZES:
+        src = torch.randint(0, 256, (SH, SW, 3), generator=torch.Generator().manual_seed(3), dtype=torch.uint8).numpy()
+        image = Image.fromarray(src)
+
+        def prepare_route():
+            image_u8 = torch.from_numpy(src[None]).to(DEV)
+            r, sr, keep, _, _ = pipe.seeded_request("bench", image_u8, 7, num_steps=steps, num_frames=F, height=H, width=W,
+                                                    frames=False, frames_u8=False)
+            return pipe.prepare(r, sr), keep
+
+        def host_route():
+            gen = torch.Generator().manual_seed(7)
+            image_u8 = torch.from_numpy(np.asarray(image.resize((W, H), resample=Image.LANCZOS))[None].copy()).to(DEV)
+            sched.set_timesteps(steps, device=DEV)
+            aug = randn_tensor((1, 3, H, W), generator=gen, device=torch.device(DEV), dtype=torch.float32)
+            lat = randn_tensor((1, F, 4, H // 8, W // 8), generator=gen, device=torch.device(DEV), dtype=torch.bfloat16)
+            return image_u8, aug, (lat * sched.init_noise_sigma).float(), list(sched._sigmas_host), list(sched._timesteps_host)
+
+        def timed(fn):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn()
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0, out
+
+        routes = {"host": host_route, "prepare": prepare_route}
+        for fn in routes.values():
+            timed(fn)                                                                     # warm
+        times = {name: [] for name in routes}
+        for _ in range(args.rounds):
+            for name, fn in routes.items():
+                times[name].append(timed(fn)[0])
+        rec = dict(tool="pipeline_plan_bench --seeded", source=f"{SH}x{SW}", size=f"{H}x{W}", frames=F, steps=steps,
+                   rounds=args.rounds, device=torch.cuda.get_device_name(0))
+        for name in routes:
+            rec[name] = dict(clip_ms=round(1e3 * statistics.median(times[name]), 3),
+                             all_clip_ms=[round(1e3 * v, 3) for v in times[name]])
+        rec["prepare_over_host"] = round(rec["prepare"]["clip_ms"] / rec["host"]["clip_ms"], 4)
+        print(json.dumps(rec), flush=True)
+        out_path = args.out or os.path.join(ROOT, "profiles", "pipeline_plan_bench.jsonl")
+        os.makedirs(os.path.dirname(out_path), exist_ok=True)
+        with open(out_path, "a") as f:
+            f.write(json.dumps(rec) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--seeded", action="store_true", help="time the prepare phase (appends to profiles/pipeline_plan_bench.jsonl)")
     ap.add_argument("--boxes", action="store_true", help="time the boxes-to-video chain (appends to profiles/box_chain_bench.jsonl)")
     ap.add_argument("--cond-frames", type=int, default=3, help="--boxes: num_cond_bbox_frames")
     ap.add_argument("--out", default=None)
@@ -170,6 +248,8 @@ def main():
     args = ap.parse_args()
     if args.boxes:
         return boxes_main(args)
+    if args.seeded:
+        return seeded_main(args)
     args.out = args.out or os.path.join(ROOT, "profiles", "pipeline_plan_bench.jsonl")
     if not 2 <= args.steps_lo < args.steps:
         ap.error("2 <= --steps-lo < --steps (the Python loop captures its graph in the second step)")
