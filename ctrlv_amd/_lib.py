@@ -146,6 +146,19 @@ class SeedRequest(ctypes.Structure):
                 ("sigmas_host", ctypes.POINTER(c_float)), ("timesteps_host", ctypes.POINTER(c_float)), ("reserved", c_int)]
 
 
+class BestBoxesRequest(ctypes.Structure):
+    """Mirror of `ctrlv_best_boxes_request`."""
+    _fields_ = [("n_candidates", c_int), ("reserved", c_int), ("candidates", ctypes.POINTER(ClipRequest)),
+                ("box_cond", BoxCondition), ("gt_u8", c_void_p), ("clean_threshold", c_float), ("reserved2", c_int),
+                ("out_pt", c_void_p), ("out_cond", c_void_p), ("out_u8", c_void_p), ("out_counts", c_void_p),
+                ("out_winner", c_void_p)]
+
+
+class BestChainRequest(ctypes.Structure):
+    """Mirror of `ctrlv_best_chain_request`."""
+    _fields_ = [("boxes", BestBoxesRequest), ("video", ClipRequest), ("reserved", c_int)]
+
+
 # name -> (restype, argtypes); lists every symbol include/ctrlv_hip.h declares (tests/test_abi.py checks this)
 SIGNATURES = {
     "ctrlv_abi_version": (c_int, []),
@@ -306,6 +319,15 @@ SIGNATURES = {
     "ctrlv_pipeline_seeded_workspace_bytes": (c_size_t, [c_void_p, ctypes.POINTER(ClipRequest), ctypes.POINTER(SeedRequest)]),
     "ctrlv_pipeline_generate_seeded": (c_int, [c_void_p, ctypes.POINTER(ClipRequest), ctypes.POINTER(SeedRequest), c_void_p,
                                                c_size_t, c_void_p]),
+    "ctrlv_best_candidate": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "ctrlv_gather_clips": (c_int, [c_void_p, c_void_p, c_int, c_int, c_size_t, c_void_p, c_void_p]),
+    "ctrlv_pipeline_best_boxes_workspace_bytes": (c_size_t, [c_void_p, ctypes.POINTER(BestBoxesRequest)]),
+    "ctrlv_pipeline_best_boxes": (c_int, [c_void_p, ctypes.POINTER(BestBoxesRequest), c_void_p, c_size_t, c_void_p]),
+    "ctrlv_pipeline_best_chain_workspace_bytes": (c_size_t, [c_void_p, c_void_p, ctypes.POINTER(BestChainRequest)]),
+    "ctrlv_pipeline_best_boxes_to_video": (c_int, [c_void_p, c_void_p, ctypes.POINTER(BestChainRequest), c_void_p, c_size_t,
+                                                   c_void_p]),
+    "ctrlv_boundary_radius": (c_int, [c_int, c_int, ctypes.c_double]),
+    "ctrlv_boundary_counts": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
 }
 
 _libs = {}                # element dtype code (2 bf16 / 1 fp16) -> CDLL
@@ -318,7 +340,10 @@ _NO_STATUS = {"ctrlv_abi_version", "ctrlv_elem_dtype", "ctrlv_build_id", "ctrlv_
               "ctrlv_gemm_tokens_ws_bytes", "ctrlv_clip_plan_workspace_bytes", "ctrlv_vae_plan_workspace_bytes",
               "ctrlv_pipeline_workspace_bytes", "ctrlv_pipeline_boxes_workspace_bytes", "ctrlv_box_frames_post_ws_bytes",
               "ctrlv_pipeline_chain_workspace_bytes", "ctrlv_resize_lanczos_ws_bytes", "ctrlv_pipeline_prepare_bytes",
-              "ctrlv_pipeline_seeded_workspace_bytes"}
+              "ctrlv_pipeline_seeded_workspace_bytes", "ctrlv_pipeline_best_boxes_workspace_bytes",
+              "ctrlv_pipeline_best_chain_workspace_bytes",
+              # a radius, or a negative status
+              "ctrlv_boundary_radius"}
 
 
 def _status_recorder(lib, fn):

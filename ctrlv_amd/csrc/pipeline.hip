@@ -4,6 +4,9 @@
 // the plan-level entry points plus the glue kernels of csrc/pipeline_io.hip.  ctrlv_pipeline_predict_boxes is the same clip with
 // the box frames written over the conditioning channels and the decoded frames clamped (VideoDiffusionPipeline.__call__ with
 // bbox_images); ctrlv_pipeline_boxes_to_video chains it, the kernels of csrc/box_frames.hip and generate.
+// ctrlv_pipeline_best_boxes runs that first stage once per candidate request, scores every result against ground-truth box frames
+// and keeps the best one per clip without coming back to the host (the kernels of csrc/box_eval.hip);
+// ctrlv_pipeline_best_boxes_to_video puts generate behind it.
 #include <math.h>
 
 #include <vector>
@@ -739,4 +742,173 @@ extern "C" int ctrlv_pipeline_boxes_to_video(ctrlv_pipeline* boxes, ctrlv_pipeli
   CTRLV_TRY(ctrlv_box_frames_post(c.boxes.out_frames, c.gb.B, c.gb.F, c.gb.H, c.gb.W, q->clean_threshold, nullptr, base + c.cond,
                                   q->out_box_frames_u8, base + c.post, c.post_bytes, stream));
   return run_clip(video, &c.video, nullptr, c.gv, nullptr, c.Lv, base + c.stage, stream);
+}
+
+namespace {
+
+constexpr int kMaxCandidates = 8;
+
+struct Best {                // ctrlv_pipeline_best_boxes: the candidates as run_clip sees them, and where things lie in the workspace
+  int C;
+  ctrlv_clip_request cand[kMaxCandidates];
+  Geo g[kMaxCandidates];
+  BoxGeo bx[kMaxCandidates];
+  Layout L[kMaxCandidates];
+  bool emit;                 // any of out_pt / out_cond / out_u8 (with need_cond: always)
+  size_t fr, clip_bytes, slots, scratch, counts, winner, gathered, cond, post, post_bytes, stage, stage_bytes;
+};
+
+// every refusal that needs no loaded plan
+int validate_best(ctrlv_pipeline* p, const ctrlv_best_boxes_request* q, Best* b) {
+  CTRLV_CHECK_ARG(p != nullptr, "best_boxes: null pipeline");
+  CTRLV_CHECK_ARG(q != nullptr, "best_boxes: null request");
+  CTRLV_CHECK_ARG(p->tag == kPipelineTag, "best_boxes: the pipeline must come from this library (element dtype code %d)",
+                  CTRLV_ELEM_DTYPE);
+  CTRLV_CHECK_SHAPE(q->n_candidates >= 1 && q->n_candidates <= kMaxCandidates, "best_boxes: n_candidates=%d must be in [1, %d]",
+                    q->n_candidates, kMaxCandidates);
+  CTRLV_CHECK_ARG(q->reserved == 0 && q->reserved2 == 0, "best_boxes: reserved=%d / reserved2=%d must be 0", q->reserved,
+                  q->reserved2);
+  CTRLV_CHECK_ARG(q->candidates != nullptr, "best_boxes: the candidates array is null");
+  CTRLV_CHECK_ARG(q->gt_u8 != nullptr, "best_boxes: gt_u8 is null");
+  CTRLV_CHECK_ARG(isfinite(q->clean_threshold), "best_boxes: clean_threshold=%g", (double)q->clean_threshold);
+  CTRLV_CHECK_ARG(((uintptr_t)q->out_counts & 7) == 0, "best_boxes: out_counts must be 8-byte aligned");
+  CTRLV_CHECK_ARG(((uintptr_t)q->out_winner & 3) == 0, "best_boxes: out_winner must be 4-byte aligned");
+  b->C = q->n_candidates;
+  const ctrlv_clip_request& r0 = q->candidates[0];
+  for (int c = 0; c < b->C; ++c) {
+    const ctrlv_clip_request& r = q->candidates[c];
+    CTRLV_CHECK_ARG(r.out_frames == nullptr && r.out_frames_u8 == nullptr, "best_boxes: candidate %d has out_frames / "
+                    "out_frames_u8 set; the driver keeps the candidates' frames in the workspace", c);
+    CTRLV_CHECK_SHAPE(r.n_clips == r0.n_clips && r.num_frames == r0.num_frames && r.height == r0.height && r.width == r0.width,
+                      "best_boxes: the candidates differ in geometry (candidate 0: %d x %d x %d x %d, candidate %d: %d x %d x %d x "
+                      "%d)", r0.n_clips, r0.num_frames, r0.height, r0.width, c, r.n_clips, r.num_frames, r.height, r.width);
+  }
+  for (int c = 0; c < b->C; ++c) {
+    b->cand[c] = q->candidates[c];
+    b->cand[c].out_frames = (void*)(uintptr_t)kAlign;       // (a placeholder until the workspace is known: the clip must decode)
+    CTRLV_TRY(validate_boxes(p, &b->cand[c], &q->box_cond, &b->g[c], &b->bx[c]));
+  }
+  return CTRLV_OK;
+}
+
+// need_cond: the chain's call -- a condition buffer is laid out when the request brings none
+int layout_best(ctrlv_pipeline* p, const ctrlv_best_boxes_request* q, bool need_cond, Best* b) {
+  b->stage_bytes = 0;
+  for (int c = 0; c < b->C; ++c) {
+    CTRLV_TRY(layout(p, &b->cand[c], b->g[c], &b->bx[c], &b->L[c]));
+    b->stage_bytes = b->L[c].total > b->stage_bytes ? b->L[c].total : b->stage_bytes;
+  }
+  const Geo& g = b->g[0];
+  b->emit = need_cond || q->out_pt || q->out_cond || q->out_u8;
+  b->clip_bytes = (size_t)g.F * 3 * g.H * g.W * sizeof(el_t);
+  b->fr = (size_t)g.B * b->clip_bytes;
+  size_t o = 0;
+  auto take = [&](size_t bytes) { const size_t at = o; o += up(bytes); return at; };
+  b->slots = take((size_t)b->C * b->fr);                    // (C, n, clip) without gaps: ctrlv_gather_clips reads it as one array
+  b->scratch = take((size_t)g.B * g.F * 3 * g.H * g.W);
+  b->counts = take(q->out_counts ? 0 : (size_t)b->C * g.B * 6 * sizeof(unsigned long long));
+  b->winner = take(q->out_winner ? 0 : (size_t)g.B * sizeof(int32_t));
+  b->gathered = take(b->emit ? b->fr : 0);
+  b->cond = take(need_cond && !q->out_cond ? b->fr : 0);
+  b->post_bytes = ctrlv_box_frames_post_ws_bytes(g.B, g.F);
+  b->post = take(b->post_bytes);
+  b->stage = o;
+  return CTRLV_OK;
+}
+
+// out_cond: the request's, or the chain's buffer
+int run_best(ctrlv_pipeline* p, const ctrlv_best_boxes_request* q, Best* b, char* base, void* out_cond, ctrlv_stream_t stream) {
+  const Geo& g = b->g[0];
+  unsigned long long* counts = q->out_counts ? q->out_counts : (unsigned long long*)(base + b->counts);
+  int32_t* winner = q->out_winner ? q->out_winner : (int32_t*)(base + b->winner);
+  for (int c = 0; c < b->C; ++c) {
+    char* slot = base + b->slots + (size_t)c * b->fr;
+    b->cand[c].out_frames = slot;
+    CTRLV_TRY(run_clip(p, &b->cand[c], &q->box_cond, b->g[c], &b->bx[c], b->L[c], base + b->stage, stream));
+    CTRLV_TRY(ctrlv_box_frames_post(slot, g.B, g.F, g.H, g.W, q->clean_threshold, nullptr, nullptr, base + b->scratch,
+                                    base + b->post, b->post_bytes, stream));
+    CTRLV_TRY(ctrlv_mask_counts(q->gt_u8, base + b->scratch, g.B, g.F, g.H, g.W, counts + (size_t)c * g.B * 6, stream));
+  }
+  CTRLV_TRY(ctrlv_best_candidate(counts, g.B, b->C, winner, stream));
+  if (!b->emit) return CTRLV_OK;
+  CTRLV_TRY(ctrlv_gather_clips(base + b->slots, winner, g.B, b->C, b->clip_bytes, base + b->gathered, stream));
+  return ctrlv_box_frames_post(base + b->gathered, g.B, g.F, g.H, g.W, q->clean_threshold, q->out_pt, out_cond, q->out_u8,
+                               base + b->post, b->post_bytes, stream);
+}
+
+int plan_best(ctrlv_pipeline* p, const ctrlv_best_boxes_request* q, Best* b) {
+  CTRLV_TRY(validate_best(p, q, b));
+  return layout_best(p, q, false, b);
+}
+
+struct BestChain {
+  Best best;
+  ctrlv_clip_request video;
+  Geo gv;
+  Layout Lv;
+  size_t total;
+};
+
+int plan_best_chain(ctrlv_pipeline* pb, ctrlv_pipeline* pv, const ctrlv_best_chain_request* q, BestChain* c) {
+  CTRLV_CHECK_ARG(pb != nullptr && pv != nullptr, "best_boxes_to_video: null pipeline");
+  CTRLV_CHECK_ARG(q != nullptr, "best_boxes_to_video: null request");
+  CTRLV_CHECK_ARG(pb->tag == kPipelineTag && pv->tag == kPipelineTag, "best_boxes_to_video: both pipelines must come from this "
+                  "library (element dtype code %d)", CTRLV_ELEM_DTYPE);
+  CTRLV_CHECK_ARG(pb->device == pv->device, "best_boxes_to_video: the pipelines live on different devices (%d and %d)", pb->device,
+                  pv->device);
+  CTRLV_CHECK_ARG(q->reserved == 0, "best_boxes_to_video: reserved=%d must be 0", q->reserved);
+  CTRLV_CHECK_ARG(pv->cn != nullptr, "best_boxes_to_video: the video pipeline has no ControlNet to take the box frames");
+  CTRLV_CHECK_ARG(q->video.cond == nullptr, "best_boxes_to_video: video.cond must be NULL on entry (the driver supplies the "
+                  "winner's frames)");
+  CTRLV_TRY(validate_best(pb, &q->boxes, &c->best));
+  const ctrlv_clip_request& r0 = q->boxes.candidates[0];
+  CTRLV_CHECK_SHAPE(r0.n_clips == q->video.n_clips && r0.num_frames == q->video.num_frames && r0.height == q->video.height &&
+                    r0.width == q->video.width,
+                    "best_boxes_to_video: the two stages differ in geometry (boxes %d x %d x %d x %d, video %d x %d x %d x %d)",
+                    r0.n_clips, r0.num_frames, r0.height, r0.width, q->video.n_clips, q->video.num_frames, q->video.height,
+                    q->video.width);
+  c->video = q->video;
+  c->video.cond = (const void*)(uintptr_t)kAlign;     // (a placeholder until the workspace is known: validate asks for non-null)
+  c->video.cond_channels = 3;
+  c->video.cond_dtype = CTRLV_ELEM_DTYPE;
+  CTRLV_TRY(validate(pv, &c->video, &c->gv));
+  CTRLV_TRY(layout_best(pb, &q->boxes, true, &c->best));
+  CTRLV_TRY(layout(pv, &c->video, c->gv, nullptr, &c->Lv));
+  c->total = c->best.stage + (c->best.stage_bytes > c->Lv.total ? c->best.stage_bytes : c->Lv.total);
+  return CTRLV_OK;
+}
+
+}  // namespace
+
+extern "C" size_t ctrlv_pipeline_best_boxes_workspace_bytes(ctrlv_pipeline* p, const ctrlv_best_boxes_request* q) {
+  std::vector<Best> b(1);
+  return plan_best(p, q, &b[0]) == CTRLV_OK ? b[0].stage + b[0].stage_bytes : 0;
+}
+
+extern "C" int ctrlv_pipeline_best_boxes(ctrlv_pipeline* p, const ctrlv_best_boxes_request* q, void* ws, size_t ws_bytes,
+                                         ctrlv_stream_t stream) {
+  std::vector<Best> b(1);      // (eight layouts: off the stack)
+  CTRLV_TRY(plan_best(p, q, &b[0]));
+  CTRLV_TRY(check_workspace("pipeline_best_boxes", "ctrlv_pipeline_best_boxes_workspace_bytes", ws, ws_bytes,
+                            b[0].stage + b[0].stage_bytes));
+  return run_best(p, q, &b[0], (char*)ws, q->out_cond, stream);
+}
+
+extern "C" size_t ctrlv_pipeline_best_chain_workspace_bytes(ctrlv_pipeline* boxes, ctrlv_pipeline* video,
+                                                            const ctrlv_best_chain_request* q) {
+  std::vector<BestChain> c(1);
+  return plan_best_chain(boxes, video, q, &c[0]) == CTRLV_OK ? c[0].total : 0;
+}
+
+extern "C" int ctrlv_pipeline_best_boxes_to_video(ctrlv_pipeline* boxes, ctrlv_pipeline* video, const ctrlv_best_chain_request* q,
+                                                  void* ws, size_t ws_bytes, ctrlv_stream_t stream) {
+  std::vector<BestChain> cv(1);
+  BestChain& c = cv[0];
+  CTRLV_TRY(plan_best_chain(boxes, video, q, &c));
+  CTRLV_TRY(check_workspace("pipeline_best_boxes_to_video", "ctrlv_pipeline_best_chain_workspace_bytes", ws, ws_bytes, c.total));
+  char* base = (char*)ws;
+  void* cond = q->boxes.out_cond ? q->boxes.out_cond : (void*)(base + c.best.cond);
+  c.video.cond = cond;
+  CTRLV_TRY(run_best(boxes, &q->boxes, &c.best, base, cond, stream));
+  return run_clip(video, &c.video, nullptr, c.gv, nullptr, c.Lv, base + c.best.stage, stream);
 }

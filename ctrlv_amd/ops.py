@@ -959,6 +959,55 @@ def mask_counts(gt_u8, pred_u8, out=None):
     return out
 
 
+def best_candidate(counts, out=None):
+    """counts int64 (C, n, 2, 3) on the device, block c what `mask_counts` gives for candidate c -> int32 (n): per clip the
+    candidate with the largest all-frames IoU, a tie to the highest c (ctrlv_best_candidate; metrics.best_of restates it)."""
+    fn = "best_candidate"
+    _need_gpu(counts, "counts")
+    if counts.dim() != 4 or tuple(counts.shape[2:]) != (2, 3) or counts.dtype != torch.int64:
+        raise ValueError(f"{fn}: counts must be int64 (C, n, 2, 3)")
+    _need_dense(fn, counts=counts)
+    C, n = counts.shape[:2]
+    out = _out_arg(True if out is None else out, (n,), torch.int32, counts.device, fn, "out")
+    check(_lib.load().ctrlv_best_candidate(_p(counts), n, C, _p(out), _stream()), "ctrlv_best_candidate")
+    return out
+
+
+def gather_clips(src, winner, out=None):
+    """src (C, n, ...) of any dtype, winner int32 (n) on the device -> (n, ...): out[i] = src[winner[i]][i], the index read on
+    the device and clamped into [0, C) (ctrlv_gather_clips).  No host sync."""
+    fn = "gather_clips"
+    _need_gpu(src, "src")
+    if src.dim() < 2:
+        raise ValueError(f"{fn}: src must be (C, n, ...)")
+    C, n = src.shape[:2]
+    if winner.dtype != torch.int32 or tuple(winner.shape) != (n,) or winner.device != src.device:
+        raise ValueError(f"{fn}: winner must be int32 ({n},) on {src.device}")
+    _need_dense(fn, src=src, winner=winner)
+    out = _out_arg(True if out is None else out, tuple(src.shape[1:]), src.dtype, src.device, fn, "out")
+    per = src[0, 0].numel() * src.element_size()
+    check(_lib.load().ctrlv_gather_clips(_p(src), _p(winner), n, C, per, _p(out), _stream()), "ctrlv_gather_clips")
+    return out
+
+
+def boundary_counts(gt_u8, pred_u8, radius, mask_mode=1, out=None):
+    """gt_u8, pred_u8 (n, F, 3, H, W) uint8 -> int64 (n, F, 4) on the device (ctrlv_boundary_counts): per frame {n_fg, n_gt,
+    fg_match, gt_match} of f_measure -- the boundary pixels of the predicted and the ground-truth mask and how many of each lie
+    within `radius` pixels (a disk) of the other's.  mask_mode 0: any channel nonzero; 1: PIL's luma != 0."""
+    fn = "boundary_counts"
+    _need_gpu(gt_u8, "gt_u8")
+    if gt_u8.dim() != 5 or gt_u8.shape[2] != 3 or gt_u8.dtype != torch.uint8:
+        raise ValueError(f"{fn}: gt_u8 must be (n, F, 3, H, W) uint8")
+    if tuple(pred_u8.shape) != tuple(gt_u8.shape) or pred_u8.dtype != torch.uint8 or pred_u8.device != gt_u8.device:
+        raise ValueError(f"{fn}: pred_u8 must be uint8 {tuple(gt_u8.shape)} on {gt_u8.device}")
+    _need_dense(fn, gt_u8=gt_u8, pred_u8=pred_u8)
+    n, F, _, H, W = gt_u8.shape
+    out = _out_arg(True if out is None else out, (n, F, 4), torch.int64, gt_u8.device, fn, "out")
+    check(_lib.load().ctrlv_boundary_counts(_p(gt_u8), _p(pred_u8), n, F, H, W, int(mask_mode), int(radius), _p(out), _stream()),
+          "ctrlv_boundary_counts")
+    return out
+
+
 def randn(seed, shape, *, clip0=0, call=0, stream_id=0, scale=1.0, round_el=False, dtype=torch.float32, el=None, device=None,
           out=None):
     """Counter-based Gaussian noise (ctrlv_randn): shape (n_clips, ...) -- element e of row i is a pure function of (seed,

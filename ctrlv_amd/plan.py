@@ -622,6 +622,125 @@ class PipelinePlan(_Handle):
         del keep, boxes
         return out
 
+    def best_boxes_request(self, who, image_u8, bbox_frames, gt_u8, guidance, num_cond_frames, *, latents=None, aug_noise=None,
+                           schedule=None, seed=None, num_steps=None, clip_index0=0, clean_threshold=50.0, pt=True, cond=True,
+                           u8=True, **kw):
+        """The `ctrlv_best_boxes_request` of C = len(guidance) stage-1 candidates, candidate c with the guidance ramp
+        guidance[c] = (min, max), latents[c] and aug_noise[c]; the other request fields (`request`) by keyword, shared.  With
+        `seed=`: what is omitted of candidate c comes from ctrlv_pipeline_prepare with call = c.  Returns (request, keep,
+        (pt, cond, u8, winner, counts)): keep the three together until the call has finished."""
+        if bbox_frames is None or gt_u8 is None:
+            raise ValueError(f"PipelinePlan.{who}: bbox_frames / gt_u8 is None")
+        C = len(guidance)
+        if not 1 <= C <= 8:
+            raise ValueError(f"PipelinePlan.{who}: {C} guidance pairs; the library takes 1 to 8 candidates")
+        for name, seq in (("latents", latents), ("aug_noise", aug_noise)):
+            if seq is not None and (isinstance(seq, torch.Tensor) or len(seq) != C):
+                raise ValueError(f"PipelinePlan.{who}: {name} must be a sequence of {C} tensors, one per candidate")
+        sig, ts = schedule if schedule is not None else (None, None)
+        rs, keep, boxes = [], [], None
+        for c, (g_min, g_max) in enumerate(guidance):
+            lat = latents[c] if latents is not None else None
+            aug = aug_noise[c] if aug_noise is not None else None
+            fields = dict(kw, min_guidance=g_min, max_guidance=g_max)
+            if seed is not None:
+                r0, sr, keep0, boxes, _ = self.seeded_request(who, image_u8, seed, num_steps=num_steps, num_frames=bbox_frames.shape[1],
+                                                              clip_index0=clip_index0, call=c, latents=lat, sigmas=sig, timesteps=ts,
+                                                              cond=bbox_frames, cond_name="bbox_frames", aug_noise=aug, frames=False,
+                                                              frames_u8=False, **fields)
+                r, prep = self.prepare(r0, sr)
+                keep.append((keep0, r0, sr, prep))
+            else:
+                if lat is None or sig is None:
+                    raise ValueError(f"PipelinePlan.{who}: latents and schedule are needed without seed=")
+                r, keep0, boxes, outs = self._checked_request(who, image_u8, lat, sig, ts, bbox_frames, "bbox_frames", aug, False,
+                                                              False, **fields)
+                keep.append((keep0, outs))
+            rs.append(r)
+        n, F, H, W = rs[0].n_clips, rs[0].num_frames, rs[0].height, rs[0].width
+        dev = self.device
+        if gt_u8.dtype != torch.uint8 or tuple(gt_u8.shape) != (n, F, 3, H, W) or not gt_u8.is_cuda or \
+                (gt_u8.device.index or 0) != (dev.index or 0):
+            raise ValueError(f"PipelinePlan.{who}: gt_u8 must be uint8 {(n, F, 3, H, W)} on {dev}")
+        gt_u8 = gt_u8.contiguous()
+        out_pt = torch.empty(n * F, 3, H, W, dtype=self.dtype, device=dev) if pt else None
+        out_cond = torch.empty(n * F, 3, H, W, dtype=self.dtype, device=dev) if cond else None
+        out_u8 = torch.empty(n, F, 3, H, W, dtype=torch.uint8, device=dev) if u8 else None
+        counts = torch.empty(C, n, 2, 3, dtype=torch.int64, device=dev)
+        winner = torch.empty(n, dtype=torch.int32, device=dev)
+        arr = (_lib.ClipRequest * C)(*rs)
+        q = _lib.BestBoxesRequest()
+        q.n_candidates, q.candidates = C, arr
+        q.box_cond = self.box_condition(boxes, num_cond_frames)
+        q.gt_u8, q.clean_threshold = gt_u8.data_ptr(), float(clean_threshold)
+        for name, t in (("out_pt", out_pt), ("out_cond", out_cond), ("out_u8", out_u8), ("out_counts", counts),
+                        ("out_winner", winner)):
+            if t is not None:
+                setattr(q, name, t.data_ptr())
+        return q, (arr, rs, keep, boxes, gt_u8), (out_pt, out_cond, out_u8, winner, counts)
+
+    def best_boxes(self, image_u8, bbox_frames, gt_u8, guidance=((1, 2), (1, 3), (2, 4), (2, 5), (3, 5)), num_cond_frames=3, *,
+                   latents=None, aug_noise=None, schedule=None, seed=None, num_steps=None, clip_index0=0, **kw):
+        """The reference's best-of-N loop over stage-1 candidates as one C call (ctrlv_pipeline_best_boxes; a plan without a
+        ControlNet): `predict_boxes` once per guidance ramp, each result cleaned (ops.box_frames_post) and counted against
+        gt_u8 (n, F, 3, H, W) uint8 (ops.mask_counts), the best one per clip chosen on the device (ops.best_candidate: largest
+        all-frames IoU, a tie to the later candidate) and post-processed.  latents / aug_noise: sequences, one tensor per
+        candidate; schedule: (sigmas, timesteps), shared; see `best_boxes_request` for the rest.  Nothing synchronises with the
+        host.  Returns (pt, cond, u8, winner, counts): the winner's [0, 1] frames and 2 (y - 0.5) condition, (n F, 3, H, W) in
+        the element type, its cleaned frames (n, F, 3, H, W) uint8, the winning candidate per clip int32 (n) and every
+        candidate's counts int64 (C, n, 2, 3) (metrics.candidate_scores turns them into the logged triples)."""
+        q, keep, out = self.best_boxes_request("best_boxes", image_u8, bbox_frames, gt_u8, guidance, num_cond_frames, latents=latents,
+                                               aug_noise=aug_noise, schedule=schedule, seed=seed, num_steps=num_steps,
+                                               clip_index0=clip_index0, **kw)
+        need = self._nonzero(self._lib.ctrlv_pipeline_best_boxes_workspace_bytes(self._h, ctypes.byref(q)),
+                             "ctrlv_pipeline_best_boxes_workspace_bytes")
+        ws = self._workspace(need)
+        check(self._lib.ctrlv_pipeline_best_boxes(self._h, ctypes.byref(q), ws.data_ptr(), ws.numel(), self._stream()),
+              "ctrlv_pipeline_best_boxes")
+        del keep
+        return out
+
+
+def best_boxes_to_video(boxes_plan, video_plan, image_u8, bbox_frames, gt_u8, guidance=((1, 2), (1, 3), (2, 4), (2, 5), (3, 5)),
+                        num_cond_frames=3, *, box_latents=None, video_latents=None, box_schedule=None, video_schedule=None,
+                        box_aug_noise=None, video_aug_noise=None, clean_threshold=50.0, box_frames_u8=True, frames=True,
+                        frames_u8=True, box_kw=None, video_kw=None, seed=None, num_steps=None, clip_index0=0):
+    """`boxes_plan.best_boxes` and `video_plan.generate` conditioned on the winner's frames, as one C call
+    (ctrlv_pipeline_best_boxes_to_video).  box_latents / box_aug_noise: one tensor per candidate; the rest as `boxes_to_video`.
+    With `seed=`: candidate c draws with call = c, stage 2 with call = C (for one candidate the convention of `boxes_to_video`);
+    num_steps: one count or (stage 1, stage 2).  Returns what `boxes_to_video` returns plus (winner int32 (n), counts int64
+    (C, n, 2, 3))."""
+    if boxes_plan._lib is not video_plan._lib:
+        raise ValueError("best_boxes_to_video: the two pipeline plans must come from one library (one element type)")
+    steps = tuple(num_steps) if isinstance(num_steps, (tuple, list)) else (num_steps, num_steps)
+    qb, keep_b, (_, _, clean, winner, counts) = boxes_plan.best_boxes_request(
+        "best_boxes_to_video", image_u8, bbox_frames, gt_u8, guidance, num_cond_frames, latents=box_latents, aug_noise=box_aug_noise,
+        schedule=box_schedule, seed=seed, num_steps=steps[0], clip_index0=clip_index0, clean_threshold=clean_threshold, pt=False,
+        cond=False, u8=box_frames_u8, **(box_kw or {}))
+    if seed is not None:
+        sig, ts = video_schedule if video_schedule is not None else (None, None)
+        r0, sr, keep0, _, out = video_plan.seeded_request(
+            "best_boxes_to_video", image_u8, seed, num_steps=steps[1], num_frames=bbox_frames.shape[1], clip_index0=clip_index0,
+            call=len(guidance), latents=video_latents, sigmas=sig, timesteps=ts, aug_noise=video_aug_noise, frames=frames,
+            frames_u8=frames_u8, **(video_kw or {}))
+        rv, prep = video_plan.prepare(r0, sr)
+        keep_v = (keep0, r0, sr, prep)
+    else:
+        if video_latents is None or video_schedule is None:
+            raise ValueError("best_boxes_to_video: video_latents and video_schedule are needed without seed=")
+        rv, keep_v, _, out = video_plan._checked_request("best_boxes_to_video", image_u8, video_latents, *video_schedule, None, "cond",
+                                                         video_aug_noise, frames, frames_u8, **(video_kw or {}))
+    q = _lib.BestChainRequest()
+    q.boxes, q.video = qb, rv
+    lib = video_plan._lib
+    need = video_plan._nonzero(lib.ctrlv_pipeline_best_chain_workspace_bytes(boxes_plan._h, video_plan._h, ctypes.byref(q)),
+                               "ctrlv_pipeline_best_chain_workspace_bytes")
+    ws = video_plan._workspace(need)
+    check(lib.ctrlv_pipeline_best_boxes_to_video(boxes_plan._h, video_plan._h, ctypes.byref(q), ws.data_ptr(), ws.numel(),
+                                                 video_plan._stream()), "ctrlv_pipeline_best_boxes_to_video")
+    del keep_b, keep_v
+    return out + (clean, winner, counts)
+
 
 def boxes_to_video(boxes_plan, video_plan, image_u8, box_latents, video_latents, box_schedule, video_schedule, bbox_frames,
                    num_cond_frames=3, *, box_aug_noise=None, video_aug_noise=None, clean_threshold=50.0, box_frames_u8=True,

@@ -1038,6 +1038,101 @@ size_t ctrlv_pipeline_seeded_workspace_bytes(ctrlv_pipeline* p, const ctrlv_clip
 int ctrlv_pipeline_generate_seeded(ctrlv_pipeline* p, const ctrlv_clip_request* r, const ctrlv_seed_request* s, void* ws,
                                    size_t ws_bytes, ctrlv_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Box evaluation around the chain (csrc/box_eval.hip, csrc/pipeline.hip): the reference's best-of-N loop over stage-1 guidance
+ * ramps (tools/eval_overall.py:83-114, tools/draw_teaser.py:160-175) and its boundary F-measure (src/ctrlv/metrics/FandJ.py:
+ * 94-156, tools/eval_video_bbox_prediction.py:85-95), with no host synchronisation between the stages.  Additive entry points:
+ * the ABI number does not change, the existing structs keep their layouts, the existing entry points their bits.
+ * ------------------------------------------------------------------------------------------------------------------ */
+/* Per clip, the candidate whose all-frames mask IoU is largest.  counts: DEVICE (C, n, 2, 3) 64-bit, candidate c's block exactly
+ * what one ctrlv_mask_counts call writes; winner: DEVICE int32 (n).  Over {gt, pred, inter} of all frames: union = gt + pred -
+ * inter, iou = union > 0 ? (double) inter / (double) union : 1.0, compared in fp64 as numpy compares; a tie goes to the HIGHEST c
+ * (the reference's `best_score = max(best_score, miou); if best_score == miou:` lets a later equal score replace an earlier
+ * one).  Two ratios that round to the same double tie, as they do there.  One thread per clip, no atomics, no host sync: the call
+ * can be captured into a graph.  CTRLV_E_BAD_ARG: NULL pointers, counts not 8-byte / winner not 4-byte aligned;
+ * CTRLV_E_BAD_SHAPE: C outside 1 .. 8, n <= 0. */
+int ctrlv_best_candidate(const unsigned long long* counts, int n, int C, int32_t* winner, ctrlv_stream_t stream);
+/* dst[i] = src[winner[i]][i]: src (C, n, bytes_per_clip), dst (n, bytes_per_clip), winner DEVICE int32 (n), read on the device.
+ * A winner outside [0, C) is clamped into the range, so a bad index never reads out of bounds.  A clip whose source and
+ * destination share their offset from a 16-byte boundary is copied with 16-byte accesses between a head and a tail of single
+ * bytes (bytes_per_clip a multiple of 16 and both pointers aligned: no head, no tail); any other clip byte by byte.
+ * CTRLV_E_BAD_ARG: NULL pointers, winner not 4-byte aligned; CTRLV_E_BAD_SHAPE: C outside 1 .. 8, n <= 0, bytes_per_clip 0. */
+int ctrlv_gather_clips(const void* src, const int32_t* winner, int n, int C, size_t bytes_per_clip, void* dst,
+                       ctrlv_stream_t stream);
+
+/* Best of C stage-1 candidates.  Clear the struct before setting fields. */
+typedef struct ctrlv_best_boxes_request {
+  int32_t n_candidates;                  /* C in 1 .. 8 */
+  int32_t reserved;                      /* must be 0 */
+  const ctrlv_clip_request* candidates;  /* HOST array of C stage-1 requests: one geometry (n_clips, num_frames, height, width);
+                                            latents, aug_noise, guidance, schedule and steps may differ.  out_frames and
+                                            out_frames_u8 must be NULL (the frames live in the workspace), out_latents as
+                                            ctrlv_pipeline_generate wants it */
+  ctrlv_box_condition box_cond;          /* one condition, shared by all candidates */
+  const void* gt_u8;                     /* (n, F, 3, H, W) uint8 ground-truth box frames */
+  float clean_threshold;                 /* the reference's 50 */
+  int32_t reserved2;                     /* must be 0 */
+  void* out_pt;                          /* (n F, 3, H, W) elements: the winner's [0, 1] frames, or NULL */
+  void* out_cond;                        /* (n F, 3, H, W) elements: the winner's 2 (y - 0.5), or NULL */
+  void* out_u8;                          /* (n, F, 3, H, W) uint8: the winner's cleaned frames, or NULL */
+  unsigned long long* out_counts;        /* DEVICE (C, n, 2, 3), or NULL (then kept in the workspace) */
+  int32_t* out_winner;                   /* DEVICE (n), or NULL (then kept in the workspace) */
+} ctrlv_best_boxes_request;
+/* 0 for a request the call would refuse (ctrlv_last_error). */
+size_t ctrlv_pipeline_best_boxes_workspace_bytes(ctrlv_pipeline* p, const ctrlv_best_boxes_request* q);
+/* In order, on `stream`: for c = 0 .. C-1 { the clip of candidate c as ctrlv_pipeline_predict_boxes runs it, its decoded
+ * (clamped) frames into workspace slot c; ctrlv_box_frames_post of slot c with out_u8 only, into one scratch buffer all
+ * candidates share; ctrlv_mask_counts(gt_u8, scratch) into block c of the counts }; one ctrlv_best_candidate; one
+ * ctrlv_gather_clips of the frame slots -- the selection is PER CLIP: two clips of one call may take different candidates --; one
+ * ctrlv_box_frames_post of the gathered frames into out_pt / out_cond / out_u8 (all three NULL: the last two calls are skipped).
+ * Nothing else: the bits are those of these calls made by hand.  The candidates' own workspaces alias one region, as the stages
+ * of ctrlv_pipeline_boxes_to_video do; nothing synchronises with the host.  Refused by name on the host before any launch:
+ * C outside 1 .. 8 (CTRLV_E_BAD_SHAPE), a NULL candidates array or gt_u8, a nonzero reserved field, a threshold that is not
+ * finite, a candidate with out_frames or out_frames_u8 set, out_counts / out_winner misaligned (CTRLV_E_BAD_ARG), candidates
+ * of different geometry (CTRLV_E_BAD_SHAPE), whatever ctrlv_pipeline_predict_boxes refuses, ws too small (CTRLV_E_WORKSPACE). */
+int ctrlv_pipeline_best_boxes(ctrlv_pipeline* p, const ctrlv_best_boxes_request* q, void* ws, size_t ws_bytes,
+                              ctrlv_stream_t stream);
+
+/* Best-of-C boxes, then the video.  Clear the struct before setting fields. */
+typedef struct ctrlv_best_chain_request {
+  ctrlv_best_boxes_request boxes;        /* out_cond NULL: the condition lives in the workspace */
+  ctrlv_clip_request video;              /* cond must be NULL on entry: the driver supplies the winner's frames */
+  int32_t reserved;                      /* must be 0 */
+} ctrlv_best_chain_request;
+/* 0 for a request the call would refuse (ctrlv_last_error). */
+size_t ctrlv_pipeline_best_chain_workspace_bytes(ctrlv_pipeline* boxes, ctrlv_pipeline* video, const ctrlv_best_chain_request* q);
+/* ctrlv_pipeline_best_boxes on `boxes`, its out_cond (the caller's, or a buffer in ws) becoming the condition of
+ * ctrlv_pipeline_generate on `video`; the two pipelines' workspaces alias.  With C = 1: the bits of
+ * ctrlv_pipeline_boxes_to_video.  Refused by name before any launch: what ctrlv_pipeline_best_boxes and
+ * ctrlv_pipeline_boxes_to_video refuse (pipelines of another library or on different devices, a video pipeline without a
+ * ControlNet, video.cond set, a video request of another geometry). */
+int ctrlv_pipeline_best_boxes_to_video(ctrlv_pipeline* boxes, ctrlv_pipeline* video, const ctrlv_best_chain_request* q, void* ws,
+                                       size_t ws_bytes, ctrlv_stream_t stream);
+
+/* The pixel radius of f_measure's boundary tolerance (host arithmetic, needs no GPU): bound_th itself when bound_th >= 1 (an
+ * integer), else ceil(bound_th * sqrt((double) (H^2 + W^2))) in double -- the square root of the integer, not hypot: at 75 x 100
+ * the product with 0.008 is exactly 1.  576 x 1024 -> 10, 320 x 512 -> 5.  < 0 on refusal (ctrlv_last_error): sizes not
+ * positive, bound_th not finite, negative, or >= 1 and not an integer. */
+int ctrlv_boundary_radius(int H, int W, double bound_th);
+/* The four counts of f_measure per frame.  gt_u8, pred_u8 (n, F, 3, H, W) uint8 as for ctrlv_mask_counts; counts: DEVICE
+ * (n, F, 4) 64-bit, 8-byte aligned, zeroed by the call: {n_fg, n_gt, fg_match, gt_match}.  With G and P the masks of a frame:
+ *   mask      mask_mode 0: any channel nonzero (binary_mask_iou's mask); mask_mode 1: (19595 R + 38470 G + 7471 B + 0x8000) >> 16
+ *             != 0, PIL's convert('L') (eval_video_bbox_prediction.py:89-92) -- not mode 0: (1, 0, 0) is outside the mask
+ *   b(S)      the one-pixel boundary map: for y < H-1, x < W-1: S[y,x] != S[y,x+1] | S[y,x] != S[y+1,x] | S[y,x] != S[y+1,x+1];
+ *             last row, x < W-1: S[y,x] != S[y,x+1]; last column, y < H-1: S[y,x] != S[y+1,x]; the bottom-right corner: 0
+ *   D(b)      dilation by a disk: D(b)[y,x] = OR of b[y+dy, x+dx] over dx^2 + dy^2 <= radius^2 inside the image (outside
+ *             contributes nothing)
+ *   counts    n_fg = |b(P)|, n_gt = |b(G)|, fg_match = |b(P) & D(b(G))|, gt_match = |b(G) & D(b(P))|
+ * Integers: precision = fg_match / n_fg, recall = gt_match / n_gt and F are formed from them on the host.  One workgroup per
+ * frame and band of rows: the mask bits of the band, `radius` rows of halo and one row below go into LDS as 64-bit words
+ * (16-byte loads where W is a multiple of 16 and the pointers are aligned, single bytes and a ballot otherwise), the boundary
+ * words by shift and xor, the dilation per dy as a horizontal OR-spread by floor(sqrt(radius^2 - dy^2)); the dilated image
+ * never reaches memory.  Refused by name on the host before any launch: NULL pointers, counts misaligned (CTRLV_E_BAD_ARG),
+ * radius outside 1 .. 32, mask_mode outside {0, 1}, sizes not positive, a width whose rows of words do not fit the LDS layout
+ * at this radius (1856 at radius 32, more at smaller radii), more than 2^31 - 1 workgroups (CTRLV_E_BAD_SHAPE). */
+int ctrlv_boundary_counts(const void* gt_u8, const void* pred_u8, int n, int F, int H, int W, int mask_mode, int radius,
+                          unsigned long long* counts, ctrlv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

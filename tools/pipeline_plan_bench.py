@@ -23,6 +23,12 @@ the two Python pipeline calls with host numpy in between; the record goes to pro
 frames.  Needs no weights: prepare reads the plans' configurations only.
 
     timeout -k 10 300 python tools/pipeline_plan_bench.py --seeded [--rounds 10]
+
+`--best-of C` times the best-of-C loop over stage-1 candidates instead (best_main below): ONE C call (ctrlv_pipeline_best_boxes)
+against C predict_boxes calls with the clean-up and the counts on the device, the counts copied to the host per candidate and the
+argmax there; the record goes to profiles/box_eval_bench.jsonl.
+
+    timeout -k 10 900 python tools/pipeline_plan_bench.py --best-of 5 --height 320 --width 512 [--steps 25 --rounds 3]
 """
 import argparse
 import json
@@ -162,6 +168,99 @@ def boxes_main(args):
         f.write(json.dumps(rec) + "\n")
 
 
+RAMPS = ((1, 2), (1, 3), (2, 4), (2, 5), (3, 5), (1, 4), (2, 3), (3, 4))      # the reference's five, then three more
+
+
+def best_main(args):
+    """--best-of C: image + first / last box frames + ground-truth box frames -> the best candidate's frames.  `one_call`:
+    PipelinePlan.best_boxes (every candidate, the scores, the choice and the winner's post-processing enqueued by one C call;
+    the host waits once, at the end).  `by_hand`: what a host of the plan route did before -- per candidate predict_boxes,
+    ops.box_frames_post, ops.mask_counts and the counts' .cpu() (one synchronisation per candidate), metrics.best_of on the
+    host, then ops.box_frames_post of the winner.  Same plans, same inputs, same device, alternated `--rounds` times after one
+    warm call each; host clock around synchronised calls.  The kernels are the same: what differs is the synchronisations."""
+    import __graft_entry__ as g
+    g.build()
+    from ctrlv_amd import metrics, ops
+    from ctrlv_amd.models import AutoencoderKLTemporalDecoder, CLIPVisionModelWithProjection, UNetSpatioTemporalConditionModel
+    from ctrlv_amd.pipelines import VideoDiffusionPipeline
+    from ctrlv_amd.pipelines.pipeline_utils import MinimalCLIPImageProcessor
+    from ctrlv_amd.schedulers import EulerDiscreteScheduler
+    from ctrlv_amd.utils import build_on_device, random_init_
+    os.environ["CTRLV_VAE_HIP"] = "plan"
+    os.environ["CTRLV_CLIP_HIP"] = "plan"
+    H, W, F, K, steps, C, thr = args.height, args.width, args.frames, args.cond_frames, args.steps, args.best_of, 50.0
+    bf = torch.bfloat16
+    box_unet = build_on_device(UNetSpatioTemporalConditionModel, DEV, num_frames=F)
+    random_init_(box_unet, seed=2)
+    torch.manual_seed(0)
+    vae = AutoencoderKLTemporalDecoder().eval().to(DEV, bf).requires_grad_(False)
+    with torch.device(DEV):
+        clip = CLIPVisionModelWithProjection(**dict(VIT_H, num_hidden_layers=args.clip_layers))
+    with torch.no_grad():
+        for p in clip.parameters():
+            if p.dim() > 1:
+                p.normal_(0.0, 0.02)
+    clip = clip.to(bf).eval().requires_grad_(False)
+    sched = EulerDiscreteScheduler()
+    boxes_pipe = VideoDiffusionPipeline(vae, clip, box_unet.eval(), sched, MinimalCLIPImageProcessor())
+    pb = boxes_pipe._pipeline_plan()
+    assert pb is not None, "the plan does not serve this pipeline"
+    gen = torch.Generator().manual_seed(3)
+    image_u8 = torch.randint(0, 256, (1, H, W, 3), generator=gen, dtype=torch.uint8).to(DEV)
+    bbox = (torch.rand(1, F, 3, H, W, generator=gen) * 2 - 1).to(DEV)
+    gt = (torch.rand(1, F, 3, H, W, generator=gen) < 0.3).to(torch.uint8).mul(255).to(DEV)
+    sched.set_timesteps(steps, device=DEV)
+    schedule = (list(sched._sigmas_host), list(sched._timesteps_host))
+    lats = [(torch.randn(1, F, 4, H // 8, W // 8, generator=gen) * sched.init_noise_sigma).to(DEV) for _ in range(C)]
+    augs = [torch.randn(1, 3, H, W, generator=gen).to(DEV) for _ in range(C)]
+    ramps = RAMPS[:C]
+    kw = dict(noise_aug_strength=0.02, fps=7, motion_bucket_id=127, decode_chunk=F)
+
+    def one_call():
+        pt, cond, u8, winner, counts = pb.best_boxes(image_u8, bbox, gt, ramps, K, latents=lats, aug_noise=augs, schedule=schedule,
+                                                     clean_threshold=thr, **kw)
+        return u8.cpu().numpy(), winner.cpu().tolist(), counts.cpu()
+
+    def by_hand():
+        frames, counts = [], []
+        for c, (lo, hi) in enumerate(ramps):
+            _, fr, _ = pb.predict_boxes(image_u8, lats[c], *schedule, bbox, K, aug_noise=augs[c], frames_u8=False, min_guidance=lo,
+                                        max_guidance=hi, **kw)
+            clean = ops.box_frames_post(fr, F, thr, pt=False, cond=False)[2]
+            frames.append(fr.clone())                                   # (the next call's frames land in a fresh tensor anyway)
+            counts.append(ops.mask_counts(gt, clean).cpu())             # the score of this candidate, on the host
+        winner = metrics.best_of(torch.stack(counts))
+        pt, cond, u8 = ops.box_frames_post(frames[winner[0]], F, thr)
+        return u8.cpu().numpy(), winner, torch.stack(counts)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    routes = {"by_hand": by_hand, "one_call": one_call}
+    with torch.no_grad():
+        ref = {name: timed(fn)[1] for name, fn in routes.items()}                     # warm
+        times = {name: [] for name in routes}
+        for _ in range(args.rounds):
+            for name, fn in routes.items():
+                times[name].append(timed(fn)[0])
+    rec = dict(tool="pipeline_plan_bench --best-of", candidates=C, size=f"{H}x{W}", frames=F, steps=steps, cond_frames=K,
+               rounds=args.rounds, clip_layers=args.clip_layers, device=torch.cuda.get_device_name(0),
+               same_winner=ref["by_hand"][1] == ref["one_call"][1], same_counts=bool(torch.equal(ref["by_hand"][2], ref["one_call"][2])),
+               same_cleaned_bytes=bool((ref["by_hand"][0] == ref["one_call"][0]).all()))
+    for name in routes:
+        rec[name] = dict(call_s=round(statistics.median(times[name]), 4), all_call_s=[round(v, 4) for v in times[name]])
+    rec["one_call_over_by_hand"] = round(rec["one_call"]["call_s"] / rec["by_hand"]["call_s"], 4)
+    print(json.dumps(rec), flush=True)
+    out_path = args.out or os.path.join(ROOT, "profiles", "box_eval_bench.jsonl")
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    with open(out_path, "a") as f:
+        f.write(json.dumps(rec) + "\n")
+
+
 SVD = dict(in_channels=8, out_channels=4, block_out_channels=(320, 640, 1280, 1280), layers_per_block=2,
            down_block_types=("CrossAttnDownBlockSpatioTemporal",) * 3 + ("DownBlockSpatioTemporal",),
            up_block_types=("UpBlockSpatioTemporal",) + ("CrossAttnUpBlockSpatioTemporal",) * 3,
@@ -236,7 +335,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seeded", action="store_true", help="time the prepare phase (appends to profiles/pipeline_plan_bench.jsonl)")
     ap.add_argument("--boxes", action="store_true", help="time the boxes-to-video chain (appends to profiles/box_chain_bench.jsonl)")
-    ap.add_argument("--cond-frames", type=int, default=3, help="--boxes: num_cond_bbox_frames")
+    ap.add_argument("--best-of", type=int, default=0, metavar="C", help="time the best-of-C candidate loop, C in 1 .. 8 (appends to "
+                    "profiles/box_eval_bench.jsonl)")
+    ap.add_argument("--cond-frames", type=int, default=3, help="--boxes / --best-of: num_cond_bbox_frames")
     ap.add_argument("--out", default=None)
     ap.add_argument("--height", type=int, default=576)
     ap.add_argument("--width", type=int, default=1024)
@@ -246,6 +347,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--clip-layers", type=int, default=32)
     args = ap.parse_args()
+    if args.best_of:
+        if not 1 <= args.best_of <= len(RAMPS):
+            ap.error("--best-of takes 1 to 8 candidates")
+        return best_main(args)
     if args.boxes:
         return boxes_main(args)
     if args.seeded:
