@@ -328,6 +328,11 @@ SIGNATURES = {
                                                    c_void_p]),
     "ctrlv_boundary_radius": (c_int, [c_int, c_int, ctypes.c_double]),
     "ctrlv_boundary_counts": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ctrlv_frame_stats": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ctrlv_frame_ssim_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "ctrlv_frame_ssim": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ctrlv_resize_frames_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "ctrlv_resize_frames_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
 }
 
 _libs = {}                # element dtype code (2 bf16 / 1 fp16) -> CDLL
@@ -341,7 +346,7 @@ _NO_STATUS = {"ctrlv_abi_version", "ctrlv_elem_dtype", "ctrlv_build_id", "ctrlv_
               "ctrlv_pipeline_workspace_bytes", "ctrlv_pipeline_boxes_workspace_bytes", "ctrlv_box_frames_post_ws_bytes",
               "ctrlv_pipeline_chain_workspace_bytes", "ctrlv_resize_lanczos_ws_bytes", "ctrlv_pipeline_prepare_bytes",
               "ctrlv_pipeline_seeded_workspace_bytes", "ctrlv_pipeline_best_boxes_workspace_bytes",
-              "ctrlv_pipeline_best_chain_workspace_bytes",
+              "ctrlv_pipeline_best_chain_workspace_bytes", "ctrlv_frame_ssim_ws_bytes", "ctrlv_resize_frames_ws_bytes",
               # a radius, or a negative status
               "ctrlv_boundary_radius"}
 

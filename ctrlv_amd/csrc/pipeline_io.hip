@@ -7,6 +7,7 @@
 //   ctrlv_randn              counter-based Gaussian noise: Philox4x32-10, fp32 uniforms, Box-Muller (keyed per clip)
 //   ctrlv_euler_schedule     EulerDiscreteScheduler.set_timesteps' tables (host arithmetic)
 //   ctrlv_resize_lanczos_u8  PIL's 8-bit Lanczos resize, byte for byte (integer arithmetic on host-built tables)
+//   ctrlv_resize_frames_u8   the same two passes on single planes with PIL's LANCZOS, BILINEAR or BICUBIC kernel
 //   ctrlv_pio_*              the doubling / repeating / scattering of the loop's inputs (pipeline_io.h; csrc/pipeline.hip)
 // All arithmetic is fp32.  Where the Python expression is a multiply followed by an add that a test compares bit for bit the two
 // roundings are kept (__fmul_rn / __fadd_rn: never contracted into an fma).  Once per clip, HBM-bound, no atomics.
@@ -329,9 +330,11 @@ __global__ __launch_bounds__(256) void randn_kernel(uint32_t k0, uint32_t k1, ui
 constexpr int kLzTx = 64, kLzTy = 4;     // a workgroup's tile of output pixels
 constexpr int kLzMaxScale = 16;          // per-axis down-scale: at most 2 * 48 + 1 = 97 taps, 64 rows of them in 24.3 KiB of LDS
 
-// src (n, Hi, Wi, 3) -> dst (n, Ho, Wo, 3); the axis that is not resampled has the same size on both sides.  bounds[o] = (first
-// tap, taps) and weights[o][ksize] (22-bit fixed point) of output index o along the axis.  The workgroup stages the weight rows
-// of its tile -- 64 along x, 4 along y -- in LDS (ksize is odd: the 64 rows of the horizontal pass fall on different banks).
+// src (n, Hi, Wi, CH) -> dst (n, Ho, Wo, CH); the axis that is not resampled has the same size on both sides.  CH = 3: interleaved
+// RGB images; CH = 1: single planes (ctrlv_resize_frames_u8).  bounds[o] = (first tap, taps) and weights[o][ksize] (22-bit fixed
+// point) of output index o along the axis.  The workgroup stages the weight rows of its tile -- 64 along x, 4 along y -- in LDS
+// (ksize is odd: the 64 rows of the horizontal pass fall on different banks).
+template <int CH>
 __global__ __launch_bounds__(256) void lanczos_pass_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                                            const int2* __restrict__ bounds, const int* __restrict__ weights,
                                                            int ksize, int axis, int Hi, int Wi, int Ho, int Wo) {
@@ -346,26 +349,26 @@ __global__ __launch_bounds__(256) void lanczos_pass_kernel(const uint8_t* __rest
   const int lo = axis == 0 ? tx : ty;
   const int2 b = bounds[o0 + lo];
   const int* k = kw + lo * ksize;
-  const uint8_t* p = axis == 0 ? src + (((long)img * Hi + y) * Wi + b.x) * 3 : src + (((long)img * Hi + b.x) * Wi + x) * 3;
-  const long step = axis == 0 ? 3 : (long)Wi * 3;
-  int s0 = 1 << 21, s1 = 1 << 21, s2 = 1 << 21;
+  const uint8_t* p = axis == 0 ? src + (((long)img * Hi + y) * Wi + b.x) * CH : src + (((long)img * Hi + b.x) * Wi + x) * CH;
+  const long step = axis == 0 ? CH : (long)Wi * CH;
+  int s[CH];
+#pragma unroll
+  for (int c = 0; c < CH; ++c) s[c] = 1 << 21;
   for (int t = 0; t < b.y; ++t) {
     const int w = k[t];
-    s0 += (int)p[0] * w;
-    s1 += (int)p[1] * w;
-    s2 += (int)p[2] * w;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) s[c] += (int)p[c] * w;
     p += step;
   }
-  uint8_t* o = dst + (((long)img * Ho + y) * Wo + x) * 3;
-  o[0] = (uint8_t)clampi(s0 >> 22, 0, 255);
-  o[1] = (uint8_t)clampi(s1 >> 22, 0, 255);
-  o[2] = (uint8_t)clampi(s2 >> 22, 0, 255);
+  uint8_t* o = dst + (((long)img * Ho + y) * Wo + x) * CH;
+#pragma unroll
+  for (int c = 0; c < CH; ++c) o[c] = (uint8_t)clampi(s[c] >> 22, 0, 255);
 }
 
-int lanczos_ksize(int in, int out) {
-  const double scale = (double)in / (double)out, fs = scale < 1.0 ? 1.0 : scale;
-  return (int)ceil(3.0 * fs) * 2 + 1;
-}
+// PIL's filter codes (Image.Resampling) and their kernels (libImaging/Resample.c): support and function
+constexpr int kFilterLanczos = 1, kFilterBilinear = 2, kFilterBicubic = 3;
+
+double resample_support(int filter) { return filter == kFilterBilinear ? 1.0 : (filter == kFilterBicubic ? 2.0 : 3.0); }
 
 double lanczos_sinc(double v) {
   if (v == 0.0) return 1.0;
@@ -373,9 +376,24 @@ double lanczos_sinc(double v) {
   return sin(v) / v;
 }
 
+double resample_filter(int filter, double v) {
+  if (filter == kFilterLanczos) return (-3.0 <= v && v < 3.0) ? lanczos_sinc(v) * lanczos_sinc(v / 3.0) : 0.0;
+  if (v < 0.0) v = -v;
+  if (filter == kFilterBilinear) return v < 1.0 ? 1.0 - v : 0.0;
+  const double a = -0.5;                                  // bicubic
+  if (v < 1.0) return ((a + 2.0) * v - (a + 3.0)) * v * v + 1;
+  if (v < 2.0) return (((v - 5) * v + 8) * v - 4) * a;
+  return 0.0;
+}
+
+int resample_ksize(int in, int out, int filter) {
+  const double scale = (double)in / (double)out, fs = scale < 1.0 ? 1.0 : scale;
+  return (int)ceil(resample_support(filter) * fs) * 2 + 1;
+}
+
 // bounds [out][2] and weights [out][ksize] of one axis, as PIL's precompute_coeffs + normalize_coeffs_8bpc form them
-void lanczos_tables(int in, int out, int ksize, int32_t* bounds, int32_t* weights) {
-  const double scale = (double)in / (double)out, fs = scale < 1.0 ? 1.0 : scale, support = 3.0 * fs;
+void resample_tables(int in, int out, int ksize, int filter, int32_t* bounds, int32_t* weights) {
+  const double scale = (double)in / (double)out, fs = scale < 1.0 ? 1.0 : scale, support = resample_support(filter) * fs;
   std::vector<double> k((size_t)ksize);
   for (int x = 0; x < out; ++x) {
     const double center = (x + 0.5) * scale;
@@ -386,8 +404,7 @@ void lanczos_tables(int in, int out, int ksize, int32_t* bounds, int32_t* weight
     if (cnt > ksize) cnt = ksize;                     // (cannot happen: 2 support + 1 <= ksize; guards the table)
     double sum = 0.0;
     for (int t = 0; t < cnt; ++t) {
-      const double v = (t + xmin - center + 0.5) / fs;
-      k[t] = (-3.0 <= v && v < 3.0) ? lanczos_sinc(v) * lanczos_sinc(v / 3.0) : 0.0;
+      k[t] = resample_filter(filter, (t + xmin - center + 0.5) / fs);
       sum += k[t];
     }
     int32_t* w = weights + (size_t)x * ksize;
@@ -402,8 +419,46 @@ void lanczos_tables(int in, int out, int ksize, int32_t* bounds, int32_t* weight
 }
 
 // the tables of one call in `ws`, in ints: bounds x [w][2] | bounds y [h][2] | weights x [w][ksx] | weights y [h][ksy]
-size_t lanczos_table_ints(int H, int W, int h, int w) {
-  return (size_t)w * (2 + lanczos_ksize(W, w)) + (size_t)h * (2 + lanczos_ksize(H, h));
+size_t resample_table_ints(int H, int W, int h, int w, int filter) {
+  return (size_t)w * (2 + resample_ksize(W, w, filter)) + (size_t)h * (2 + resample_ksize(H, h, filter));
+}
+
+// Both passes of one resize of `imgs` images of CH interleaved channels: the tables of `filter` built on the host, one upload,
+// horizontal into `mid` (imgs, H, w, CH), vertical into dst.  ws holds the tables, then (256-byte aligned) mid.  At most 65535
+// images per launch: the images go out in runs of that many.
+template <int CH>
+int resample_two_pass(const uint8_t* src, long imgs, int H, int W, uint8_t* dst, int h, int w, int filter, void* ws, hipStream_t s) {
+  const int ksx = resample_ksize(W, w, filter), ksy = resample_ksize(H, h, filter);
+  const size_t ints = resample_table_ints(H, W, h, w, filter);
+  // the host staging of the one upload: the copy of a pageable source is staged before hipMemcpyAsync returns, as with the
+  // driver's constants block (csrc/pipeline.hip)
+  static thread_local std::vector<int32_t> tab;
+  tab.assign(ints, 0);
+  int32_t* bx = tab.data();
+  int32_t* by = bx + 2 * (size_t)w;
+  int32_t* wx = by + 2 * (size_t)h;
+  int32_t* wy = wx + (size_t)w * ksx;
+  resample_tables(W, w, ksx, filter, bx, wx);
+  resample_tables(H, h, ksy, filter, by, wy);
+  int32_t* d = (int32_t*)ws;
+  uint8_t* mid = (uint8_t*)ws + up256(ints * sizeof(int32_t));
+  CTRLV_HIP_TRY(hipMemcpyAsync(d, tab.data(), ints * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  const dim3 block(kLzTx, kLzTy);
+  for (long i0 = 0; i0 < imgs; i0 += 65535) {
+    const unsigned run = (unsigned)(imgs - i0 < 65535 ? imgs - i0 : 65535);
+    const uint8_t* sp = src + (size_t)i0 * H * W * CH;
+    uint8_t* mp = mid + (size_t)i0 * H * w * CH;
+    uint8_t* dp = dst + (size_t)i0 * h * w * CH;
+    hipLaunchKernelGGL(lanczos_pass_kernel<CH>, dim3((unsigned)((w + kLzTx - 1) / kLzTx), (unsigned)((H + kLzTy - 1) / kLzTy), run),
+                       block, (size_t)kLzTx * ksx * sizeof(int), s, sp, mp, (const int2*)d,
+                       (const int*)(d + 2 * (size_t)w + 2 * (size_t)h), ksx, 0, H, W, H, w);
+    CTRLV_LAUNCH_CHECK();
+    hipLaunchKernelGGL(lanczos_pass_kernel<CH>, dim3((unsigned)((w + kLzTx - 1) / kLzTx), (unsigned)((h + kLzTy - 1) / kLzTy), run),
+                       block, (size_t)kLzTy * ksy * sizeof(int), s, (const uint8_t*)mp, dp, (const int2*)(d + 2 * (size_t)w),
+                       (const int*)(d + 2 * (size_t)w + 2 * (size_t)h + (size_t)w * ksx), ksy, 1, H, w, h, w);
+    CTRLV_LAUNCH_CHECK();
+  }
+  return CTRLV_OK;
 }
 
 inline unsigned blocks_for(long n) { return (unsigned)((n + 255) / 256); }
@@ -616,7 +671,7 @@ int ctrlv_resize_lanczos_check(int n, int H, int W, int h, int w) {
 
 extern "C" size_t ctrlv_resize_lanczos_ws_bytes(int n, int H, int W, int h, int w) {
   if (ctrlv_resize_lanczos_check(n, H, W, h, w) != CTRLV_OK) return 0;
-  return up256(lanczos_table_ints(H, W, h, w) * sizeof(int32_t)) + up256((size_t)n * H * w * 3);
+  return up256(resample_table_ints(H, W, h, w, kFilterLanczos) * sizeof(int32_t)) + up256((size_t)n * H * w * 3);
 }
 
 extern "C" int ctrlv_resize_lanczos_u8(const void* src_u8, int n, int H, int W, void* dst_u8, int h, int w, void* ws,
@@ -630,31 +685,37 @@ extern "C" int ctrlv_resize_lanczos_u8(const void* src_u8, int n, int H, int W, 
                     ws_bytes, need);
     return CTRLV_E_WORKSPACE;
   }
-  const int ksx = lanczos_ksize(W, w), ksy = lanczos_ksize(H, h);
-  const size_t ints = lanczos_table_ints(H, W, h, w);
-  // the host staging of the one upload: the copy of a pageable source is staged before hipMemcpyAsync returns, as with the
-  // driver's constants block (csrc/pipeline.hip)
-  static thread_local std::vector<int32_t> tab;
-  tab.assign(ints, 0);
-  int32_t* bx = tab.data();
-  int32_t* by = bx + 2 * (size_t)w;
-  int32_t* wx = by + 2 * (size_t)h;
-  int32_t* wy = wx + (size_t)w * ksx;
-  lanczos_tables(W, w, ksx, bx, wx);
-  lanczos_tables(H, h, ksy, by, wy);
-  const hipStream_t s = (hipStream_t)stream;
-  int32_t* d = (int32_t*)ws;
-  uint8_t* mid = (uint8_t*)ws + up256(ints * sizeof(int32_t));
-  CTRLV_HIP_TRY(hipMemcpyAsync(d, tab.data(), ints * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  const dim3 block(kLzTx, kLzTy);
-  hipLaunchKernelGGL(lanczos_pass_kernel, dim3((unsigned)((w + kLzTx - 1) / kLzTx), (unsigned)((H + kLzTy - 1) / kLzTy), (unsigned)n),
-                     block, (size_t)kLzTx * ksx * sizeof(int), s, (const uint8_t*)src_u8, mid, (const int2*)d,
-                     (const int*)(d + 2 * (size_t)w + 2 * (size_t)h), ksx, 0, H, W, H, w);
-  CTRLV_LAUNCH_CHECK();
-  hipLaunchKernelGGL(lanczos_pass_kernel, dim3((unsigned)((w + kLzTx - 1) / kLzTx), (unsigned)((h + kLzTy - 1) / kLzTy), (unsigned)n),
-                     block, (size_t)kLzTy * ksy * sizeof(int), s, (const uint8_t*)mid, (uint8_t*)dst_u8,
-                     (const int2*)(d + 2 * (size_t)w), (const int*)(d + 2 * (size_t)w + 2 * (size_t)h + (size_t)w * ksx), ksy, 1, H, w,
-                     h, w);
-  CTRLV_LAUNCH_CHECK();
+  return resample_two_pass<3>((const uint8_t*)src_u8, n, H, W, (uint8_t*)dst_u8, h, w, kFilterLanczos, ws, (hipStream_t)stream);
+}
+
+// Host-side validation of one resize of planes.
+static int resize_frames_check(int planes, int H, int W, int h, int w, int filter) {
+  CTRLV_CHECK_ARG(filter == kFilterLanczos || filter == kFilterBilinear || filter == kFilterBicubic, "resize_frames: filter=%d "
+                  "must be one of PIL's codes 1 (LANCZOS), 2 (BILINEAR), 3 (BICUBIC)", filter);
+  CTRLV_CHECK_SHAPE(planes > 0 && H > 0 && W > 0 && h > 0 && w > 0, "resize_frames: a zero dimension (planes=%d, %dx%d -> %dx%d)",
+                    planes, H, W, h, w);
+  CTRLV_CHECK_SHAPE((h + kLzTy - 1) / kLzTy <= 65535 && (H + kLzTy - 1) / kLzTy <= 65535, "resize_frames: %d -> %d rows: at most "
+                    "262140 rows", H, h);
+  CTRLV_CHECK_SHAPE((long)H <= (long)kLzMaxScale * h && (long)W <= (long)kLzMaxScale * w, "resize_frames: a down-scale above %d "
+                    "(%dx%d -> %dx%d)", kLzMaxScale, H, W, h, w);
   return CTRLV_OK;
+}
+
+extern "C" size_t ctrlv_resize_frames_ws_bytes(int planes, int H, int W, int h, int w, int filter) {
+  if (resize_frames_check(planes, H, W, h, w, filter) != CTRLV_OK) return 0;
+  return up256(resample_table_ints(H, W, h, w, filter) * sizeof(int32_t)) + up256((size_t)planes * H * w);
+}
+
+extern "C" int ctrlv_resize_frames_u8(const void* src_u8, int planes, int H, int W, void* dst_u8, int h, int w, int filter, void* ws,
+                                      size_t ws_bytes, ctrlv_stream_t stream) {
+  CTRLV_CHECK_ARG(src_u8 != nullptr && dst_u8 != nullptr, "resize_frames: null pointer");
+  CTRLV_TRY(resize_frames_check(planes, H, W, h, w, filter));
+  CTRLV_CHECK_ARG(ws != nullptr && ((uintptr_t)ws & 15) == 0, "resize_frames: the workspace must be non-null and 16-byte aligned");
+  const size_t need = ctrlv_resize_frames_ws_bytes(planes, H, W, h, w, filter);
+  if (ws_bytes < need) {
+    ctrlv_set_error("resize_frames: ws_bytes=%zu is smaller than the %zu bytes this resize needs (ctrlv_resize_frames_ws_bytes)",
+                    ws_bytes, need);
+    return CTRLV_E_WORKSPACE;
+  }
+  return resample_two_pass<1>((const uint8_t*)src_u8, planes, H, W, (uint8_t*)dst_u8, h, w, filter, ws, (hipStream_t)stream);
 }

@@ -7,7 +7,15 @@
 - `boundary_f_measure` (FandJ.py:94-156; tools/eval_video_bbox_prediction.py:85-95): the boundary F-measure of the box
   predictor.  ops.boundary_counts gives four integers per frame; precision, recall and F are formed here in double.
 
-FVD and the other evaluation metrics stay out of scope."""
+- `frame_quality` / `psnr_from_stats` / `quality_summary` (src/ctrlv/metrics/fvd.py:251-286): the per-frame SSIM and PSNR of a
+  generated clip against its ground truth, as evaluate_vids computes them with PIL and scikit-image -- the ssim_score_image
+  and psnr_score_image numbers and their error terms.  The resize, the three integers of PSNR and SSIM itself run on the
+  device (ops.resize_frames_u8, ops.frame_stats, ops.frame_ssim); n F doubles and 3 n F integers come to the host.
+
+FVD (a TorchScript I3D fetched from a URL), LPIPS (AlexNet weights) and the per-video 3-D SSIM / PSNR the reference computes
+but no longer prints stay out of scope."""
+import math
+
 import numpy as np
 import torch
 
@@ -118,5 +126,50 @@ def boundary_f_measure(gt_u8, pred_u8, mask="luma", bound_th=0.008):
     return out[0] if single else out
 
 
+def psnr_from_stats(min_byte, max_byte, sse, count):
+    """peak_signal_noise_ratio(gt, gen, data_range=R) from the integers of ops.frame_stats, in double: R = max - min, count the
+    number of compared values (3 H W): 10 log10(R^2 count / sse).  inf for sse = 0 with R > 0 (skimage's division by a zero
+    error), NaN for R = 0 (both frames one constant: the reference's log10(0 / 0))."""
+    r, sse, count = int(max_byte) - int(min_byte), int(sse), int(count)
+    if r == 0:
+        return math.nan
+    if sse == 0:
+        return math.inf
+    return 10.0 * math.log10((r * r * count) / sse)
+
+
+def frame_quality(gt_u8, gen_u8, size=None, resample="bicubic"):
+    """gt_u8, gen_u8: (F, 3, H, W) or (n, F, 3, H, W) uint8 frames on a HIP device -> {"ssim": float64 (F) or (n, F), "psnr":
+    the same}: per frame, scikit-image's structural_similarity(channel_axis=0, data_range=R, gaussian_weights=True, sigma=1.5)
+    and peak_signal_noise_ratio(data_range=R) with R the joint value range of the two frames -- evaluate_vids'
+    ssim_score_image / psnr_score_image.  size=(h, w): both clips are first resized on the device as PIL resizes them
+    (evaluate_vids: size=(256, 410), PIL's default bicubic).  A frame pair of one constant value is NaN in both."""
+    single = gt_u8.dim() == 4
+    if single:
+        gt_u8, gen_u8 = gt_u8[None], gen_u8[None]
+    gt_u8, gen_u8 = gt_u8.contiguous(), gen_u8.contiguous()
+    if size is not None:
+        h, w = (int(v) for v in size)
+        gt_u8 = ops.resize_frames_u8(gt_u8, h, w, resample)
+        gen_u8 = ops.resize_frames_u8(gen_u8, h, w, resample)
+    stats = ops.frame_stats(gt_u8, gen_u8)
+    ssim = ops.frame_ssim(gt_u8, gen_u8, stats).cpu().numpy()
+    count = 3 * gt_u8.shape[-2] * gt_u8.shape[-1]
+    psnr = np.array([[psnr_from_stats(*row, count) for row in clip] for clip in stats.cpu().tolist()], dtype=np.float64)
+    return {"ssim": ssim[0], "psnr": psnr[0]} if single else {"ssim": ssim, "psnr": psnr}
+
+
+def quality_summary(ssim, psnr, denominator=200):
+    """The four numbers evaluate_vids prints from its (samples, frames) arrays: ssim_score_image and psnr_score_image (the
+    means) and their error terms sqrt(sum((v - mean)^2) / denominator).  The reference divides by a literal 200 whatever the
+    sample count (fvd.py:275-276): that is the default here."""
+    out = {}
+    for name, v in (("ssim", ssim), ("psnr", psnr)):
+        v = np.asarray(v, dtype=np.float64)
+        out[f"{name}_score_image"] = float(v.mean())
+        out[f"{name}_score_image_error"] = float(np.sqrt(((v - v.mean()) ** 2).sum() / denominator))
+    return out
+
+
 __all__ = ["binary_mask_iou", "iou_from_counts", "best_of", "candidate_scores", "f_from_counts", "boundary_radius",
-           "pt_frames_to_u8", "boundary_f_measure"]
+           "pt_frames_to_u8", "boundary_f_measure", "psnr_from_stats", "frame_quality", "quality_summary"]

@@ -1057,3 +1057,83 @@ def resize_lanczos_u8(image_u8, h, w, out=None, workspace=None):
     check(lib.ctrlv_resize_lanczos_u8(_p(image_u8), n, H, W, _p(out), int(h), int(w), _p(ws), ws.numel(), _stream()),
           "ctrlv_resize_lanczos_u8")
     return out
+
+
+def _frame_pair(fn, gt_u8, gen_u8):
+    _need_gpu(gt_u8, "gt_u8")
+    if gt_u8.dim() != 5 or gt_u8.shape[2] != 3 or gt_u8.dtype != torch.uint8:
+        raise ValueError(f"{fn}: gt_u8 must be (n, F, 3, H, W) uint8")
+    if tuple(gen_u8.shape) != tuple(gt_u8.shape) or gen_u8.dtype != torch.uint8 or gen_u8.device != gt_u8.device:
+        raise ValueError(f"{fn}: gen_u8 must be uint8 {tuple(gt_u8.shape)} on {gt_u8.device}")
+    _need_dense(fn, gt_u8=gt_u8, gen_u8=gen_u8)
+    n, F, _, H, W = gt_u8.shape
+    return n, F, H, W
+
+
+def frame_stats(gt_u8, gen_u8, out=None):
+    """gt_u8, gen_u8 (n, F, 3, H, W) uint8 -> int64 (n, F, 3) on the device (ctrlv_frame_stats): per frame {min byte, max byte,
+    sum of (gt - gen)^2} over the three channels of both frames -- the integers of PSNR (metrics.psnr_from_stats) and the value
+    range `frame_ssim` scales by.  Exact; no host sync."""
+    fn = "frame_stats"
+    n, F, H, W = _frame_pair(fn, gt_u8, gen_u8)
+    out = _out_arg(True if out is None else out, (n, F, 3), torch.int64, gt_u8.device, fn, "out")
+    check(_lib.load().ctrlv_frame_stats(_p(gt_u8), _p(gen_u8), n, F, H, W, _p(out), _stream()), "ctrlv_frame_stats")
+    return out
+
+
+def frame_ssim(gt_u8, gen_u8, stats=None, out=None, workspace=None):
+    """gt_u8, gen_u8 (n, F, 3, H, W) uint8 -> float64 (n, F) on the device (ctrlv_frame_ssim): scikit-image's
+    structural_similarity(channel_axis=0, data_range=R, gaussian_weights=True, sigma=1.5) of every frame, R the joint value range
+    of the two frames.  stats: what `frame_stats` gave for these frames (computed here when None).  out / workspace: dense
+    tensors to use (the workspace uint8, 8-byte aligned, at least ctrlv_frame_ssim_ws_bytes long), else fresh ones.  A frame pair
+    of one constant value is NaN.  No host sync."""
+    fn = "frame_ssim"
+    n, F, H, W = _frame_pair(fn, gt_u8, gen_u8)
+    dev = gt_u8.device
+    if stats is None:
+        stats = frame_stats(gt_u8, gen_u8)
+    elif tuple(stats.shape) != (n, F, 3) or stats.dtype != torch.int64 or stats.device != dev:
+        raise ValueError(f"{fn}: stats must be int64 {(n, F, 3)} on {dev}")
+    _need_dense(fn, stats=stats)
+    lib = _lib.load()
+    need = lib.ctrlv_frame_ssim_ws_bytes(n, F, H, W)
+    if need == 0:
+        check(-2, "ctrlv_frame_ssim_ws_bytes", lib=lib)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if workspace is None else workspace
+    _need_dense(fn, workspace=ws)
+    out = _out_arg(True if out is None else out, (n, F), torch.float64, dev, fn, "out")
+    check(lib.ctrlv_frame_ssim(_p(gt_u8), _p(gen_u8), n, F, H, W, _p(stats), _p(out), _p(ws), ws.numel() * ws.element_size(),
+                               _stream()), "ctrlv_frame_ssim")
+    return out
+
+
+RESAMPLE = {"lanczos": 1, "bilinear": 2, "bicubic": 3}       # PIL's Image.Resampling codes
+
+
+def resize_frames_u8(frames_u8, h, w, resample="bicubic", out=None, workspace=None):
+    """(..., H, W) uint8 planes -> (..., h, w) uint8 = PIL.Image.resize((w, h), resample=...) of every plane, byte for byte
+    (ctrlv_resize_frames_u8); on (n, F, 3, H, W) frames that is PIL's resize of every RGB frame.  resample: "bicubic", "bilinear",
+    "lanczos" or PIL's integer code.  out / workspace: dense uint8 tensors to use (the workspace 16-byte aligned, at least
+    ctrlv_resize_frames_ws_bytes long), else fresh ones."""
+    fn = "resize_frames_u8"
+    _need_gpu(frames_u8, "frames_u8")
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() < 2:
+        raise ValueError(f"{fn}: frames_u8 must be (..., H, W) uint8")
+    code = RESAMPLE.get(resample, resample) if isinstance(resample, str) else int(resample)
+    if not isinstance(code, int):
+        raise ValueError(f"{fn}: resample {resample!r} must be one of {sorted(RESAMPLE)} or PIL's integer code")
+    frames_u8 = frames_u8.contiguous()
+    lead, (H, W) = tuple(frames_u8.shape[:-2]), frames_u8.shape[-2:]
+    planes = 1
+    for v in lead:
+        planes *= v
+    lib = _lib.load()
+    need = lib.ctrlv_resize_frames_ws_bytes(planes, H, W, int(h), int(w), code)
+    if need == 0:
+        check(-2, "ctrlv_resize_frames_ws_bytes", lib=lib)
+    ws = torch.empty(need, dtype=torch.uint8, device=frames_u8.device) if workspace is None else workspace
+    _need_dense(fn, workspace=ws)
+    out = _out_arg(True if out is None else out, lead + (int(h), int(w)), torch.uint8, frames_u8.device, fn, "out")
+    check(lib.ctrlv_resize_frames_u8(_p(frames_u8), planes, H, W, _p(out), int(h), int(w), code, _p(ws), ws.numel(), _stream()),
+          "ctrlv_resize_frames_u8")
+    return out

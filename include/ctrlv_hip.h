@@ -47,7 +47,9 @@ enum {
  * (ctrlv_attention_tokens, ctrlv_clip_patch_rows, ctrlv_clip_tokens, ctrlv_act_rows) or ctrlv_gemm_tokens and the CLIP plan
  * (ctrlv_clip_*) ctrlv_vae_posterior or the VAE plan (ctrlv_vae_*) or the whole-clip driver and its I/O kernels (ctrlv_pipeline_*,
  * ctrlv_resize_antialias, ctrlv_pixels_prepare, ctrlv_frames_to_u8) or the seeded-clip entry points (ctrlv_randn,
- * ctrlv_euler_schedule, ctrlv_resize_lanczos_u8, ctrlv_pipeline_prepare, ctrlv_pipeline_generate_seeded), and a host that needs them fails at symbol lookup on a library without them.
+ * ctrlv_euler_schedule, ctrlv_resize_lanczos_u8, ctrlv_pipeline_prepare, ctrlv_pipeline_generate_seeded) or the per-frame quality
+ * entry points (ctrlv_frame_stats, ctrlv_frame_ssim, ctrlv_frame_ssim_ws_bytes, ctrlv_resize_frames_u8,
+ * ctrlv_resize_frames_ws_bytes), and a host that needs them fails at symbol lookup on a library without them.
  * NOT neutral, although the number did not move: ctrlv_gemm_desc.pad_br gives meaning to four bytes that were alignment
  * padding, so descriptors must now be zero-initialised (see the field). */
 int ctrlv_abi_version(void);
@@ -1132,6 +1134,58 @@ int ctrlv_boundary_radius(int H, int W, double bound_th);
  * at this radius (1856 at radius 32, more at smaller radii), more than 2^31 - 1 workgroups (CTRLV_E_BAD_SHAPE). */
 int ctrlv_boundary_counts(const void* gt_u8, const void* pred_u8, int n, int F, int H, int W, int mask_mode, int radius,
                           unsigned long long* counts, ctrlv_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Per-frame SSIM and PSNR of generated clips (csrc/frame_quality.hip, csrc/pipeline_io.hip): the ssim_score_image and
+ * psnr_score_image numbers of the reference's evaluate_vids (src/ctrlv/metrics/fvd.py:187-289), which resizes every frame with
+ * PIL, maps both clips to v / 127.5 - 1 in fp32 and calls scikit-image per frame with data_range = the joint value range of the
+ * two frames.  Here the frames stay on the device as bytes; n F doubles and 3 n F integers come back.  Additive entry points: the
+ * ABI number does not change.  All validation on the host, by name, before any launch; no host synchronisation (the calls can
+ * be captured into a graph); outputs are set by the call, the caller zeroes nothing.  tests/frame_quality_ref.py restates the
+ * arithmetic in numpy.
+ * ------------------------------------------------------------------------------------------------------------------ */
+/* gt_u8, gen_u8 (n, F, 3, H, W) uint8 as for ctrlv_mask_counts; stats: DEVICE (n, F, 3) 64-bit, 8-byte aligned: per frame {min
+ * byte, max byte, sum of (gt - gen)^2} over all three channels of BOTH frames.  Integer reductions only (wave reductions, then
+ * integer atomics): exact and independent of order.  PSNR = 10 log10((max - min)^2 3 H W / sum) is formed from them on the host in
+ * double.  16-byte loads where 3 H W is a multiple of 16 and both pointers are 16-byte aligned, single bytes otherwise.
+ * CTRLV_E_BAD_ARG: NULL pointers, stats misaligned; CTRLV_E_BAD_SHAPE: sizes not positive, more than 2^31 - 1 frames. */
+int ctrlv_frame_stats(const void* gt_u8, const void* gen_u8, int n, int F, int H, int W, long long* stats, ctrlv_stream_t stream);
+/* ssim: DEVICE (n, F) double = structural_similarity(gt, gen, channel_axis=0, data_range=R, gaussian_weights=True, sigma=1.5) of
+ * every frame; stats: what ctrlv_frame_stats wrote for the same frames, read on the device.  With x = gt - 127.5 and
+ * y = gen - 127.5 in byte units (SSIM is scale-invariant once R is in the same units) and R = max - min:
+ *   g[i]  = exp(-i^2 / 4.5) / sum, i = -5 .. 5, formed on the host in double;   u. = (g (x) g) * .   (the 11 x 11 window)
+ *   v_x   = (121 / 120) (u_xx - u_x^2), likewise v_y and v_xy = (121 / 120) (u_xy - u_x u_y);   C1 = (0.01 R)^2, C2 = (0.03 R)^2
+ *   S     = (2 u_x u_y + C1) (2 v_xy + C2) / ((u_x^2 + u_y^2 + C1) (v_x + v_y + C2))
+ *   ssim  = the mean of S over 5 <= row < H - 5, 5 <= col < W - 5 and the three channels: structural_similarity's crop, so no
+ *           window touches a border and its `reflect` padding is never evaluated.
+ * The kernel takes the moments about m = (min + max) / 2: it filters x' = gt - m and y' = gen - m (exact in fp32), forms the
+ * v from those (they are shift-invariant) and adds m - 127.5 to the two means.  Every term then scales with R^2 as C1 and C2 do;
+ * about 127.5, fp32 loses u_xx - u_x^2 to cancellation on low-contrast frames (a 12 x 75 frame of 250 with one pixel at 247 is
+ * off by 1e-3).  fp32 inside a pixel, each compared product rounded by its own operation (gen == gt gives exactly 1); S is
+ * summed in double.  One workgroup per (frame, channel, 16 x 64 tile of outputs): the tile and 5 pixels of halo of both frames
+ * in LDS, a horizontal pass into LDS, the vertical pass from there -- the filtered images never reach memory.  A workgroup adds
+ * its S in a fixed order (per thread in pixel order, wave shuffles, the four waves in order) into its own slot of ws; a second
+ * launch adds a frame's slots (one wave per frame: lane l the slots l, l + 64, ... in index order, then a shuffle tree) and
+ * divides.  No floating-point atomics: a frame's value is bit-identical run to run and independent of n, of the other frames
+ * and of pointer alignment.  R = 0 (both frames one constant): NaN, the reference's 0 / 0; other frames are not disturbed.
+ * ws: ctrlv_frame_ssim_ws_bytes bytes (0 for a shape the call would refuse), 8-byte aligned.  CTRLV_E_BAD_SHAPE: H or W below 11
+ * (scikit-image raises there too), sizes not positive, more than 2^31 - 1 workgroups; CTRLV_E_BAD_ARG: NULL pointers, stats /
+ * ssim / ws not 8-byte aligned; CTRLV_E_WORKSPACE: ws_bytes too small. */
+size_t ctrlv_frame_ssim_ws_bytes(int n, int F, int H, int W);
+int ctrlv_frame_ssim(const void* gt_u8, const void* gen_u8, int n, int F, int H, int W, const long long* stats, double* ssim,
+                     void* ws, size_t ws_bytes, ctrlv_stream_t stream);
+/* PIL.Image.resize((w, h), resample=filter) of 8-bit planes, every byte: src (planes, H, W) uint8 -> dst (planes, h, w) uint8,
+ * planes = n F 3 for a batch of clips.  PIL filters the bands of an RGB image independently with the same coefficients, so the
+ * planar result equals PIL's on the stacked RGB image.  filter takes PIL's codes: 1 LANCZOS (support 3, as
+ * ctrlv_resize_lanczos_u8), 2 BILINEAR (support 1, 1 - |v|), 3 BICUBIC (support 2, a = -0.5: ((a + 2) |v| - (a + 3)) v^2 + 1 for
+ * |v| < 1, (((|v| - 5) |v| + 8) |v| - 4) a for |v| < 2); anything else is CTRLV_E_BAD_ARG (NEAREST is another code path in PIL and
+ * is not built).  Everything else is as stated for ctrlv_resize_lanczos_u8 with `support` for its 3: ksize = 2 ceil(support fs) +
+ * 1, 22-bit fixed-point weights, two passes through a uint8 intermediate (planes, H, w) in ws.  ws:
+ * ctrlv_resize_frames_ws_bytes bytes (0 for a request the call would refuse), 16-byte aligned.  CTRLV_E_BAD_SHAPE: a zero
+ * dimension, a down-scale above 16 per axis, more than 262140 rows; CTRLV_E_WORKSPACE: ws_bytes too small. */
+size_t ctrlv_resize_frames_ws_bytes(int planes, int H, int W, int h, int w, int filter);
+int ctrlv_resize_frames_u8(const void* src_u8, int planes, int H, int W, void* dst_u8, int h, int w, int filter, void* ws,
+                           size_t ws_bytes, ctrlv_stream_t stream);
 
 #ifdef __cplusplus
 }
