@@ -35,6 +35,19 @@ constexpr int kMaxSteps = 1024;
 constexpr size_t kAlign = 256;
 inline size_t up(size_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
 
+struct Carver {              // regions of a workspace, one behind the other, each on a kAlign boundary
+  size_t o = 0;
+  size_t take(size_t bytes) { const size_t at = o; o += up(bytes); return at; }
+};
+
+// What the driver knows of a stage beyond its request.  The fields it will supply from its own workspace count as present for
+// the null checks and for `decode`; the request itself keeps NULL there until the workspace's base is known.
+enum : unsigned {
+  kCond = 1, kOutFrames = 2,                       // the chains: stage 2's ControlNet condition, stage 1's frames
+  kImage = 4, kAugNoise = 8, kLatents = 16,        // prepare: the resized image and the two draws
+  kBoxStage = 32,                                  // a box predictor's stage: the box condition is required
+};
+
 // the element type's rounding on the host (added time ids: torch.tensor([...], dtype=<model dtype>))
 float round_el(float v) {
 #ifdef CTRLV_ELEM_F16
@@ -52,7 +65,7 @@ float round_el(float v) {
 
 struct Geo {                 // a validated request's derived sizes
   int B, F, H, W, h, w, hw, L, nb, cfg, D, S;      // nb = model batch (2 B with cfg), D = embedding width, S = CLIP image size
-  bool decode;
+  bool decode, frames_out;    // frames_out: out_frames is the caller's or the driver's (the decoder writes there, not in its phase)
 };
 
 struct BoxGeo {              // a validated ctrlv_box_condition
@@ -73,7 +86,7 @@ struct Layout {              // byte offsets into the workspace
   size_t dec_z, dec_frames, dec_ws, dec_bytes;
 };
 
-int validate(const ctrlv_pipeline* p, const ctrlv_clip_request* r, Geo* g) {
+int validate(const ctrlv_pipeline* p, const ctrlv_clip_request* r, unsigned supplied, Geo* g) {
   CTRLV_CHECK_ARG(p != nullptr, "pipeline: null pipeline");
   CTRLV_CHECK_ARG(r != nullptr, "pipeline: null request");
   const ctrlv_model_config* uc = ctrlv_plan_info(p->unet, nullptr, nullptr);
@@ -89,11 +102,11 @@ int validate(const ctrlv_pipeline* p, const ctrlv_clip_request* r, Geo* g) {
   const int h = r->height / 8, w = r->width / 8;
   CTRLV_CHECK_SHAPE((h * w) % 64 == 0 && h * w <= 16384, "pipeline: height=%d / width=%d give %d latent pixels; the VAE's attention "
                     "takes a multiple of 64, at most 16384", r->height, r->width, h * w);
-  CTRLV_CHECK_ARG(r->image_u8 != nullptr, "pipeline: image_u8 is null");
-  CTRLV_CHECK_ARG(r->latents != nullptr, "pipeline: latents is null");
+  CTRLV_CHECK_ARG(r->image_u8 != nullptr || (supplied & kImage), "pipeline: image_u8 is null");
+  CTRLV_CHECK_ARG(r->latents != nullptr || (supplied & kLatents), "pipeline: latents is null");
   CTRLV_CHECK_ARG(r->out_latents != nullptr, "pipeline: out_latents is null");
   if (p->cn) {
-    CTRLV_CHECK_ARG(r->cond != nullptr, "pipeline: cond is null but the pipeline has a ControlNet");
+    CTRLV_CHECK_ARG(r->cond != nullptr || (supplied & kCond), "pipeline: cond is null but the pipeline has a ControlNet");
   }
   if (r->cond) {
     CTRLV_CHECK_SHAPE(r->cond_channels == 3 || r->cond_channels == vc->latent_channels,
@@ -111,7 +124,8 @@ int validate(const ctrlv_pipeline* p, const ctrlv_clip_request* r, Geo* g) {
   CTRLV_CHECK_ARG(r->noise_aug_strength >= 0.f && isfinite(r->noise_aug_strength), "pipeline: noise_aug_strength=%g",
                   (double)r->noise_aug_strength);
   CTRLV_CHECK_ARG(isfinite(r->min_guidance) && isfinite(r->max_guidance), "pipeline: min_guidance / max_guidance are not finite");
-  const bool decode = r->out_frames != nullptr || r->out_frames_u8 != nullptr;
+  const bool frames_out = r->out_frames != nullptr || (supplied & kOutFrames);
+  const bool decode = frames_out || r->out_frames_u8 != nullptr;
   if (decode) {
     CTRLV_CHECK_SHAPE(r->decode_chunk >= 1, "pipeline: decode_chunk=%d must be >= 1 when frames are asked for", r->decode_chunk);
     CTRLV_CHECK_ARG(((uintptr_t)r->out_frames_u8 & 3) == 0, "pipeline: out_frames_u8 must be 4-byte aligned");
@@ -130,12 +144,14 @@ int validate(const ctrlv_pipeline* p, const ctrlv_clip_request* r, Geo* g) {
   g->D = cc->projection_dim;
   g->S = cc->image_size;
   g->decode = decode;
+  g->frames_out = frames_out;
   return CTRLV_OK;
 }
 
 // The box condition of ctrlv_pipeline_predict_boxes against a validated request: the refusals that name the box predictor come
 // first (a ControlNet pipeline would otherwise be refused for its missing cond), then the request as generate validates it.
-int validate_boxes(const ctrlv_pipeline* p, const ctrlv_clip_request* r, const ctrlv_box_condition* bc, Geo* g, BoxGeo* bg) {
+int validate_boxes(const ctrlv_pipeline* p, const ctrlv_clip_request* r, const ctrlv_box_condition* bc, unsigned supplied, Geo* g,
+                   BoxGeo* bg) {
   CTRLV_CHECK_ARG(p != nullptr, "predict_boxes: null pipeline");
   CTRLV_CHECK_ARG(r != nullptr, "predict_boxes: null request");
   CTRLV_CHECK_ARG(bc != nullptr, "predict_boxes: null box condition");
@@ -143,7 +159,7 @@ int validate_boxes(const ctrlv_pipeline* p, const ctrlv_clip_request* r, const c
                   "(ctrlv_pipeline_create with controlnet = NULL)");
   CTRLV_CHECK_ARG(r->cond == nullptr, "predict_boxes: cond is set; the box predictor takes its box frames through "
                   "ctrlv_box_condition, not the ControlNet condition");
-  CTRLV_TRY(validate(p, r, g));
+  CTRLV_TRY(validate(p, r, supplied, g));
   CTRLV_CHECK_ARG(bc->reserved == 0, "predict_boxes: box condition reserved=%d must be 0", bc->reserved);
   CTRLV_CHECK_ARG(bc->frames != nullptr, "predict_boxes: box condition frames is null");
   CTRLV_CHECK_SHAPE(bc->channels == 3 || bc->channels == g->L, "predict_boxes: box condition channels=%d must be 3 (pixels) or "
@@ -168,18 +184,17 @@ int layout(ctrlv_pipeline* p, const ctrlv_clip_request* r, const Geo& g, const B
   CTRLV_CHECK_ARG(lu && lv && lc && ln, "pipeline: plan not loaded (load the weights of every plan first)");
   const size_t el = sizeof(el_t);
   const size_t lat = (size_t)g.B * g.F * g.L * g.hw;              // elements of the latents of the B clips
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += up(bytes); return at; };
-  L->consts = take((size_t)(kMaxSteps + 32 + 3 * 2 * 4096) * sizeof(float));
-  L->ehs = take((size_t)g.nb * g.D * el);
-  L->first = take((size_t)g.B * g.L * g.hw * el);
-  L->lmi = take((size_t)g.nb * g.F * 2 * g.L * g.hw * el);
-  L->scaled = take(lat * el);
-  L->pred = take((size_t)g.nb * g.F * g.L * g.hw * el);
+  Carver cv;
+  L->consts = cv.take((size_t)(kMaxSteps + 32 + 3 * 2 * 4096) * sizeof(float));
+  L->ehs = cv.take((size_t)g.nb * g.D * el);
+  L->first = cv.take((size_t)g.B * g.L * g.hw * el);
+  L->lmi = cv.take((size_t)g.nb * g.F * 2 * g.L * g.hw * el);
+  L->scaled = cv.take(lat * el);
+  L->pred = cv.take((size_t)g.nb * g.F * g.L * g.hw * el);
   L->cond_em = 0;
   L->n_res = 0;
   if (p->cn) {
-    L->cond_em = take((size_t)g.nb * g.F * g.L * g.hw * el);
+    L->cond_em = cv.take((size_t)g.nb * g.F * g.L * g.hw * el);
     const int nd = ctrlv_plan_num_down_residuals(p->cn);
     CTRLV_CHECK_SHAPE(nd + 1 <= (int)(sizeof(L->res) / sizeof(L->res[0])), "pipeline: %d residual tensors", nd + 1);
     for (int i = 0; i <= nd; ++i) {
@@ -187,12 +202,12 @@ int layout(ctrlv_pipeline* p, const ctrlv_clip_request* r, const Geo& g, const B
       int32_t ch = 0;
       const int rc = ctrlv_plan_residual_shape(p->cn, i, g.nb, g.F, g.h, g.w, &rows, &ch);
       if (rc != CTRLV_OK) return rc;
-      L->res[i] = take((size_t)rows * ch * el);
+      L->res[i] = cv.take((size_t)rows * ch * el);
     }
     L->n_res = nd + 1;
   }
-  L->phase = o;
-  size_t end = o;
+  L->phase = cv.o;
+  size_t end = cv.o;
   // the loop: UNet and ControlNet work side by side in disjoint regions
   L->unet_bytes = ctrlv_plan_workspace_bytes(p->unet, g.nb, g.F, g.h, g.w);
   if (L->unet_bytes == 0) return CTRLV_E_BAD_SHAPE;
@@ -201,18 +216,18 @@ int layout(ctrlv_pipeline* p, const ctrlv_clip_request* r, const Geo& g, const B
     L->cn_bytes = ctrlv_plan_workspace_bytes(p->cn, g.nb, g.F, g.h, g.w);
     if (L->cn_bytes == 0) return CTRLV_E_BAD_SHAPE;
   }
-  o = L->phase;
-  L->unet_ws = take(L->unet_bytes);
-  L->cn_ws = take(L->cn_bytes);
-  end = o > end ? o : end;
+  cv.o = L->phase;
+  L->unet_ws = cv.take(L->unet_bytes);
+  L->cn_ws = cv.take(L->cn_bytes);
+  end = cv.o > end ? cv.o : end;
   // CLIP: resized pixels, embeddings, the tower's workspace
   L->clip_bytes = ctrlv_clip_plan_workspace_bytes(p->clip, g.B);
   if (L->clip_bytes == 0) return CTRLV_E_BAD_SHAPE;
-  o = L->phase;
-  L->clip_px = take((size_t)g.B * 3 * g.S * g.S * el);
-  L->clip_emb = take((size_t)g.B * g.D * el);
-  L->clip_ws = take(L->clip_bytes);
-  end = o > end ? o : end;
+  cv.o = L->phase;
+  L->clip_px = cv.take((size_t)g.B * 3 * g.S * g.S * el);
+  L->clip_emb = cv.take((size_t)g.B * g.D * el);
+  L->clip_ws = cv.take(L->clip_bytes);
+  end = cv.o > end ? cv.o : end;
   // VAE encode: the image's pixels, the condition's latents, the encoder's workspace (the larger of the two calls)
   L->enc_bytes = ctrlv_vae_plan_workspace_bytes(p->vae, 0, g.B, 1, g.H, g.W);
   if (L->enc_bytes == 0) return CTRLV_E_BAD_SHAPE;
@@ -233,11 +248,11 @@ int layout(ctrlv_pipeline* p, const ctrlv_clip_request* r, const Geo& g, const B
     }
     box_lat = (size_t)g.B * bx->take * g.L * g.hw * el;
   }
-  o = L->phase;
-  L->enc_px = take((size_t)g.B * 3 * g.H * g.W * el);
-  L->enc_lat = take(enc_cond ? lat * el : box_lat);
-  L->enc_ws = take(L->enc_bytes);
-  end = o > end ? o : end;
+  cv.o = L->phase;
+  L->enc_px = cv.take((size_t)g.B * 3 * g.H * g.W * el);
+  L->enc_lat = cv.take(enc_cond ? lat * el : box_lat);
+  L->enc_ws = cv.take(L->enc_bytes);
+  end = cv.o > end ? cv.o : end;
   // decode: the scaled latents, the frames (unless the caller takes them), the decoder's workspace
   L->dec_bytes = 0;
   if (g.decode) {
@@ -249,14 +264,43 @@ int layout(ctrlv_pipeline* p, const ctrlv_clip_request* r, const Geo& g, const B
       if (b2 == 0) return CTRLV_E_BAD_SHAPE;
       L->dec_bytes = b2 > L->dec_bytes ? b2 : L->dec_bytes;
     }
-    o = L->phase;
-    L->dec_z = take(lat * el);
-    L->dec_frames = take(r->out_frames ? 0 : (size_t)total * 3 * g.H * g.W * el);
-    L->dec_ws = take(L->dec_bytes);
-    end = o > end ? o : end;
+    cv.o = L->phase;
+    L->dec_z = cv.take(lat * el);
+    L->dec_frames = cv.take(g.frames_out ? 0 : (size_t)total * 3 * g.H * g.W * el);
+    L->dec_ws = cv.take(L->dec_bytes);
+    end = cv.o > end ? cv.o : end;
   }
   L->total = end;
   return CTRLV_OK;
+}
+
+struct Stage {               // everything one clip needs: ctrlv_pipeline_generate's, or with bc ctrlv_pipeline_predict_boxes'
+  ctrlv_pipeline* p;
+  ctrlv_clip_request r;      // the request as the stage sees it: what the driver supplies is NULL until its call knows the base
+  const ctrlv_box_condition* bc;     // NULL: no box condition (bx is unset)
+  Geo g;
+  BoxGeo bx;
+  Layout L;
+};
+
+// every refusal of a stage that needs no loaded plan
+int validate_stage(ctrlv_pipeline* p, const ctrlv_clip_request* r, const ctrlv_box_condition* bc, unsigned supplied, Stage* st) {
+  if (supplied & kBoxStage) {
+    CTRLV_TRY(validate_boxes(p, r, bc, supplied, &st->g, &st->bx));
+  } else {
+    CTRLV_TRY(validate(p, r, supplied, &st->g));
+  }
+  st->p = p;
+  st->r = *r;
+  st->bc = (supplied & kBoxStage) ? bc : nullptr;
+  return CTRLV_OK;
+}
+
+int layout_stage(Stage* st) { return layout(st->p, &st->r, st->g, st->bc ? &st->bx : nullptr, &st->L); }
+
+int plan_stage(ctrlv_pipeline* p, const ctrlv_clip_request* r, const ctrlv_box_condition* bc, unsigned supplied, Stage* st) {
+  CTRLV_TRY(validate_stage(p, r, bc, supplied, st));
+  return layout_stage(st);
 }
 
 }  // namespace
@@ -324,10 +368,15 @@ int check_workspace(const char* who, const char* query, const void* ws, size_t w
   return CTRLV_OK;
 }
 
-// The clip of a validated request in a workspace of L.total bytes: ctrlv_pipeline_generate (bc = NULL), or
+// The clip of a planned stage in a workspace of L.total bytes: ctrlv_pipeline_generate (bc = NULL), or
 // ctrlv_pipeline_predict_boxes (bc / bx: the box frames overwrite the conditioning channels, the decoded frames are clamped).
-int run_clip(ctrlv_pipeline* p, const ctrlv_clip_request* r, const ctrlv_box_condition* bc, const Geo& g, const BoxGeo* bx,
-             const Layout& L, void* ws, ctrlv_stream_t stream) {
+int run_stage(const Stage& st, void* ws, ctrlv_stream_t stream) {
+  ctrlv_pipeline* p = st.p;
+  const ctrlv_clip_request* r = &st.r;
+  const ctrlv_box_condition* bc = st.bc;
+  const Geo& g = st.g;
+  const BoxGeo* bx = bc ? &st.bx : nullptr;
+  const Layout& L = st.L;
   const hipStream_t s = (hipStream_t)stream;
   char* base = (char*)ws;
   const bool overlap = p->cn && p->overlap;
@@ -460,268 +509,106 @@ int run_clip(ctrlv_pipeline* p, const ctrlv_clip_request* r, const ctrlv_box_con
   return CTRLV_OK;
 }
 
-struct Chain {               // ctrlv_pipeline_boxes_to_video: the two requests as the stages see them, and where things lie
-  ctrlv_clip_request boxes, video;
-  Geo gb, gv;
-  BoxGeo bx;
-  Layout Lb, Lv;
-  size_t frames, cond, post, post_bytes, stage, total;
-};
-
-int plan_chain(ctrlv_pipeline* pb, ctrlv_pipeline* pv, const ctrlv_two_stage_request* q, Chain* c) {
-  CTRLV_CHECK_ARG(pb != nullptr && pv != nullptr, "boxes_to_video: null pipeline");
-  CTRLV_CHECK_ARG(q != nullptr, "boxes_to_video: null request");
-  CTRLV_CHECK_ARG(pb->tag == kPipelineTag && pv->tag == kPipelineTag, "boxes_to_video: both pipelines must come from this library "
-                  "(element dtype code %d)", CTRLV_ELEM_DTYPE);
-  CTRLV_CHECK_ARG(pb->device == pv->device, "boxes_to_video: the pipelines live on different devices (%d and %d)", pb->device,
-                  pv->device);
-  CTRLV_CHECK_ARG(q->reserved == 0, "boxes_to_video: reserved=%d must be 0", q->reserved);
-  CTRLV_CHECK_ARG(pv->cn != nullptr, "boxes_to_video: the video pipeline has no ControlNet to take the box frames");
-  CTRLV_CHECK_ARG(q->video.cond == nullptr, "boxes_to_video: video.cond must be NULL on entry (the driver supplies stage 1's frames)");
-  CTRLV_CHECK_ARG(isfinite(q->clean_threshold), "boxes_to_video: clean_threshold=%g", (double)q->clean_threshold);
-  CTRLV_CHECK_SHAPE(q->boxes.n_clips == q->video.n_clips && q->boxes.num_frames == q->video.num_frames &&
-                    q->boxes.height == q->video.height && q->boxes.width == q->video.width,
-                    "boxes_to_video: the two requests differ in geometry (boxes %d x %d x %d x %d, video %d x %d x %d x %d)",
-                    q->boxes.n_clips, q->boxes.num_frames, q->boxes.height, q->boxes.width, q->video.n_clips, q->video.num_frames,
-                    q->video.height, q->video.width);
-  c->boxes = q->boxes;
-  c->video = q->video;
-  c->video.cond = (const void*)(uintptr_t)kAlign;     // (a placeholder until the workspace is known: validate asks for non-null)
-  c->video.cond_channels = 3;
-  c->video.cond_dtype = CTRLV_ELEM_DTYPE;
-  // stage 1 must decode: its frames are what stage 2 is conditioned on.  Without out_frames they go into the chain's workspace
-  const bool own_frames = c->boxes.out_frames == nullptr;
-  if (own_frames) c->boxes.out_frames = (void*)(uintptr_t)kAlign;
-  CTRLV_TRY(validate_boxes(pb, &c->boxes, &q->box_cond, &c->gb, &c->bx));
-  CTRLV_TRY(validate(pv, &c->video, &c->gv));
-  CTRLV_TRY(layout(pb, &c->boxes, c->gb, &c->bx, &c->Lb));
-  CTRLV_TRY(layout(pv, &c->video, c->gv, nullptr, &c->Lv));
-  const size_t fr = (size_t)c->gb.B * c->gb.F * 3 * c->gb.H * c->gb.W * sizeof(el_t);
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += up(bytes); return at; };
-  c->frames = take(own_frames ? fr : 0);
-  c->cond = take(fr);
-  c->post_bytes = ctrlv_box_frames_post_ws_bytes(c->gb.B, c->gb.F);
-  c->post = take(c->post_bytes);
-  c->stage = o;
-  c->total = o + (c->Lb.total > c->Lv.total ? c->Lb.total : c->Lv.total);
-  if (own_frames) c->boxes.out_frames = nullptr;      // (resolved against the workspace by the call)
-  return CTRLV_OK;
-}
-
 }  // namespace
 
 extern "C" size_t ctrlv_pipeline_workspace_bytes(ctrlv_pipeline* p, const ctrlv_clip_request* r) {
-  Geo g;
-  Layout L;
-  if (validate(p, r, &g) != CTRLV_OK) return 0;
-  if (layout(p, r, g, nullptr, &L) != CTRLV_OK) return 0;
-  return L.total;
+  Stage st;
+  return plan_stage(p, r, nullptr, 0, &st) == CTRLV_OK ? st.L.total : 0;
 }
 
 extern "C" int ctrlv_pipeline_generate(ctrlv_pipeline* p, const ctrlv_clip_request* r, void* ws, size_t ws_bytes,
                                        ctrlv_stream_t stream) {
-  Geo g;
-  Layout L;
-  CTRLV_TRY(validate(p, r, &g));
-  CTRLV_TRY(layout(p, r, g, nullptr, &L));
-  CTRLV_TRY(check_workspace("pipeline_generate", "ctrlv_pipeline_workspace_bytes", ws, ws_bytes, L.total));
-  return run_clip(p, r, nullptr, g, nullptr, L, ws, stream);
-}
-
-namespace {
-
-struct Prep {                // ctrlv_pipeline_prepare: the filled request (pointers into prep_ws as offsets from 0) and the layout
-  ctrlv_clip_request filled;
-  size_t resize_ws, resize_bytes, image, aug, lat, total;
-  bool resize, draw_aug, draw_lat, schedule;
-  double init_noise_sigma;
-  Geo g;
-};
-
-// Everything prepare decides on the host.  sig / ts: where a schedule the request asks for is written (the caller's arrays, the
-// pipeline's, or a size query's scratch).  The filled request is validated as generate validates it; what prepare would place
-// in prep_ws stands in as the placeholder `kAlign + offset` until the workspace is known.
-int plan_prepare(const ctrlv_pipeline* p, const ctrlv_clip_request* in, const ctrlv_seed_request* s, float* sig, float* ts, Prep* q) {
-  CTRLV_CHECK_ARG(p != nullptr, "pipeline_prepare: null pipeline");
-  CTRLV_CHECK_ARG(in != nullptr, "pipeline_prepare: null request");
-  CTRLV_CHECK_ARG(s != nullptr, "pipeline_prepare: null seed request");
-  CTRLV_CHECK_ARG(s->reserved == 0, "pipeline_prepare: seed request reserved=%d must be 0", s->reserved);
-  ctrlv_clip_request& f = q->filled;
-  f = *in;
-  q->schedule = in->sigmas == nullptr || in->timesteps == nullptr;
-  if (q->schedule) {
-    CTRLV_CHECK_SHAPE(in->num_steps >= 1 && in->num_steps <= kMaxSteps, "pipeline_prepare: num_steps=%d must be in [1, %d]",
-                      in->num_steps, kMaxSteps);
-    CTRLV_CHECK_ARG(sig != nullptr && ts != nullptr, "pipeline_prepare: the request leaves sigmas / timesteps NULL, and "
-                    "sigmas_host / timesteps_host of the seed request are null (host arrays of num_steps + 1 and num_steps floats)");
-    // into scratch first: a table the caller did set is kept
-    std::vector<float> tmp((size_t)2 * in->num_steps + 1);
-    CTRLV_TRY(ctrlv_euler_schedule(in->num_steps, s->sigma_min, s->sigma_max, tmp.data(), tmp.data() + in->num_steps + 1, nullptr));
-    if (!in->sigmas) {
-      memcpy(sig, tmp.data(), ((size_t)in->num_steps + 1) * sizeof(float));
-      f.sigmas = sig;
-    }
-    if (!in->timesteps) {
-      memcpy(ts, tmp.data() + in->num_steps + 1, (size_t)in->num_steps * sizeof(float));
-      f.timesteps = ts;
-    }
-  }
-  q->init_noise_sigma = sqrt((double)f.sigmas[0] * (double)f.sigmas[0] + 1.0);
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += up(bytes); return at; };
-  auto hold = [](size_t at) { return (const void*)((uintptr_t)kAlign + at); };
-  q->resize = false;
-  q->resize_ws = q->resize_bytes = q->image = q->aug = q->lat = 0;
-  if (s->src_image_u8) {
-    CTRLV_CHECK_ARG(in->image_u8 == nullptr, "pipeline_prepare: image_u8 and src_image_u8 are both set");
-    CTRLV_CHECK_SHAPE(s->src_height > 0 && s->src_width > 0, "pipeline_prepare: src_image_u8 without sizes (src_height=%d, "
-                      "src_width=%d)", s->src_height, s->src_width);
-    if (s->src_height == in->height && s->src_width == in->width) {
-      f.image_u8 = s->src_image_u8;
-    } else {
-      CTRLV_CHECK_SHAPE(in->n_clips >= 1 && in->height > 0 && in->width > 0, "pipeline_prepare: n_clips=%d, height=%d, width=%d "
-                        "must be positive", in->n_clips, in->height, in->width);
-      CTRLV_TRY(ctrlv_resize_lanczos_check(in->n_clips, s->src_height, s->src_width, in->height, in->width));
-      q->resize = true;
-      q->resize_bytes = ctrlv_resize_lanczos_ws_bytes(in->n_clips, s->src_height, s->src_width, in->height, in->width);
-      q->resize_ws = take(q->resize_bytes);
-      q->image = take((size_t)in->n_clips * in->height * in->width * 3);
-      f.image_u8 = hold(q->image);
-    }
-  }
-  q->draw_aug = in->aug_noise == nullptr;
-  q->draw_lat = in->latents == nullptr;
-  if (q->draw_aug) f.aug_noise = (const float*)hold(0);
-  if (q->draw_lat) f.latents = (const float*)hold(0);
-  // (a ControlNet pipeline's request may still lack its cond here: stage 2 of a ctrlv_two_stage_request receives it from the
-  // chain.  The consuming call validates the request it is given)
-  ctrlv_clip_request v = f;
-  if (p->cn && !v.cond) {
-    v.cond = hold(0);
-    v.cond_channels = 3;
-    v.cond_dtype = CTRLV_ELEM_DTYPE;
-  }
-  Geo& g = q->g;
-  CTRLV_TRY(validate(p, &v, &g));
-  if (q->draw_aug) {
-    q->aug = take((size_t)g.B * 3 * g.H * g.W * sizeof(float));
-    f.aug_noise = (const float*)hold(q->aug);
-  }
-  if (q->draw_lat) {
-    q->lat = take((size_t)g.B * g.F * g.L * g.hw * sizeof(float));
-    f.latents = (const float*)hold(q->lat);
-  }
-  q->total = o;
-  return CTRLV_OK;
-}
-
-// the placeholders of plan_prepare against the workspace
-void resolve_prepare(Prep* q, void* prep_ws) {
-  char* base = (char*)prep_ws;
-  if (q->resize) q->filled.image_u8 = base + q->image;
-  if (q->draw_aug) q->filled.aug_noise = (const float*)(base + q->aug);
-  if (q->draw_lat) q->filled.latents = (const float*)(base + q->lat);
-}
-
-int run_prepare(const Prep& q, const ctrlv_seed_request* s, void* prep_ws, ctrlv_stream_t stream) {
-  char* base = (char*)prep_ws;
-  const ctrlv_clip_request& f = q.filled;
-  if (q.resize)
-    CTRLV_TRY(ctrlv_resize_lanczos_u8(s->src_image_u8, f.n_clips, s->src_height, s->src_width, base + q.image, f.height, f.width,
-                                      base + q.resize_ws, q.resize_bytes, stream));
-  if (q.draw_aug)
-    CTRLV_TRY(ctrlv_randn(s->seed, s->clip_index0, s->call, 0, f.n_clips, (size_t)3 * f.height * f.width, 1.0f, 0, base + q.aug, 0,
-                          stream));
-  if (q.draw_lat)
-    CTRLV_TRY(ctrlv_randn(s->seed, s->clip_index0, s->call, 1, f.n_clips,
-                          (size_t)q.g.F * q.g.L * q.g.hw, (float)q.init_noise_sigma, 1, base + q.lat,
-                          0, stream));
-  return CTRLV_OK;
-}
-
-// the schedule's home of a size query or of a generate_seeded call without host arrays
-float* sched_store(std::vector<float>* v, const ctrlv_clip_request* r) {
-  const int n = r && r->num_steps >= 1 && r->num_steps <= kMaxSteps ? r->num_steps : 1;
-  v->assign((size_t)2 * n + 1, 0.f);
-  return v->data();
-}
-
-}  // namespace
-
-extern "C" size_t ctrlv_pipeline_prepare_bytes(ctrlv_pipeline* p, const ctrlv_clip_request* r, const ctrlv_seed_request* s) {
-  Prep q;
-  std::vector<float> tmp;
-  float* sig = sched_store(&tmp, r);
-  if (plan_prepare(p, r, s, sig, sig + (tmp.size() + 1) / 2, &q) != CTRLV_OK) return 0;
-  return q.total > 0 ? q.total : kAlign;
-}
-
-extern "C" int ctrlv_pipeline_prepare(ctrlv_pipeline* p, const ctrlv_clip_request* in, const ctrlv_seed_request* s,
-                                      ctrlv_clip_request* out, void* prep_ws, size_t prep_bytes, ctrlv_stream_t stream) {
-  CTRLV_CHECK_ARG(out != nullptr, "pipeline_prepare: null output request");
-  Prep q;
-  CTRLV_TRY(plan_prepare(p, in, s, s ? s->sigmas_host : nullptr, s ? s->timesteps_host : nullptr, &q));
-  CTRLV_TRY(check_workspace("pipeline_prepare", "ctrlv_pipeline_prepare_bytes", prep_ws, prep_bytes, q.total > 0 ? q.total : kAlign));
-  resolve_prepare(&q, prep_ws);
-  CTRLV_TRY(run_prepare(q, s, prep_ws, stream));
-  *out = q.filled;
-  return CTRLV_OK;
-}
-
-extern "C" size_t ctrlv_pipeline_seeded_workspace_bytes(ctrlv_pipeline* p, const ctrlv_clip_request* r,
-                                                        const ctrlv_seed_request* s) {
-  Prep q;
-  std::vector<float> tmp;
-  float* sig = sched_store(&tmp, r);
-  if (plan_prepare(p, r, s, sig, sig + (tmp.size() + 1) / 2, &q) != CTRLV_OK) return 0;
-  const size_t rest = ctrlv_pipeline_workspace_bytes(p, &q.filled);
-  return rest ? (q.total > 0 ? q.total : kAlign) + rest : 0;
-}
-
-extern "C" int ctrlv_pipeline_generate_seeded(ctrlv_pipeline* p, const ctrlv_clip_request* r, const ctrlv_seed_request* s, void* ws,
-                                              size_t ws_bytes, ctrlv_stream_t stream) {
-  CTRLV_CHECK_ARG(p != nullptr, "pipeline_generate_seeded: null pipeline");
-  CTRLV_CHECK_ARG(s != nullptr, "pipeline_generate_seeded: null seed request");
-  Prep q;
-  float* sig = s->sigmas_host;
-  float* ts = s->timesteps_host;
-  if (!sig || !ts) {
-    float* own = sched_store(&p->sched, r);
-    if (!sig) sig = own;
-    if (!ts) ts = own + (p->sched.size() + 1) / 2;
-  }
-  CTRLV_TRY(plan_prepare(p, r, s, sig, ts, &q));
-  Layout L;
-  CTRLV_TRY(validate(p, &q.filled, &q.g));
-  CTRLV_TRY(layout(p, &q.filled, q.g, nullptr, &L));
-  const size_t front = q.total > 0 ? q.total : kAlign;
-  CTRLV_TRY(check_workspace("pipeline_generate_seeded", "ctrlv_pipeline_seeded_workspace_bytes", ws, ws_bytes, front + L.total));
-  resolve_prepare(&q, ws);
-  CTRLV_TRY(run_prepare(q, s, ws, stream));
-  return run_clip(p, &q.filled, nullptr, q.g, nullptr, L, (char*)ws + front, stream);
+  Stage st;
+  CTRLV_TRY(plan_stage(p, r, nullptr, 0, &st));
+  CTRLV_TRY(check_workspace("pipeline_generate", "ctrlv_pipeline_workspace_bytes", ws, ws_bytes, st.L.total));
+  return run_stage(st, ws, stream);
 }
 
 extern "C" size_t ctrlv_pipeline_boxes_workspace_bytes(ctrlv_pipeline* p, const ctrlv_clip_request* r,
                                                        const ctrlv_box_condition* bc) {
-  Geo g;
-  BoxGeo bx;
-  Layout L;
-  if (validate_boxes(p, r, bc, &g, &bx) != CTRLV_OK) return 0;
-  if (layout(p, r, g, &bx, &L) != CTRLV_OK) return 0;
-  return L.total;
+  Stage st;
+  return plan_stage(p, r, bc, kBoxStage, &st) == CTRLV_OK ? st.L.total : 0;
 }
 
 extern "C" int ctrlv_pipeline_predict_boxes(ctrlv_pipeline* p, const ctrlv_clip_request* r, const ctrlv_box_condition* bc, void* ws,
                                             size_t ws_bytes, ctrlv_stream_t stream) {
-  Geo g;
-  BoxGeo bx;
-  Layout L;
-  CTRLV_TRY(validate_boxes(p, r, bc, &g, &bx));
-  CTRLV_TRY(layout(p, r, g, &bx, &L));
-  CTRLV_TRY(check_workspace("pipeline_predict_boxes", "ctrlv_pipeline_boxes_workspace_bytes", ws, ws_bytes, L.total));
-  return run_clip(p, r, bc, g, &bx, L, ws, stream);
+  Stage st;
+  CTRLV_TRY(plan_stage(p, r, bc, kBoxStage, &st));
+  CTRLV_TRY(check_workspace("pipeline_predict_boxes", "ctrlv_pipeline_boxes_workspace_bytes", ws, ws_bytes, st.L.total));
+  return run_stage(st, ws, stream);
 }
+
+namespace {
+
+// ---- the two chains' shared front: the pipeline pair, then stage 2's request as the chain sees it
+
+// Q: ctrlv_two_stage_request or ctrlv_best_chain_request (`reserved` and `video`)
+template <class Q>
+int check_pair(const char* who, const ctrlv_pipeline* pb, const ctrlv_pipeline* pv, const Q* q) {
+  CTRLV_CHECK_ARG(pb != nullptr && pv != nullptr, "%s: null pipeline", who);
+  CTRLV_CHECK_ARG(q != nullptr, "%s: null request", who);
+  CTRLV_CHECK_ARG(pb->tag == kPipelineTag && pv->tag == kPipelineTag, "%s: both pipelines must come from this library (element "
+                  "dtype code %d)", who, CTRLV_ELEM_DTYPE);
+  CTRLV_CHECK_ARG(pb->device == pv->device, "%s: the pipelines live on different devices (%d and %d)", who, pb->device, pv->device);
+  CTRLV_CHECK_ARG(q->reserved == 0, "%s: reserved=%d must be 0", who, q->reserved);
+  CTRLV_CHECK_ARG(pv->cn != nullptr, "%s: the video pipeline has no ControlNet to take the box frames", who);
+  CTRLV_CHECK_ARG(q->video.cond == nullptr, "%s: video.cond must be NULL on entry (the driver supplies stage 1's box frames)", who);
+  return CTRLV_OK;
+}
+
+// first: stage 1's (first) request.  The condition is the driver's: pixels in the element type, validated with kCond
+int video_request(const char* who, const ctrlv_clip_request* first, const ctrlv_clip_request* video, ctrlv_clip_request* v) {
+  CTRLV_CHECK_SHAPE(first->n_clips == video->n_clips && first->num_frames == video->num_frames && first->height == video->height &&
+                    first->width == video->width,
+                    "%s: the two stages differ in geometry (boxes %d x %d x %d x %d, video %d x %d x %d x %d)", who, first->n_clips,
+                    first->num_frames, first->height, first->width, video->n_clips, video->num_frames, video->height, video->width);
+  *v = *video;
+  v->cond_channels = 3;
+  v->cond_dtype = CTRLV_ELEM_DTYPE;
+  return CTRLV_OK;
+}
+
+struct Chain {               // ctrlv_pipeline_boxes_to_video: the two stages, and where things lie in the workspace
+  Stage boxes, video;
+  size_t frames, cond, post, post_bytes, stage, total;
+};
+
+int plan_chain(ctrlv_pipeline* pb, ctrlv_pipeline* pv, const ctrlv_two_stage_request* q, Chain* c) {
+  CTRLV_TRY(check_pair("boxes_to_video", pb, pv, q));
+  CTRLV_CHECK_ARG(isfinite(q->clean_threshold), "boxes_to_video: clean_threshold=%g", (double)q->clean_threshold);
+  ctrlv_clip_request v;
+  CTRLV_TRY(video_request("boxes_to_video", &q->boxes, &q->video, &v));
+  // stage 1 must decode: its frames are what stage 2 is conditioned on.  Without out_frames they go into the chain's workspace
+  const bool own_frames = q->boxes.out_frames == nullptr;
+  CTRLV_TRY(validate_stage(pb, &q->boxes, &q->box_cond, kBoxStage | (own_frames ? kOutFrames : 0u), &c->boxes));
+  CTRLV_TRY(validate_stage(pv, &v, nullptr, kCond, &c->video));
+  CTRLV_TRY(layout_stage(&c->boxes));
+  CTRLV_TRY(layout_stage(&c->video));
+  const Geo& g = c->boxes.g;
+  const size_t fr = (size_t)g.B * g.F * 3 * g.H * g.W * sizeof(el_t);
+  Carver cv;
+  c->frames = cv.take(own_frames ? fr : 0);
+  c->cond = cv.take(fr);
+  c->post_bytes = ctrlv_box_frames_post_ws_bytes(g.B, g.F);
+  c->post = cv.take(c->post_bytes);
+  c->stage = cv.o;
+  c->total = cv.o + (c->boxes.L.total > c->video.L.total ? c->boxes.L.total : c->video.L.total);
+  return CTRLV_OK;
+}
+
+// the three calls a host would make by hand; the two stages' own workspaces share one region
+int run_chain(Chain* c, const ctrlv_two_stage_request* q, void* ws, ctrlv_stream_t stream) {
+  char* base = (char*)ws;
+  if (!c->boxes.r.out_frames) c->boxes.r.out_frames = base + c->frames;
+  c->video.r.cond = base + c->cond;
+  const Geo& g = c->boxes.g;
+  CTRLV_TRY(run_stage(c->boxes, base + c->stage, stream));
+  CTRLV_TRY(ctrlv_box_frames_post(c->boxes.r.out_frames, g.B, g.F, g.H, g.W, q->clean_threshold, nullptr, base + c->cond,
+                                  q->out_box_frames_u8, base + c->post, c->post_bytes, stream));
+  return run_stage(c->video, base + c->stage, stream);
+}
+
+}  // namespace
 
 extern "C" size_t ctrlv_pipeline_chain_workspace_bytes(ctrlv_pipeline* boxes, ctrlv_pipeline* video,
                                                        const ctrlv_two_stage_request* q) {
@@ -734,26 +621,181 @@ extern "C" int ctrlv_pipeline_boxes_to_video(ctrlv_pipeline* boxes, ctrlv_pipeli
   Chain c;
   CTRLV_TRY(plan_chain(boxes, video, q, &c));
   CTRLV_TRY(check_workspace("pipeline_boxes_to_video", "ctrlv_pipeline_chain_workspace_bytes", ws, ws_bytes, c.total));
-  char* base = (char*)ws;
-  if (!c.boxes.out_frames) c.boxes.out_frames = base + c.frames;
-  c.video.cond = base + c.cond;
-  // the three calls a host would make by hand; the two stages' own workspaces share one region
-  CTRLV_TRY(run_clip(boxes, &c.boxes, &q->box_cond, c.gb, &c.bx, c.Lb, base + c.stage, stream));
-  CTRLV_TRY(ctrlv_box_frames_post(c.boxes.out_frames, c.gb.B, c.gb.F, c.gb.H, c.gb.W, q->clean_threshold, nullptr, base + c.cond,
-                                  q->out_box_frames_u8, base + c.post, c.post_bytes, stream));
-  return run_clip(video, &c.video, nullptr, c.gv, nullptr, c.Lv, base + c.stage, stream);
+  return run_chain(&c, q, ws, stream);
+}
+
+namespace {
+
+struct Sched {               // where a schedule the request asks for is written
+  float *sig, *ts;
+};
+
+struct Prep {                // ctrlv_pipeline_prepare: the filled request and the layout of prep_ws
+  ctrlv_clip_request filled; // (what prepare places in prep_ws -- `supplied` -- is NULL until place_prepared)
+  unsigned supplied;         // kImage (a Lanczos resize) | kAugNoise | kLatents (the two draws)
+  size_t resize_ws, resize_bytes, image, aug, lat, front;      // front: the bytes of prep_ws, at least kAlign
+  bool schedule;
+  double init_noise_sigma;
+  Geo g;
+};
+
+// Everything prepare decides on the host.  sc: the caller's arrays, the pipeline's, or a size query's scratch.  The filled
+// request is validated as generate validates it.
+int plan_prepare(const ctrlv_pipeline* p, const ctrlv_clip_request* in, const ctrlv_seed_request* s, Sched sc, Prep* q) {
+  CTRLV_CHECK_ARG(p != nullptr, "pipeline_prepare: null pipeline");
+  CTRLV_CHECK_ARG(in != nullptr, "pipeline_prepare: null request");
+  CTRLV_CHECK_ARG(s != nullptr, "pipeline_prepare: null seed request");
+  CTRLV_CHECK_ARG(s->reserved == 0, "pipeline_prepare: seed request reserved=%d must be 0", s->reserved);
+  ctrlv_clip_request& f = q->filled;
+  f = *in;
+  q->schedule = in->sigmas == nullptr || in->timesteps == nullptr;
+  if (q->schedule) {
+    CTRLV_CHECK_SHAPE(in->num_steps >= 1 && in->num_steps <= kMaxSteps, "pipeline_prepare: num_steps=%d must be in [1, %d]",
+                      in->num_steps, kMaxSteps);
+    CTRLV_CHECK_ARG(sc.sig != nullptr && sc.ts != nullptr, "pipeline_prepare: the request leaves sigmas / timesteps NULL, and "
+                    "sigmas_host / timesteps_host of the seed request are null (host arrays of num_steps + 1 and num_steps floats)");
+    // into scratch first: a table the caller did set is kept
+    std::vector<float> tmp((size_t)2 * in->num_steps + 1);
+    CTRLV_TRY(ctrlv_euler_schedule(in->num_steps, s->sigma_min, s->sigma_max, tmp.data(), tmp.data() + in->num_steps + 1, nullptr));
+    if (!in->sigmas) {
+      memcpy(sc.sig, tmp.data(), ((size_t)in->num_steps + 1) * sizeof(float));
+      f.sigmas = sc.sig;
+    }
+    if (!in->timesteps) {
+      memcpy(sc.ts, tmp.data() + in->num_steps + 1, (size_t)in->num_steps * sizeof(float));
+      f.timesteps = sc.ts;
+    }
+  }
+  q->init_noise_sigma = sqrt((double)f.sigmas[0] * (double)f.sigmas[0] + 1.0);
+  Carver cv;
+  q->supplied = 0;
+  q->resize_ws = q->resize_bytes = q->image = q->aug = q->lat = 0;
+  if (s->src_image_u8) {
+    CTRLV_CHECK_ARG(in->image_u8 == nullptr, "pipeline_prepare: image_u8 and src_image_u8 are both set");
+    CTRLV_CHECK_SHAPE(s->src_height > 0 && s->src_width > 0, "pipeline_prepare: src_image_u8 without sizes (src_height=%d, "
+                      "src_width=%d)", s->src_height, s->src_width);
+    if (s->src_height == in->height && s->src_width == in->width) {
+      f.image_u8 = s->src_image_u8;
+    } else {
+      CTRLV_CHECK_SHAPE(in->n_clips >= 1 && in->height > 0 && in->width > 0, "pipeline_prepare: n_clips=%d, height=%d, width=%d "
+                        "must be positive", in->n_clips, in->height, in->width);
+      CTRLV_TRY(ctrlv_resize_lanczos_check(in->n_clips, s->src_height, s->src_width, in->height, in->width));
+      q->supplied |= kImage;
+      q->resize_bytes = ctrlv_resize_lanczos_ws_bytes(in->n_clips, s->src_height, s->src_width, in->height, in->width);
+      q->resize_ws = cv.take(q->resize_bytes);
+      q->image = cv.take((size_t)in->n_clips * in->height * in->width * 3);
+    }
+  }
+  if (!in->aug_noise) q->supplied |= kAugNoise;
+  if (!in->latents) q->supplied |= kLatents;
+  // (a ControlNet pipeline's request may still lack its cond here -- kCond --: stage 2 of a ctrlv_two_stage_request receives it
+  // from the chain.  The consuming call validates the request it is given)
+  const Geo& g = q->g;
+  CTRLV_TRY(validate(p, &f, q->supplied | kCond, &q->g));
+  if (q->supplied & kAugNoise) q->aug = cv.take((size_t)g.B * 3 * g.H * g.W * sizeof(float));
+  if (q->supplied & kLatents) q->lat = cv.take((size_t)g.B * g.F * g.L * g.hw * sizeof(float));
+  q->front = cv.o > 0 ? cv.o : kAlign;
+  return CTRLV_OK;
+}
+
+// what prepare supplies gets its address in a request: the one place, where the workspace is known
+void place_prepared(const Prep& q, void* prep_ws, ctrlv_clip_request* r) {
+  char* base = (char*)prep_ws;
+  if (q.supplied & kImage) r->image_u8 = base + q.image;
+  if (q.supplied & kAugNoise) r->aug_noise = (const float*)(base + q.aug);
+  if (q.supplied & kLatents) r->latents = (const float*)(base + q.lat);
+}
+
+int run_prepare(const Prep& q, const ctrlv_seed_request* s, void* prep_ws, ctrlv_stream_t stream) {
+  char* base = (char*)prep_ws;
+  const ctrlv_clip_request& f = q.filled;
+  if (q.supplied & kImage)
+    CTRLV_TRY(ctrlv_resize_lanczos_u8(s->src_image_u8, f.n_clips, s->src_height, s->src_width, base + q.image, f.height, f.width,
+                                      base + q.resize_ws, q.resize_bytes, stream));
+  if (q.supplied & kAugNoise)
+    CTRLV_TRY(ctrlv_randn(s->seed, s->clip_index0, s->call, 0, f.n_clips, (size_t)3 * f.height * f.width, 1.0f, 0, base + q.aug, 0,
+                          stream));
+  if (q.supplied & kLatents)
+    CTRLV_TRY(ctrlv_randn(s->seed, s->clip_index0, s->call, 1, f.n_clips,
+                          (size_t)q.g.F * q.g.L * q.g.hw, (float)q.init_noise_sigma, 1, base + q.lat,
+                          0, stream));
+  return CTRLV_OK;
+}
+
+// the schedule's home of a size query or of a generate_seeded call without host arrays
+Sched sched_store(std::vector<float>* v, const ctrlv_clip_request* r) {
+  const int n = r && r->num_steps >= 1 && r->num_steps <= kMaxSteps ? r->num_steps : 1;
+  v->assign((size_t)2 * n + 1, 0.f);
+  return {v->data(), v->data() + n + 1};
+}
+
+struct Seeded {              // ctrlv_pipeline_generate_seeded: prepare in the front of the workspace, the clip behind it
+  Prep prep;
+  Stage clip;
+};
+
+int plan_seeded(ctrlv_pipeline* p, const ctrlv_clip_request* r, const ctrlv_seed_request* s, Sched sc, Seeded* sd) {
+  CTRLV_TRY(plan_prepare(p, r, s, sc, &sd->prep));
+  return plan_stage(p, &sd->prep.filled, nullptr, sd->prep.supplied, &sd->clip);
+}
+
+int run_seeded(Seeded* sd, const ctrlv_seed_request* s, void* ws, ctrlv_stream_t stream) {
+  place_prepared(sd->prep, ws, &sd->clip.r);
+  CTRLV_TRY(run_prepare(sd->prep, s, ws, stream));
+  return run_stage(sd->clip, (char*)ws + sd->prep.front, stream);
+}
+
+}  // namespace
+
+extern "C" size_t ctrlv_pipeline_prepare_bytes(ctrlv_pipeline* p, const ctrlv_clip_request* r, const ctrlv_seed_request* s) {
+  Prep q;
+  std::vector<float> tmp;
+  return plan_prepare(p, r, s, sched_store(&tmp, r), &q) == CTRLV_OK ? q.front : 0;
+}
+
+extern "C" int ctrlv_pipeline_prepare(ctrlv_pipeline* p, const ctrlv_clip_request* in, const ctrlv_seed_request* s,
+                                      ctrlv_clip_request* out, void* prep_ws, size_t prep_bytes, ctrlv_stream_t stream) {
+  CTRLV_CHECK_ARG(out != nullptr, "pipeline_prepare: null output request");
+  Prep q;
+  CTRLV_TRY(plan_prepare(p, in, s, {s ? s->sigmas_host : nullptr, s ? s->timesteps_host : nullptr}, &q));
+  CTRLV_TRY(check_workspace("pipeline_prepare", "ctrlv_pipeline_prepare_bytes", prep_ws, prep_bytes, q.front));
+  CTRLV_TRY(run_prepare(q, s, prep_ws, stream));
+  place_prepared(q, prep_ws, &q.filled);
+  *out = q.filled;
+  return CTRLV_OK;
+}
+
+extern "C" size_t ctrlv_pipeline_seeded_workspace_bytes(ctrlv_pipeline* p, const ctrlv_clip_request* r,
+                                                        const ctrlv_seed_request* s) {
+  Seeded sd;
+  std::vector<float> tmp;
+  return plan_seeded(p, r, s, sched_store(&tmp, r), &sd) == CTRLV_OK ? sd.prep.front + sd.clip.L.total : 0;
+}
+
+extern "C" int ctrlv_pipeline_generate_seeded(ctrlv_pipeline* p, const ctrlv_clip_request* r, const ctrlv_seed_request* s, void* ws,
+                                              size_t ws_bytes, ctrlv_stream_t stream) {
+  CTRLV_CHECK_ARG(p != nullptr, "pipeline_generate_seeded: null pipeline");
+  CTRLV_CHECK_ARG(s != nullptr, "pipeline_generate_seeded: null seed request");
+  Sched sc = {s->sigmas_host, s->timesteps_host};
+  if (!sc.sig || !sc.ts) {
+    const Sched own = sched_store(&p->sched, r);
+    if (!sc.sig) sc.sig = own.sig;
+    if (!sc.ts) sc.ts = own.ts;
+  }
+  Seeded sd;
+  CTRLV_TRY(plan_seeded(p, r, s, sc, &sd));
+  CTRLV_TRY(check_workspace("pipeline_generate_seeded", "ctrlv_pipeline_seeded_workspace_bytes", ws, ws_bytes,
+                            sd.prep.front + sd.clip.L.total));
+  return run_seeded(&sd, s, ws, stream);
 }
 
 namespace {
 
 constexpr int kMaxCandidates = 8;
 
-struct Best {                // ctrlv_pipeline_best_boxes: the candidates as run_clip sees them, and where things lie in the workspace
+struct Best {                // ctrlv_pipeline_best_boxes: the candidates' stages, and where things lie in the workspace
   int C;
-  ctrlv_clip_request cand[kMaxCandidates];
-  Geo g[kMaxCandidates];
-  BoxGeo bx[kMaxCandidates];
-  Layout L[kMaxCandidates];
+  Stage cand[kMaxCandidates];
   bool emit;                 // any of out_pt / out_cond / out_u8 (with need_cond: always)
   size_t fr, clip_bytes, slots, scratch, counts, winner, gathered, cond, post, post_bytes, stage, stage_bytes;
 };
@@ -783,48 +825,44 @@ int validate_best(ctrlv_pipeline* p, const ctrlv_best_boxes_request* q, Best* b)
                       "best_boxes: the candidates differ in geometry (candidate 0: %d x %d x %d x %d, candidate %d: %d x %d x %d x "
                       "%d)", r0.n_clips, r0.num_frames, r0.height, r0.width, c, r.n_clips, r.num_frames, r.height, r.width);
   }
-  for (int c = 0; c < b->C; ++c) {
-    b->cand[c] = q->candidates[c];
-    b->cand[c].out_frames = (void*)(uintptr_t)kAlign;       // (a placeholder until the workspace is known: the clip must decode)
-    CTRLV_TRY(validate_boxes(p, &b->cand[c], &q->box_cond, &b->g[c], &b->bx[c]));
-  }
+  for (int c = 0; c < b->C; ++c)       // (kOutFrames: the clip must decode, into its frame slot)
+    CTRLV_TRY(validate_stage(p, &q->candidates[c], &q->box_cond, kBoxStage | kOutFrames, &b->cand[c]));
   return CTRLV_OK;
 }
 
 // need_cond: the chain's call -- a condition buffer is laid out when the request brings none
-int layout_best(ctrlv_pipeline* p, const ctrlv_best_boxes_request* q, bool need_cond, Best* b) {
+int layout_best(const ctrlv_best_boxes_request* q, bool need_cond, Best* b) {
   b->stage_bytes = 0;
   for (int c = 0; c < b->C; ++c) {
-    CTRLV_TRY(layout(p, &b->cand[c], b->g[c], &b->bx[c], &b->L[c]));
-    b->stage_bytes = b->L[c].total > b->stage_bytes ? b->L[c].total : b->stage_bytes;
+    CTRLV_TRY(layout_stage(&b->cand[c]));
+    b->stage_bytes = b->cand[c].L.total > b->stage_bytes ? b->cand[c].L.total : b->stage_bytes;
   }
-  const Geo& g = b->g[0];
+  const Geo& g = b->cand[0].g;
   b->emit = need_cond || q->out_pt || q->out_cond || q->out_u8;
   b->clip_bytes = (size_t)g.F * 3 * g.H * g.W * sizeof(el_t);
   b->fr = (size_t)g.B * b->clip_bytes;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += up(bytes); return at; };
-  b->slots = take((size_t)b->C * b->fr);                    // (C, n, clip) without gaps: ctrlv_gather_clips reads it as one array
-  b->scratch = take((size_t)g.B * g.F * 3 * g.H * g.W);
-  b->counts = take(q->out_counts ? 0 : (size_t)b->C * g.B * 6 * sizeof(unsigned long long));
-  b->winner = take(q->out_winner ? 0 : (size_t)g.B * sizeof(int32_t));
-  b->gathered = take(b->emit ? b->fr : 0);
-  b->cond = take(need_cond && !q->out_cond ? b->fr : 0);
+  Carver cv;
+  b->slots = cv.take((size_t)b->C * b->fr);                 // (C, n, clip) without gaps: ctrlv_gather_clips reads it as one array
+  b->scratch = cv.take((size_t)g.B * g.F * 3 * g.H * g.W);
+  b->counts = cv.take(q->out_counts ? 0 : (size_t)b->C * g.B * 6 * sizeof(unsigned long long));
+  b->winner = cv.take(q->out_winner ? 0 : (size_t)g.B * sizeof(int32_t));
+  b->gathered = cv.take(b->emit ? b->fr : 0);
+  b->cond = cv.take(need_cond && !q->out_cond ? b->fr : 0);
   b->post_bytes = ctrlv_box_frames_post_ws_bytes(g.B, g.F);
-  b->post = take(b->post_bytes);
-  b->stage = o;
+  b->post = cv.take(b->post_bytes);
+  b->stage = cv.o;
   return CTRLV_OK;
 }
 
 // out_cond: the request's, or the chain's buffer
-int run_best(ctrlv_pipeline* p, const ctrlv_best_boxes_request* q, Best* b, char* base, void* out_cond, ctrlv_stream_t stream) {
-  const Geo& g = b->g[0];
+int run_best(const ctrlv_best_boxes_request* q, Best* b, char* base, void* out_cond, ctrlv_stream_t stream) {
+  const Geo& g = b->cand[0].g;
   unsigned long long* counts = q->out_counts ? q->out_counts : (unsigned long long*)(base + b->counts);
   int32_t* winner = q->out_winner ? q->out_winner : (int32_t*)(base + b->winner);
   for (int c = 0; c < b->C; ++c) {
     char* slot = base + b->slots + (size_t)c * b->fr;
-    b->cand[c].out_frames = slot;
-    CTRLV_TRY(run_clip(p, &b->cand[c], &q->box_cond, b->g[c], &b->bx[c], b->L[c], base + b->stage, stream));
+    b->cand[c].r.out_frames = slot;
+    CTRLV_TRY(run_stage(b->cand[c], base + b->stage, stream));
     CTRLV_TRY(ctrlv_box_frames_post(slot, g.B, g.F, g.H, g.W, q->clean_threshold, nullptr, nullptr, base + b->scratch,
                                     base + b->post, b->post_bytes, stream));
     CTRLV_TRY(ctrlv_mask_counts(q->gt_u8, base + b->scratch, g.B, g.F, g.H, g.W, counts + (size_t)c * g.B * 6, stream));
@@ -838,47 +876,38 @@ int run_best(ctrlv_pipeline* p, const ctrlv_best_boxes_request* q, Best* b, char
 
 int plan_best(ctrlv_pipeline* p, const ctrlv_best_boxes_request* q, Best* b) {
   CTRLV_TRY(validate_best(p, q, b));
-  return layout_best(p, q, false, b);
+  return layout_best(q, false, b);
 }
 
-struct BestChain {
+struct BestChain {           // ctrlv_pipeline_best_boxes_to_video
   Best best;
-  ctrlv_clip_request video;
-  Geo gv;
-  Layout Lv;
+  Stage video;
   size_t total;
 };
 
 int plan_best_chain(ctrlv_pipeline* pb, ctrlv_pipeline* pv, const ctrlv_best_chain_request* q, BestChain* c) {
-  CTRLV_CHECK_ARG(pb != nullptr && pv != nullptr, "best_boxes_to_video: null pipeline");
-  CTRLV_CHECK_ARG(q != nullptr, "best_boxes_to_video: null request");
-  CTRLV_CHECK_ARG(pb->tag == kPipelineTag && pv->tag == kPipelineTag, "best_boxes_to_video: both pipelines must come from this "
-                  "library (element dtype code %d)", CTRLV_ELEM_DTYPE);
-  CTRLV_CHECK_ARG(pb->device == pv->device, "best_boxes_to_video: the pipelines live on different devices (%d and %d)", pb->device,
-                  pv->device);
-  CTRLV_CHECK_ARG(q->reserved == 0, "best_boxes_to_video: reserved=%d must be 0", q->reserved);
-  CTRLV_CHECK_ARG(pv->cn != nullptr, "best_boxes_to_video: the video pipeline has no ControlNet to take the box frames");
-  CTRLV_CHECK_ARG(q->video.cond == nullptr, "best_boxes_to_video: video.cond must be NULL on entry (the driver supplies the "
-                  "winner's frames)");
+  CTRLV_TRY(check_pair("best_boxes_to_video", pb, pv, q));
   CTRLV_TRY(validate_best(pb, &q->boxes, &c->best));
-  const ctrlv_clip_request& r0 = q->boxes.candidates[0];
-  CTRLV_CHECK_SHAPE(r0.n_clips == q->video.n_clips && r0.num_frames == q->video.num_frames && r0.height == q->video.height &&
-                    r0.width == q->video.width,
-                    "best_boxes_to_video: the two stages differ in geometry (boxes %d x %d x %d x %d, video %d x %d x %d x %d)",
-                    r0.n_clips, r0.num_frames, r0.height, r0.width, q->video.n_clips, q->video.num_frames, q->video.height,
-                    q->video.width);
-  c->video = q->video;
-  c->video.cond = (const void*)(uintptr_t)kAlign;     // (a placeholder until the workspace is known: validate asks for non-null)
-  c->video.cond_channels = 3;
-  c->video.cond_dtype = CTRLV_ELEM_DTYPE;
-  CTRLV_TRY(validate(pv, &c->video, &c->gv));
-  CTRLV_TRY(layout_best(pb, &q->boxes, true, &c->best));
-  CTRLV_TRY(layout(pv, &c->video, c->gv, nullptr, &c->Lv));
-  c->total = c->best.stage + (c->best.stage_bytes > c->Lv.total ? c->best.stage_bytes : c->Lv.total);
+  ctrlv_clip_request v;
+  CTRLV_TRY(video_request("best_boxes_to_video", &q->boxes.candidates[0], &q->video, &v));
+  CTRLV_TRY(validate_stage(pv, &v, nullptr, kCond, &c->video));
+  CTRLV_TRY(layout_best(&q->boxes, true, &c->best));
+  CTRLV_TRY(layout_stage(&c->video));
+  c->total = c->best.stage + (c->best.stage_bytes > c->video.L.total ? c->best.stage_bytes : c->video.L.total);
   return CTRLV_OK;
 }
 
+int run_best_chain(BestChain* c, const ctrlv_best_chain_request* q, void* ws, ctrlv_stream_t stream) {
+  char* base = (char*)ws;
+  void* cond = q->boxes.out_cond ? q->boxes.out_cond : (void*)(base + c->best.cond);
+  c->video.r.cond = cond;
+  CTRLV_TRY(run_best(&q->boxes, &c->best, base, cond, stream));
+  return run_stage(c->video, base + c->best.stage, stream);
+}
+
 }  // namespace
+
+// (eight stages: Best and BestChain live off the stack)
 
 extern "C" size_t ctrlv_pipeline_best_boxes_workspace_bytes(ctrlv_pipeline* p, const ctrlv_best_boxes_request* q) {
   std::vector<Best> b(1);
@@ -887,11 +916,11 @@ extern "C" size_t ctrlv_pipeline_best_boxes_workspace_bytes(ctrlv_pipeline* p, c
 
 extern "C" int ctrlv_pipeline_best_boxes(ctrlv_pipeline* p, const ctrlv_best_boxes_request* q, void* ws, size_t ws_bytes,
                                          ctrlv_stream_t stream) {
-  std::vector<Best> b(1);      // (eight layouts: off the stack)
+  std::vector<Best> b(1);
   CTRLV_TRY(plan_best(p, q, &b[0]));
   CTRLV_TRY(check_workspace("pipeline_best_boxes", "ctrlv_pipeline_best_boxes_workspace_bytes", ws, ws_bytes,
                             b[0].stage + b[0].stage_bytes));
-  return run_best(p, q, &b[0], (char*)ws, q->out_cond, stream);
+  return run_best(q, &b[0], (char*)ws, q->out_cond, stream);
 }
 
 extern "C" size_t ctrlv_pipeline_best_chain_workspace_bytes(ctrlv_pipeline* boxes, ctrlv_pipeline* video,
@@ -902,13 +931,8 @@ extern "C" size_t ctrlv_pipeline_best_chain_workspace_bytes(ctrlv_pipeline* boxe
 
 extern "C" int ctrlv_pipeline_best_boxes_to_video(ctrlv_pipeline* boxes, ctrlv_pipeline* video, const ctrlv_best_chain_request* q,
                                                   void* ws, size_t ws_bytes, ctrlv_stream_t stream) {
-  std::vector<BestChain> cv(1);
-  BestChain& c = cv[0];
-  CTRLV_TRY(plan_best_chain(boxes, video, q, &c));
-  CTRLV_TRY(check_workspace("pipeline_best_boxes_to_video", "ctrlv_pipeline_best_chain_workspace_bytes", ws, ws_bytes, c.total));
-  char* base = (char*)ws;
-  void* cond = q->boxes.out_cond ? q->boxes.out_cond : (void*)(base + c.best.cond);
-  c.video.cond = cond;
-  CTRLV_TRY(run_best(boxes, &q->boxes, &c.best, base, cond, stream));
-  return run_clip(video, &c.video, nullptr, c.gv, nullptr, c.Lv, base + c.best.stage, stream);
+  std::vector<BestChain> c(1);
+  CTRLV_TRY(plan_best_chain(boxes, video, q, &c[0]));
+  CTRLV_TRY(check_workspace("pipeline_best_boxes_to_video", "ctrlv_pipeline_best_chain_workspace_bytes", ws, ws_bytes, c[0].total));
+  return run_best_chain(&c[0], q, ws, stream);
 }

@@ -5,6 +5,7 @@ This is what `UNetSpatioTemporalConditionModel.forward` / `ControlNetModel.forwa
 executor in models/blocks.py issues the same kernels with the same descriptors (bit-identical results) and is kept for
 per-block tests, the error-growth trace and the per-kernel timing of bench.py.
 """
+import collections
 import ctypes
 
 import torch
@@ -373,6 +374,12 @@ def euler_schedule(num_steps, sigma_min=0.0, sigma_max=0.0):
     return list(sig), list(ts), ins.value
 
 
+StageRequest = collections.namedtuple("StageRequest", "request seed_request cond out keep")
+StageRequest.__doc__ = """One stage of a driver call: its `ctrlv_clip_request`, its `ctrlv_seed_request` (None without a seed), the
+contiguous condition or box frames, out = (out_latents, out_frames, out_frames_u8), and in `keep` every other object the
+request points into.  Hold the record until the call has been enqueued."""
+
+
 class PipelinePlan(_Handle):
     """Owns one `ctrlv_pipeline`: a whole clip as one C call (include/ctrlv_hip.h: ctrlv_pipeline_generate) on four borrowed
     plans of ONE library -- `Plan("unet")`, `Plan("controlnet")` or None, `VaePlan`, `ClipPlan`.  The object keeps them alive."""
@@ -438,51 +445,19 @@ class PipelinePlan(_Handle):
         return self._nonzero(self._lib.ctrlv_pipeline_workspace_bytes(self._h, ctypes.byref(request)),
                              "ctrlv_pipeline_workspace_bytes")
 
-    def _checked_request(self, who, image_u8, latents, sigmas, timesteps, cond, cond_name, aug_noise, frames, frames_u8, **kw):
-        """Validate the tensors of a generate / predict_boxes call, allocate the outputs and build the request around them.
-        `cond` is the ControlNet condition of generate or the box frames of predict_boxes (which do not enter the request).
-        Returns (request, keep, cond, (out_latents, out_frames, out_frames_u8))."""
-        dev = self.device
-        for name, t in (("image_u8", image_u8), ("latents", latents), (cond_name, cond), ("aug_noise", aug_noise)):
-            if t is not None and (not t.is_cuda or (t.device.index or 0) != (dev.index or 0)):
-                raise ValueError(f"PipelinePlan.{who}: {name} on {t.device}, the plans' weights on {dev}")
-        if image_u8.dtype != torch.uint8 or image_u8.dim() != 4 or image_u8.shape[3] != 3:
-            raise ValueError(f"PipelinePlan.{who}: image_u8 must be (n, H, W, 3) uint8")
-        if latents.dtype != torch.float32 or latents.dim() != 5:
-            raise ValueError(f"PipelinePlan.{who}: latents must be fp32 (n, F, L, h, w)")
-        n, H, W, _ = image_u8.shape
-        F = latents.shape[1]
-        if tuple(latents.shape) != (n, F, latents.shape[2], H // 8, W // 8):
-            raise ValueError(f"PipelinePlan.{who}: latents {tuple(latents.shape)} do not match a {n} x {H} x {W} image")
-        if cond is not None:
-            want = (n, F, 3, H, W) if cond.dim() == 5 and cond.shape[2] == 3 else (n, F, latents.shape[2], H // 8, W // 8)
-            if tuple(cond.shape) != want or cond.dtype not in _DT:
-                raise ValueError(f"PipelinePlan.{who}: {cond_name} {tuple(cond.shape)} must be {want} in fp32 / fp16 / bf16")
-            cond = cond.contiguous()
-        if aug_noise is not None:
-            if aug_noise.dtype != torch.float32 or tuple(aug_noise.shape) != (n, 3, H, W):
-                raise ValueError(f"PipelinePlan.{who}: aug_noise must be fp32 {(n, 3, H, W)}")
-            aug_noise = aug_noise.contiguous()
-        image_u8, latents = image_u8.contiguous(), latents.contiguous()
-        out_lat = torch.empty_like(latents)
-        out_fr = torch.empty(n * F, 3, H, W, dtype=self.dtype, device=dev) if frames else None
-        out_u8 = torch.empty(n, F, H, W, 3, dtype=torch.uint8, device=dev) if frames_u8 else None
-        r, keep = self.request(image_u8, latents, sigmas, timesteps, cond=cond if cond_name == "cond" else None,
-                               aug_noise=aug_noise, out_latents=out_lat, out_frames=out_fr, out_frames_u8=out_u8, **kw)
-        return r, keep, cond, (out_lat, out_fr, out_u8)
-
     def _workspace(self, need):
         if self._ws is None or self._ws.numel() < need or self._ws.device != self.device:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._ws
 
-    def seeded_request(self, who, image_u8, seed, *, num_steps=None, num_frames=None, height=None, width=None, clip_index0=0,
-                       call=0, sigma_min=0.0, sigma_max=0.0, latents=None, sigmas=None, timesteps=None, cond=None,
+    def _stage_request(self, who, image_u8, *, seed=None, prepare=False, latents=None, sigmas=None, timesteps=None, num_steps=None,
+                       num_frames=None, height=None, width=None, clip_index0=0, call=0, sigma_min=0.0, sigma_max=0.0, cond=None,
                        cond_name="cond", aug_noise=None, frames=True, frames_u8=True, **kw):
-        """The (`ctrlv_clip_request`, `ctrlv_seed_request`) pair of a seeded call: image_u8 (n, Hs, Ws, 3) uint8 of ANY size --
-        the library resizes it to (height, width), default its own size --, and NULL for whatever of latents / aug_noise /
-        sigmas / timesteps is not given: ctrlv_pipeline_prepare fills those from (seed, clip_index0, call).  Returns
-        (request, seed request, keep, cond, (out_latents, out_frames, out_frames_u8)); keep the five together."""
+        """Validate the tensors of one stage, allocate its outputs and build its `StageRequest`.  `cond` is the ControlNet
+        condition of generate (cond_name "cond") or the box frames of predict_boxes, which do not enter the request.  With
+        `seed=`: the `ctrlv_seed_request` beside it; image_u8 (n, Hs, Ws, 3) may have ANY size -- the library resizes it to
+        (height, width), default its own --, and whatever of latents / aug_noise / sigmas / timesteps is not given stays NULL for
+        ctrlv_pipeline_prepare to fill from (seed, clip_index0, call); `prepare=True` runs it and swaps the filled request in."""
         dev = self.device
         for name, t in (("image_u8", image_u8), ("latents", latents), (cond_name, cond), ("aug_noise", aug_noise)):
             if t is not None and (not t.is_cuda or (t.device.index or 0) != (dev.index or 0)):
@@ -491,13 +466,18 @@ class PipelinePlan(_Handle):
             raise ValueError(f"PipelinePlan.{who}: image_u8 must be (n, H, W, 3) uint8")
         n, Hs, Ws, _ = image_u8.shape
         H, W = int(height or Hs), int(width or Ws)
+        if seed is None and (H, W) != (Hs, Ws):
+            raise ValueError(f"PipelinePlan.{who}: image_u8 of another size than {H} x {W} is resized with seed= only")
         L = self.vae._cfg.latent_channels
         if latents is not None:
             if latents.dtype != torch.float32 or latents.dim() != 5:
                 raise ValueError(f"PipelinePlan.{who}: latents must be fp32 (n, F, L, h, w)")
+            if seed is None:
+                L, num_frames = latents.shape[2], latents.shape[1]
             num_frames = latents.shape[1] if num_frames is None else num_frames
             if tuple(latents.shape) != (n, num_frames, L, H // 8, W // 8):
-                raise ValueError(f"PipelinePlan.{who}: latents {tuple(latents.shape)} do not match {n} clips of {num_frames} x {H} x {W}")
+                what = f"a {n} x {H} x {W} image" if seed is None else f"{n} clips of {num_frames} x {H} x {W}"
+                raise ValueError(f"PipelinePlan.{who}: latents {tuple(latents.shape)} do not match {what}")
             latents = latents.contiguous()
         if num_frames is None and cond is not None:
             num_frames = cond.shape[1]
@@ -520,10 +500,10 @@ class PipelinePlan(_Handle):
                 raise ValueError(f"PipelinePlan.{who}: aug_noise must be fp32 {(n, 3, H, W)}")
             aug_noise = aug_noise.contiguous()
         image_u8 = image_u8.contiguous()
-        out_lat = torch.empty(n, F, L, H // 8, W // 8, dtype=torch.float32, device=dev)
-        out_fr = torch.empty(n * F, 3, H, W, dtype=self.dtype, device=dev) if frames else None
-        out_u8 = torch.empty(n, F, H, W, 3, dtype=torch.uint8, device=dev) if frames_u8 else None
-        r = _lib.ClipRequest()                  # image_u8 stays NULL: the source goes through the seed request
+        out = (torch.empty(n, F, L, H // 8, W // 8, dtype=torch.float32, device=dev),
+               torch.empty(n * F, 3, H, W, dtype=self.dtype, device=dev) if frames else None,
+               torch.empty(n, F, H, W, 3, dtype=torch.uint8, device=dev) if frames_u8 else None)
+        r = _lib.ClipRequest()
         r.n_clips, r.num_frames, r.height, r.width = n, F, H, W
         r.num_steps = int(num_steps)
         sig = ts = None
@@ -533,17 +513,29 @@ class PipelinePlan(_Handle):
             r.sigmas, r.timesteps = sig, ts
         if latents is not None:
             r.latents = latents.data_ptr()
-        self._request_fields(r, cond=cond if cond_name == "cond" else None, aug_noise=aug_noise, out_latents=out_lat,
-                             out_frames=out_fr, out_frames_u8=out_u8, **kw)
-        keep = (sig, ts, cond, aug_noise)
-        steps = min(max(r.num_steps, 1), 1024)
-        sig_host, ts_host = (ctypes.c_float * (steps + 1))(), (ctypes.c_float * steps)()
-        sr = _lib.SeedRequest()
-        sr.seed, sr.clip_index0, sr.call = int(seed) & 0xFFFFFFFFFFFFFFFF, int(clip_index0), int(call)
-        sr.src_image_u8, sr.src_height, sr.src_width = image_u8.data_ptr(), Hs, Ws
-        sr.sigma_min, sr.sigma_max = float(sigma_min), float(sigma_max)
-        sr.sigmas_host, sr.timesteps_host = sig_host, ts_host
-        return r, sr, (keep, image_u8, latents, sig_host, ts_host, out_lat, out_fr, out_u8), cond, (out_lat, out_fr, out_u8)
+        self._request_fields(r, cond=cond if cond_name == "cond" else None, aug_noise=aug_noise, out_latents=out[0],
+                             out_frames=out[1], out_frames_u8=out[2], **kw)
+        sr = sig_host = ts_host = None
+        if seed is None:
+            r.image_u8 = image_u8.data_ptr()
+        else:                                   # image_u8 stays NULL: the source goes through the seed request
+            steps = min(max(r.num_steps, 1), 1024)
+            sr = _lib.SeedRequest()
+            sr.seed, sr.clip_index0, sr.call = int(seed) & 0xFFFFFFFFFFFFFFFF, int(clip_index0), int(call)
+            sr.src_image_u8, sr.src_height, sr.src_width = image_u8.data_ptr(), Hs, Ws
+            sr.sigma_min, sr.sigma_max = float(sigma_min), float(sigma_max)
+            sig_host, ts_host = (ctypes.c_float * (steps + 1))(), (ctypes.c_float * steps)()
+            sr.sigmas_host, sr.timesteps_host = sig_host, ts_host
+        st = StageRequest(r, sr, cond, out, (sig, ts, image_u8, latents, aug_noise, sig_host, ts_host))
+        if prepare and sr is not None:
+            filled, prep_ws = self.prepare(r, sr)
+            st = st._replace(request=filled, keep=(st.keep, r, prep_ws))
+        return st
+
+    def _run(self, query, call, *args):
+        """One driver call in the plan's workspace, sized by the call's own query, on torch's current stream."""
+        ws = self._workspace(self._nonzero(getattr(self._lib, query)(*args), query))
+        check(getattr(self._lib, call)(*args, ws.data_ptr(), ws.numel(), self._stream()), call)
 
     def prepare(self, request, seed_request):
         """ctrlv_pipeline_prepare: the request with its NULL fields filled -- Lanczos resize, the two draws, the schedule -- and
@@ -566,27 +558,17 @@ class PipelinePlan(_Handle):
 
         With `seed=` (ctrlv_pipeline_generate_seeded): latents, sigmas and timesteps may be omitted -- give num_steps= and
         num_frames= --, image_u8 may have any size when height= and width= are given, and what is omitted comes from the
-        library: see `seeded_request` for the other keywords (clip_index0, call, sigma_min, sigma_max)."""
-        if seed is not None:
-            r, sr, keep, cond, out = self.seeded_request("generate", image_u8, seed, latents=latents, sigmas=sigmas,
-                                                         timesteps=timesteps, cond=cond, aug_noise=aug_noise, frames=frames,
-                                                         frames_u8=frames_u8, **kw)
-            need = self._nonzero(self._lib.ctrlv_pipeline_seeded_workspace_bytes(self._h, ctypes.byref(r), ctypes.byref(sr)),
-                                 "ctrlv_pipeline_seeded_workspace_bytes")
-            ws = self._workspace(need)
-            check(self._lib.ctrlv_pipeline_generate_seeded(self._h, ctypes.byref(r), ctypes.byref(sr), ws.data_ptr(), ws.numel(),
-                                                           self._stream()), "ctrlv_pipeline_generate_seeded")
-            del keep
-            return out
-        if latents is None or sigmas is None or timesteps is None:
+        library: see `_stage_request` for the other keywords (clip_index0, call, sigma_min, sigma_max)."""
+        if seed is None and (latents is None or sigmas is None or timesteps is None):
             raise ValueError("PipelinePlan.generate: latents, sigmas and timesteps are needed without seed=")
-        r, keep, cond, out = self._checked_request("generate", image_u8, latents, sigmas, timesteps, cond, "cond", aug_noise,
-                                                   frames, frames_u8, **kw)
-        ws = self._workspace(self.workspace_bytes(r))
-        check(self._lib.ctrlv_pipeline_generate(self._h, ctypes.byref(r), ws.data_ptr(), ws.numel(), self._stream()),
-              "ctrlv_pipeline_generate")
-        del keep
-        return out
+        st = self._stage_request("generate", image_u8, seed=seed, latents=latents, sigmas=sigmas, timesteps=timesteps, cond=cond,
+                                 aug_noise=aug_noise, frames=frames, frames_u8=frames_u8, **kw)
+        if seed is None:
+            self._run("ctrlv_pipeline_workspace_bytes", "ctrlv_pipeline_generate", self._h, ctypes.byref(st.request))
+        else:
+            self._run("ctrlv_pipeline_seeded_workspace_bytes", "ctrlv_pipeline_generate_seeded", self._h, ctypes.byref(st.request),
+                      ctypes.byref(st.seed_request))
+        return st.out
 
     @staticmethod
     def box_condition(bbox_frames, num_cond_frames):
@@ -601,26 +583,17 @@ class PipelinePlan(_Handle):
                       frames_u8=True, seed=None, **kw):
         """The box predictor (ctrlv_pipeline_predict_boxes; a plan without a ControlNet): `generate` with the conditioning
         channels of frames [0, num_cond_frames) and F - 1 overwritten by bbox_frames -- (n, F, 3, H, W) pixels in [-1, 1], VAE
-        encoded, or (n, F, L, h, w) latents -- and the decoded frames clamped to [-1, 1].  Same returns as `generate`."""
+        encoded, or (n, F, L, h, w) latents -- and the decoded frames clamped to [-1, 1].  Same returns as `generate`; with
+        `seed=`, latents / sigmas / timesteps may be None: ctrlv_pipeline_prepare fills them."""
         if bbox_frames is None:
             raise ValueError("PipelinePlan.predict_boxes: bbox_frames is None")
-        if seed is not None:       # latents / sigmas / timesteps may be None: ctrlv_pipeline_prepare fills them (see `generate`)
-            r0, sr, keep0, boxes, out = self.seeded_request("predict_boxes", image_u8, seed, latents=latents, sigmas=sigmas,
-                                                            timesteps=timesteps, cond=bbox_frames, cond_name="bbox_frames",
-                                                            aug_noise=aug_noise, frames=frames, frames_u8=frames_u8, **kw)
-            r, prep = self.prepare(r0, sr)
-            keep = (keep0, r0, sr, prep)
-        else:
-            r, keep, boxes, out = self._checked_request("predict_boxes", image_u8, latents, sigmas, timesteps, bbox_frames,
-                                                        "bbox_frames", aug_noise, frames, frames_u8, **kw)
-        bc = self.box_condition(boxes, num_cond_frames)
-        need = self._nonzero(self._lib.ctrlv_pipeline_boxes_workspace_bytes(self._h, ctypes.byref(r), ctypes.byref(bc)),
-                             "ctrlv_pipeline_boxes_workspace_bytes")
-        ws = self._workspace(need)
-        check(self._lib.ctrlv_pipeline_predict_boxes(self._h, ctypes.byref(r), ctypes.byref(bc), ws.data_ptr(), ws.numel(),
-                                                     self._stream()), "ctrlv_pipeline_predict_boxes")
-        del keep, boxes
-        return out
+        st = self._stage_request("predict_boxes", image_u8, seed=seed, prepare=True, latents=latents, sigmas=sigmas,
+                                 timesteps=timesteps, cond=bbox_frames, cond_name="bbox_frames", aug_noise=aug_noise, frames=frames,
+                                 frames_u8=frames_u8, **kw)
+        bc = self.box_condition(st.cond, num_cond_frames)
+        self._run("ctrlv_pipeline_boxes_workspace_bytes", "ctrlv_pipeline_predict_boxes", self._h, ctypes.byref(st.request),
+                  ctypes.byref(bc))
+        return st.out
 
     def best_boxes_request(self, who, image_u8, bbox_frames, gt_u8, guidance, num_cond_frames, *, latents=None, aug_noise=None,
                            schedule=None, seed=None, num_steps=None, clip_index0=0, clean_threshold=50.0, pt=True, cond=True,
@@ -638,26 +611,16 @@ class PipelinePlan(_Handle):
             if seq is not None and (isinstance(seq, torch.Tensor) or len(seq) != C):
                 raise ValueError(f"PipelinePlan.{who}: {name} must be a sequence of {C} tensors, one per candidate")
         sig, ts = schedule if schedule is not None else (None, None)
-        rs, keep, boxes = [], [], None
-        for c, (g_min, g_max) in enumerate(guidance):
-            lat = latents[c] if latents is not None else None
-            aug = aug_noise[c] if aug_noise is not None else None
-            fields = dict(kw, min_guidance=g_min, max_guidance=g_max)
-            if seed is not None:
-                r0, sr, keep0, boxes, _ = self.seeded_request(who, image_u8, seed, num_steps=num_steps, num_frames=bbox_frames.shape[1],
-                                                              clip_index0=clip_index0, call=c, latents=lat, sigmas=sig, timesteps=ts,
-                                                              cond=bbox_frames, cond_name="bbox_frames", aug_noise=aug, frames=False,
-                                                              frames_u8=False, **fields)
-                r, prep = self.prepare(r0, sr)
-                keep.append((keep0, r0, sr, prep))
-            else:
-                if lat is None or sig is None:
-                    raise ValueError(f"PipelinePlan.{who}: latents and schedule are needed without seed=")
-                r, keep0, boxes, outs = self._checked_request(who, image_u8, lat, sig, ts, bbox_frames, "bbox_frames", aug, False,
-                                                              False, **fields)
-                keep.append((keep0, outs))
-            rs.append(r)
-        n, F, H, W = rs[0].n_clips, rs[0].num_frames, rs[0].height, rs[0].width
+        if seed is None and (latents is None or sig is None):
+            raise ValueError(f"PipelinePlan.{who}: latents and schedule are needed without seed=")
+        stages = [self._stage_request(who, image_u8, seed=seed, prepare=True, num_steps=num_steps, num_frames=bbox_frames.shape[1],
+                                      clip_index0=clip_index0, call=c, latents=latents[c] if latents is not None else None,
+                                      sigmas=sig, timesteps=ts, cond=bbox_frames, cond_name="bbox_frames",
+                                      aug_noise=aug_noise[c] if aug_noise is not None else None, frames=False, frames_u8=False,
+                                      **dict(kw, min_guidance=g_min, max_guidance=g_max))
+                  for c, (g_min, g_max) in enumerate(guidance)]
+        r0 = stages[0].request
+        n, F, H, W = r0.n_clips, r0.num_frames, r0.height, r0.width
         dev = self.device
         if gt_u8.dtype != torch.uint8 or tuple(gt_u8.shape) != (n, F, 3, H, W) or not gt_u8.is_cuda or \
                 (gt_u8.device.index or 0) != (dev.index or 0):
@@ -668,16 +631,16 @@ class PipelinePlan(_Handle):
         out_u8 = torch.empty(n, F, 3, H, W, dtype=torch.uint8, device=dev) if u8 else None
         counts = torch.empty(C, n, 2, 3, dtype=torch.int64, device=dev)
         winner = torch.empty(n, dtype=torch.int32, device=dev)
-        arr = (_lib.ClipRequest * C)(*rs)
+        arr = (_lib.ClipRequest * C)(*[st.request for st in stages])
         q = _lib.BestBoxesRequest()
         q.n_candidates, q.candidates = C, arr
-        q.box_cond = self.box_condition(boxes, num_cond_frames)
+        q.box_cond = self.box_condition(stages[-1].cond, num_cond_frames)
         q.gt_u8, q.clean_threshold = gt_u8.data_ptr(), float(clean_threshold)
         for name, t in (("out_pt", out_pt), ("out_cond", out_cond), ("out_u8", out_u8), ("out_counts", counts),
                         ("out_winner", winner)):
             if t is not None:
                 setattr(q, name, t.data_ptr())
-        return q, (arr, rs, keep, boxes, gt_u8), (out_pt, out_cond, out_u8, winner, counts)
+        return q, (arr, stages, gt_u8), (out_pt, out_cond, out_u8, winner, counts)
 
     def best_boxes(self, image_u8, bbox_frames, gt_u8, guidance=((1, 2), (1, 3), (2, 4), (2, 5), (3, 5)), num_cond_frames=3, *,
                    latents=None, aug_noise=None, schedule=None, seed=None, num_steps=None, clip_index0=0, **kw):
@@ -692,13 +655,19 @@ class PipelinePlan(_Handle):
         q, keep, out = self.best_boxes_request("best_boxes", image_u8, bbox_frames, gt_u8, guidance, num_cond_frames, latents=latents,
                                                aug_noise=aug_noise, schedule=schedule, seed=seed, num_steps=num_steps,
                                                clip_index0=clip_index0, **kw)
-        need = self._nonzero(self._lib.ctrlv_pipeline_best_boxes_workspace_bytes(self._h, ctypes.byref(q)),
-                             "ctrlv_pipeline_best_boxes_workspace_bytes")
-        ws = self._workspace(need)
-        check(self._lib.ctrlv_pipeline_best_boxes(self._h, ctypes.byref(q), ws.data_ptr(), ws.numel(), self._stream()),
-              "ctrlv_pipeline_best_boxes")
-        del keep
+        self._run("ctrlv_pipeline_best_boxes_workspace_bytes", "ctrlv_pipeline_best_boxes", self._h, ctypes.byref(q))
         return out
+
+
+def _video_stage(who, video_plan, image_u8, num_frames, video_latents, video_schedule, video_aug_noise, frames, frames_u8, video_kw,
+                 seed, num_steps, clip_index0, call):
+    """Stage 2 of a chain: `video_plan.generate`'s request without its cond, which the chain call supplies."""
+    if seed is None and (video_latents is None or video_schedule is None):
+        raise ValueError(f"{who}: video_latents and video_schedule are needed without seed=")
+    sig, ts = video_schedule if video_schedule is not None else (None, None)
+    return video_plan._stage_request(who, image_u8, seed=seed, prepare=True, num_steps=num_steps, num_frames=num_frames,
+                                     clip_index0=clip_index0, call=call, latents=video_latents, sigmas=sig, timesteps=ts,
+                                     aug_noise=video_aug_noise, frames=frames, frames_u8=frames_u8, **(video_kw or {}))
 
 
 def best_boxes_to_video(boxes_plan, video_plan, image_u8, bbox_frames, gt_u8, guidance=((1, 2), (1, 3), (2, 4), (2, 5), (3, 5)),
@@ -717,29 +686,13 @@ def best_boxes_to_video(boxes_plan, video_plan, image_u8, bbox_frames, gt_u8, gu
         "best_boxes_to_video", image_u8, bbox_frames, gt_u8, guidance, num_cond_frames, latents=box_latents, aug_noise=box_aug_noise,
         schedule=box_schedule, seed=seed, num_steps=steps[0], clip_index0=clip_index0, clean_threshold=clean_threshold, pt=False,
         cond=False, u8=box_frames_u8, **(box_kw or {}))
-    if seed is not None:
-        sig, ts = video_schedule if video_schedule is not None else (None, None)
-        r0, sr, keep0, _, out = video_plan.seeded_request(
-            "best_boxes_to_video", image_u8, seed, num_steps=steps[1], num_frames=bbox_frames.shape[1], clip_index0=clip_index0,
-            call=len(guidance), latents=video_latents, sigmas=sig, timesteps=ts, aug_noise=video_aug_noise, frames=frames,
-            frames_u8=frames_u8, **(video_kw or {}))
-        rv, prep = video_plan.prepare(r0, sr)
-        keep_v = (keep0, r0, sr, prep)
-    else:
-        if video_latents is None or video_schedule is None:
-            raise ValueError("best_boxes_to_video: video_latents and video_schedule are needed without seed=")
-        rv, keep_v, _, out = video_plan._checked_request("best_boxes_to_video", image_u8, video_latents, *video_schedule, None, "cond",
-                                                         video_aug_noise, frames, frames_u8, **(video_kw or {}))
+    sv = _video_stage("best_boxes_to_video", video_plan, image_u8, bbox_frames.shape[1], video_latents, video_schedule,
+                      video_aug_noise, frames, frames_u8, video_kw, seed, steps[1], clip_index0, len(guidance))
     q = _lib.BestChainRequest()
-    q.boxes, q.video = qb, rv
-    lib = video_plan._lib
-    need = video_plan._nonzero(lib.ctrlv_pipeline_best_chain_workspace_bytes(boxes_plan._h, video_plan._h, ctypes.byref(q)),
-                               "ctrlv_pipeline_best_chain_workspace_bytes")
-    ws = video_plan._workspace(need)
-    check(lib.ctrlv_pipeline_best_boxes_to_video(boxes_plan._h, video_plan._h, ctypes.byref(q), ws.data_ptr(), ws.numel(),
-                                                 video_plan._stream()), "ctrlv_pipeline_best_boxes_to_video")
-    del keep_b, keep_v
-    return out + (clean, winner, counts)
+    q.boxes, q.video = qb, sv.request
+    video_plan._run("ctrlv_pipeline_best_chain_workspace_bytes", "ctrlv_pipeline_best_boxes_to_video", boxes_plan._h, video_plan._h,
+                    ctypes.byref(q))
+    return sv.out + (clean, winner, counts)
 
 
 def boxes_to_video(boxes_plan, video_plan, image_u8, box_latents, video_latents, box_schedule, video_schedule, bbox_frames,
@@ -757,41 +710,24 @@ def boxes_to_video(boxes_plan, video_plan, image_u8, box_latents, video_latents,
         raise ValueError("boxes_to_video: the two pipeline plans must come from one library (one element type)")
     if bbox_frames is None:
         raise ValueError("boxes_to_video: bbox_frames is None")
-    if seed is not None:
-        steps = tuple(num_steps) if isinstance(num_steps, (tuple, list)) else (num_steps, num_steps)
-        filled = []
-        for call, (pl, lat, schedule, aug, fr, u8, kw) in enumerate((
-                (boxes_plan, box_latents, box_schedule, box_aug_noise, False, False, box_kw),
-                (video_plan, video_latents, video_schedule, video_aug_noise, frames, frames_u8, video_kw))):
-            sig, ts = schedule if schedule is not None else (None, None)
-            r0, sr, keep0, cond, outs = pl.seeded_request(
-                "boxes_to_video", image_u8, seed, num_steps=steps[call], num_frames=bbox_frames.shape[1], clip_index0=clip_index0,
-                call=call, latents=lat, sigmas=sig, timesteps=ts, cond=bbox_frames if call == 0 else None,
-                cond_name="bbox_frames", aug_noise=aug, frames=fr, frames_u8=u8, **(kw or {}))
-            r, prep = pl.prepare(r0, sr)
-            filled.append((r, (keep0, r0, sr, prep), cond, outs))
-        (rb, keep_b, boxes, _), (rv, keep_v, _, out) = filled
-        n, F, H, W = rb.n_clips, rb.num_frames, rb.height, rb.width
-    else:
-        rb, keep_b, boxes, _ = boxes_plan._checked_request("boxes_to_video", image_u8, box_latents, *box_schedule, bbox_frames,
-                                                           "bbox_frames", box_aug_noise, False, False, **(box_kw or {}))
-        rv, keep_v, _, out = video_plan._checked_request("boxes_to_video", image_u8, video_latents, *video_schedule, None, "cond",
-                                                         video_aug_noise, frames, frames_u8, **(video_kw or {}))
-        n, F = box_latents.shape[0], box_latents.shape[1]
-        H, W = image_u8.shape[1], image_u8.shape[2]
-    clean = torch.empty(n, F, 3, H, W, dtype=torch.uint8, device=video_plan.device) if box_frames_u8 else None
+    steps = tuple(num_steps) if isinstance(num_steps, (tuple, list)) else (num_steps, num_steps)
+    sig, ts = box_schedule if box_schedule is not None else (None, None)
+    sb = boxes_plan._stage_request("boxes_to_video", image_u8, seed=seed, prepare=True, num_steps=steps[0],
+                                   num_frames=bbox_frames.shape[1], clip_index0=clip_index0, call=0, latents=box_latents, sigmas=sig,
+                                   timesteps=ts, cond=bbox_frames, cond_name="bbox_frames", aug_noise=box_aug_noise, frames=False,
+                                   frames_u8=False, **(box_kw or {}))
+    sv = _video_stage("boxes_to_video", video_plan, image_u8, bbox_frames.shape[1], video_latents, video_schedule, video_aug_noise,
+                      frames, frames_u8, video_kw, seed, steps[1], clip_index0, 1)
+    rb = sb.request
+    clean = torch.empty(rb.n_clips, rb.num_frames, 3, rb.height, rb.width, dtype=torch.uint8, device=video_plan.device) \
+        if box_frames_u8 else None
     q = _lib.TwoStageRequest()
-    q.boxes, q.video, q.box_cond = rb, rv, boxes_plan.box_condition(boxes, num_cond_frames)
+    q.boxes, q.video, q.box_cond = rb, sv.request, boxes_plan.box_condition(sb.cond, num_cond_frames)
     q.out_box_frames_u8 = clean.data_ptr() if clean is not None else None
     q.clean_threshold = float(clean_threshold)
-    lib = video_plan._lib
-    need = video_plan._nonzero(lib.ctrlv_pipeline_chain_workspace_bytes(boxes_plan._h, video_plan._h, ctypes.byref(q)),
-                               "ctrlv_pipeline_chain_workspace_bytes")
-    ws = video_plan._workspace(need)
-    check(lib.ctrlv_pipeline_boxes_to_video(boxes_plan._h, video_plan._h, ctypes.byref(q), ws.data_ptr(), ws.numel(),
-                                            video_plan._stream()), "ctrlv_pipeline_boxes_to_video")
-    del keep_b, keep_v, boxes
-    return out + (clean,)
+    video_plan._run("ctrlv_pipeline_chain_workspace_bytes", "ctrlv_pipeline_boxes_to_video", boxes_plan._h, video_plan._h,
+                    ctypes.byref(q))
+    return sv.out + (clean,)
 
 
 _VAE_PLANS = {}

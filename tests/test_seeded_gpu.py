@@ -203,9 +203,11 @@ def test_prepared_noise_is_keyed_per_clip_and_the_sizes_add_up(setup):
     s = setup
     pipe, lib = s.pipe, s.pipe._lib
     kw = dict(num_steps=STEPS, num_frames=F, height=H, width=W, cond=s.cond, **KW)
-    r2, s2, keep2, _, _ = pipe.seeded_request("test", s.src, SEED, **kw)
+    keep2 = pipe._stage_request("test", s.src, seed=SEED, **kw)
+    r2, s2 = keep2.request, keep2.seed_request
     f2, ws2 = pipe.prepare(r2, s2)
-    r1, s1, keep1, _, _ = pipe.seeded_request("test", s.src[1:], SEED, clip_index0=1, **dict(kw, cond=s.cond[1:]))
+    keep1 = pipe._stage_request("test", s.src[1:], seed=SEED, clip_index0=1, **dict(kw, cond=s.cond[1:]))
+    r1, s1 = keep1.request, keep1.seed_request
     f1, ws1 = pipe.prepare(r1, s1)
     torch.cuda.synchronize()
     for name, shape in (("latents", (F, 4, H // 8, W // 8)), ("aug_noise", (3, H, W))):

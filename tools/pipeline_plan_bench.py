@@ -273,7 +273,7 @@ SEEDED_SIZES = (((375, 1242), (320, 512)), ((720, 1280), (576, 1024)))
 
 def seeded_main(args):
     """--seeded: what fills a clip request before the loop, per clip.  `prepare`: the source image's bytes go up and
-    ctrlv_pipeline_prepare resizes, draws and tabulates (PipelinePlan.seeded_request + prepare).  `host`: what the pipelines'
+    ctrlv_pipeline_prepare resizes, draws and tabulates (PipelinePlan._stage_request + prepare).  `host`: what the pipelines'
     plan route does today -- PIL's Lanczos resize, the upload, randn_tensor twice with a CPU generator (augmentation noise
     fp32, latents in bf16 times init_noise_sigma, widened), EulerDiscreteScheduler.set_timesteps.  Alternated `--rounds` times
     after one warm call each; host clock around synchronised phases."""
@@ -292,9 +292,9 @@ def seeded_main(args):
 
         def prepare_route():
             image_u8 = torch.from_numpy(src[None]).to(DEV)
-            r, sr, keep, _, _ = pipe.seeded_request("bench", image_u8, 7, num_steps=steps, num_frames=F, height=H, width=W,
-                                                    frames=False, frames_u8=False)
-            return pipe.prepare(r, sr), keep
+            st = pipe._stage_request("bench", image_u8, seed=7, num_steps=steps, num_frames=F, height=H, width=W, frames=False,
+                                     frames_u8=False)
+            return pipe.prepare(st.request, st.seed_request), st
 
         def host_route():
             gen = torch.Generator().manual_seed(7)
