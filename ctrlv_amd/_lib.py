@@ -159,6 +159,21 @@ class BestChainRequest(ctypes.Structure):
     _fields_ = [("boxes", BestBoxesRequest), ("video", ClipRequest), ("reserved", c_int)]
 
 
+class TrainBatchRequest(ctypes.Structure):
+    """Mirror of `ctrlv_train_batch_request` (ctypes clears it: the library requires a cleared struct)."""
+    _fields_ = [
+        ("n_clips", c_int), ("num_frames", c_int), ("height", c_int), ("width", c_int),
+        ("clips", c_void_p), ("box_frames", c_void_p), ("clips_dtype", c_int), ("box_dtype", c_int),
+        ("mode", c_int), ("num_cond_frames", c_int), ("dropout_prob", ctypes.c_double),
+        ("seed", ctypes.c_uint64), ("clip_index0", ctypes.c_uint32), ("call", ctypes.c_uint32),
+        ("sigma_table", c_void_p), ("timestep_table", c_void_p), ("table_size", c_int), ("scaling_factor", c_float),
+        ("clip_mean", c_float * 3), ("clip_std", c_float * 3), ("sample_dtype", c_int), ("reserved", c_int),
+        ("target_latents", c_void_p), ("noisy_latents", c_void_p), ("sample", c_void_p), ("control_cond", c_void_p),
+        ("encoder_hidden_states", c_void_p), ("sigmas", c_void_p), ("timesteps", c_void_p), ("indices", c_void_p),
+        ("random_p", c_void_p), ("noise", c_void_p),
+    ]
+
+
 # name -> (restype, argtypes); lists every symbol include/ctrlv_hip.h declares (tests/test_abi.py checks this)
 SIGNATURES = {
     "ctrlv_abi_version": (c_int, []),
@@ -333,6 +348,15 @@ SIGNATURES = {
     "ctrlv_frame_ssim": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ctrlv_resize_frames_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "ctrlv_resize_frames_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "ctrlv_resize_antialias_clamped": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int,
+                                               ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_void_p]),
+    "ctrlv_train_draws": (c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, c_int, c_void_p, c_void_p, c_int,
+                                  ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ctrlv_train_assemble": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                     c_int, c_int, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, c_void_p, c_void_p, c_int,
+                                     c_void_p, c_void_p]),
+    "ctrlv_train_batch_workspace_bytes": (c_size_t, [c_void_p, c_void_p, ctypes.POINTER(TrainBatchRequest)]),
+    "ctrlv_train_batch_prepare": (c_int, [c_void_p, c_void_p, ctypes.POINTER(TrainBatchRequest), c_void_p, c_size_t, c_void_p]),
 }
 
 _libs = {}                # element dtype code (2 bf16 / 1 fp16) -> CDLL
@@ -347,6 +371,7 @@ _NO_STATUS = {"ctrlv_abi_version", "ctrlv_elem_dtype", "ctrlv_build_id", "ctrlv_
               "ctrlv_pipeline_chain_workspace_bytes", "ctrlv_resize_lanczos_ws_bytes", "ctrlv_pipeline_prepare_bytes",
               "ctrlv_pipeline_seeded_workspace_bytes", "ctrlv_pipeline_best_boxes_workspace_bytes",
               "ctrlv_pipeline_best_chain_workspace_bytes", "ctrlv_frame_ssim_ws_bytes", "ctrlv_resize_frames_ws_bytes",
+              "ctrlv_train_batch_workspace_bytes",
               # a radius, or a negative status
               "ctrlv_boundary_radius"}
 

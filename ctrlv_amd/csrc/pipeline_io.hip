@@ -1,7 +1,8 @@
 // Image pre- / post-processing and classifier-free-guidance assembly of a whole clip (gfx950): what sits between the plan-level
 // calls of StableVideoControlPipeline.__call__ and so far existed only as torch ops in ctrlv_amd/pipelines/pipeline_utils.py.
 //   ctrlv_resize_antialias   _resize_with_antialiasing (Gaussian pre-blur + bicubic, align_corners) fused with the affine steps
-//                            around it: uint8 -> [-1, 1] in front, the CLIP normalisation behind
+//                            around it: uint8 -> [-1, 1] in front, the CLIP normalisation behind (_clamped: with the training
+//                            prologue's clamp to [0, 1] in it)
 //   ctrlv_pixels_prepare     VaeImageProcessor.preprocess + the noise augmentation of prepare_clip
 //   ctrlv_frames_to_u8       VaeImageProcessor.postprocess + numpy_to_pil's (x * 255).round()
 //   ctrlv_randn              counter-based Gaussian noise: Philox4x32-10, fp32 uniforms, Box-Muller (keyed per clip)
@@ -15,6 +16,7 @@
 
 #include <vector>
 
+#include "philox.h"
 #include "pipeline_io.h"
 
 namespace {
@@ -28,16 +30,9 @@ struct ResizeParams {
   float ky[kMaxTaps], kx[kMaxTaps];
   float sy, sx;                  // align_corners source step per output pixel: (in - 1) / (out - 1), 0 for one output pixel
   int th, span_y, span_x;        // output rows per workgroup; rows / columns of the LDS tile (upper bounds of what a tile needs)
-  int src_u8, dst_dtype, normalize;
+  int src_u8, dst_dtype, normalize, clamp;   // clamp: (y + 1) / 2 limited to [0, 1] in the normalising epilogue
   float mean[3], stdv[3];
 };
-
-// fp32 -> element as its OWN rounding: the empty asm keeps the compiler from folding the fp32 operation in front of it into a
-// mixed-precision instruction (v_fma_mixlo_f16 rounds the exact product once; torch rounds to fp32 first, then to fp16)
-__device__ __forceinline__ el_t round_to_el(float v) {
-  asm volatile("" : "+v"(v));
-  return f32_to_el(v);
-}
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 // index of F.pad(mode="reflect") for i in [-(n - 1), 2 (n - 1)]; the clamp only guards the address
@@ -113,7 +108,11 @@ __global__ __launch_bounds__(256) void resize_antialias_kernel(const void* __res
       }
       out += wy[a] * rv;
     }
-    if (P.normalize) out = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(out, 1.0f), 0.5f), P.mean[c]), P.stdv[c]);
+    if (P.normalize) {
+      float u = __fmul_rn(__fadd_rn(out, 1.0f), 0.5f);
+      if (P.clamp) u = u < 0.0f ? 0.0f : (u > 1.0f ? 1.0f : u);          // torch.clamp: a NaN stays
+      out = __fdiv_rn(__fsub_rn(u, P.mean[c]), P.stdv[c]);
+    }
     const long di = (((long)img * 3 + c) * P.h + oy) * P.w + ox;
     if (P.dst_dtype == 0) ((float*)dst)[di] = out;
     else ((el_t*)dst)[di] = round_to_el(out);
@@ -261,30 +260,8 @@ __global__ void decode_input_kernel(const float* __restrict__ x, el_t* __restric
   z[i] = round_to_el(__fmul_rn(el_to_f32(round_to_el(x[i])), inv));
 }
 
-// ---- ctrlv_randn: Philox4x32-10 -> fp32 uniforms -> Box-Muller (the arithmetic is stated in include/ctrlv_hip.h)
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                              uint32_t* x) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {           // the key is bumped between rounds (the bump behind the last one is dead)
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-    c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  x[0] = c0; x[1] = c1; x[2] = c2; x[3] = c3;
-}
-
-// (x + 0.5) / 2^32 rounded ONCE: the 33-bit odd integer 2 x + 1 converted to fp32 (nearest even), times 2^-33 (exact)
-__device__ __forceinline__ float philox_uniform(uint32_t x) { return (float)(2ull * x + 1ull) * 0x1p-33f; }
-
-__device__ __forceinline__ void box_muller(float ua, float ub, float* z) {
-  const float r = sqrtf(-2.0f * logf(ua));
-  float s, c;
-  sincospif(2.0f * ub, &s, &c);
-  z[0] = __fmul_rn(r, c);
-  z[1] = __fmul_rn(r, s);
-}
-
+// ---- ctrlv_randn: Philox4x32-10 -> fp32 uniforms -> Box-Muller (the arithmetic is stated in include/ctrlv_hip.h; the device
+// functions are csrc/philox.h's)
 // One Philox block (four normals) per thread and iteration over (clip, block) pairs.  A block's four elements go out as one
 // 16-byte (fp32) / 8-byte (elements) store where their address allows it -- decided per block from the address, so the values
 // never depend on the alignment --, one by one elsewhere and in the tail block of a per_clip that is no multiple of 4.
@@ -498,8 +475,9 @@ int ctrlv_resize_check(int n, int H, int W, int h, int w) {
   return CTRLV_OK;
 }
 
-extern "C" int ctrlv_resize_antialias(const void* src, int src_u8, int n, int H, int W, void* dst, int dst_dtype, int h, int w,
-                                      const float* mean, const float* std, ctrlv_stream_t stream) {
+// the one launch behind ctrlv_resize_antialias (clamp = 0) and ctrlv_resize_antialias_clamped (clamp = 1)
+static int resize_antialias_launch(const void* src, int src_u8, int n, int H, int W, void* dst, int dst_dtype, int h, int w,
+                                   const float* mean, const float* std, int clamp, ctrlv_stream_t stream) {
   CTRLV_CHECK_ARG(src && dst, "resize_antialias: null pointer");
   CTRLV_CHECK_ARG((mean == nullptr) == (std == nullptr), "resize_antialias: mean and std come together");
   if (dst_dtype != 0 && dst_dtype != CTRLV_ELEM_DTYPE) {
@@ -518,6 +496,7 @@ extern "C" int ctrlv_resize_antialias(const void* src, int src_u8, int n, int H,
   P.src_u8 = src_u8 ? 1 : 0;
   P.dst_dtype = dst_dtype;
   P.normalize = mean ? 1 : 0;
+  P.clamp = clamp;
   for (int c = 0; c < 3; ++c) {
     P.mean[c] = mean ? mean[c] : 0.f;
     P.stdv[c] = std ? std[c] : 1.f;
@@ -537,6 +516,18 @@ extern "C" int ctrlv_resize_antialias(const void* src, int src_u8, int n, int H,
   hipLaunchKernelGGL(resize_antialias_kernel, grid, dim3(256), lds, (hipStream_t)stream, src, dst, P);
   CTRLV_LAUNCH_CHECK();
   return CTRLV_OK;
+}
+
+extern "C" int ctrlv_resize_antialias(const void* src, int src_u8, int n, int H, int W, void* dst, int dst_dtype, int h, int w,
+                                      const float* mean, const float* std, ctrlv_stream_t stream) {
+  return resize_antialias_launch(src, src_u8, n, H, W, dst, dst_dtype, h, w, mean, std, 0, stream);
+}
+
+extern "C" int ctrlv_resize_antialias_clamped(const void* src, int src_u8, int n, int H, int W, void* dst, int dst_dtype, int h,
+                                              int w, const float* mean, const float* std, ctrlv_stream_t stream) {
+  CTRLV_CHECK_ARG(mean != nullptr && std != nullptr, "resize_antialias_clamped: mean and std are required (the clamp belongs to "
+                  "the normalising epilogue)");
+  return resize_antialias_launch(src, src_u8, n, H, W, dst, dst_dtype, h, w, mean, std, 1, stream);
 }
 
 extern "C" int ctrlv_pixels_prepare(const void* image_u8, const float* noise, float strength, int n, int H, int W, void* out,

@@ -852,17 +852,20 @@ def time_conv_rows_to_nchw_bwd(dout, rows, n_frames, clip_frames, C, HW, weight,
     return drows
 
 
-def resize_antialias(image, size, mean=None, std=None, out_dtype=torch.float32):
+def resize_antialias(image, size, mean=None, std=None, out_dtype=torch.float32, clamp=False):
     """`_resize_with_antialiasing(image, size)` (Gaussian pre-blur + bicubic, align_corners) as one kernel
     (ctrlv_resize_antialias).  image: (n, H, W, 3) uint8 -- read as (v / 255) * 2 - 1 -- or (n, 3, H, W) fp32.  mean / std
-    (three floats each): the epilogue ((y + 1) / 2 - mean) / std.  Returns (n, 3, h, w) in fp32 or in an element type (the fp32
-    value rounded once)."""
+    (three floats each): the epilogue ((y + 1) / 2 - mean) / std.  clamp=True (ctrlv_resize_antialias_clamped; needs mean / std):
+    (y + 1) / 2 is limited to [0, 1] first, as the training loops' encode_video_image does.  Returns (n, 3, h, w) in fp32 or in
+    an element type (the fp32 value rounded once)."""
     _need_gpu(image, "image")
     u8 = image.dtype == torch.uint8
     if image.dim() != 4 or (image.shape[3] if u8 else image.shape[1]) != 3 or (not u8 and image.dtype != torch.float32):
         raise ValueError("resize_antialias: image must be (n, H, W, 3) uint8 or (n, 3, H, W) fp32")
     if (mean is None) != (std is None):
         raise ValueError("resize_antialias: mean and std come together")
+    if clamp and mean is None:
+        raise ValueError("resize_antialias: clamp=True belongs to the normalising epilogue (give mean and std)")
     image = image.contiguous()
     n = image.shape[0]
     H, W = (image.shape[1], image.shape[2]) if u8 else (image.shape[2], image.shape[3])
@@ -870,8 +873,9 @@ def resize_antialias(image, size, mean=None, std=None, out_dtype=torch.float32):
     f3 = ctypes.c_float * 3
     m = f3(*[float(v) for v in mean]) if mean is not None else None
     sd = f3(*[float(v) for v in std]) if std is not None else None
-    check(_L(out).ctrlv_resize_antialias(_p(image), 1 if u8 else 0, n, H, W, _p(out), _DT[out_dtype], int(size[0]),
-                                         int(size[1]), m, sd, _stream()), "ctrlv_resize_antialias")
+    symbol = "ctrlv_resize_antialias_clamped" if clamp else "ctrlv_resize_antialias"
+    check(getattr(_L(out), symbol)(_p(image), 1 if u8 else 0, n, H, W, _p(out), _DT[out_dtype], int(size[0]), int(size[1]), m, sd,
+                                   _stream()), symbol)
     return out
 
 
@@ -1036,6 +1040,60 @@ def randn(seed, shape, *, clip0=0, call=0, stream_id=0, scale=1.0, round_el=Fals
     check(_lib.load(el).ctrlv_randn(int(seed) & 0xFFFFFFFFFFFFFFFF, int(clip0), int(call), int(stream_id), shape[0], per,
                                     float(scale), 1 if round_el else 0, _p(out), _DT[dtype], _stream()), "ctrlv_randn")
     return out
+
+
+def train_draws(seed, n_clips, sigma_table, timestep_table, *, clip0=0, call=0, dropout_prob=None, el=None):
+    """The per-clip draws of a training step (ctrlv_train_draws): one Philox block per clip, keyed on (seed, clip0 + i, call).
+    sigma_table / timestep_table: fp32 [T] on the device (EulerDiscreteScheduler().sigmas[:T] and .timesteps).  Returns a dict
+    of device tensors of n_clips entries: indices (int32), sigmas, timesteps, random_p, prompt_keep, image_mask (fp32; the masks
+    are 0 or 1, all ones for dropout_prob=None).  el: the element type whose library runs it (both export it; default bf16).  No
+    host sync."""
+    fn = "train_draws"
+    _need_gpu(sigma_table, "sigma_table")
+    T = sigma_table.numel()
+    for name, t in (("sigma_table", sigma_table), ("timestep_table", timestep_table)):
+        if t.dtype != torch.float32 or t.dim() != 1 or t.numel() != T or t.device != sigma_table.device:
+            raise ValueError(f"{fn}: {name} must be fp32 ({T},) on {sigma_table.device}")
+    _need_dense(fn, sigma_table=sigma_table, timestep_table=timestep_table)
+    n, dev = int(n_clips), sigma_table.device
+    out = {k: torch.empty(max(n, 0), dtype=torch.int32 if k == "indices" else torch.float32, device=dev)
+           for k in ("indices", "sigmas", "timesteps", "random_p", "prompt_keep", "image_mask")}
+    check(_lib.load(el).ctrlv_train_draws(int(seed) & 0xFFFFFFFFFFFFFFFF, int(clip0), int(call), n, _p(sigma_table),
+                                          _p(timestep_table), T, -1.0 if dropout_prob is None else float(dropout_prob),
+                                          *[_p(t) for t in out.values()], _stream()), "ctrlv_train_draws")
+    return out
+
+
+def train_assemble(target, sigmas, cond_image, *, noise=None, image_mask=None, cond_frames=None, layout=0, num_cond_frames=0,
+                   seed=0, clip0=0, call=0, sample_dtype=torch.bfloat16, return_noise=False, el=None):
+    """One pass over the latents of a batch (ctrlv_train_assemble).  target fp32 (n, F, L, h, w): the clean, scaled latents;
+    noise the same, or None: drawn in the kernel as `randn(seed, target.shape, clip0=, call=, stream_id=3)`; sigmas, image_mask
+    fp32 (n); cond_image fp32 (n, L, h, w); cond_frames fp32 like target (layout 1: frames [0, num_cond_frames) and F - 1 of the
+    conditioning channels come from it).  Returns (noisy fp32, sample (n, F, 2 L, h, w) of sample_dtype -- fp32 or an element
+    type --, noise_out or None): noisy = target + noise * sigma, sample = [noisy / sqrt(sigma^2 + 1) | image_mask * c], every
+    operation rounded on its own.  el: the library that serves an fp32 sample (default bf16's).  Tensors are taken as they are (any
+    element alignment); no host sync."""
+    fn = "train_assemble"
+    _need_gpu(target, "target")
+    if target.dim() != 5 or target.dtype != torch.float32:
+        raise ValueError(f"{fn}: target must be fp32 (n, F, L, h, w)")
+    n, F, L, h, w = target.shape
+    dev = target.device
+    for name, t, shape in (("noise", noise, (n, F, L, h, w)), ("sigmas", sigmas, (n,)), ("image_mask", image_mask, (n,)),
+                           ("cond_frames", cond_frames, (n, F, L, h, w)), ("cond_image", cond_image, (n, L, h, w))):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shape or t.device != dev):
+            raise ValueError(f"{fn}: {name} must be fp32 {shape} on {dev}")
+    if sample_dtype not in _DT:
+        raise ValueError(f"{fn}: sample_dtype {sample_dtype} (fp32, fp16 or bf16)")
+    _need_dense(fn, target=target, noise=noise, sigmas=sigmas, image_mask=image_mask, cond_frames=cond_frames, cond_image=cond_image)
+    noisy = torch.empty_like(target)
+    sample = torch.empty(n, F, 2 * L, h, w, dtype=sample_dtype, device=dev)
+    noise_out = torch.empty_like(target) if return_noise else None
+    lib = _lib.load(el) if sample_dtype == torch.float32 else _L(sample)
+    check(lib.ctrlv_train_assemble(_p(target), _p(noise), _p(sigmas), _p(image_mask), _p(cond_frames), _p(cond_image), int(layout),
+                                   int(num_cond_frames), n, F, L, h, w, int(seed) & 0xFFFFFFFFFFFFFFFF, int(clip0), int(call),
+                                   _p(noisy), _p(sample), _DT[sample_dtype], _p(noise_out), _stream()), "ctrlv_train_assemble")
+    return noisy, sample, noise_out
 
 
 def resize_lanczos_u8(image_u8, h, w, out=None, workspace=None):

@@ -328,24 +328,27 @@ class VaePlan(_Handle):
         if (t.device.index or 0) != (self.device.index or 0):
             raise ValueError(f"VaePlan.{what}: input on {t.device}, the plan's weights on {self.device}")
 
-    def encode(self, x, noise=None, scale=1.0, moments=True, workspace=None):
+    def encode(self, x, noise=None, scale=1.0, moments=True, workspace=None, out_dtype=None):
         """x (n, 3, H, W) in [-1, 1] -> (latents, moments): latents (n, L, H/8, W/8) = scale * (mean + std * noise) -- noise
         fp32 (n, L, H/8, W/8), None = the distribution's mode --, moments (n, 2 L, H/8, W/8) after quant_conv (or None).  Both
-        in x.dtype, enqueued on torch's current stream."""
+        in out_dtype (default x.dtype), enqueued on torch's current stream."""
         self._check(x, "encode")
         x = x.contiguous()
         n, _, H, W = x.shape
         L = self._cfg.latent_channels
         ws = self.workspace("encode", n, 1, H, W) if workspace is None else workspace
-        lat = torch.empty(n, L, H // 8, W // 8, dtype=x.dtype, device=x.device)
-        mom = torch.empty(n, 2 * L, H // 8, W // 8, dtype=x.dtype, device=x.device) if moments else None
+        out_dtype = x.dtype if out_dtype is None else out_dtype
+        if out_dtype not in _DT:
+            raise ValueError(f"VaePlan.encode: out_dtype {out_dtype} (fp32, fp16 or bf16)")
+        lat = torch.empty(n, L, H // 8, W // 8, dtype=out_dtype, device=x.device)
+        mom = torch.empty(n, 2 * L, H // 8, W // 8, dtype=out_dtype, device=x.device) if moments else None
         if noise is not None:
             noise = noise.to(device=x.device, dtype=torch.float32).contiguous()
             if noise.shape != lat.shape:
                 raise ValueError(f"VaePlan.encode: noise {tuple(noise.shape)} must be {tuple(lat.shape)}")
         check(self._lib.ctrlv_vae_encode(self._h, x.data_ptr(), _DT[x.dtype], n, H, W,
                                          noise.data_ptr() if noise is not None else None, float(scale), lat.data_ptr(),
-                                         mom.data_ptr() if moments else None, _DT[x.dtype], ws.data_ptr(), ws.numel(),
+                                         mom.data_ptr() if moments else None, _DT[out_dtype], ws.data_ptr(), ws.numel(),
                                          self._stream()), "ctrlv_vae_encode")
         return lat, mom
 
@@ -728,6 +731,116 @@ def boxes_to_video(boxes_plan, video_plan, image_u8, box_latents, video_latents,
     video_plan._run("ctrlv_pipeline_chain_workspace_bytes", "ctrlv_pipeline_boxes_to_video", boxes_plan._h, video_plan._h,
                     ctypes.byref(q))
     return sv.out + (clean,)
+
+
+TRAIN_MODES = {"controlnet": 0, "unet": 1, "boxes": 2}
+
+
+class TrainBatchPlan:
+    """A training batch as one C call (include/ctrlv_hip.h: ctrlv_train_batch_prepare) on a borrowed `VaePlan` and `ClipPlan`
+    of ONE library: pixels plus (seed, step, clip index) in, what `train_step` / `unet_train_step` read out.  The object keeps
+    the plans alive and holds the scheduler's two tables on the device."""
+
+    def __init__(self, vae_plan, clip_plan, sigma_table=None, timestep_table=None):
+        """sigma_table / timestep_table: fp32 [T]; default `EulerDiscreteScheduler().sigmas[:-1]` and `.timesteps` as __init__
+        builds them (the 1000 training entries: the lookup is the reference's get_sigmas)."""
+        if vae_plan._lib is not clip_plan._lib:
+            raise ValueError("TrainBatchPlan: the two plans must come from one library (one element type)")
+        self.vae, self.clip = vae_plan, clip_plan
+        self.dtype, self.device, self._lib = vae_plan.dtype, vae_plan.device, vae_plan._lib
+        if (sigma_table is None) != (timestep_table is None):
+            raise ValueError("TrainBatchPlan: sigma_table and timestep_table come together")
+        if sigma_table is None:
+            from .schedulers import EulerDiscreteScheduler
+            sched = EulerDiscreteScheduler()
+            sigma_table, timestep_table = sched.sigmas[:-1], sched.timesteps
+        self.sigma_table = sigma_table.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        self.timestep_table = timestep_table.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        if self.sigma_table.dim() != 1 or self.sigma_table.shape != self.timestep_table.shape:
+            raise ValueError("TrainBatchPlan: the tables must be one-dimensional and of one length")
+        self._ws = None
+
+    @staticmethod
+    def _mode(mode):
+        if isinstance(mode, str) and mode not in TRAIN_MODES:
+            raise ValueError(f"TrainBatchPlan: mode {mode!r} (one of {', '.join(TRAIN_MODES)}, or the library's code 0 .. 2)")
+        return TRAIN_MODES[mode] if isinstance(mode, str) else int(mode)
+
+    def request(self, clips, box_frames, out, *, mode, seed, step, num_cond_frames=0, dropout_prob=None, scaling_factor=0.0,
+                clip_mean=None, clip_std=None):
+        """The `ctrlv_train_batch_request` of a call; `out`: name -> output tensor.  Keep the tensors alive beside it."""
+        n, F, _, H, W = clips.shape
+        r = _lib.TrainBatchRequest()
+        r.n_clips, r.num_frames, r.height, r.width = n, F, H, W
+        r.clips, r.clips_dtype = clips.data_ptr(), _DT[clips.dtype]
+        if box_frames is not None:
+            r.box_frames, r.box_dtype = box_frames.data_ptr(), _DT[box_frames.dtype]
+        r.mode = self._mode(mode)
+        r.num_cond_frames = int(num_cond_frames)
+        r.dropout_prob = -1.0 if dropout_prob is None else float(dropout_prob)
+        r.seed, r.clip_index0, r.call = seed.seed, seed.clip_index0, int(step) & 0xFFFFFFFF
+        r.sigma_table, r.timestep_table = self.sigma_table.data_ptr(), self.timestep_table.data_ptr()
+        r.table_size = self.sigma_table.numel()
+        r.scaling_factor = float(scaling_factor)
+        if clip_mean is not None:
+            for i in range(3):
+                r.clip_mean[i], r.clip_std[i] = float(clip_mean[i]), float(clip_std[i])
+        for name, t in out.items():
+            if name == "sample":
+                r.sample_dtype = _DT[t.dtype]
+            setattr(r, name, t.data_ptr())
+        return r
+
+    def workspace_bytes(self, request):
+        n = self._lib.ctrlv_train_batch_workspace_bytes(self.vae._h, self.clip._h, ctypes.byref(request))
+        if n == 0:
+            check(-2, "ctrlv_train_batch_workspace_bytes", lib=self._lib)
+        return n
+
+    def prepare(self, clips, box_frames=None, *, mode, seed, step, num_cond_frames=0, dropout_prob=None, scaling_factor=0.0,
+                clip_mean=None, clip_std=None, sample_dtype=None, return_noise=False):
+        """clips / box_frames (n, F, 3, H, W) pixels in [-1, 1] (fp32, fp16 or bf16) on the plans' device; mode "controlnet"
+        (box_frames become control_cond), "unet" (no box_frames) or "boxes" (the box predictor: box_frames are the target, frames
+        [0, num_cond_frames) and F - 1 condition on them); seed: a `DeviceSeed`; step: the optimisation step.  Returns a dict of
+        device tensors: target_latents, noisy_latents (fp32 (n, F, L, h, w)), sample ((n, F, 2 L, h, w) of sample_dtype, default
+        the plans' element type), control_cond (fp32, mode "controlnet"), encoder_hidden_states ((n, 1, D) elements), sigmas,
+        timesteps, random_p (fp32 (n)), indices (int32 (n)) and, with return_noise, noise.  Clip i's values depend on (seed.seed,
+        seed.clip_index0 + i, step) only.  Enqueued on torch's current stream; no host sync."""
+        who = "TrainBatchPlan.prepare"
+        dev = self.device
+        for name, t in (("clips", clips), ("box_frames", box_frames)):
+            if t is None:
+                continue
+            if t.dim() != 5 or t.shape[2] != 3 or t.dtype not in _DT:
+                raise ValueError(f"{who}: {name} must be (n, F, 3, H, W) fp32 / fp16 / bf16")
+            if not t.is_cuda or (t.device.index or 0) != (dev.index or 0):
+                raise ValueError(f"{who}: {name} on {t.device}, the plans' weights on {dev}")
+        if box_frames is not None and box_frames.shape != clips.shape:
+            raise ValueError(f"{who}: box_frames {tuple(box_frames.shape)} must have the shape of clips {tuple(clips.shape)}")
+        clips = clips.contiguous()
+        box_frames = box_frames.contiguous() if box_frames is not None else None
+        n, F, _, H, W = clips.shape
+        L, D = self.vae._cfg.latent_channels, self.clip._cfg.projection_dim
+        lat = (n, F, L, H // 8, W // 8)
+        f32 = dict(dtype=torch.float32, device=dev)
+        out = {"target_latents": torch.empty(lat, **f32), "noisy_latents": torch.empty(lat, **f32),
+               "sample": torch.empty(n, F, 2 * L, H // 8, W // 8, dtype=sample_dtype or self.dtype, device=dev),
+               "encoder_hidden_states": torch.empty(n, 1, D, dtype=self.dtype, device=dev),
+               "sigmas": torch.empty(n, **f32), "timesteps": torch.empty(n, **f32),
+               "indices": torch.empty(n, dtype=torch.int32, device=dev), "random_p": torch.empty(n, **f32)}
+        if self._mode(mode) == 0:
+            out["control_cond"] = torch.empty(lat, **f32)
+        if return_noise:
+            out["noise"] = torch.empty(lat, **f32)
+        r = self.request(clips, box_frames, out, mode=mode, seed=seed, step=step, num_cond_frames=num_cond_frames,
+                         dropout_prob=dropout_prob, scaling_factor=scaling_factor, clip_mean=clip_mean, clip_std=clip_std)
+        need = self.workspace_bytes(r)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        check(self._lib.ctrlv_train_batch_prepare(self.vae._h, self.clip._h, ctypes.byref(r), self._ws.data_ptr(), self._ws.numel(),
+                                                  stream), "ctrlv_train_batch_prepare")
+        return out
 
 
 _VAE_PLANS = {}

@@ -294,7 +294,12 @@ def unet_train_step(unet, batch, optimizer=None, world_size=1, buckets=None, acc
 
 def _noised_inputs(batch):
     """EDM noising of a batch (train_video_controlnet.py:404-410, train_video_diffusion.py:519-527): (clean latents,
-    sigmas, noisy latents, continuous timesteps 0.25 ln sigma, bf16 model input = [scaled noisy | image latents])."""
+    sigmas, noisy latents, continuous timesteps 0.25 ln sigma, bf16 model input = [scaled noisy | image latents]).  A batch
+    from `prepare_batch` carries noisy_latents / sample / timesteps already (ctrlv_train_assemble wrote them, the timesteps
+    are the scheduler's table entries): they are used as they are."""
+    if "noisy_latents" in batch and "sample" in batch and "timesteps" in batch:
+        return (batch["latents"].float(), batch["sigmas"].float(), batch["noisy_latents"].float(), batch["timesteps"].float(),
+                batch["sample"].to(torch.bfloat16))
     lat, noise, sig = batch["latents"].float(), batch["noise"].float(), batch["sigmas"].float()
     B = lat.shape[0]
     s5 = sig.reshape(B, 1, 1, 1, 1)
@@ -303,6 +308,29 @@ def _noised_inputs(batch):
     timesteps = 0.25 * torch.log(sig)                                           # continuous timestep of sigma
     sample = torch.cat([inp, batch["image_latents"].float()], dim=2).to(torch.bfloat16)
     return lat, sig, noisy, timesteps, sample
+
+
+def prepare_batch(plan, clips, box_frames=None, *, mode, seed, step, num_cond_frames=0, dropout_prob=None, fps=7,
+                  motion_bucket_id=127, noise_aug_strength=0.02, return_noise=False):
+    """A data-loader batch -> the dict `train_step` (mode "controlnet") / `unet_train_step` (modes "unet" and "boxes") take,
+    in one library call (plan: a `ctrlv_amd.plan.TrainBatchPlan`; tools/train_video_controlnet.py:366-449,
+    tools/train_video_diffusion.py:428-514): CLIP on the clamped first frame, the VAE posterior samples, the draws into the
+    scheduler's tables, the noising, both conditioning-dropout masks, the frame layout and the channel concat, all keyed on
+    (seed: a `DeviceSeed`, step, clip index).  clips / box_frames: (n, F, 3, H, W) pixels in [-1, 1] on the plan's device.  The
+    dict carries noisy_latents / sample / timesteps, which `_noised_inputs` then takes as they are; added_time_ids is
+    [fps - 1, motion_bucket_id, noise_aug_strength] per clip, as the reference's get_add_time_ids (the one upload of the call; nothing is read back)."""
+    out = plan.prepare(clips, box_frames, mode=mode, seed=seed, step=step, num_cond_frames=num_cond_frames,
+                       dropout_prob=dropout_prob, return_noise=return_noise)
+    n = clips.shape[0]
+    batch = {"latents": out["target_latents"], "sigmas": out["sigmas"], "noisy_latents": out["noisy_latents"],
+             "sample": out["sample"], "timesteps": out["timesteps"], "encoder_hidden_states": out["encoder_hidden_states"],
+             "added_time_ids": torch.tensor([[float(fps - 1), float(motion_bucket_id), float(noise_aug_strength)]],
+                                            dtype=torch.float32).repeat(n, 1).to(clips.device, non_blocking=True),
+             "indices": out["indices"], "random_p": out["random_p"]}
+    for k in ("control_cond", "noise"):
+        if k in out:
+            batch[k] = out[k]
+    return batch
 
 
 def _backward_and_step(model, loss, optimizer, world_size, buckets, accumulate, loss_scale):

@@ -1187,6 +1187,116 @@ size_t ctrlv_resize_frames_ws_bytes(int planes, int H, int W, int h, int w, int 
 int ctrlv_resize_frames_u8(const void* src_u8, int planes, int H, int W, void* dst_u8, int h, int w, int filter, void* ws,
                            size_t ws_bytes, ctrlv_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Training batches: what the reference's training loops do between a data-loader batch and their model call
+ * (tools/train_video_controlnet.py:366-449, tools/train_video_diffusion.py:428-514) -- the clamped CLIP prologue, the VAE
+ * posterior samples, the per-clip draws into the scheduler's tables, the noising, the conditioning dropout, the box predictor's
+ * frame layout and the channel concat -- as library calls (csrc/train_batch.hip, csrc/train_batch_plan.hip).  Pixels plus
+ * (seed, step, clip index) go in, what train_step reads comes out.  Additive entry points: the ABI number does not change, the
+ * existing structs keep their layouts, the existing entry points their bits.  The arithmetic stated here is the contract:
+ * tests/train_batch_ref.py restates it in numpy on top of tests/seeded_ref.py.
+ * ------------------------------------------------------------------------------------------------------------------ */
+/* ctrlv_resize_antialias with encode_video_image's clamp (utils/util.py:97-125) in the normalising epilogue:
+ * (min(max((y + 1) * 0.5, 0), 1) - mean[c]) / std[c]; a NaN stays a NaN, as with torch.clamp.  The same kernel: the clamp is one
+ * runtime branch, and where nothing clamps the bits are ctrlv_resize_antialias'.  mean / std are required here
+ * (CTRLV_E_BAD_ARG). */
+int ctrlv_resize_antialias_clamped(const void* src, int src_u8, int n, int H, int W, void* dst, int dst_dtype, int h, int w,
+                                   const float* mean, const float* std, ctrlv_stream_t stream);
+/* The per-clip draws of a training step.  One Philox4x32-10 block per clip (the key and rounds of ctrlv_randn): counter
+ * (0, call, 2, clip0 + i) under the key (seed & 0xffffffff, seed >> 32) -> x0 .. x3.  sigma_table / timestep_table: DEVICE fp32
+ * [T], 1 <= T <= 65536 (EulerDiscreteScheduler().sigmas[:T] and .timesteps as __init__ builds them: the lookup is then the
+ * reference's get_sigmas).  Outputs, DEVICE arrays of n_clips entries, any of them may be NULL:
+ *   indices[i]     (int32) = (uint64(x0) * T) >> 32: in [0, T), the multiply-shift form of randint
+ *   sigmas[i]      = sigma_table[indices[i]];  timesteps[i] = timestep_table[indices[i]]
+ *   random_p[i]    = ctrlv_randn's uniform rule applied to x1 (in [2^-33, 1])
+ *   prompt_keep[i] = !(p < t2);  image_mask[i] = 1 - (p >= t1) * (p < t3)        (fp32: 0 or 1)
+ * with t1 = (float) dropout_prob, t2 = (float) (2.0 * dropout_prob), t3 = (float) (3.0 * dropout_prob): the products formed in
+ * double and rounded once, torch's rule for an fp32 tensor compared with a Python scalar.  dropout_prob < 0 switches both masks
+ * off (all ones: conditioning_dropout_prob=None).  One thread per clip, no atomics: clip i's values depend on (seed, clip0 + i,
+ * call) only.  CTRLV_E_BAD_ARG: a NULL table, a dropout_prob that is not finite; CTRLV_E_BAD_SHAPE: T or n_clips (1 .. 65536)
+ * out of range. */
+int ctrlv_train_draws(uint64_t seed, uint32_t clip0, uint32_t call, int n_clips, const float* sigma_table,
+                      const float* timestep_table, int T, double dropout_prob, int32_t* indices, float* sigmas, float* timesteps,
+                      float* random_p, float* prompt_keep, float* image_mask, ctrlv_stream_t stream);
+/* One pass over the latents of a batch: the noising, the model input and the conditioning channels.  All tensors DEVICE,
+ * contiguous; plane = L h w, per_clip = F plane.
+ *   target      fp32 (n, F, L, h, w): the clean latents, already scaled.  L <= 8, F <= 32
+ *   noise       fp32 of the same shape, or NULL: the noise is then drawn in the kernel by ctrlv_randn's contract -- (seed,
+ *               clip0 + i, call), stream_id 3, scale 1, round_dtype 0, per_clip as above -- and the outputs have the bits of
+ *               ctrlv_randn followed by this call with that noise.  seed / clip0 / call are ignored when noise is given
+ *   sigmas      fp32 (n);  image_mask fp32 (n) or NULL (all ones)
+ *   cond_image  fp32 (n, L, h, w);  cond_frames fp32 (n, F, L, h, w), required for layout 1 and ignored for layout 0
+ *   layout      0 (Box2Video, plain stage 1): c = cond_image for every frame;  1 (box predictor, train_video_diffusion.py:457-458):
+ *               c = cond_frames for f < K or f == F - 1, cond_image otherwise.  0 <= K <= F
+ *   noisy       fp32 (n, F, L, h, w) = target + noise * sigma
+ *   sample      (n, F, 2 L, h, w), sample_dtype 0 fp32 or the library's element code:
+ *               sample[:, :, :L] = rne(noisy / sqrtf(sigma * sigma + 1)),  sample[:, :, L:] = rne(image_mask * c)
+ *   noise_out   fp32 (n, F, L, h, w) or NULL: the noise that was used
+ * Every operation is rounded on its own in fp32 (no contraction), division and square root correctly rounded: the bits of the
+ * eager torch expressions of ctrlv_amd.training._noised_inputs.  One thread per four consecutive elements of a clip (one Philox
+ * block): 16-byte accesses (8 for a 16-bit sample) when plane is a multiple of 4 and every pointer is 16-byte aligned, element by
+ * element otherwise and in the tail of a per_clip that is no multiple of 4.  No atomics; a clip's bits depend neither on the
+ * batch, nor on the grid, nor on which of the two paths ran.  noisy / sample / noise_out must not overlap the inputs. */
+int ctrlv_train_assemble(const float* target, const float* noise, const float* sigmas, const float* image_mask,
+                         const float* cond_frames, const float* cond_image, int layout, int K, int n, int F, int L, int h, int w,
+                         uint64_t seed, uint32_t clip0, uint32_t call, float* noisy, void* sample, int sample_dtype,
+                         float* noise_out, ctrlv_stream_t stream);
+
+/* One training batch.  Clear the struct before setting fields.  Device pointers; h = height / 8, w = width / 8, L = the VAE's
+ * latent channels, D = the CLIP plan's projection_dim. */
+typedef struct ctrlv_train_batch_request {
+  int32_t n_clips, num_frames, height, width;   /* clips (<= 4096), frames per clip (<= 32), pixels (what the VAE plan takes) */
+  const void* clips;             /* (n, F, 3, H, W) pixels in [-1, 1] */
+  const void* box_frames;        /* the same shape: required for modes 0 and 2, NULL for mode 1 */
+  int32_t clips_dtype, box_dtype;      /* dtype codes (0 fp32, 1 fp16, 2 bf16) */
+  int32_t mode;                  /* 0 ControlNet step, 1 stage-1 UNet step, 2 box-predictor step */
+  int32_t num_cond_frames;       /* K of mode 2, 0 <= K <= F (the other modes ignore it) */
+  double dropout_prob;           /* conditioning_dropout_prob; negative: none */
+  uint64_t seed;
+  uint32_t clip_index0;          /* clip i draws as clip clip_index0 + i */
+  uint32_t call;                 /* the optimisation step */
+  const float* sigma_table;      /* DEVICE fp32 [table_size] */
+  const float* timestep_table;
+  int32_t table_size;            /* T, 1 .. 65536 */
+  float scaling_factor;          /* of the target latents; 0: the VAE plan's */
+  float clip_mean[3], clip_std[3];     /* all six zero = CLIP's own values */
+  int32_t sample_dtype;          /* 0 fp32, or the library's element code */
+  int32_t reserved;              /* must be 0 */
+  float* target_latents;         /* fp32 (n, F, L, h, w) */
+  float* noisy_latents;          /* fp32 (n, F, L, h, w) */
+  void* sample;                  /* (n, F, 2 L, h, w) of sample_dtype */
+  float* control_cond;           /* fp32 (n, F, L, h, w): mode 0 only (required there, NULL elsewhere) */
+  void* encoder_hidden_states;   /* (n, 1, D) elements */
+  float* sigmas;                 /* fp32 (n) */
+  float* timesteps;              /* fp32 (n) */
+  int32_t* indices;              /* int32 (n) */
+  float* random_p;               /* fp32 (n) */
+  float* noise;                  /* fp32 (n, F, L, h, w), or NULL */
+} ctrlv_train_batch_request;
+/* Bytes of workspace ctrlv_train_batch_prepare needs for `r`; 0 for a request the call would refuse, or plans without weights
+ * (ctrlv_last_error). */
+size_t ctrlv_train_batch_workspace_bytes(ctrlv_vae_plan* vae, ctrlv_clip_plan* clip, const ctrlv_train_batch_request* r);
+/* The batch, enqueued on `stream` in this order (img = clips[:, 0] as fp32 (n, 3, H, W), one gather kernel in front):
+ *   1. ctrlv_resize_antialias_clamped of img to the CLIP plan's image_size in the element type, ctrlv_clip_forward
+ *   2. ctrlv_train_draws(seed, clip_index0, call) into indices / sigmas / timesteps / random_p
+ *   3. encoder_hidden_states = rne_el(prompt_keep * embeds)
+ *   4. / 5. per encoded tensor, ctrlv_randn(seed, clip_index0, call, stream_id, n, per_clip = its latents per clip, scale 1,
+ *      round_dtype 0, fp32) as the `noise` of one ctrlv_vae_encode with fp32 latents out:
+ *        mode 0: target = clips (stream 4, scale scaling_factor), image = img (5, scale 1), control_cond = box_frames (6, scale 1)
+ *        mode 1: target and image as in mode 0
+ *        mode 2: cond_frames = box_frames (stream 4, scale 1) -- encoded once, as the reference reuses one sample
+ *                (train_video_diffusion.py:442-460) --, target = cond_frames * scaling_factor (one fp32 multiply), image as above
+ *   6. ctrlv_train_assemble with in-kernel noise (stream 3): layout 0, or for mode 2 layout 1 with K = num_cond_frames
+ * No host synchronisation and no host-device copy after the first launch.  Every field and size is refused by name on the host
+ * before the first launch: reserved != 0, a mode outside 0 .. 2, NULL tables or table_size outside 1 .. 65536, num_cond_frames
+ * outside [0, F], box_frames missing (modes 0, 2) or set (mode 1), control_cond missing (mode 0) or set, NULL outputs, dtype codes,
+ * a geometry the VAE or the resize refuses, plans on two devices or with other than 3 image channels; `ws` (256-byte aligned, caller-owned) too small:
+ * CTRLV_E_WORKSPACE -- against the driver's own buffers first (host arithmetic on the plans' configurations), then against
+ * ctrlv_train_batch_workspace_bytes (plans with weights).  The bits are those of the calls made by hand.  The CLIP phase and the
+ * VAE phase alias one region of the workspace.  The plans are borrowed; not thread-safe on one pair of plans. */
+int ctrlv_train_batch_prepare(ctrlv_vae_plan* vae, ctrlv_clip_plan* clip, const ctrlv_train_batch_request* r, void* ws,
+                              size_t ws_bytes, ctrlv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
