@@ -55,7 +55,7 @@ class ProfileRecord(ctypes.Structure):
 
 
 FAMILIES = ("gemm_linear", "gemm_conv3x3", "gemm_conv_temporal", "attention_spatial", "attention_temporal", "groupnorm",
-            "layernorm", "residual_add", "gemm_temporal_block")
+            "layernorm", "residual_add", "gemm_temporal_block", "gemm_spatial_entry")
 
 
 class TemporalFusedDesc(ctypes.Structure):
@@ -67,6 +67,20 @@ class TemporalFusedDesc(ctypes.Structure):
         ("out", c_void_p), ("out_lo", c_void_p), ("ldo", c_int),
         ("B", c_int), ("F", c_int), ("S", c_int), ("C", c_int),
         ("ln_gamma", c_void_p), ("ln_beta", c_void_p), ("ln_eps", c_float),
+    ]
+
+
+class SpatialEntryDesc(ctypes.Structure):
+    """Mirror of `ctrlv_spatial_entry_desc`."""
+    _fields_ = [
+        ("x", c_void_p), ("x_lo", c_void_p), ("ldx", c_int), ("wf", c_void_p),
+        ("bias_in", c_void_p), ("bias_qkv", c_void_p), ("stats", c_void_p),
+        ("gn_gamma", c_void_p), ("gn_beta", c_void_p),
+        ("ln_gamma", c_void_p), ("ln_beta", c_void_p), ("ln_eps", c_float),
+        ("h0", c_void_p), ("h0_lo", c_void_p), ("ldh", c_int),
+        ("qkv", c_void_p), ("ldq", c_int),
+        ("n_img", c_int), ("S", c_int), ("C", c_int), ("head_dim", c_int),
+        ("q_scale", c_float),
     ]
 
 
@@ -222,6 +236,11 @@ SIGNATURES = {
     "ctrlv_temporal_fused_pack": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "ctrlv_temporal_fused": (c_int, [ctypes.POINTER(TemporalFusedDesc), c_void_p]),
     "ctrlv_temporal_fused_serves": (c_int, [ctypes.POINTER(TemporalFusedDesc)]),
+    "ctrlv_spatial_entry_fused_weight_bytes": (c_size_t, []),
+    "ctrlv_spatial_entry_fused_pack": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "ctrlv_spatial_entry_fused": (c_int, [ctypes.POINTER(SpatialEntryDesc), c_void_p]),
+    "ctrlv_spatial_entry_fused_serves": (c_int, [ctypes.POINTER(SpatialEntryDesc)]),
+    "ctrlv_groupnorm_finalize": (c_int, [c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     "ctrlv_attention_spatial": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ctrlv_attention_spatial_prescaled": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ctrlv_attention_temporal": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
@@ -364,7 +383,7 @@ _tls = threading.local()  # .failed = the library whose call returned a negative
 # c_int-returning entry points whose value is NOT a status code
 _NO_STATUS = {"ctrlv_abi_version", "ctrlv_elem_dtype", "ctrlv_build_id", "ctrlv_last_error", "ctrlv_ff_fused_w1f_bytes",
               "ctrlv_gemm_gn_partials_serves", "ctrlv_gemm_up_phase_serves", "ctrlv_ff_fused_serves", "ctrlv_plan_num_down_residuals",
-              "ctrlv_temporal_fused_serves", "ctrlv_gemm_f8_serves",
+              "ctrlv_temporal_fused_serves", "ctrlv_gemm_f8_serves", "ctrlv_spatial_entry_fused_serves",
               # size queries (size_t: never wrapped, listed with their kin for the reader)
               "ctrlv_gemm_tokens_ws_bytes", "ctrlv_clip_plan_workspace_bytes", "ctrlv_vae_plan_workspace_bytes",
               "ctrlv_pipeline_workspace_bytes", "ctrlv_pipeline_boxes_workspace_bytes", "ctrlv_box_frames_post_ws_bytes",

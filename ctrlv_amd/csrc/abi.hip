@@ -41,6 +41,7 @@ const ctrlv_debug_t& ctrlv_debug() {
     d.wgrad_pp = env("CTRLV_WGRAD_PP", 1);
     d.wgrad_slabs = env("CTRLV_WGRAD_SLABS", 0);
     d.up_phase = env("CTRLV_UP_PHASE", 1);
+    d.spatial_entry = env("CTRLV_SPATIAL_ENTRY", 1);
     return d;
   }();
   return dbg;

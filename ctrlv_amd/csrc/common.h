@@ -352,6 +352,7 @@ struct ctrlv_debug_t {
   int wgrad_pp;     // CTRLV_WGRAD_PP [1]     0: every weight gradient on the register-staged kernel of backward.hip
   int wgrad_slabs;  // CTRLV_WGRAD_SLABS [0]  n > 0: that many row slabs per wgrad_pp launch (tools/wgrad_bench.py sweeps)
   int up_phase;     // CTRLV_UP_PHASE [1]     0: the upsampler convs as a 3x3 gather over the upsampled grid (up = 1), not as four 2x2 phases
+  int spatial_entry;  // CTRLV_SPATIAL_ENTRY [1]  0: GroupNorm apply + proj_in + LayerNorm + q|k|v of the C = 320 spatial transformer entry as four launches
 };
 const ctrlv_debug_t& ctrlv_debug();
 void ctrlv_set_error(const char* fmt, ...);

@@ -607,6 +607,22 @@ extern "C" int ctrlv_groupnorm_from_partials_split(const void* x, const void* x_
   return CTRLV_OK;
 }
 
+// ... its finalize step alone (the fused spatial-transformer entry applies the norm itself, spatial_entry_fused.hip)
+extern "C" int ctrlv_groupnorm_finalize(int n_img, int S, int C, int imgs_per_stat, float eps, float* partials,
+                                        ctrlv_stream_t stream) {
+  CTRLV_CHECK_ARG(partials, "groupnorm_finalize: null pointer");
+  CTRLV_CHECK_SHAPE(S > 0 && S % 64 == 0, "groupnorm_finalize: S=%d must be a multiple of 64", S);
+  GnShape sp;
+  int rc = gn_shape(n_img, S, C, imgs_per_stat, 0, false, &sp);
+  if (rc < 0) return rc;
+  sp.rows_per_chunk = 64;               // the producer's chunking
+  sp.n_chunks = S / 64;
+  hipLaunchKernelGGL(gn_finalize_kernel, dim3(n_img / imgs_per_stat, 32 / kFinGroups), dim3(1024), 0, (hipStream_t)stream, sp,
+                     partials, eps, partials + (size_t)n_img * sp.n_chunks * 64);
+  CTRLV_LAUNCH_CHECK();
+  return CTRLV_OK;
+}
+
 extern "C" int ctrlv_layernorm(const void* x, int M, int C, const float* gamma, const float* beta, float eps,
                                const float* V, int vdiv, int vmod, int ldv, void* y, ctrlv_stream_t stream) {
   return ctrlv_layernorm_split(x, nullptr, M, C, gamma, beta, eps, V, vdiv, vmod, ldv, y, stream);

@@ -63,6 +63,7 @@ struct Transformer {
   Linear pin, pout, s_qkv, s_o, t_qkv, t_o, tpe1, tpe2;
   FeedFwd s_ff, t_ffin, t_ff;
   el_t* t_wf = nullptr;           // C = 320 only: fragment-major q|k|v + to_out of the temporal attention (temporal_fused.hip)
+  el_t* se_wf = nullptr;          // C = 320 only: fragment-major proj_in + spatial q|k|v (spatial_entry_fused.hip)
   int xattn_off[2] = {0, 0};
   float* frame_emb = nullptr;     // [cfg.num_frames][C] fp32, prepared at load time
   std::string name;
@@ -265,6 +266,10 @@ int load_tr(WeightLoader& L, ctrlv_plan* p, Transformer& t, int cross_dim) {
   if (C == 320 && t.t_qkv.n == 960 && t.t_qkv.k == 320 && t.t_o.n == 320 && t.t_o.k == 320) {
     CTRLV_TRY(L.alloc(ctrlv_temporal_fused_weight_bytes(), (void**)&t.t_wf, false));
     CTRLV_TRY(ctrlv_temporal_fused_pack(t.t_qkv.w, t.t_qkv.k, t.t_o.w, t.t_o.k, t.t_wf, L.st));
+  }
+  if (C == 320 && t.pin.n == 320 && t.pin.k == 320 && t.s_qkv.n == 960 && t.s_qkv.k == 320) {
+    CTRLV_TRY(L.alloc(ctrlv_spatial_entry_fused_weight_bytes(), (void**)&t.se_wf, false));
+    CTRLV_TRY(ctrlv_spatial_entry_fused_pack(t.pin.w, t.pin.k, t.s_qkv.w, t.s_qkv.k, t.se_wf, L.st));
   }
   CTRLV_TRY(L.linear(t.name + ".time_pos_embed.linear_1", 4 * C, C, t.tpe1));
   CTRLV_TRY(L.linear(t.name + ".time_pos_embed.linear_2", C, 4 * C, t.tpe2));
@@ -623,27 +628,62 @@ int run_tr(Ctx& c, const Transformer& t, const Trk& x, int H, int W, Trk* out_) 
     emb = e;
   }
   el_t* tt = c.rows(M, C);
-  if (c.gn_cross_valid) {     // statistics from the res block's last GEMM (run_res, feeds_norm: set on the live walk only)
-    c.gn_cross_valid = false;
-    CTRLV_TRY(c.launch(gn_work(N, S, C, 1), [&] {
-      return ctrlv_groupnorm_from_partials_split(x.hi, x.lo, N, S, C, 1, 1e-6f, c.gn_cross, t.gn.g, t.gn.b, 0, tt, c.st);
-    }));
+  Trk h0;
+  el_t* qkv = nullptr;
+  // GroupNorm apply + proj_in + norm1 + q|k|v: at C = 320 ONE launch behind the statistics (or the finalize of the producer's
+  // partials) -- the normalised rows never reach HBM (spatial_entry_fused.hip; CTRLV_SPATIAL_ENTRY=0: the four launches).  The
+  // predicate reads shapes and the trunk mode only, so the measuring walk takes the same route.
+  ctrlv_spatial_entry_desc sd;
+  memset(&sd, 0, sizeof(sd));
+  sd.ldx = C; sd.ldh = C; sd.ldq = 3 * C; sd.n_img = N; sd.S = S; sd.C = C; sd.head_dim = 64;
+  const bool split = c.p->trunk_mode == 1;
+  const bool entry_fused = ctrlv_debug().spatial_entry && t.se_wf && !split && ctrlv_spatial_entry_fused_serves(&sd);
+  if (entry_fused) {
+    h0 = c.trunk(M, C);
+    qkv = c.rows(M, 3 * C);
+    const size_t mk2 = c.mark();
+    if (c.gn_cross_valid) {   // statistics from the res block's last GEMM (run_res, feeds_norm: set on the live walk only)
+      c.gn_cross_valid = false;
+      CTRLV_TRY(c.launch({CTRLV_FAM_GROUPNORM, 0.0, 0.0, N * S, C, 0, 3},
+                         [&] { return ctrlv_groupnorm_finalize(N, S, C, 1, 1e-6f, c.gn_cross, c.st); }));
+      sd.stats = c.gn_cross + (size_t)N * (S / 64) * 64;
+    } else {
+      const int chunks = ctrlv_groupnorm_chunks(N, S, C, 1);
+      if (chunks < 0) return chunks;
+      float* part = (float*)c.alloc(((size_t)N * chunks + N) * 64 * 4);
+      CTRLV_TRY(c.launch({CTRLV_FAM_GROUPNORM, 0.0, 2.0 * (double)M * C, N * S, C, 0, 2},
+                         [&] { return ctrlv_groupnorm_stats_split(x.hi, nullptr, nullptr, nullptr, 0, N, S, C, 1, 1e-6f, part, c.st); }));
+      sd.stats = part + (size_t)N * chunks * 64;
+    }
+    sd.x = x.hi; sd.wf = t.se_wf; sd.bias_in = t.pin.b; sd.bias_qkv = t.s_qkv.b;
+    sd.gn_gamma = t.gn.g; sd.gn_beta = t.gn.b; sd.ln_gamma = t.s_ln1.g; sd.ln_beta = t.s_ln1.b; sd.ln_eps = 1e-5f;
+    sd.h0 = h0.hi; sd.qkv = qkv; sd.q_scale = 0.125f * 1.44269504088896340736f;      // q block pre-scaled: (1/sqrt(64)) log2(e)
+    CTRLV_TRY(c.launch({CTRLV_FAM_GEMM_SPATIAL_ENTRY, 2.0 * M * C * 4.0 * C, (double)M * C * 2 * 5, (int)M, 4 * C, C},
+                       [&] { return ctrlv_spatial_entry_fused(&sd, c.st); }));
+    c.release(mk2);           // stream order keeps the statistics alive until the launch has read them
   } else {
-    CTRLV_TRY(groupnorm(c, x, Trk{}, 0, N, S, C, 1, t.gn, 1e-6f, 0, tt));
-  }
-  const Trk h0 = c.trunk(M, C);
-  {
-    ctrlv_gemm_desc d = ctrlv_linear_desc(tt, C, t.pin, h0.hi, C, (int)M, C, C, C);
-    set_out(d, h0);
-    CTRLV_TRY(gemm(c, d));
-  }
-  // ---- spatial BasicTransformerBlock
-  CTRLV_TRY(layernorm(c, h0, (int)M, C, t.s_ln1, tt));
-  el_t* qkv = c.rows(M, 3 * C);
-  {
-    ctrlv_gemm_desc d = ctrlv_linear_desc(tt, C, t.s_qkv, qkv, 3 * C, (int)M, 3 * C, C, 3 * C);
-    d.n_scale2 = C; d.s_acc2 = 0.125f * 1.44269504088896340736f;      // q block pre-scaled: (1/sqrt(64)) log2(e)
-    CTRLV_TRY(gemm(c, d));
+    if (c.gn_cross_valid) {     // statistics from the res block's last GEMM (run_res, feeds_norm: set on the live walk only)
+      c.gn_cross_valid = false;
+      CTRLV_TRY(c.launch(gn_work(N, S, C, 1), [&] {
+        return ctrlv_groupnorm_from_partials_split(x.hi, x.lo, N, S, C, 1, 1e-6f, c.gn_cross, t.gn.g, t.gn.b, 0, tt, c.st);
+      }));
+    } else {
+      CTRLV_TRY(groupnorm(c, x, Trk{}, 0, N, S, C, 1, t.gn, 1e-6f, 0, tt));
+    }
+    h0 = c.trunk(M, C);
+    {
+      ctrlv_gemm_desc d = ctrlv_linear_desc(tt, C, t.pin, h0.hi, C, (int)M, C, C, C);
+      set_out(d, h0);
+      CTRLV_TRY(gemm(c, d));
+    }
+    // ---- spatial BasicTransformerBlock
+    CTRLV_TRY(layernorm(c, h0, (int)M, C, t.s_ln1, tt));
+    qkv = c.rows(M, 3 * C);
+    {
+      ctrlv_gemm_desc d = ctrlv_linear_desc(tt, C, t.s_qkv, qkv, 3 * C, (int)M, 3 * C, C, 3 * C);
+      d.n_scale2 = C; d.s_acc2 = 0.125f * 1.44269504088896340736f;      // q block pre-scaled: (1/sqrt(64)) log2(e)
+      CTRLV_TRY(gemm(c, d));
+    }
   }
   el_t* a = c.rows(M, C);
   CTRLV_TRY(c.launch({CTRLV_FAM_ATTENTION_SPATIAL, 4.0 * N * (C / 64) * (double)S * S * 64, 2.0 * 4 * N * (double)S * C, N, S, C},

@@ -146,6 +146,7 @@ def _trk_epi(epi, out):
 
 _FF_FUSED = os.environ.get("CTRLV_FF_FUSED", "1") != "0"      # the plan's switch (csrc/plan.hip ff_pair)
 _TEMPORAL_FUSED = os.environ.get("CTRLV_TEMPORAL_FUSED", "1") != "0"     # the plan's switch (csrc/plan.hip run_tr)
+_SPATIAL_ENTRY = os.environ.get("CTRLV_SPATIAL_ENTRY", "1") != "0"       # the plan's switch (csrc/plan.hip run_tr)
 
 
 def _ff_pair(ws, x, ffp, ubox, out, C, rows_per_image=0, **epi):
@@ -379,13 +380,15 @@ class TransformerSpatioTemporalModel(nn.Module):
             t_qkv=packing.pack_qkv(merged_weight(tb.attn1.to_q), merged_weight(tb.attn1.to_k), merged_weight(tb.attn1.to_v)),
             t_o=(packing.pack_linear(merged_weight(tb.attn1.to_out[0])), _f32(tb.attn1.to_out[0].bias)),
             t_ff=ff(tb.ff),
-            t_wf=None,
+            t_wf=None, se_wf=None,
             tpe=(packing.pack_linear(self.time_pos_embed.linear_1.weight), _f32(self.time_pos_embed.linear_1.bias),
                  packing.pack_linear(self.time_pos_embed.linear_2.weight), _f32(self.time_pos_embed.linear_2.bias)),
             alpha=_sigmoid(float(self.time_mixer.mix_factor.detach().float().cpu())),
         )
         if tuple(pk["t_qkv"].shape) == (960, 320) and tuple(pk["t_o"][0].shape) == (320, 320) and pk["t_qkv"].is_cuda:
             pk["t_wf"] = ops.temporal_fused_pack(pk["t_qkv"].contiguous(), pk["t_o"][0].contiguous())   # (csrc/plan.hip load_tr)
+        if tuple(pk["pin"][0].shape) == (320, 320) and tuple(pk["s_qkv"].shape) == (960, 320) and pk["s_qkv"].is_cuda:
+            pk["se_wf"] = ops.spatial_entry_fused_pack(pk["pin"][0].contiguous(), pk["s_qkv"].contiguous())   # (csrc/plan.hip load_tr)
         self._pk = pk
         self._frame_emb = {}
 
@@ -420,17 +423,28 @@ class TransformerSpatioTemporalModel(nn.Module):
         mk = ws.mark()
         part = _gn_scratch(ctx, N, S, C, 1)
         t = ws.alloc((M, C))
-        if ctx.gn_cross_valid:       # statistics from the res block's last GEMM (SpatioTemporalResBlock.run, feeds_norm)
-            ctx.gn_cross_valid = False
-            ops.groupnorm_from_partials(x, N, S, C, 1, pk["gn"][0], pk["gn"][1], 1e-6, False, t, ctx.gn_cross, x_lo=_lo(x))
-        else:
-            ops.groupnorm(x, None, N, S, C, 1, pk["gn"][0], pk["gn"][1], 1e-6, False, t, part, x_lo=_lo(x))
         h0 = ws.trunk((M, C))
-        ops.gemm(t, pk["pin"][0], h0, N=C, cin=C, bias=pk["pin"][1], out_lo=_lo(h0))
-        # ---- spatial BasicTransformerBlock
-        ops.layernorm(h0, pk["s_ln1"][0], pk["s_ln1"][1], 1e-5, t, x_lo=_lo(h0))
         qkv = ws.alloc((M, 3 * C))
-        ops.gemm(t, pk["s_qkv"], qkv, N=3 * C, cin=C, n_scale2=C, s_acc2=ops.Q_PRESCALE)   # q block pre-scaled
+        ln1 = (pk["s_ln1"][0], pk["s_ln1"][1], 1e-5)
+        ekw = dict(bias_in=pk["pin"][1], x_lo=_lo(x), h0_lo=_lo(h0))
+        if _SPATIAL_ENTRY and ops.spatial_entry_fused_serves(x, pk["se_wf"], part, pk["gn"], ln1, h0, qkv, N, S, **ekw):
+            # GroupNorm apply + proj_in + norm1 + q|k|v in ONE launch behind the statistics (csrc/plan.hip run_tr)
+            if ctx.gn_cross_valid:   # statistics from the res block's last GEMM (SpatioTemporalResBlock.run, feeds_norm)
+                ctx.gn_cross_valid = False
+                stats = ops.groupnorm_finalize(x, N, S, C, 1, 1e-6, ctx.gn_cross)
+            else:
+                stats = ops.groupnorm_stats(x, N, S, C, 1, 1e-6, part)
+            ops.spatial_entry_fused(x, pk["se_wf"], stats, pk["gn"], ln1, h0, qkv, N, S, **ekw)
+        else:
+            if ctx.gn_cross_valid:
+                ctx.gn_cross_valid = False
+                ops.groupnorm_from_partials(x, N, S, C, 1, pk["gn"][0], pk["gn"][1], 1e-6, False, t, ctx.gn_cross, x_lo=_lo(x))
+            else:
+                ops.groupnorm(x, None, N, S, C, 1, pk["gn"][0], pk["gn"][1], 1e-6, False, t, part, x_lo=_lo(x))
+            ops.gemm(t, pk["pin"][0], h0, N=C, cin=C, bias=pk["pin"][1], out_lo=_lo(h0))
+            # ---- spatial BasicTransformerBlock
+            ops.layernorm(h0, pk["s_ln1"][0], pk["s_ln1"][1], 1e-5, t, x_lo=_lo(h0))
+            ops.gemm(t, pk["s_qkv"], qkv, N=3 * C, cin=C, n_scale2=C, s_acc2=ops.Q_PRESCALE)   # q block pre-scaled
         a = ws.alloc((M, C))
         ops.attention_spatial(qkv, a, N, S, C, prescaled=True)
         h1 = ws.trunk((M, C))

@@ -717,6 +717,89 @@ def temporal_fused(x, wf, out, B, F, S, **kw):
     return out
 
 
+def spatial_entry_fused_pack(win_packed, wqkv_packed):
+    """Fragment-major weights of `spatial_entry_fused` from the packed [320, >= 320] proj_in and [960, >= 320] q|k|v projection."""
+    _need_gpu(win_packed, "win_packed")
+    assert win_packed.shape[0] == 320 and wqkv_packed.shape[0] == 960 and wqkv_packed.dtype == win_packed.dtype
+    lib = _L(win_packed)
+    wf = torch.empty(lib.ctrlv_spatial_entry_fused_weight_bytes() // 2, dtype=win_packed.dtype, device=win_packed.device)
+    check(lib.ctrlv_spatial_entry_fused_pack(_p(win_packed), win_packed.stride(0), _p(wqkv_packed), wqkv_packed.stride(0), _p(wf),
+                                             _stream()), "ctrlv_spatial_entry_fused_pack")
+    return wf
+
+
+def _spatial_entry_desc(x, wf, stats, gn, ln, h0, qkv, n_img, S, bias_in=None, bias_qkv=None, x_lo=None, h0_lo=None,
+                        head_dim=64, q_scale=None):
+    from ._lib import SpatialEntryDesc
+    _need_rows("spatial_entry_fused", x=x, h0=h0, qkv=qkv)
+    d = SpatialEntryDesc()
+    d.x, d.x_lo, d.ldx, d.wf = _p(x), _p(x_lo), x.stride(0), _p(wf)
+    d.bias_in, d.bias_qkv, d.stats = _p(bias_in), _p(bias_qkv), _p(stats)
+    d.gn_gamma, d.gn_beta = _p(gn[0]), _p(gn[1])
+    d.ln_gamma, d.ln_beta, d.ln_eps = _p(ln[0]), _p(ln[1]), float(ln[2])
+    d.h0, d.h0_lo, d.ldh = _p(h0), _p(h0_lo), h0.stride(0)
+    d.qkv, d.ldq = _p(qkv), qkv.stride(0)
+    d.n_img, d.S, d.C, d.head_dim = n_img, S, x.shape[1], head_dim
+    d.q_scale = Q_PRESCALE if q_scale is None else q_scale
+    return d
+
+
+def spatial_entry_fused_serves(x, wf, stats, gn, ln, h0, qkv, n_img, S, **kw):
+    return wf is not None and bool(_L(x).ctrlv_spatial_entry_fused_serves(
+        ctypes.byref(_spatial_entry_desc(x, wf, stats, gn, ln, h0, qkv, n_img, S, **kw))))
+
+
+def spatial_entry_fused(x, wf, stats, gn, ln, h0, qkv, n_img, S, **kw):
+    """h0 = el(el(GN(x)) W_in^T + bias_in), qkv = el(el(LN(h0)) W_qkv^T + bias_qkv) with the q block scaled by q_scale: the
+    opening of the spatial transformer block at C = 320 in one launch (csrc/spatial_entry_fused.hip).  stats: the finalized
+    (mean, rstd) table fp32 [n_img, 32, 2] (`groupnorm_stats` / `groupnorm_finalize`); gn = (gamma, beta), ln = (gamma, beta, eps)."""
+    d = _spatial_entry_desc(x, wf, stats, gn, ln, h0, qkv, n_img, S, **kw)
+    _need_gpu(x, "x")
+    assert stats.dtype == torch.float32 and stats.numel() >= n_img * 64
+    ev = _prof.begin()
+    check(_L(x).ctrlv_spatial_entry_fused(ctypes.byref(d), _stream()), "ctrlv_spatial_entry_fused")
+    M, C = n_img * S, x.shape[1]
+    _prof.end(ev, "gemm_spatial_entry", 2.0 * M * C * 4 * C, 2.0 * 5 * M * C)
+    return h0, qkv
+
+
+def groupnorm_stats(x, n_img, S, C, imgs_per_stat, eps, partials, x_lo=None):
+    """The statistics pass of `groupnorm` alone (with its finalize); returns the (mean, rstd) table behind the chunk partials,
+    fp32 [n_img / imgs_per_stat, 32, 2] (a view of `partials`)."""
+    _need_dense("groupnorm_stats", x=x, x_lo=x_lo, partials=partials)
+    _need_gpu(x, "x")
+    ev = _prof.begin()
+    check(_L(x).ctrlv_groupnorm_stats_split(_p(x), _p(x_lo), None, None, 0, n_img, S, C, imgs_per_stat, eps, _p(partials),
+                                            _stream()), "ctrlv_groupnorm_stats")
+    _prof.end(ev, "groupnorm", 0.0, 2.0 * n_img * S * C)           # algorithmic: 1 read
+    off = n_img * groupnorm_chunks(n_img, S, C, imgs_per_stat) * 64
+    return partials.view(-1)[off:off + (n_img // imgs_per_stat) * 64]
+
+
+def groupnorm_apply(x, n_img, S, C, imgs_per_stat, gamma, beta, silu, y, partials, x_lo=None):
+    """The apply pass of `groupnorm` alone, on the statistics `groupnorm_stats` left in `partials`."""
+    _need_dense("groupnorm_apply", x=x, x_lo=x_lo, y=y, partials=partials, gamma=gamma, beta=beta)
+    _need_gpu(x, "x")
+    ev = _prof.begin()
+    check(_L(x).ctrlv_groupnorm_apply_split(_p(x), _p(x_lo), None, None, 0, n_img, S, C, imgs_per_stat, _p(partials), _p(gamma),
+                                            _p(beta), 1 if silu else 0, _p(y), _stream()), "ctrlv_groupnorm_apply")
+    _prof.end(ev, "groupnorm", 0.0, 2.0 * 2 * n_img * S * C)
+    return y
+
+
+def groupnorm_finalize(x, n_img, S, C, imgs_per_stat, eps, partials):
+    """The finalize step of `groupnorm_from_partials` alone; returns the (mean, rstd) table behind the producer's partials.
+    x: the normalised tensor (selects the element library only)."""
+    _need_dense("groupnorm_finalize", partials=partials)
+    _need_gpu(partials, "partials")
+    assert partials.numel() >= groupnorm_fused_scratch_floats(n_img, S, imgs_per_stat)
+    ev = _prof.begin()
+    check(_L(x).ctrlv_groupnorm_finalize(n_img, S, C, imgs_per_stat, eps, _p(partials), _stream()), "ctrlv_groupnorm_finalize")
+    _prof.end(ev, "groupnorm", 0.0, 0.0)
+    off = n_img * (S // 64) * 64
+    return partials.view(-1)[off:off + (n_img // imgs_per_stat) * 64]
+
+
 def nchw_to_rows(src, dst, c_off=0):
     """src: contiguous (n_img, C, H, W) fp32/fp16/bf16 -> dst rows [n_img*H*W, ldc] bf16, channels [c_off, c_off+C)."""
     _need_dense("nchw_to_rows", src=src)

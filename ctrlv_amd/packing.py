@@ -99,6 +99,29 @@ def pack_qkv(wq, wk, wv):
     return pack_linear(torch.cat([wq.detach(), wk.detach(), wv.detach()], 0))
 
 
+def spatial_entry_fragments(win_packed, wqkv_packed):
+    """The fragment-major weight of the fused spatial-transformer entry (csrc/spatial_entry_fused.hip) from the packed
+    [320, >= 320] proj_in and [960, >= 320] q|k|v weights, in plain torch: what `ops.spatial_entry_fused_pack` writes on the
+    device (the layout's statement; the models pack through the kernel).  40 chunks of 32 output channels x K = 320, one KiB
+    per K step of 16, lane-linear: element [c, ks, lane, e] with lane = 32 hs + 8 q + 4 hs_r + r is row 32 nb + 16 hs_r + 4 q + r
+    (a lane of the accumulator ends with 16 consecutive channels) at column 16 ks + 8 hs + e for proj_in (chunks 0..9: natural K
+    order) and 32 (ks // 2) + 16 hs + 8 (ks % 2) + e for q|k|v (chunks 10..39: the order in which h0 leaves the proj_in chains)."""
+    C = 320
+    lane = torch.arange(64)
+    hs, i32 = lane // 32, lane % 32
+    q, hs_r, r = i32 // 8, (i32 // 4) % 2, i32 % 4
+    row_in_block = 16 * hs_r + 4 * q + r                                     # [64]
+    ks, e = torch.arange(C // 16), torch.arange(8)
+    k_in = (16 * ks[:, None, None] + 8 * hs[None, :, None] + e[None, None, :])                                   # [20, 64, 8]
+    k_qkv = (32 * (ks // 2)[:, None, None] + 16 * hs[None, :, None] + 8 * (ks % 2)[:, None, None] + e[None, None, :])
+    out = []
+    for w, kidx, nblk in ((win_packed, k_in, C // 32), (wqkv_packed, k_qkv, 3 * C // 32)):
+        w = w.detach().cpu()
+        rows = (32 * torch.arange(nblk)[:, None, None, None] + row_in_block[None, None, :, None]).expand(nblk, C // 16, 64, 8)
+        out.append(w[rows, kidx[None].expand(nblk, C // 16, 64, 8)].reshape(-1))
+    return torch.cat(out)
+
+
 def pad_bias(bias, mult=32):
     b = bias.detach().float()
     n = b.shape[0]

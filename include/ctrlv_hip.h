@@ -212,6 +212,9 @@ int ctrlv_groupnorm_from_partials(const void* x, int n_img, int S, int C, int im
 int ctrlv_groupnorm_from_partials_split(const void* x, const void* x_lo, int n_img, int S, int C, int imgs_per_stat, float eps,
                                         float* partials, const float* gamma, const float* beta, int silu, void* y,
                                         ctrlv_stream_t stream);
+/* The finalize step of ctrlv_groupnorm_from_partials alone: the producer's 64-row chunk partials -> (mean, rstd) per
+ * (statistics row, group) behind them, at partials + n_img * (S / 64) * 64 (what ctrlv_spatial_entry_fused reads as `stats`). */
+int ctrlv_groupnorm_finalize(int n_img, int S, int C, int imgs_per_stat, float eps, float* partials, ctrlv_stream_t stream);
 /* The statistics and apply passes on a SPLIT input (ctrlv_gemm_desc.out_lo): x_lo / x2_lo are the lo planes of x / x2 (same shapes and
  * pitches; either may be NULL = that half has no lo plane); the normalised value is x + x_lo.  y is a plain tensor. */
 int ctrlv_groupnorm_stats_split(const void* x, const void* x_lo, const void* x2, const void* x2_lo, int c_split, int n_img,
@@ -313,6 +316,36 @@ int ctrlv_temporal_fused(const ctrlv_temporal_fused_desc* d, ctrlv_stream_t stre
 /* 1 if ctrlv_temporal_fused serves this descriptor (C = 320, F <= 32, pitches multiples of 8, 32-bit byte offsets, a per-clip
  * row vector) -- 0 = use the three launches.  The launcher applies exactly these conditions. */
 int ctrlv_temporal_fused_serves(const ctrlv_temporal_fused_desc* d);
+
+/* Fused entry of the spatial transformer block at C = 320 (additive entry points; csrc/spatial_entry_fused.hip):
+ *     h0 = el( el(GroupNorm(x)) . W_in^T + bias_in ),     q|k|v = el( el(LayerNorm(h0)) . W_qkv^T + bias_qkv ),  q block x q_scale
+ * -- the GroupNorm apply pass, proj_in, norm1 and the q|k|v projection of TransformerSpatioTemporalModel's opening in ONE
+ * launch instead of ctrlv_groupnorm_apply + ctrlv_gemm + ctrlv_layernorm + ctrlv_gemm (n_scale2 = C): the normalised rows never
+ * reach HBM.  x: raw rows [n_img S][ldx]; stats: the finalized (mean, rstd) per (image, group), fp32 [n_img][32][2], as
+ * ctrlv_groupnorm_stats leaves it behind its chunk partials (ctrlv_groupnorm_finalize for a producer's partials); wf =
+ * ctrlv_spatial_entry_fused_weight_bytes() bytes written by ctrlv_spatial_entry_fused_pack from the packed [C][ld_in] proj_in
+ * weight and the packed [3C][ld_qkv] q|k|v weight; bias_in fp32 [C] / bias_qkv fp32 [3C] or NULL.  h0: [M][ldh], qkv: [M][ldq].
+ * Results: the arithmetic and rounding points of the four launches (the normalised rows, h0 and q|k|v are rounded to the
+ * element type) up to the summation order of the LayerNorm statistics and of the q|k|v contraction. */
+typedef struct ctrlv_spatial_entry_desc {
+  const void* x; const void* x_lo; int32_t ldx;     /* x_lo / h0_lo: split trunk planes -- NOT served (the predicate says so) */
+  const void* wf;
+  const float* bias_in; const float* bias_qkv;
+  const float* stats;
+  const float* gn_gamma; const float* gn_beta;
+  const float* ln_gamma; const float* ln_beta; float ln_eps;
+  void* h0; void* h0_lo; int32_t ldh;
+  void* qkv; int32_t ldq;
+  int32_t n_img, S, C, head_dim;
+  float q_scale;
+} ctrlv_spatial_entry_desc;
+size_t ctrlv_spatial_entry_fused_weight_bytes(void);
+int ctrlv_spatial_entry_fused_pack(const void* win_packed, int ld_in, const void* wqkv_packed, int ld_qkv, void* wf,
+                                   ctrlv_stream_t stream);
+int ctrlv_spatial_entry_fused(const ctrlv_spatial_entry_desc* d, ctrlv_stream_t stream);
+/* 1 if ctrlv_spatial_entry_fused serves this descriptor (C = 320, head_dim 64, S a multiple of 32, no split planes, pitches
+ * multiples of 8, 31-bit byte offsets) -- 0 = use the four launches.  Shape and operands only; the launcher applies exactly these. */
+int ctrlv_spatial_entry_fused_serves(const ctrlv_spatial_entry_desc* d);
 
 /* Row softmax of fp32 scores into bf16 probabilities: probs[r, :cols] = softmax(scores[r, :cols]) (cols a multiple of 4,
  * <= 16384).  The VAE mid block's single-head attention (head dim 512; AutoencoderKLTemporalDecoder, called by
@@ -693,6 +726,7 @@ enum {
   CTRLV_FAM_GEMM_LINEAR = 0, CTRLV_FAM_GEMM_CONV3X3 = 1, CTRLV_FAM_GEMM_CONV_TEMPORAL = 2, CTRLV_FAM_ATTENTION_SPATIAL = 3,
   CTRLV_FAM_ATTENTION_TEMPORAL = 4, CTRLV_FAM_GROUPNORM = 5, CTRLV_FAM_LAYERNORM = 6, CTRLV_FAM_RESIDUAL_ADD = 7,
   CTRLV_FAM_GEMM_TEMPORAL_BLOCK = 8,    /* ctrlv_temporal_fused: q|k|v projection + attention over the frames + output projection */
+  CTRLV_FAM_GEMM_SPATIAL_ENTRY = 9,     /* ctrlv_spatial_entry_fused: GroupNorm apply + proj_in + LayerNorm + q|k|v projection */
 };
 typedef struct ctrlv_profile_record {
   int32_t family;             /* CTRLV_FAM_* */
