@@ -433,7 +433,10 @@ class LayerNormFn(torch.autograd.Function):
             # (the table's gradient is the column sum of the NORM's dx: without the skip gradient)
             ops.layernorm_bwd(x, dy.contiguous(), g32, 1e-5, dx, dg, db, V=V, vdiv=vdiv, vmod=vmod)
             dV = torch.zeros_like(V)
-            ops.colsum(dx, dV, vmode=1, vdiv=vdiv, vmod=vmod)
+            if vdiv % 4 == 0 or not ops.DETERMINISTIC:
+                ops.colsum(dx, dV, vmode=1, vdiv=vdiv, vmod=vmod)
+            else:       # (a row group that is no multiple of 4 has no ordered form in ctrlv_colsum: see _epilogue_grads)
+                _row_vector_grad_by_table_row(dx, dV, GemmSpec(vmode=1, vdiv=vdiv, vmod=vmod))
             if dskip is not None:
                 dx = dx + dskip
         else:

@@ -201,6 +201,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const el_t* __restr
     asm volatile("s_barrier" ::: "memory");
     tile(full_tiles, std::true_type{});
   }
+  // One key: the softmax is the constant 1 and dS = P (dP - D) is exactly zero.  dP (MFMA) and D (fma chain over the saved
+  // out = v) add the same 64 products in different orders, so their difference would leave rounding dust where the
+  // gradient is zero (tests/test_backward_ops_gpu.py, case S1).
+  if (S == 1) {
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) dq[dt][e] = 0.f;
+  }
   if (qok) store_row64(dqkv + (row0 + qrow) * ld + head * 64, dq, hsel, kScale);
 }
 
@@ -328,6 +337,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(const el_t* __res
     if (t + 1 < nt) issue(t + 1, (t + 1) & 1);
     tile(t);
   }
+  if (S == 1) {      // one key: dS is exactly zero (see attn_bwd_dq_kernel)
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) dk[dt][e] = 0.f;
+  }
   if (kok) {
     store_row64(dqkv + (row0 + krow) * ld + C + head * 64, dk, hsel, kScale);
     store_row64(dqkv + (row0 + krow) * ld + 2 * C + head * 64, dv, hsel, 1.0f);
@@ -447,6 +462,12 @@ __global__ __launch_bounds__(256, 1) void attn_temporal_bwd_kernel(const el_t* _
     for (int dt = 0; dt < 2; ++dt)
       acc[dt] = mfma_32x32x16(t_frag(k_tr, t_off(kb, dt * 32 + vcol), t_off(kb + 8, dt * 32 + vcol)), pf, acc[dt]);
   }
+  if (F == 1) {      // one key: dS is exactly zero (see attn_bwd_dq_kernel)
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[dt][e] = 0.f;
+  }
   if (r32 < F) store_row64(dqkv + ((long)(b * F + r32) * S + s) * ld + head * 64, acc, hsel, kScale);
 
   // ---- orientation B (lane = key): S = Q.K^T, dP = dO.V^T with L, D per register; dV^T = dO^T.P, dK^T = Q^T.dS
@@ -493,6 +514,12 @@ __global__ __launch_bounds__(256, 1) void attn_temporal_bwd_kernel(const el_t* _
       acc[dt] = mfma_32x32x16(t_frag(g_tr, o_lo, o_hi), pf, acc[dt]);
       dk[dt] = mfma_32x32x16(t_frag(q_tr, o_lo, o_hi), dsf, dk[dt]);
     }
+  }
+  if (F == 1) {
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) dk[dt][e] = 0.f;
   }
   if (r32 < F) {
     el_t* drow = dqkv + ((long)(b * F + r32) * S + s) * ld + head * 64;
