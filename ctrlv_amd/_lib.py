@@ -367,6 +367,18 @@ SIGNATURES = {
     "ctrlv_frame_ssim": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ctrlv_resize_frames_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "ctrlv_resize_frames_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "ctrlv_lpips_im2col_split": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ctrlv_lpips_pack_weight": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ctrlv_relu_maxpool_rows": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "ctrlv_lpips_distance_blocks": (c_int, [c_int]),
+    "ctrlv_lpips_layer_distance": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ctrlv_lpips_finish": (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_int), c_void_p, c_void_p]),
+    "ctrlv_lpips_plan_create": (c_int, [c_int, ctypes.POINTER(c_void_p)]),
+    "ctrlv_lpips_plan_load_weights": (c_int, [c_void_p, ctypes.POINTER(TensorDesc), c_size_t]),
+    "ctrlv_lpips_ws_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
+    "ctrlv_lpips_frames": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t,
+                                   c_void_p]),
+    "ctrlv_lpips_plan_destroy": (c_int, [c_void_p]),
     "ctrlv_resize_antialias_clamped": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int,
                                                ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_void_p]),
     "ctrlv_train_draws": (c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, c_int, c_void_p, c_void_p, c_int,
@@ -390,7 +402,9 @@ _NO_STATUS = {"ctrlv_abi_version", "ctrlv_elem_dtype", "ctrlv_build_id", "ctrlv_
               "ctrlv_pipeline_chain_workspace_bytes", "ctrlv_resize_lanczos_ws_bytes", "ctrlv_pipeline_prepare_bytes",
               "ctrlv_pipeline_seeded_workspace_bytes", "ctrlv_pipeline_best_boxes_workspace_bytes",
               "ctrlv_pipeline_best_chain_workspace_bytes", "ctrlv_frame_ssim_ws_bytes", "ctrlv_resize_frames_ws_bytes",
-              "ctrlv_train_batch_workspace_bytes",
+              "ctrlv_train_batch_workspace_bytes", "ctrlv_lpips_ws_bytes",
+              # a count of workgroups
+              "ctrlv_lpips_distance_blocks",
               # a radius, or a negative status
               "ctrlv_boundary_radius"}
 

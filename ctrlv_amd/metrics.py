@@ -11,9 +11,12 @@
   generated clip against its ground truth, as evaluate_vids computes them with PIL and scikit-image -- the ssim_score_image
   and psnr_score_image numbers and their error terms.  The resize, the three integers of PSNR and SSIM itself run on the
   device (ops.resize_frames_u8, ops.frame_stats, ops.frame_ssim); n F doubles and 3 n F integers come to the host.
+- `lpips_frames` (fvd.py:241-248): `lpips.LPIPS(net='alex')` of every frame pair, the third number evaluate_vids prints, through
+  a `plan.LpipsPlan` -- AlexNet on split 16-bit operands with fp32 maps between the layers; n F doubles
+  come to the host.  The weights are the caller's (models.lpips_alex: the two published files, or a seeded network).
 
-FVD (a TorchScript I3D fetched from a URL), LPIPS (AlexNet weights) and the per-video 3-D SSIM / PSNR the reference computes
-but no longer prints stay out of scope."""
+FVD (a TorchScript I3D fetched from a URL) and the per-video 3-D SSIM / PSNR the reference computes but no longer prints stay
+out of scope."""
 import math
 
 import numpy as np
@@ -138,12 +141,8 @@ def psnr_from_stats(min_byte, max_byte, sse, count):
     return 10.0 * math.log10((r * r * count) / sse)
 
 
-def frame_quality(gt_u8, gen_u8, size=None, resample="bicubic"):
-    """gt_u8, gen_u8: (F, 3, H, W) or (n, F, 3, H, W) uint8 frames on a HIP device -> {"ssim": float64 (F) or (n, F), "psnr":
-    the same}: per frame, scikit-image's structural_similarity(channel_axis=0, data_range=R, gaussian_weights=True, sigma=1.5)
-    and peak_signal_noise_ratio(data_range=R) with R the joint value range of the two frames -- evaluate_vids'
-    ssim_score_image / psnr_score_image.  size=(h, w): both clips are first resized on the device as PIL resizes them
-    (evaluate_vids: size=(256, 410), PIL's default bicubic).  A frame pair of one constant value is NaN in both."""
+def _clip_pair(gt_u8, gen_u8, size, resample):
+    """The two clips as contiguous (n, F, 3, h, w) uint8 after the optional PIL-exact resize, and whether a clip axis was added."""
     single = gt_u8.dim() == 4
     if single:
         gt_u8, gen_u8 = gt_u8[None], gen_u8[None]
@@ -152,24 +151,50 @@ def frame_quality(gt_u8, gen_u8, size=None, resample="bicubic"):
         h, w = (int(v) for v in size)
         gt_u8 = ops.resize_frames_u8(gt_u8, h, w, resample)
         gen_u8 = ops.resize_frames_u8(gen_u8, h, w, resample)
+    return gt_u8, gen_u8, single
+
+
+def lpips_frames(gt_u8, gen_u8, plan, size=None, resample="bicubic"):
+    """gt_u8, gen_u8: (F, 3, H, W) or (n, F, 3, H, W) uint8 frames on a HIP device, plan: a `plan.LpipsPlan` -> float64 array (F)
+    or (n, F): lpips.LPIPS(net='alex') of every frame pair on frames scaled to [-1, 1] (u8 / 127.5 - 1), as evaluate_vids feeds
+    it.  size / resample: as `frame_quality`.  The mean over everything is its lpips_score (`quality_summary`)."""
+    gt_u8, gen_u8, single = _clip_pair(gt_u8, gen_u8, size, resample)
+    out = plan.frames(gt_u8, gen_u8).cpu().numpy()
+    return out[0] if single else out
+
+
+def frame_quality(gt_u8, gen_u8, size=None, resample="bicubic", lpips=None):
+    """gt_u8, gen_u8: (F, 3, H, W) or (n, F, 3, H, W) uint8 frames on a HIP device -> {"ssim": float64 (F) or (n, F), "psnr":
+    the same}: per frame, scikit-image's structural_similarity(channel_axis=0, data_range=R, gaussian_weights=True, sigma=1.5)
+    and peak_signal_noise_ratio(data_range=R) with R the joint value range of the two frames -- evaluate_vids'
+    ssim_score_image / psnr_score_image.  size=(h, w): both clips are first resized on the device as PIL resizes them
+    (evaluate_vids: size=(256, 410), PIL's default bicubic).  A frame pair of one constant value is NaN in both.
+    lpips: a `plan.LpipsPlan`; the result then also has "lpips", the array `lpips_frames` gives for the same (resized) frames."""
+    gt_u8, gen_u8, single = _clip_pair(gt_u8, gen_u8, size, resample)
     stats = ops.frame_stats(gt_u8, gen_u8)
     ssim = ops.frame_ssim(gt_u8, gen_u8, stats).cpu().numpy()
     count = 3 * gt_u8.shape[-2] * gt_u8.shape[-1]
     psnr = np.array([[psnr_from_stats(*row, count) for row in clip] for clip in stats.cpu().tolist()], dtype=np.float64)
-    return {"ssim": ssim[0], "psnr": psnr[0]} if single else {"ssim": ssim, "psnr": psnr}
+    out = {"ssim": ssim, "psnr": psnr}
+    if lpips is not None:
+        out["lpips"] = lpips.frames(gt_u8, gen_u8).cpu().numpy()
+    return {k: v[0] for k, v in out.items()} if single else out
 
 
-def quality_summary(ssim, psnr, denominator=200):
+def quality_summary(ssim, psnr, denominator=200, lpips=None):
     """The four numbers evaluate_vids prints from its (samples, frames) arrays: ssim_score_image and psnr_score_image (the
     means) and their error terms sqrt(sum((v - mean)^2) / denominator).  The reference divides by a literal 200 whatever the
-    sample count (fvd.py:275-276): that is the default here."""
+    sample count (fvd.py:275-276): that is the default here.  lpips: the per-frame array of `lpips_frames`; adds lpips_score, its
+    plain mean (fvd.py:245-248 averages the frames of a clip, then the clips: clips of one length, so the same number)."""
     out = {}
     for name, v in (("ssim", ssim), ("psnr", psnr)):
         v = np.asarray(v, dtype=np.float64)
         out[f"{name}_score_image"] = float(v.mean())
         out[f"{name}_score_image_error"] = float(np.sqrt(((v - v.mean()) ** 2).sum() / denominator))
+    if lpips is not None:
+        out["lpips_score"] = float(np.asarray(lpips, dtype=np.float64).mean())
     return out
 
 
 __all__ = ["binary_mask_iou", "iou_from_counts", "best_of", "candidate_scores", "f_from_counts", "boundary_radius",
-           "pt_frames_to_u8", "boundary_f_measure", "psnr_from_stats", "frame_quality", "quality_summary"]
+           "pt_frames_to_u8", "boundary_f_measure", "psnr_from_stats", "frame_quality", "quality_summary", "lpips_frames"]

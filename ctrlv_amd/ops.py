@@ -1278,3 +1278,108 @@ def resize_frames_u8(frames_u8, h, w, resample="bicubic", out=None, workspace=No
     check(lib.ctrlv_resize_frames_u8(_p(frames_u8), planes, H, W, _p(out), int(h), int(w), code, _p(ws), ws.numel(), _stream()),
           "ctrlv_resize_frames_u8")
     return out
+
+
+# ---- LPIPS (csrc/lpips.hip): the split-operand im2col, the pool on fp32 rows and the per-layer distance
+LPIPS_SRC = {torch.float32: 0, torch.uint8: 3}       # src_dtype codes of the first-layer im2col and of ctrlv_lpips_frames
+
+
+def lpips_kp(C, k):
+    """Columns of one block of a split im2col row: k k C rounded up to a multiple of 64."""
+    return (k * k * C + 63) // 64 * 64
+
+
+def lpips_im2col_split(src, k=11, hw=None, dtype=torch.bfloat16, out=None):
+    """The A operand of one LPIPS convolution as element rows [M, 3 Kp] = lo | hi | hi (ctrlv_lpips_im2col_split), hi = rne(x),
+    lo = rne(x - hi) in the element type `dtype`.
+    src (m, 3, H, W) uint8 or fp32 in [-1, 1], k = 11: the first layer -- the scaling layer in fp32, 11 x 11 windows of stride 4
+    and padding 2, columns (c, ky, kx); M = m Ho Wo.
+    src fp32 rows [m H W, C] (unit column stride) with hw = (m, H, W), k = 3 or 5: a later layer -- max(v, 0) on read, stride 1,
+    padding (k - 1) / 2, columns (ky, kx, c); M = m H W."""
+    fn = "lpips_im2col_split"
+    _need_gpu(src, "src")
+    lib = _lib.load(dtype)
+    if src.dim() == 4:
+        if src.shape[1] != 3 or src.dtype not in LPIPS_SRC or k != 11:
+            raise ValueError(f"{fn}: the first layer takes (m, 3, H, W) uint8 / fp32 frames and k = 11")
+        _need_dense(fn, src=src)
+        m, C, H, W = src.shape
+        if H < 7 or W < 7:
+            raise ValueError(f"{fn}: a {H} x {W} frame is smaller than the window")
+        M, form, code, ld = m * ((H - 7) // 4 + 1) * ((W - 7) // 4 + 1), 0, LPIPS_SRC[src.dtype], 0
+    else:
+        if src.dim() != 2 or src.dtype != torch.float32 or hw is None:
+            raise ValueError(f"{fn}: later layers take fp32 rows [m H W, C] and hw = (m, H, W)")
+        _need_rows(fn, src=src)
+        m, H, W = (int(v) for v in hw)
+        C, ld = src.shape[1], src.stride(0)
+        if src.shape[0] != m * H * W:
+            raise ValueError(f"{fn}: {src.shape[0]} rows are not {m} x {H} x {W} pixels")
+        M, form, code = m * H * W, 1, 0
+    out = _out_arg(True if out is None else out, (M, 3 * lpips_kp(C, k)), dtype, src.device, fn, "out")
+    check(lib.ctrlv_lpips_im2col_split(_p(src), form, code, m, H, W, C, ld, int(k), _p(out), _stream()), "ctrlv_lpips_im2col_split")
+    return out
+
+
+def lpips_pack_weight(weight, order, dtype=torch.bfloat16):
+    """A convolution's parameter (N, C, k, k) -> element rows [N, 3 Kp] = whi | wlo | whi in the column order of the matching
+    im2col: order 0 (c, ky, kx), 1 (ky, kx, c) (ctrlv_lpips_pack_weight)."""
+    w = weight.detach().contiguous()
+    _need_gpu(w, "weight")
+    if w.dim() != 4 or w.shape[2] != w.shape[3] or w.dtype not in _DT:
+        raise ValueError(f"lpips_pack_weight: expected a float (N, C, k, k) parameter, got {tuple(w.shape)} {w.dtype}")
+    N, C, k, _ = w.shape
+    dst = torch.empty(N, 3 * lpips_kp(C, k), dtype=dtype, device=w.device)
+    check(_lib.load(dtype).ctrlv_lpips_pack_weight(_p(w), _DT[w.dtype], N, C, k, int(order), _p(dst), _stream()),
+          "ctrlv_lpips_pack_weight")
+    return dst
+
+
+def relu_maxpool_rows(x, hw, out=None):
+    """fp32 rows [m H W, C] with hw = (m, H, W) -> fp32 rows [m Ho Wo, C] = max_pool2d(relu(x), 3, stride 2), floor mode, no
+    padding (ctrlv_relu_maxpool_rows); exact."""
+    fn = "relu_maxpool_rows"
+    _need_gpu(x, "x")
+    m, H, W = (int(v) for v in hw)
+    if x.dim() != 2 or x.dtype != torch.float32 or x.shape[0] != m * H * W:
+        raise ValueError(f"{fn}: x must be fp32 rows [{m} x {H} x {W}, C], got {tuple(x.shape)} {x.dtype}")
+    _need_rows(fn, x=x)
+    if H < 3 or W < 3:
+        raise ValueError(f"{fn}: a {H} x {W} image holds no 3 x 3 window")
+    C = x.shape[1]
+    out = _out_arg(True if out is None else out, (m * ((H - 3) // 2 + 1) * ((W - 3) // 2 + 1), C), torch.float32, x.device, fn, "out")
+    check(_lib.load().ctrlv_relu_maxpool_rows(_p(x), m, H, W, C, x.stride(0), _p(out), out.stride(0), _stream()),
+          "ctrlv_relu_maxpool_rows")
+    return out
+
+
+def lpips_layer_distance(gt, gen, lin, frames):
+    """gt, gen fp32 rows [frames pix, C] of one layer (pre-ReLU), lin fp32 [C] -> float64 [frames, ceil(pix / 64)] per-block partial
+    sums of d = sum_c lin[c] (n_gt - n_gen)^2 over a frame's pixels, n = relu(x) / (|relu(x)|_2 + 1e-10)
+    (ctrlv_lpips_layer_distance).  `lpips_finish` adds them."""
+    fn = "lpips_layer_distance"
+    _need_gpu(gt, "gt")
+    frames = int(frames)
+    if (gt.dim() != 2 or gt.dtype != torch.float32 or gen.dtype != torch.float32 or tuple(gen.shape) != tuple(gt.shape)
+            or gen.stride(0) != gt.stride(0) or frames < 1 or gt.shape[0] % frames):
+        raise ValueError(f"{fn}: gt and gen must be fp32 rows of one shape and pitch, a whole number of pixels per frame")
+    _need_rows(fn, gt=gt, gen=gen)
+    C, pix = gt.shape[1], gt.shape[0] // frames
+    if lin.dtype != torch.float32 or lin.numel() != C or not lin.is_contiguous():
+        raise ValueError(f"{fn}: lin must be dense fp32 [{C}]")
+    lib = _lib.load()
+    out = torch.empty(frames, lib.ctrlv_lpips_distance_blocks(pix), dtype=torch.float64, device=gt.device)
+    check(lib.ctrlv_lpips_layer_distance(_p(gt), _p(gen), gt.stride(0), _p(lin), frames, pix, C, _p(out), _stream()),
+          "ctrlv_lpips_layer_distance")
+    return out
+
+
+def lpips_finish(partials, pix):
+    """partials: the layers' float64 [frames, blocks] arrays of `lpips_layer_distance`; pix: their pixel counts -> float64 [frames]
+    = sum over the layers of (the frame's partials added in block order) / pix (ctrlv_lpips_finish)."""
+    frames = partials[0].shape[0]
+    flat = torch.cat([p.reshape(-1) for p in partials])
+    arr = (ctypes.c_int32 * len(pix))(*[int(v) for v in pix])
+    out = torch.empty(frames, dtype=torch.float64, device=flat.device)
+    check(_lib.load().ctrlv_lpips_finish(_p(flat), frames, len(pix), arr, _p(out), _stream()), "ctrlv_lpips_finish")
+    return out

@@ -285,6 +285,49 @@ class ClipPlan(_Handle):
         return (embeds, hidden) if return_hidden else embeds
 
 
+class LpipsPlan(_Handle):
+    """Owns one `ctrlv_lpips_plan`: LPIPS (AlexNet, v0.1) of frame pairs as one C call on split 16-bit operands
+    (include/ctrlv_hip.h "LPIPS of generated frames") -- create, load the weights, workspace, `frames`."""
+    _destroy = "ctrlv_lpips_plan_destroy"
+    _SRC = {torch.float32: 0, torch.uint8: 3}
+
+    def __init__(self, weights, device, dtype=torch.bfloat16):
+        """weights: a models.lpips_alex.LpipsAlexWeights, or a state dict with its names; dtype: the element type the operands
+        are split in, as for `Plan`."""
+        self._open(device, dtype)
+        check(self._lib.ctrlv_lpips_plan_create(self.device.index or 0, ctypes.byref(self._h)), "ctrlv_lpips_plan_create")
+        self._ws = {}            # stream -> uint8 workspace tensor
+        self.load_state_dict(weights.state_dict() if hasattr(weights, "state_dict") else weights)
+
+    def load_state_dict(self, state_dict):
+        self._load("ctrlv_lpips_plan_load_weights", state_dict, floating_only=True)
+
+    def workspace_bytes(self, H, W, frames_per_chunk=1):
+        return self._nonzero(self._lib.ctrlv_lpips_ws_bytes(self._h, int(H), int(W), int(frames_per_chunk)), "ctrlv_lpips_ws_bytes")
+
+    def frames(self, gt, gen, workspace=None, frames_per_chunk=8):
+        """gt, gen: (n, F, 3, H, W) uint8, or fp32 in [-1, 1], on the plan's device -> float64 (n, F) on the device: the LPIPS of
+        every frame pair.  workspace: a uint8 tensor (256-byte aligned) to use; else one of the plan's, sized for
+        frames_per_chunk frame pairs at a time.  A frame's bits depend on neither.  No host sync."""
+        fn = "LpipsPlan.frames"
+        if gt.dim() != 5 or gt.shape[2] != 3 or gt.dtype not in self._SRC or not gt.is_cuda:
+            raise ValueError(f"{fn}: gt must be (n, F, 3, H, W) uint8 or fp32 on the HIP device")
+        if tuple(gen.shape) != tuple(gt.shape) or gen.dtype != gt.dtype or gen.device != gt.device:
+            raise ValueError(f"{fn}: gen must be {gt.dtype} {tuple(gt.shape)} on {gt.device}, got {gen.dtype} {tuple(gen.shape)} on "
+                             f"{gen.device}")
+        if (gt.device.index or 0) != (self.device.index or 0):
+            raise ValueError(f"{fn}: frames on {gt.device}, the plan's weights on {self.device}")
+        gt, gen = gt.contiguous(), gen.contiguous()
+        n, F, _, H, W = gt.shape
+        if workspace is None:
+            workspace = self._stream_workspace(self.workspace_bytes(H, W, max(1, min(int(frames_per_chunk), n * F))))
+        out = torch.empty(n, F, dtype=torch.float64, device=gt.device)
+        check(self._lib.ctrlv_lpips_frames(self._h, gt.data_ptr(), gen.data_ptr(), self._SRC[gt.dtype], n, F, H, W, out.data_ptr(),
+                                           workspace.data_ptr(), workspace.numel() * workspace.element_size(), self._stream()),
+              "ctrlv_lpips_frames")
+        return out
+
+
 class VaePlan(_Handle):
     """Owns one `ctrlv_vae_plan`: the SVD VAE (AutoencoderKLTemporalDecoder) as one C call each way -- create,
     `load_state_dict` (diffusers keys: encoder.*, decoder.*, quant_conv.*), workspace, `encode` / `decode`

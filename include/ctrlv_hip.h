@@ -49,7 +49,7 @@ enum {
  * ctrlv_resize_antialias, ctrlv_pixels_prepare, ctrlv_frames_to_u8) or the seeded-clip entry points (ctrlv_randn,
  * ctrlv_euler_schedule, ctrlv_resize_lanczos_u8, ctrlv_pipeline_prepare, ctrlv_pipeline_generate_seeded) or the per-frame quality
  * entry points (ctrlv_frame_stats, ctrlv_frame_ssim, ctrlv_frame_ssim_ws_bytes, ctrlv_resize_frames_u8,
- * ctrlv_resize_frames_ws_bytes), and a host that needs them fails at symbol lookup on a library without them.
+ * ctrlv_resize_frames_ws_bytes) or the LPIPS entry points (ctrlv_lpips_*, ctrlv_relu_maxpool_rows), and a host that needs them fails at symbol lookup on a library without them.
  * NOT neutral, although the number did not move: ctrlv_gemm_desc.pad_br gives meaning to four bytes that were alignment
  * padding, so descriptors must now be zero-initialised (see the field). */
 int ctrlv_abi_version(void);
@@ -1220,6 +1220,72 @@ int ctrlv_frame_ssim(const void* gt_u8, const void* gen_u8, int n, int F, int H,
 size_t ctrlv_resize_frames_ws_bytes(int planes, int H, int W, int h, int w, int filter);
 int ctrlv_resize_frames_u8(const void* src_u8, int planes, int H, int W, void* dst_u8, int h, int w, int filter, void* ws,
                            size_t ws_bytes, ctrlv_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * LPIPS of generated frames (csrc/lpips.hip): `lpips.LPIPS(net='alex')(gt, gen)` of evaluate_vids (src/ctrlv/metrics/fvd.py:
+ * 241-248) per frame -- the scaling layer, AlexNet's five convolutions and two max-pools, the channel normalisation of the five
+ * ReLU outputs, the five bias-free 1x1 "lin" layers and the spatial mean -- on frames in [-1, 1].  Additive entry points: the ABI
+ * number does not change and no existing struct or kernel does.
+ *
+ * The metric subtracts two normalised feature maps, so 16-bit activations lose it where the frames are close (17 % on frames one
+ * grey level apart).  Every convolution therefore runs on SPLIT operands through ctrlv_gemm with fp32 output:
+ *     x = hi + lo,  hi = rne_el(x),  lo = rne_el(x - hi)  (x - hi is exact in fp32), the weight w split the same way,
+ *     y = b + lo whi + hi wlo + hi whi   as ONE ctrlv_gemm launch: A rows [lo | hi | hi] against W rows [whi | wlo | whi].
+ * The launch walks K in order, so the two small products are summed first and the fp32 chain that carries the full-size sum is
+ * one block long, not three.
+ * In the fp16 library hi SATURATES at +-65504 (lo then carries what is left, itself saturated): real AlexNet activations stay
+ * far below.  Activations between layers are fp32 channels-last rows [m H W, C] holding the convolution output BEFORE ReLU;
+ * every consumer (the next im2col, the pool, the distance kernel) applies max(v, 0) when it reads.
+ * ------------------------------------------------------------------------------------------------------------------ */
+/* The A operand of one convolution: element rows [M, 3 Kp], column blocks lo | hi | hi, Kp = k k C rounded up to a multiple of
+ * 64, columns [k k C, Kp) of each block zero, taps outside the image zero.  rows dense, 16-byte aligned, M Kp 3 < 2^31.
+ *   form 0 (first layer): src planar frames (m, 3, H, W), src_dtype 3 = uint8, 0 = fp32 in [-1, 1].  In fp32, each operation
+ *     rounded: v = u8 / 127.5f - 1.0f (skipped for fp32), then (v - shift[c]) / scale[c], shift = (-.030, -.088, -.188), scale =
+ *     (.458, .448, .450).  k = 11, stride 4, padding 2: M = m Ho Wo, Ho = (H - 7) / 4 + 1; columns in (c, ky, kx) order.  C = 3;
+ *     ld is ignored.
+ *   form 1 (rows): src fp32 rows [m H W, ld] of C channels (C a multiple of 8, ld a multiple of 4 and >= C), read as max(v, 0);
+ *     k = 3 or 5, stride 1, padding (k - 1) / 2: M = m H W; columns tap-major (ky, kx, c). */
+int ctrlv_lpips_im2col_split(const void* src, int form, int src_dtype, int m, int H, int W, int C, int ld, int k, void* rows,
+                             ctrlv_stream_t stream);
+/* A convolution's parameter [N][C][k][k] (dtype_code 0 / 1 / 2) -> element rows [N][3 Kp] = whi | wlo | whi in the column order
+ * of the matching im2col: order 0 (c, ky, kx), order 1 (ky, kx, c); padding columns zero.  dst dense, 16-byte aligned. */
+int ctrlv_lpips_pack_weight(const void* w, int dtype_code, int N, int C, int k, int order, void* dst, ctrlv_stream_t stream);
+/* max_pool2d(relu(x), 3, stride 2) in floor mode without padding on fp32 rows: x [m H W, ldx] of C channels (C, ldx, ldo
+ * multiples of 4) -> out [m Ho Wo, ldo], Ho = (H - 3) / 2 + 1.  One value per output is selected: exact.  H, W >= 3. */
+int ctrlv_relu_maxpool_rows(const float* x, int m, int H, int W, int C, int ldx, float* out, int ldo, ctrlv_stream_t stream);
+/* One layer's distance: gt, gen fp32 rows [frames pix, ld] of C channels (the same pixels of both), read as max(v, 0); lin fp32
+ * [C].  Per pixel in fp32: n = x / (sqrt(sum_c x^2) + 1e-10) for both, d = sum_c lin[c] (n_gt - n_gen)^2 -- the channel sums
+ * per lane in channel order, then a fixed shuffle tree.  The d of a frame are added in fp64: a workgroup owns 64 consecutive
+ * pixels of one frame (a wave 16, in order; the four waves in order) and writes its sum to partials[frame][block], block <
+ * ctrlv_lpips_distance_blocks(pix) = ceil(pix / 64).  No atomics: a frame's partials do not depend on the other frames.  C a
+ * multiple of 4, at most 512; ld a multiple of 4. */
+int ctrlv_lpips_distance_blocks(int pix);
+int ctrlv_lpips_layer_distance(const float* gt, const float* gen, int ld, const float* lin, int frames, int pix, int C,
+                               double* partials, ctrlv_stream_t stream);
+/* out[frame] = sum over the layers, in order, of (the layer's partials of the frame summed in block order) / pix[layer].
+ * partials: the layers' [frames][blocks] arrays one behind the other; pix: n_layers (at most 8) pixel counts, a HOST array. */
+int ctrlv_lpips_finish(const double* partials, int frames, int n_layers, const int* pix, double* out, ctrlv_stream_t stream);
+
+/* The metric as one call: ctrlv_lpips_plan_create -> ctrlv_lpips_plan_load_weights -> ctrlv_lpips_ws_bytes ->
+ * ctrlv_lpips_frames.  Weights (host or device tensors, fp32 or 16-bit; extra names are ignored, a missing one is an error that
+ * names it): torchvision's alexnet `features.{0,3,6,8,10}.{weight,bias}` and lpips' `lin{0..4}.model.1.weight`.  The plan owns
+ * the packed split weights; load_weights may be called again and synchronises the device. */
+typedef struct ctrlv_lpips_plan ctrlv_lpips_plan;
+int ctrlv_lpips_plan_create(int device, ctrlv_lpips_plan** out);
+int ctrlv_lpips_plan_load_weights(ctrlv_lpips_plan* plan, const ctrlv_tensor_desc* tensors, size_t n);
+/* Bytes of workspace for frames of H x W taken frames_per_chunk at a time; 0 on error (ctrlv_last_error). */
+size_t ctrlv_lpips_ws_bytes(ctrlv_lpips_plan* plan, int H, int W, int frames_per_chunk);
+/* gt, gen: planar frames (n, F, 3, H, W), src_dtype 3 = uint8 or 0 = fp32 in [-1, 1]; out: n F doubles, the LPIPS of every frame
+ * pair (evaluate_vids averages them).  The frames are taken in chunks; a chunk's gt and gen frames are stacked as 2 chunk images:
+ *     im2col -> ctrlv_gemm (mode 0, taps 1, Cin = 3 Kp, fp32 output, bias, the 128 x 128 tile named per layer) for conv1;
+ *     distance, pool, conv2;  distance, pool, conv3;  distance, conv4;  distance, conv5;  distance, finish.
+ * The chunk is the largest the workspace holds (every im2col buffer below 2^31 elements); a frame's bits do not depend on n, F,
+ * the chunk or the workspace size.  No host synchronisation, nothing read back: capturable into a HIP graph.  Everything is
+ * checked before the first launch.  CTRLV_E_BAD_SHAPE: H or W below 31 (the second pool has no output), n or F not positive;
+ * CTRLV_E_WORKSPACE: ws (256-byte aligned) smaller than ctrlv_lpips_ws_bytes(plan, H, W, 1). */
+int ctrlv_lpips_frames(ctrlv_lpips_plan* plan, const void* gt, const void* gen, int src_dtype, int n, int F, int H, int W,
+                       double* out, void* ws, size_t ws_bytes, ctrlv_stream_t stream);
+int ctrlv_lpips_plan_destroy(ctrlv_lpips_plan* plan);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Training batches: what the reference's training loops do between a data-loader batch and their model call
