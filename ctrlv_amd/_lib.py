@@ -388,6 +388,9 @@ SIGNATURES = {
                                      c_void_p, c_void_p]),
     "ctrlv_train_batch_workspace_bytes": (c_size_t, [c_void_p, c_void_p, ctypes.POINTER(TrainBatchRequest)]),
     "ctrlv_train_batch_prepare": (c_int, [c_void_p, c_void_p, ctypes.POINTER(TrainBatchRequest), c_void_p, c_size_t, c_void_p]),
+    "ctrlv_adamw_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float, c_float, c_float,
+                                 c_float, c_float, c_float, c_float, c_float, c_void_p]),
+    "ctrlv_ema_step": (c_int, [c_void_p, c_void_p, c_size_t, c_float, c_void_p]),
 }
 
 _libs = {}                # element dtype code (2 bf16 / 1 fp16) -> CDLL

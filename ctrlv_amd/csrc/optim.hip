@@ -1,0 +1,191 @@
+// Optimiser pass of the training steps (gfx950): AdamW over one flat fp32 buffer with the EMA shadow update fused in, and
+// the EMA update alone.  One pass, 16-byte loads and stores per lane, a scalar tail for n % 4; no pointer tables, no atomics,
+// no barrier.  HBM-bound: 28 bytes per element (p, m, v read and written, g read), 36 with the shadow.  All arithmetic is
+// fp32 and does not depend on the library's element type.
+//
+// Every fused multiply-add is EXPLICIT and the unit is compiled with contraction off (EXTRA_FLAGS of the build): the fused
+// kernel and the two-launch form (AdamW, then ctrlv_ema_step) must give the same bits, so the rounding of each operation may
+// not depend on which kernel inlines it.
+#include <math.h>
+
+#include "common.h"
+
+namespace {
+
+struct adamw_consts {
+  float decay_mul;     // 1 - lr * weight_decay
+  float w1, omw1;      // 1 - beta1 (the lerp weight) and 1 - w1 in fp32
+  int w1_small;        // |w1| < 0.5: which of lerp's two forms applies
+  float beta2, omb2;   // beta2, 1 - beta2
+  float neg_step;      // -lr / bias1
+  float inv_bias2_sqrt;  // 1 / sqrt(bias2), the reciprocal taken in fp32
+  float eps;
+  float grad_scale;
+  float ema_omd;       // 1 - ema_decay
+};
+
+// torch.optim.AdamW (amsgrad=False, maximize=False):
+//   p *= 1 - lr*wd;  m = b1*m + (1-b1)*g;  v = b2*v + (1-b2)*g*g;  p -= (lr/bias1) * m / (sqrt(v)/sqrt(bias2) + eps)
+// evaluated in the rounding order of torch's own single-tensor path on the device (optim/adam.py _single_tensor_adam and the
+// ATen kernels behind it), so that a run continued from a torch checkpoint follows torch's trajectory as closely as fp32 allows:
+//   mul_(1 - lr*wd);  lerp_(g, 1 - b1): m + w (g - m) as one fma for w < 0.5, g - (g - m)(1 - w) otherwise;
+//   mul_(b2) then addcmul_: fma(1 - b2, g*g, b2*v);  sqrt, times the fp32 reciprocal of sqrt(bias2), plus eps;
+//   addcdiv_: fma(-lr/bias1, m / denom, p).
+// sqrtf and '/' are the correctly rounded ones (hipcc's default for fp32).
+__device__ __forceinline__ void adamw_one(float& p, float g, float& m, float& v, const adamw_consts& c) {
+  g = g * c.grad_scale;
+  const float pd = p * c.decay_mul;
+  const float d = g - m;
+  m = c.w1_small ? __builtin_fmaf(c.w1, d, m) : __builtin_fmaf(-d, c.omw1, g);
+  v = __builtin_fmaf(c.omb2, g * g, v * c.beta2);
+  const float denom = sqrtf(v) * c.inv_bias2_sqrt + c.eps;
+  p = __builtin_fmaf(c.neg_step, m / denom, pd);
+}
+
+// diffusers' EMAModel.step: ema -= (1 - decay) * (ema - p)
+__device__ __forceinline__ float ema_one(float e, float p, float omd) { return __builtin_fmaf(-omd, e - p, e); }
+
+constexpr int kThreads = 256, kVecPerThread = 4;            // one workgroup: 256 lanes x 4 vectors x 4 floats = 4096 elements
+constexpr size_t kBlockElems = (size_t)kThreads * kVecPerThread * 4;
+
+template <bool EMA>
+__global__ __launch_bounds__(kThreads) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                         float* __restrict__ v, float* __restrict__ ema, size_t n, adamw_consts c) {
+  const size_t nvec = n / 4;
+  const size_t v0 = (size_t)blockIdx.x * (kThreads * kVecPerThread) + threadIdx.x;
+  f32x4 pp[kVecPerThread], gg[kVecPerThread], mm[kVecPerThread], vv[kVecPerThread], ee[kVecPerThread];
+#pragma unroll
+  for (int j = 0; j < kVecPerThread; ++j) {                 // all loads of the thread in flight before the first use
+    const size_t i = v0 + (size_t)j * kThreads;
+    if (i < nvec) {
+      pp[j] = ((const f32x4*)p)[i];
+      gg[j] = ((const f32x4*)g)[i];
+      mm[j] = ((const f32x4*)m)[i];
+      vv[j] = ((const f32x4*)v)[i];
+      if (EMA) ee[j] = ((const f32x4*)ema)[i];
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < kVecPerThread; ++j) {
+    const size_t i = v0 + (size_t)j * kThreads;
+    if (i < nvec) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        float pk = pp[j][k], mk = mm[j][k], vk = vv[j][k];
+        adamw_one(pk, gg[j][k], mk, vk, c);
+        pp[j][k] = pk, mm[j][k] = mk, vv[j][k] = vk;
+        if (EMA) ee[j][k] = ema_one(ee[j][k], pk, c.ema_omd);
+      }
+      ((f32x4*)p)[i] = pp[j];
+      ((f32x4*)m)[i] = mm[j];
+      ((f32x4*)v)[i] = vv[j];
+      if (EMA) ((f32x4*)ema)[i] = ee[j];
+    }
+  }
+  // scalar tail: elements [4 * nvec, n), at most three, by the first lanes of the first workgroup
+  const size_t t = nvec * 4 + threadIdx.x;
+  if (blockIdx.x == 0 && t < n) {
+    float pk = p[t], mk = m[t], vk = v[t];
+    adamw_one(pk, g[t], mk, vk, c);
+    p[t] = pk, m[t] = mk, v[t] = vk;
+    if (EMA) ema[t] = ema_one(ema[t], pk, c.ema_omd);
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void ema_kernel(float* __restrict__ ema, const float* __restrict__ p, size_t n, float omd) {
+  const size_t nvec = n / 4;
+  const size_t v0 = (size_t)blockIdx.x * (kThreads * kVecPerThread) + threadIdx.x;
+  f32x4 pp[kVecPerThread], ee[kVecPerThread];
+#pragma unroll
+  for (int j = 0; j < kVecPerThread; ++j) {
+    const size_t i = v0 + (size_t)j * kThreads;
+    if (i < nvec) {
+      pp[j] = ((const f32x4*)p)[i];
+      ee[j] = ((const f32x4*)ema)[i];
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < kVecPerThread; ++j) {
+    const size_t i = v0 + (size_t)j * kThreads;
+    if (i < nvec) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) ee[j][k] = ema_one(ee[j][k], pp[j][k], omd);
+      ((f32x4*)ema)[i] = ee[j];
+    }
+  }
+  const size_t t = nvec * 4 + threadIdx.x;
+  if (blockIdx.x == 0 && t < n) ema[t] = ema_one(ema[t], p[t], omd);
+}
+
+inline bool aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
+inline bool unit_open(float x) { return x >= 0.f && x < 1.f; }          // [0, 1); false for NaN
+
+// bias = 1 - beta^t reaches the entry point rounded to fp32.  The step count t it encodes is recovered and the correction is
+// recomputed in double, so that lr / bias1 and sqrt(bias2) are rounded ONCE, as where the host derives them from (beta, t) in
+// double.  A value that is not of this form (or beta = 0, where every t gives 1) is taken as given.
+inline double exact_bias(float beta, float bias) {
+  if (!(beta > 0.f) || !(bias < 1.f)) return (double)bias;
+  const double t = round(log1p(-(double)bias) / log((double)beta));
+  if (!(t >= 1.0 && t <= 1e9)) return (double)bias;
+  const double b = 1.0 - pow((double)beta, t);
+  return fabs(b - (double)bias) <= 1e-6 * b ? b : (double)bias;
+}
+
+// workgroups of kBlockElems elements that cover n; the launches below pass at most 2^30 elements each
+inline unsigned blocks_for(size_t n) { return (unsigned)((n + kBlockElems - 1) / kBlockElems); }
+constexpr size_t kMaxLaunchElems = (size_t)1 << 30;                      // a multiple of kBlockElems: chunk bases stay aligned
+
+}  // namespace
+
+extern "C" int ctrlv_adamw_step(float* p, const float* g, float* m, float* v, float* ema, size_t n, float lr, float beta1,
+                                float beta2, float eps, float weight_decay, float bias1, float bias2, float grad_scale,
+                                float ema_decay, ctrlv_stream_t stream) {
+  CTRLV_CHECK_ARG(p && g && m && v, "adamw_step: p, g, m and v must be non-null");
+  CTRLV_CHECK_SHAPE(n > 0, "adamw_step: n must be positive");
+  CTRLV_CHECK_ARG(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(ema),
+                  "adamw_step: every buffer must be 16-byte aligned");
+  CTRLV_CHECK_ARG(isfinite(lr), "adamw_step: lr must be finite");
+  CTRLV_CHECK_ARG(unit_open(beta1) && unit_open(beta2), "adamw_step: beta1 and beta2 must lie in [0, 1)");
+  CTRLV_CHECK_ARG(eps > 0.f && isfinite(eps), "adamw_step: eps must be positive");
+  CTRLV_CHECK_ARG(isfinite(weight_decay), "adamw_step: weight_decay must be finite");
+  CTRLV_CHECK_ARG(bias1 > 0.f && bias1 <= 1.f && bias2 > 0.f && bias2 <= 1.f,
+                  "adamw_step: bias1 and bias2 (1 - beta^t) must lie in (0, 1]");
+  CTRLV_CHECK_ARG(isfinite(grad_scale), "adamw_step: grad_scale must be finite");
+  CTRLV_CHECK_ARG(ema == nullptr || (ema_decay >= 0.f && ema_decay <= 1.f), "adamw_step: ema decay must lie in [0, 1]");
+  adamw_consts c;
+  c.decay_mul = (float)(1.0 - (double)lr * (double)weight_decay);
+  c.w1 = (float)(1.0 - (double)beta1);
+  c.omw1 = 1.0f - c.w1;
+  c.w1_small = fabsf(c.w1) < 0.5f;
+  c.beta2 = beta2, c.omb2 = (float)(1.0 - (double)beta2);
+  c.neg_step = (float)(-(double)lr / exact_bias(beta1, bias1));
+  c.inv_bias2_sqrt = 1.0f / (float)sqrt(exact_bias(beta2, bias2));
+  c.eps = eps;
+  c.grad_scale = grad_scale;
+  c.ema_omd = ema ? (float)(1.0 - (double)ema_decay) : 0.f;
+  for (size_t off = 0; off < n; off += kMaxLaunchElems) {
+    const size_t cnt = n - off < kMaxLaunchElems ? n - off : kMaxLaunchElems;
+    if (ema)
+      hipLaunchKernelGGL(adamw_kernel<true>, dim3(blocks_for(cnt)), dim3(kThreads), 0, (hipStream_t)stream, p + off, g + off,
+                         m + off, v + off, ema + off, cnt, c);
+    else
+      hipLaunchKernelGGL(adamw_kernel<false>, dim3(blocks_for(cnt)), dim3(kThreads), 0, (hipStream_t)stream, p + off, g + off,
+                         m + off, v + off, (float*)nullptr, cnt, c);
+    CTRLV_LAUNCH_CHECK();
+  }
+  return CTRLV_OK;
+}
+
+extern "C" int ctrlv_ema_step(float* ema, const float* p, size_t n, float decay, ctrlv_stream_t stream) {
+  CTRLV_CHECK_ARG(ema && p, "ema_step: ema and p must be non-null");
+  CTRLV_CHECK_SHAPE(n > 0, "ema_step: n must be positive");
+  CTRLV_CHECK_ARG(aligned16(ema) && aligned16(p), "ema_step: every buffer must be 16-byte aligned");
+  CTRLV_CHECK_ARG(decay >= 0.f && decay <= 1.f, "ema_step: decay must lie in [0, 1]");
+  const float omd = (float)(1.0 - (double)decay);
+  for (size_t off = 0; off < n; off += kMaxLaunchElems) {
+    const size_t cnt = n - off < kMaxLaunchElems ? n - off : kMaxLaunchElems;
+    hipLaunchKernelGGL(ema_kernel, dim3(blocks_for(cnt)), dim3(kThreads), 0, (hipStream_t)stream, ema + off, p + off, cnt, omd);
+    CTRLV_LAUNCH_CHECK();
+  }
+  return CTRLV_OK;
+}

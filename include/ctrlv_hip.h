@@ -49,7 +49,7 @@ enum {
  * ctrlv_resize_antialias, ctrlv_pixels_prepare, ctrlv_frames_to_u8) or the seeded-clip entry points (ctrlv_randn,
  * ctrlv_euler_schedule, ctrlv_resize_lanczos_u8, ctrlv_pipeline_prepare, ctrlv_pipeline_generate_seeded) or the per-frame quality
  * entry points (ctrlv_frame_stats, ctrlv_frame_ssim, ctrlv_frame_ssim_ws_bytes, ctrlv_resize_frames_u8,
- * ctrlv_resize_frames_ws_bytes) or the LPIPS entry points (ctrlv_lpips_*, ctrlv_relu_maxpool_rows), and a host that needs them fails at symbol lookup on a library without them.
+ * ctrlv_resize_frames_ws_bytes) or the LPIPS entry points (ctrlv_lpips_*, ctrlv_relu_maxpool_rows) or the optimiser pass (ctrlv_adamw_step, ctrlv_ema_step), and a host that needs them fails at symbol lookup on a library without them.
  * NOT neutral, although the number did not move: ctrlv_gemm_desc.pad_br gives meaning to four bytes that were alignment
  * padding, so descriptors must now be zero-initialised (see the field). */
 int ctrlv_abi_version(void);
@@ -1396,6 +1396,30 @@ size_t ctrlv_train_batch_workspace_bytes(ctrlv_vae_plan* vae, ctrlv_clip_plan* c
  * VAE phase alias one region of the workspace.  The plans are borrowed; not thread-safe on one pair of plans. */
 int ctrlv_train_batch_prepare(ctrlv_vae_plan* vae, ctrlv_clip_plan* clip, const ctrlv_train_batch_request* r, void* ws,
                               size_t ws_bytes, ctrlv_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Optimiser pass of the training steps (csrc/optim.hip): replaces torch.optim.AdamW's per-tensor launches
+ * (tools/train_video_diffusion.py:196-201) and diffusers' EMAModel.step (:550) for parameters kept in ONE flat fp32 buffer.
+ *
+ * ctrlv_adamw_step: torch.optim.AdamW with amsgrad=False, maximize=False over n elements, in torch's operation order:
+ *     g *= grad_scale (in registers);  p *= 1 - lr*weight_decay;  m = beta1*m + (1-beta1)*g;  v = beta2*v + (1-beta2)*g*g;
+ *     p -= (lr/bias1) * m / (sqrt(v)/sqrt(bias2) + eps)
+ * each operation rounded as torch's single-tensor path rounds it on the device (m as lerp(m, g, 1 - beta1), v as
+ * fma(1 - beta2, g*g, beta2*v), the division by sqrt(bias2) as a product with its fp32 reciprocal, the last line as one fma).
+ * bias1 = 1 - beta1^t and bias2 = 1 - beta2^t are computed by the host in double; they arrive as fp32, so the entry point
+ * recovers t from them and recomputes both in double (a value not of that form is used as given).  With ema != NULL the same pass then does
+ * ema -= (1 - ema_decay) * (ema - p) on the new p (diffusers' form, applied after optimizer.step()); the result equals
+ * ctrlv_adamw_step(ema = NULL) followed by ctrlv_ema_step bit for bit.  All buffers are fp32, contiguous and 16-byte aligned;
+ * nothing at or past element n is read or written; an all-zero element (alignment padding of a flat layout) stays all-zero.
+ * One pass, no atomics: the same bits in every run.  Buffers above 2^30 elements are split into launches of 2^30.
+ * Refused on the host (CTRLV_E_BAD_ARG; n == 0: CTRLV_E_BAD_SHAPE): NULL p / g / m / v, a misaligned base, a non-finite lr,
+ * weight_decay or grad_scale, a beta outside [0, 1), eps <= 0, bias1 / bias2 outside (0, 1], with ema an ema_decay outside [0, 1].
+ * The code is the same in both element libraries.  Additive: the ABI number does not move. */
+int ctrlv_adamw_step(float* p, const float* g, float* m, float* v, float* ema, size_t n, float lr, float beta1, float beta2,
+                     float eps, float weight_decay, float bias1, float bias2, float grad_scale, float ema_decay,
+                     ctrlv_stream_t stream);
+/* ema -= (1 - decay) * (ema - p) over n fp32 elements: the last line of ctrlv_adamw_step alone (same refusals). */
+int ctrlv_ema_step(float* ema, const float* p, size_t n, float decay, ctrlv_stream_t stream);
 
 #ifdef __cplusplus
 }

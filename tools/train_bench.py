@@ -4,7 +4,9 @@ full SVD width; tools/train_video_controlnet.py:366-488) through ctrlv_amd.train
 ms per optimisation step, its split (forward / backward / optimizer, HIP events), peak device memory, and the analytic
 work of SURVEY.md 8 a11 (219 TFLOP: ControlNet fwd 29.3 + UNet fwd 80.0 + ControlNet bwd 58.6 + UNet decoder dgrad 51).
 Synthetic data, random-init weights (there are no checkpoints in this image).
-usage: python tools/train_bench.py [--steps 3] [--warmup 1] [--frames 25] [--height 576] [--width 1024]
+usage: python tools/train_bench.py [--steps 3] [--warmup 1] [--frames 25] [--height 576] [--width 1024] [--optimizer torch|hip] [--ema 0|1]
+--optimizer hip: ctrlv_amd.optim.AdamW (flat buffers, one ctrlv_adamw_step launch) instead of torch.optim.AdamW; --ema 1: an EMA of
+the ControlNet's parameters inside optimizer_ms (fused into the AdamW pass with hip, torch's foreach ops with torch).
 Data parallel (one process per GPU, RCCL): `python tools/train_bench.py --gpus N` starts the N ranks itself from a GPU-free
 parent; or python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P
 tools/train_bench.py --gpus N ...  -- every rank trains on its own clip, the fp32 gradients are
@@ -30,6 +32,9 @@ def main():
     ap.add_argument("--width", type=int, default=1024)
     ap.add_argument("--lr", type=float, default=1e-5)
     ap.add_argument("--fused-adamw", type=int, default=1, help="torch.optim.AdamW(fused=...)")
+    ap.add_argument("--optimizer", choices=("torch", "hip"), default="torch",
+                    help="torch: torch.optim.AdamW; hip: ctrlv_amd.optim.AdamW (flat buffers, csrc/optim.hip)")
+    ap.add_argument("--ema", type=int, default=0, help="1: EMA of the trained parameters (ctrlv_amd.optim.EMAModel), timed in optimizer_ms")
     ap.add_argument("--gradient-checkpointing", type=int, default=0,
                     help="1: unet.enable_gradient_checkpointing() + controlnet.enable_gradient_checkpointing() (the GEGLU "
                          "feed-forward intermediates are recomputed in the backward; tools/train_video_controlnet.py:185-186)")
@@ -70,7 +75,12 @@ def main():
         unet.enable_gradient_checkpointing()
         ctrl.enable_gradient_checkpointing()
     params = [p for p in ctrl.parameters() if p.requires_grad]
-    opt = torch.optim.AdamW(params, lr=args.lr, weight_decay=1e-2, fused=bool(args.fused_adamw))
+    from ctrlv_amd import optim
+    ema = optim.EMAModel(params) if args.ema else None
+    if args.optimizer == "hip":
+        opt = optim.AdamW(params, lr=args.lr, weight_decay=1e-2).attach_ema(ema)      # the shadow update rides in the AdamW pass
+    else:
+        opt = torch.optim.AdamW(params, lr=args.lr, weight_decay=1e-2, fused=bool(args.fused_adamw))
     buckets = training.GradientBuckets(params) if world > 1 else None
     B, F, h, w = 1, args.frames, args.height // 8, args.width // 8
     g = torch.Generator(device=dev).manual_seed(1234 + rank)             # every rank: its own clip
@@ -105,6 +115,8 @@ def main():
             buckets.finish()
         e[2].record()
         opt.step()
+        if ema is not None and args.optimizer != "hip":
+            ema.step(params)
         opt.zero_grad(set_to_none=True)
         e[3].record()
         torch.cuda.synchronize()
@@ -128,7 +140,8 @@ def main():
                       "steps": n, "warmup": args.warmup, "frames": F, "latent": [h, w], "analytic_tflop_per_step": round(tf, 1),
                       "tflops": round(tf / avg[0] * 1e3, 1), "peak_mem_gb": round(torch.cuda.max_memory_allocated() / 2**30, 1),
                       "losses": [round(v, 5) for v in losses],
-                      "gradient_checkpointing": bool(args.gradient_checkpointing), "dtype": "bf16 compute, fp32 master parameters + AdamW",
+                      "gradient_checkpointing": bool(args.gradient_checkpointing), "optimizer": args.optimizer, "ema": bool(args.ema),
+                      "dtype": "bf16 compute, fp32 master parameters + AdamW",
                       "data": "synthetic, random-init weights"}))
 
 

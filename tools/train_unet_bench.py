@@ -8,7 +8,10 @@ recomputes are not counted).  Synthetic data, random-init weights (there are no 
 Default size: the stage-1 training size 320 x 512 (src/ctrlv/datasets/kitti_abstract.py:86-90); --height 576 --width 1024
 for the full frame.
 usage: python tools/train_unet_bench.py [--steps 3] [--warmup 1] [--frames 25] [--height 320] [--width 512]
-       [--mode all|temporal|lora] [--rank 4] [--gradient-checkpointing 0|1] [--gpus N]
+       [--mode all|temporal|lora] [--rank 4] [--gradient-checkpointing 0|1] [--gpus N] [--optimizer torch|hip] [--ema 0|1]
+--optimizer hip: ctrlv_amd.optim.AdamW (flat buffers, one ctrlv_adamw_step launch) instead of torch.optim.AdamW; --ema 1: an EMA of
+the trained parameters inside optimizer_ms -- fused into the AdamW pass with --optimizer hip, torch's foreach ops on per-tensor
+shadows with --optimizer torch (a stand-in for diffusers' per-tensor Python loop, and a conservative one: fewer launches).
 Data parallel: --gpus N as in tools/train_bench.py (one rank process per GPU, its own clip per rank, the fp32 gradients
 all-reduced in 25 MB buckets while the backward runs); the time is the MAX over ranks."""
 import argparse
@@ -69,6 +72,9 @@ def main():
     ap.add_argument("--rank", type=int, default=4, help="LoRA rank of --mode lora (lora_alpha = rank, as the reference)")
     ap.add_argument("--lr", type=float, default=1e-5)
     ap.add_argument("--fused-adamw", type=int, default=1, help="torch.optim.AdamW(fused=...)")
+    ap.add_argument("--optimizer", choices=("torch", "hip"), default="torch",
+                    help="torch: torch.optim.AdamW; hip: ctrlv_amd.optim.AdamW (flat buffers, csrc/optim.hip)")
+    ap.add_argument("--ema", type=int, default=0, help="1: EMA of the trained parameters (ctrlv_amd.optim.EMAModel), timed in optimizer_ms")
     ap.add_argument("--gradient-checkpointing", type=int, default=0,
                     help="1: unet.enable_gradient_checkpointing() (the GEGLU feed-forward intermediates are recomputed in "
                          "the backward)")
@@ -109,7 +115,12 @@ def main():
     if args.gradient_checkpointing:
         unet.enable_gradient_checkpointing()
     params = unet.get_parameters_with_grad()
-    opt = torch.optim.AdamW(params, lr=args.lr, weight_decay=1e-2, fused=bool(args.fused_adamw))
+    from ctrlv_amd import optim
+    ema = optim.EMAModel(params) if args.ema else None
+    if args.optimizer == "hip":
+        opt = optim.AdamW(params, lr=args.lr, weight_decay=1e-2).attach_ema(ema)      # the shadow update rides in the AdamW pass
+    else:
+        opt = torch.optim.AdamW(params, lr=args.lr, weight_decay=1e-2, fused=bool(args.fused_adamw))
     buckets = training.GradientBuckets(params) if world > 1 else None
     B, F, h, w = 1, args.frames, args.height // 8, args.width // 8
     g = torch.Generator(device=dev).manual_seed(1234 + rank)             # every rank: its own clip
@@ -135,6 +146,8 @@ def main():
         training._backward_and_step(unet, loss, None, world, buckets, False, 1.0)
         e[2].record()
         opt.step()
+        if ema is not None and args.optimizer != "hip":
+            ema.step(params)
         opt.zero_grad(set_to_none=True)
         e[3].record()
         torch.cuda.synchronize()
@@ -161,7 +174,7 @@ def main():
                       "peak_mem_gb": round(torch.cuda.max_memory_allocated() / 2**30, 1),
                       "trainable_params_m": round(sum(p.numel() for p in params) / 1e6, 1),
                       "losses": [round(v, 5) for v in losses],
-                      "gradient_checkpointing": bool(args.gradient_checkpointing),
+                      "gradient_checkpointing": bool(args.gradient_checkpointing), "optimizer": args.optimizer, "ema": bool(args.ema),
                       **({"rank": args.rank} if args.mode == "lora" else {}),
                       "dtype": "bf16 compute, fp32 master parameters + AdamW", "data": "synthetic, random-init weights"}))
 
