@@ -391,6 +391,11 @@ SIGNATURES = {
     "ctrlv_adamw_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float, c_float, c_float,
                                  c_float, c_float, c_float, c_float, c_float, c_void_p]),
     "ctrlv_ema_step": (c_int, [c_void_p, c_void_p, c_size_t, c_float, c_void_p]),
+    "ctrlv_grad_sumsq_partials": (c_size_t, [c_size_t]),
+    "ctrlv_grad_sumsq": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_void_p]),
+    "ctrlv_grad_finish": (c_int, [c_void_p, c_size_t, c_float, c_float, c_void_p, c_void_p]),
+    "ctrlv_adamw_step_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float, c_float, c_float,
+                                     c_float, c_float, c_float, c_float, c_float, c_void_p, c_void_p]),
 }
 
 _libs = {}                # element dtype code (2 bf16 / 1 fp16) -> CDLL

@@ -105,10 +105,23 @@ class AdamW(torch.optim.Optimizer):
         torch's single-tensor path rounds it on the device: with fp32-representable hyper-parameters the tests find no bit of p,
         exp_avg or exp_avg_sq that differs from `torch.optim.AdamW(foreach=False, fused=False)`;
       * every step bumps the version counter of every updated parameter (the kernel writes through a raw pointer): values
-        cached on `p._version` (ctrlv_amd.frozen) are rebuilt after a step.
+        cached on `p._version` (ctrlv_amd.frozen) are rebuilt after a step;
+      * `step(max_grad_norm=...)` skips a step whose gradient norm is not finite ON THE DEVICE, and the host cannot know
+        without a read: `state[p]["step"]` and the bias corrections count ATTEMPTED steps, skipped ones included
+        (`grad_state()["skipped_total"]` tells how many those were).
 
     `step(ema=ema_model)` fuses the shadow update of a `ctrlv_amd.optim.EMAModel` into the same pass (replaces the
-    `ema_unet.step(unet.parameters())` line that follows `optimizer.step()`)."""
+    `ema_unet.step(unet.parameters())` line that follows `optimizer.step()`).
+
+    `step(max_grad_norm=x)` clips the gradients to a global L2 norm of x first, as `accelerator.clip_grad_norm_(params, x)` in
+    front of `optimizer.step()` does (`torch.nn.utils.clip_grad_norm_`: one norm over every trainable parameter of every
+    group; frozen parameters and padding do not take part): one more read of the gradient buffers sums their squares in
+    fp64 (`ctrlv_grad_sumsq`), one small launch forms norm, coefficient and skip flag on the device (`ctrlv_grad_finish`), and
+    the AdamW pass multiplies each gradient by the coefficient as it reads it (`ctrlv_adamw_step_dev`).  The gradient buffers
+    are not written and nothing is read back; `grad_state()` hands out the record.  A norm that is not finite (an inf or NaN
+    gradient) leaves parameters and moments untouched; an attached EMA still averages the unchanged parameters, as
+    `ema.step()` after a skipped `optimizer.step()` would.  `max_grad_norm=math.inf` computes norm and flag without clipping;
+    None (the default) is the plain step, with no norm at all."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
         if not math.isfinite(lr) or lr < 0.0:
@@ -125,6 +138,9 @@ class AdamW(torch.optim.Optimizer):
         defaults.update(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)
         self._flat = []
         self._ema = None
+        self._max_grad_norm = None  # clip_grad_norm(): the default of step(max_grad_norm=None)
+        self._grad_state = None     # device record of step(max_grad_norm=...): ctrlv_grad_state as four 32-bit words
+        self._partials = None       # fp64 partial sums of squares of all groups; dropped (regrown) by add_param_group
         super().__init__(params, defaults)
 
     # ---- layout
@@ -161,11 +177,21 @@ class AdamW(torch.optim.Optimizer):
                     p.grad = gv
                 _set_home(p, self, gi, i)
         self._flat.append(flat)
+        self._partials = None
 
     def attach_ema(self, ema):
         """Every later `step()` carries `ema` (a `ctrlv_amd.optim.EMAModel`, or None to detach) as `step(ema=ema)` would: for
         callers that do not make the `step()` call themselves (`training.unet_train_step(unet, batch, optimizer)`)."""
         self._ema = ema
+        return self
+
+    def clip_grad_norm(self, max_grad_norm):
+        """Every later `step()` without a `max_grad_norm` of its own clips to this global norm, as `step(max_grad_norm=...)` would
+        (None: no clipping again): for callers that do not make the `step()` call themselves and whose step function takes no such
+        argument (`training.vae_train_step(vae, batch, optimizer)`)."""
+        if max_grad_norm is not None and not _f32(max_grad_norm) > 0.0:
+            raise ValueError(f"Invalid max_grad_norm: {max_grad_norm} (must be positive; math.inf: the norm without clipping)")
+        self._max_grad_norm = max_grad_norm
         return self
 
     def flat_buffers(self, group_index):
@@ -234,7 +260,11 @@ class AdamW(torch.optim.Optimizer):
         return runs
 
     @torch.no_grad()
-    def step(self, closure=None, ema=None, grad_scale=1.0):
+    def step(self, closure=None, ema=None, grad_scale=1.0, max_grad_norm=None):
+        if max_grad_norm is None:
+            max_grad_norm = self._max_grad_norm                                      # (None unless clip_grad_norm() set one)
+        if max_grad_norm is not None and not _f32(max_grad_norm) > 0.0:             # (false for NaN too) before any device work
+            raise ValueError(f"Invalid max_grad_norm: {max_grad_norm} (must be positive; math.inf: the norm without clipping)")
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -242,6 +272,11 @@ class AdamW(torch.optim.Optimizer):
         if ema is None:
             ema = self._ema
         ema_decay = ema._begin_fused_step(self) if ema is not None else 0.0
+        if max_grad_norm is not None:
+            self._step_clipped(ema, ema_decay, float(grad_scale), float(max_grad_norm))
+            if ema is not None:
+                ema._end_fused_step(self)
+            return loss
         for gi, group in enumerate(self.param_groups):
             params = group["params"]
             if not params:
@@ -269,6 +304,69 @@ class AdamW(torch.optim.Optimizer):
         if ema is not None:
             ema._end_fused_step(self)
         return loss
+
+    def _step_clipped(self, ema, ema_decay, grad_scale, max_grad_norm):
+        """`step(max_grad_norm=...)`: the sum of squares of every run of every group into one partials array, one finish, then
+        `ctrlv_adamw_step_dev` per run, all on the current stream and without a host read."""
+        plan, dev, lib = [], None, None
+        for gi, group in enumerate(self.param_groups):
+            params = group["params"]
+            if not params:
+                continue
+            flat = self._flat[gi]
+            lib = _lib_for_device(flat.p)
+            if dev is None:
+                dev = flat.p.device
+            elif flat.p.device != dev:
+                raise ValueError(f"ctrlv_amd.optim.AdamW.step: max_grad_norm takes ONE norm over all groups, and group {gi} lives on "
+                                 f"{flat.p.device}, not on {dev}")
+            for i, p in enumerate(params):
+                self._check_home(gi, i, p)
+            self._own_gradients(gi, group)
+            plan.append((gi, group, flat, [(flat.offsets[first], flat.offsets[last] + params[last].numel() - flat.offsets[first],
+                                            first, last, t) for first, last, t in self._runs(gi, group)]))
+        if not any(runs for _, _, _, runs in plan):
+            return
+        if self._grad_state is None or self._grad_state.device != dev:
+            self._grad_state = torch.zeros(4, dtype=torch.int32, device=dev)          # ctrlv_grad_state: norm, coef, skip, skipped_total
+        if self._partials is None or self._partials.device != dev:
+            # a run of n elements takes ceil(n / 4096) slots: at most numel // 4096 + 1 + (number of parameters) per group,
+            # however the runs fall
+            cap = sum(f.numel // 4096 + 1 + len(f.offsets) for f in self._flat)
+            self._partials = torch.empty(cap, dtype=torch.float64, device=dev)
+        partials, state, slot = self._partials, ctypes.c_void_p(self._grad_state.data_ptr()), 0
+        for gi, group, flat, runs in plan:
+            for off, n, _, _, _ in runs:
+                _lib.check(lib.ctrlv_grad_sumsq(_ptr(flat.g, off), n, ctypes.c_void_p(partials.data_ptr()), partials.numel(), slot,
+                                                _stream()), "ctrlv_grad_sumsq", lib)
+                slot += lib.ctrlv_grad_sumsq_partials(n)
+        _lib.check(lib.ctrlv_grad_finish(ctypes.c_void_p(partials.data_ptr()), slot, grad_scale, max_grad_norm, state, _stream()),
+                   "ctrlv_grad_finish", lib)
+        for gi, group, flat, runs in plan:
+            params = group["params"]
+            lr, wd, eps = float(group["lr"]), float(group["weight_decay"]), float(group["eps"])
+            b1, b2 = _f32(group["betas"][0]), _f32(group["betas"][1])
+            shadow = ema._shadow_flat(self, gi) if ema is not None else None
+            for off, n, first, last, t in runs:
+                bias1, bias2 = 1.0 - b1 ** (t + 1), 1.0 - b2 ** (t + 1)
+                _lib.check(lib.ctrlv_adamw_step_dev(_ptr(flat.p, off), _ptr(flat.g, off), _ptr(flat.m, off), _ptr(flat.v, off),
+                                                    _ptr(shadow, off) if shadow is not None else None, n, lr, b1, b2, eps, wd,
+                                                    bias1, bias2, grad_scale, ema_decay, state, _stream()),
+                           "ctrlv_adamw_step_dev", lib)
+                for p in params[first:last + 1]:
+                    self.state[p]["step"] += 1                      # ATTEMPTED steps: the host does not know about a skip
+            torch.autograd.graph.increment_version([p for p in params if p.requires_grad])
+
+    def grad_state(self):
+        """The record of the last `step(max_grad_norm=...)` as 0-dim DEVICE tensors: `norm` (fp32, of the gradients times
+        grad_scale, over all groups), `coef` (fp32, what the gradients were multiplied by), `skip` (int32, 1: the norm was not
+        finite and the step left parameters and moments alone) and `skipped_total` (int32, skipped steps so far).  No
+        synchronisation happens here; the tensors are views of the record, which the next such step overwrites -- read or clone
+        them when convenient (with the loss, at logging time)."""
+        s = self._grad_state
+        if s is None:
+            raise RuntimeError("ctrlv_amd.optim.AdamW.grad_state: no step(max_grad_norm=...) has run yet")
+        return {"norm": s[0].view(torch.float32), "coef": s[1].view(torch.float32), "skip": s[2], "skipped_total": s[3]}
 
     def load_state_dict(self, state_dict):
         """torch's layout (per-parameter step / exp_avg / exp_avg_sq, param_groups): the moments are copied into the flat

@@ -22,6 +22,7 @@ import torch.distributed as dist
 import torch.nn.functional as Fn
 
 from . import ops
+from . import optim as _optim
 from .autograd import (GroupNormSiLU, TimeConvOut, f32, gemm, gradient_checkpointing, prefetch_mix_factors,
                        res_block_train_forward, sinusoid, transformer_train_forward, vae_attention_train_forward,
                        vae_res_block_train_forward, zero_conv_train_forward)
@@ -258,8 +259,9 @@ def edm_loss(pred_rows, noisy_latents, target_latents, sigmas):
 
 
 def train_step(controlnet, unet, batch, optimizer=None, conditioning_scale=1.0, world_size=1, buckets=None,
-               accumulate=False, loss_scale=1.0):
-    """One optimisation step.  Data parallel: pass `buckets=GradientBuckets(params)` (all-reduce overlapped with the
+               accumulate=False, loss_scale=1.0, max_grad_norm=None):
+    """One optimisation step.  max_grad_norm: clip the gradients to that global norm in front of the optimiser step (the
+    reference's --max_grad_norm; see `_backward_and_step`; None: no clipping).  Data parallel: pass `buckets=GradientBuckets(params)` (all-reduce overlapped with the
     backward pass), or only `world_size > 1` for the simple reduce-after-backward path.
     Gradient accumulation (`accelerator.accumulate`, gradient_accumulation_steps of train_video_controlnet.py:376): call
     with accumulate=True and loss_scale=1/steps for every micro-batch but the last -- gradients add up locally, nothing is
@@ -273,23 +275,23 @@ def train_step(controlnet, unet, batch, optimizer=None, conditioning_scale=1.0, 
                                          conditioning_scale)
     pred = unet_train_forward(unet, sample, timesteps, batch["encoder_hidden_states"], batch["added_time_ids"], down, mid)
     loss = edm_loss(pred, noisy, lat, sig)
-    return _backward_and_step(controlnet, loss, optimizer, world_size, buckets, accumulate, loss_scale)
+    return _backward_and_step(controlnet, loss, optimizer, world_size, buckets, accumulate, loss_scale, max_grad_norm)
 
 
-def unet_train_step(unet, batch, optimizer=None, world_size=1, buckets=None, accumulate=False, loss_scale=1.0):
+def unet_train_step(unet, batch, optimizer=None, world_size=1, buckets=None, accumulate=False, loss_scale=1.0, max_grad_norm=None):
     """One stage-1 optimisation step: the whole UNet fine-tuned (tools/train_video_diffusion.py:515-541; UNet forward,
     EDM loss, backward, optimizer step).  Which parameters train is the caller's choice through `unet.enable_grad(...)`
     (all=True: the demo scripts; temporal_transformer_block=True: temporal-only mode) -- frozen parameters get no gradient,
     and switching modes between steps needs nothing else (packed forms are cached only for frozen parameters, keyed on
     their version).  batch: `train_step`'s keys without control_cond; image_latents (B,F,4,h,w) per frame (the
     predict-bbox layout passes unchanged), encoder_hidden_states with the caller's conditioning dropout already applied.
-    Data parallel / gradient accumulation / zero gradients for parameters without a gradient path: as in `train_step`.
-    Returns the detached loss."""
+    Data parallel / gradient accumulation / max_grad_norm / zero gradients for parameters without a gradient path: as in
+    `train_step`.  Returns the detached loss."""
     prefetch_mix_factors(unet)
     lat, sig, noisy, timesteps, sample = _noised_inputs(batch)
     pred = unet_full_train_forward(unet, sample, timesteps, batch["encoder_hidden_states"], batch["added_time_ids"])
     loss = edm_loss(pred, noisy, lat, sig)
-    return _backward_and_step(unet, loss, optimizer, world_size, buckets, accumulate, loss_scale)
+    return _backward_and_step(unet, loss, optimizer, world_size, buckets, accumulate, loss_scale, max_grad_norm)
 
 
 def _noised_inputs(batch):
@@ -333,8 +335,12 @@ def prepare_batch(plan, clips, box_frames=None, *, mode, seed, step, num_cond_fr
     return batch
 
 
-def _backward_and_step(model, loss, optimizer, world_size, buckets, accumulate, loss_scale):
-    """backward, gradient reduction and optimizer step of `train_step` / `unet_train_step` (model: the trained one)."""
+def _backward_and_step(model, loss, optimizer, world_size, buckets, accumulate, loss_scale, max_grad_norm=None):
+    """backward, gradient reduction and optimizer step of `train_step` / `unet_train_step` (model: the trained one).
+    max_grad_norm: the gradients are clipped to that global L2 norm in front of the step (the reference's --max_grad_norm,
+    `accelerator.clip_grad_norm_`): a `ctrlv_amd.optim.AdamW` does it inside its own pass on the device
+    (`step(max_grad_norm=...)`), any other optimiser gets `torch.nn.utils.clip_grad_norm_` over its parameters.  Either way the
+    norm is taken AFTER the gradient reduction: every rank computes the same bits from the same gradients, no collective is added."""
     if buckets is not None:
         buckets.enabled = not accumulate
     (loss * loss_scale if loss_scale != 1.0 else loss).backward()
@@ -350,7 +356,14 @@ def _backward_and_step(model, loss, optimizer, world_size, buckets, accumulate, 
         if p.requires_grad and p.grad is None:
             p.grad = torch.zeros_like(p)
     if optimizer is not None:
-        optimizer.step()
+        if max_grad_norm is None:
+            optimizer.step()
+        elif isinstance(optimizer, _optim.AdamW):
+            optimizer.step(max_grad_norm=max_grad_norm)
+        else:
+            torch.nn.utils.clip_grad_norm_([p for g in optimizer.param_groups for p in g["params"] if p.grad is not None],
+                                           max_grad_norm)
+            optimizer.step()
         optimizer.zero_grad(set_to_none=True)
     return loss.detach()
 
@@ -551,7 +564,9 @@ def vae_train_step(vae, batch, optimizer=None, num_frames=1, sample_posterior=Tr
     no_grad on the HIP encoder path; the decoder runs `vae_decoder_train_forward`; clamp and MSE are plain torch on the
     image-sized fp32 prediction.  Which decoder parameters train is the caller's choice through requires_grad (the
     reference: all of them); encoder and quant_conv are never touched.  Data parallel / gradient accumulation: as in
-    `train_step` (the reduced model is the decoder).  Returns the detached loss."""
+    `train_step` (the reduced model is the decoder).  Gradient clipping: this step's argument list is pinned by its tests, so the
+    norm is set on the optimiser -- `ctrlv_amd.optim.AdamW(...).clip_grad_norm(max_norm)` clips in every later `step()`.
+    Returns the detached loss."""
     px = batch["pixel_values"]
     if px.dim() != 4 or px.shape[1] != vae.config.in_channels:
         raise ValueError(f"vae_train_step: pixel_values must be (B, {vae.config.in_channels}, H, W), got {tuple(px.shape)}")

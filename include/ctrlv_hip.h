@@ -49,7 +49,9 @@ enum {
  * ctrlv_resize_antialias, ctrlv_pixels_prepare, ctrlv_frames_to_u8) or the seeded-clip entry points (ctrlv_randn,
  * ctrlv_euler_schedule, ctrlv_resize_lanczos_u8, ctrlv_pipeline_prepare, ctrlv_pipeline_generate_seeded) or the per-frame quality
  * entry points (ctrlv_frame_stats, ctrlv_frame_ssim, ctrlv_frame_ssim_ws_bytes, ctrlv_resize_frames_u8,
- * ctrlv_resize_frames_ws_bytes) or the LPIPS entry points (ctrlv_lpips_*, ctrlv_relu_maxpool_rows) or the optimiser pass (ctrlv_adamw_step, ctrlv_ema_step), and a host that needs them fails at symbol lookup on a library without them.
+ * ctrlv_resize_frames_ws_bytes) or the LPIPS entry points (ctrlv_lpips_*, ctrlv_relu_maxpool_rows) or the optimiser pass (ctrlv_adamw_step, ctrlv_ema_step)
+ * or the gradient-norm clipping in front of it (ctrlv_grad_sumsq, ctrlv_grad_sumsq_partials, ctrlv_grad_finish,
+ * ctrlv_adamw_step_dev), and a host that needs them fails at symbol lookup on a library without them.
  * NOT neutral, although the number did not move: ctrlv_gemm_desc.pad_br gives meaning to four bytes that were alignment
  * padding, so descriptors must now be zero-initialised (see the field). */
 int ctrlv_abi_version(void);
@@ -1420,6 +1422,50 @@ int ctrlv_adamw_step(float* p, const float* g, float* m, float* v, float* ema, s
                      ctrlv_stream_t stream);
 /* ema -= (1 - decay) * (ema - p) over n fp32 elements: the last line of ctrlv_adamw_step alone (same refusals). */
 int ctrlv_ema_step(float* ema, const float* p, size_t n, float decay, ctrlv_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Global gradient-norm clipping on the device, fused into the AdamW pass (csrc/optim.hip): what
+ * `accelerator.clip_grad_norm_(params, max_grad_norm)` in front of `optimizer.step()` does, without a second pass over the
+ * gradients and without a host read.  Three stages on one stream; the record stays on the device.
+ *
+ * The device record.  16 bytes, 16-byte aligned, zero-initialised by the caller once (skipped_total is a running count). */
+typedef struct ctrlv_grad_state {
+  float norm;            /* fp32(|grad_scale| * sqrt(S)), S the fp64 sum of squares: rounded ONCE, from double */
+  float coef;            /* clamp(max_norm / (norm + 1e-6f), max = 1), torch's clip_grad_norm_ formula with the add and ONE
+                          * correctly rounded divide in fp32: what fp32 tensors give on the device (with max_norm as a Python
+                          * scalar torch divides as reciprocal() * max_norm, which can differ in the last bit).  A NaN norm
+                          * gives NaN, as there; 1 when max_norm is +inf */
+  int32_t skip;          /* 1 when norm is not finite (a NaN or inf element, or S beyond fp32 after the scale), else 0 */
+  int32_t skipped_total; /* += skip on every ctrlv_grad_finish */
+} ctrlv_grad_state;
+
+/* Stage 1.  Slots of `partials` that ctrlv_grad_sumsq fills for n elements: one per block of 4096 elements,
+ * ceil(n / 4096).  A function of n alone -- not of the device, its CU count or the environment: the same partition, and so the same
+ * bits, everywhere. */
+size_t ctrlv_grad_sumsq_partials(size_t n);
+/* partials[slot0 + b] = sum of (double)g[i] * (double)g[i] (each product exact) over block b = [4096 b, min(n, 4096 (b + 1))),
+ * added in fp64 in a fixed order (per lane in element order, then a fixed tree over the workgroup).  No atomics: the same bits in
+ * every run.  g (fp32, 16-byte aligned) is read once, with 16-byte loads and a scalar tail for n % 4, and never written;
+ * nothing at or past element n is read; exactly the slots [slot0, slot0 + ctrlv_grad_sumsq_partials(n)) are written, so the runs
+ * of several parameter groups fill one array.  Refused on the host (CTRLV_E_BAD_ARG; n == 0: CTRLV_E_BAD_SHAPE): NULL or
+ * misaligned g, NULL or 8-byte-misaligned partials, a slot range that ends beyond partials_len. */
+int ctrlv_grad_sumsq(const float* g, size_t n, double* partials, size_t partials_len, size_t slot0, ctrlv_stream_t stream);
+/* Stage 2, one workgroup.  S = partials[0] + ... + partials[count - 1] in fp64 in a fixed order (lane l of 1024 adds slots
+ * l, l + 1024, ... in index order, then a fixed tree), then the record as its fields say.  grad_scale is the multiplier the
+ * step applies to the gradients (the norm is that of the scaled gradients); max_norm = +inf asks for the norm and the skip flag
+ * without clipping.  Refused on the host: NULL / misaligned pointers, count == 0 (CTRLV_E_BAD_SHAPE), max_norm that is not
+ * positive or is NaN, a grad_scale that is not finite. */
+int ctrlv_grad_finish(const double* partials, size_t count, float grad_scale, float max_norm, ctrlv_grad_state* state,
+                      ctrlv_stream_t stream);
+/* Stage 3.  ctrlv_adamw_step with the gradient taken as (g * grad_scale) * state->coef -- two fp32 multiplications in that order,
+ * as an unscale followed by torch's mul_(clip_coef) -- and every constant derived on the host exactly as there.  state->skip
+ * set: nothing is written to p, m or v (g, m and v are not even read); with ema != NULL the shadow is still updated against the
+ * UNCHANGED p, bit for bit what ctrlv_ema_step gives (`ema.step()` after a skipped `optimizer.step()`).  With coef = 1 and
+ * skip = 0 the result equals ctrlv_adamw_step's bit for bit.  coef and skip are read from device memory by the kernel: no host
+ * synchronisation.  Same refusals as ctrlv_adamw_step, plus a NULL or misaligned state. */
+int ctrlv_adamw_step_dev(float* p, const float* g, float* m, float* v, float* ema, size_t n, float lr, float beta1, float beta2,
+                         float eps, float weight_decay, float bias1, float bias2, float grad_scale, float ema_decay,
+                         const ctrlv_grad_state* state, ctrlv_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -35,6 +35,9 @@ def main():
     ap.add_argument("--optimizer", choices=("torch", "hip"), default="torch",
                     help="torch: torch.optim.AdamW; hip: ctrlv_amd.optim.AdamW (flat buffers, csrc/optim.hip)")
     ap.add_argument("--ema", type=int, default=0, help="1: EMA of the trained parameters (ctrlv_amd.optim.EMAModel), timed in optimizer_ms")
+    ap.add_argument("--max-grad-norm", type=float, default=None,
+                    help="clip the gradients to this global norm, timed in optimizer_ms (the reference's --max_grad_norm, default 1.0 "
+                         "there): inside the AdamW pass with --optimizer hip, torch.nn.utils.clip_grad_norm_ with torch")
     ap.add_argument("--gradient-checkpointing", type=int, default=0,
                     help="1: unet.enable_gradient_checkpointing() + controlnet.enable_gradient_checkpointing() (the GEGLU "
                          "feed-forward intermediates are recomputed in the backward; tools/train_video_controlnet.py:185-186)")
@@ -114,7 +117,13 @@ def main():
         if buckets is not None:
             buckets.finish()
         e[2].record()
-        opt.step()
+        if args.max_grad_norm is None:
+            opt.step()
+        elif args.optimizer == "hip":
+            opt.step(max_grad_norm=args.max_grad_norm)            # norm, coefficient and skip flag on the device, inside the pass
+        else:
+            torch.nn.utils.clip_grad_norm_(params, args.max_grad_norm)
+            opt.step()
         if ema is not None and args.optimizer != "hip":
             ema.step(params)
         opt.zero_grad(set_to_none=True)
@@ -141,6 +150,7 @@ def main():
                       "tflops": round(tf / avg[0] * 1e3, 1), "peak_mem_gb": round(torch.cuda.max_memory_allocated() / 2**30, 1),
                       "losses": [round(v, 5) for v in losses],
                       "gradient_checkpointing": bool(args.gradient_checkpointing), "optimizer": args.optimizer, "ema": bool(args.ema),
+                      **({"max_grad_norm": args.max_grad_norm} if args.max_grad_norm is not None else {}),
                       "dtype": "bf16 compute, fp32 master parameters + AdamW",
                       "data": "synthetic, random-init weights"}))
 
