@@ -396,6 +396,9 @@ SIGNATURES = {
     "ctrlv_grad_finish": (c_int, [c_void_p, c_size_t, c_float, c_float, c_void_p, c_void_p]),
     "ctrlv_adamw_step_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float, c_float, c_float,
                                      c_float, c_float, c_float, c_float, c_float, c_void_p, c_void_p]),
+    "ctrlv_grad_finish_scaled": (c_int, [c_void_p, c_size_t, c_float, c_float, c_void_p, c_void_p, c_void_p]),
+    "ctrlv_adamw_step_scaled": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float, c_float, c_float,
+                                        c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
 }
 
 _libs = {}                # element dtype code (2 bf16 / 1 fp16) -> CDLL

@@ -9,7 +9,9 @@ per-clip row vector V, s_acc}, GroupNorm(+SiLU) in its 4-D and 5-D forms, and th
   dgrad  = the forward kernel on role-swapped weights (Linear: W^T; convs: taps reversed, channels transposed)
   wgrad  = ctrlv_gemm_wgrad (transposed-LDS-read MFMA kernel), bias / row-vector gradients = ctrlv_colsum
   norms  = ctrlv_groupnorm_bwd on the statistics the forward saved
-Activations and activation gradients are bf16 rows; parameter gradients are fp32 in the PyTorch layouts.
+Activations and activation gradients are 16-bit rows of ONE element type per call -- bf16, or fp16 where the input rows are fp16
+(every allocation takes the type of the rows it belongs to, `ops` picks the library by it, and the cached packed forms of frozen
+parameters key on it) --; parameter gradients are fp32 in the PyTorch layouts.
 Second slice: LayerNorm, GEGLU, the attention cores (flash-style backward, csrc/attention_bwd.hip), the second residual
 and the indexed row vector of the epilogue => a complete `TransformerSpatioTemporalModel`; stride-2 and upsample-fused
 convs; LoRA factors.  The model-level training step built from these lives in ctrlv_amd/training.py.
@@ -29,8 +31,16 @@ from . import frozen as frozen_cache, lora as lora_mod, ops, packing
 from .frozen import frozen
 
 
+_ELEMENT_TYPES = (torch.bfloat16, torch.float16)
+
+
+def _el(t):
+    """The element type of the rows `t` belongs to: its own 16-bit type (bf16 for anything else)."""
+    return t.dtype if t.dtype in _ELEMENT_TYPES else torch.bfloat16
+
+
 def _rows(M, C, like):
-    return torch.empty(M, C, dtype=torch.bfloat16, device=like.device)
+    return torch.empty(M, C, dtype=_el(like), device=like.device)
 
 
 def clear_pack_cache():
@@ -61,14 +71,25 @@ def _bias32(bias):
     return _packed(bias, "bias32", packing.pad_bias)
 
 
-def _pack_fwd(weight, mode, geglu=False):
-    """bf16 forward GEMM layout of a parameter: one kernel (ctrlv_pack_weight) where the shape allows, else packing.py."""
-    out = ops.pack_weight(weight, 0, geglu) if weight.is_cuda else None
+def _pack_fwd(weight, mode, geglu=False, el=torch.bfloat16):
+    """Forward GEMM layout of a parameter in the element type `el`: one kernel (ctrlv_pack_weight) where the shape allows, else
+    packing.py."""
+    out = ops.pack_weight(weight, 0, geglu, el) if weight.is_cuda else None
     if out is not None:
         return out
-    if geglu:
-        return packing.pack_geglu(weight, weight.new_zeros(weight.shape[0]))[0]
-    return (packing.pack_linear if mode == 0 else (packing.pack_conv3x3 if mode == 1 else packing.pack_conv_temporal))(weight)
+    with packing.element_dtype(el):
+        if geglu:
+            return packing.pack_geglu(weight, weight.new_zeros(weight.shape[0]))[0]
+        return (packing.pack_linear if mode == 0 else (packing.pack_conv3x3 if mode == 1 else packing.pack_conv_temporal))(weight)
+
+
+def _packed_fwd(weight, mode, el):
+    """... cached per element type for frozen parameters: the same model may be stepped in either type"""
+    return _packed(weight, ("fwd", mode, el), lambda w: _pack_fwd(w, mode, el=el))
+
+
+def _packed_geglu(weight, el):
+    return _packed(weight, ("fwd_geglu", el), lambda w: _pack_fwd(w, 0, geglu=True, el=el))
 
 
 _TAPS = {0: 1, 1: 9, 2: 3}
@@ -103,7 +124,7 @@ def _gemm_forward(A, weight, bias, R1, R2, V, spec):
         H, W, Ho, Wo = spec.conv[:4]
         m_out = A.shape[0] // (H * W) * Ho * Wo
     out = _rows(m_out, N, A)
-    ops.gemm(A, _packed(weight, ("fwd", mode), lambda w: _pack_fwd(w, mode)), out, N=(N + 31) // 32 * 32, cin=cin,
+    ops.gemm(A, _packed_fwd(weight, mode, _el(A)), out, N=(N + 31) // 32 * 32, cin=cin,
              taps=_TAPS[mode], mode=mode, conv=spec.conv, temporal=spec.temporal,
              bias=None if bias is None else _bias32(bias), s_acc=float(spec.s_acc), R1=R1, s1=float(spec.s1), R2=R2,
              s2=float(spec.s2), V=V, vmode=spec.vmode if V is not None else 0, vdiv=spec.vdiv, vmod=spec.vmod, vS=spec.vS)
@@ -220,21 +241,23 @@ def gemm_grads(A, weight, dY, geom, s_acc, need_dA=True, need_dW=True, need_db=T
         npad = (N + 63) // 64 * 64
         dYd = _pad_cols(dY, npad)
         conv = geom.get("conv")
+        el = _el(dY)
 
         def swapped(_):
-            direct = ops.pack_weight(weight, 1) if weight.is_cuda else None     # one kernel incl. the zero padding of N
+            direct = ops.pack_weight(weight, 1, dtype=el) if weight.is_cuda else None     # one kernel incl. the zero padding of N
             if direct is not None:
                 return direct
             wd = weight.detach()
             if npad != N:
                 wd = torch.cat([wd, wd.new_zeros((npad - N,) + tuple(wd.shape[1:]))], 0)
-            if mode == 0:
-                return packing.pack_linear(wd.reshape(npad, cin).t())
-            if mode == 1:
-                return packing.pack_conv3x3(wd.flip(2, 3).transpose(0, 1))
-            return packing.pack_conv_temporal(wd.flip(2).transpose(0, 1))
+            with packing.element_dtype(el):
+                if mode == 0:
+                    return packing.pack_linear(wd.reshape(npad, cin).t())
+                if mode == 1:
+                    return packing.pack_conv3x3(wd.flip(2, 3).transpose(0, 1))
+                return packing.pack_conv_temporal(wd.flip(2).transpose(0, 1))
 
-        wt = _packed(weight, ("dgrad", mode), swapped)
+        wt = _packed(weight, ("dgrad", mode, el), swapped)
         if mode == 1:
             H, W, Ho, Wo, stride, up = conv
             n_img = dY.shape[0] // (Ho * Wo)
@@ -252,7 +275,7 @@ def gemm_grads(A, weight, dY, geom, s_acc, need_dA=True, need_dW=True, need_db=T
         if mode == 1 and geom["conv"][5]:
             H, W = geom["conv"][0], geom["conv"][1]
             n_img = A.shape[0] // (H * W)
-            dA = dA.view(n_img, H, 2, W, 2, cin).float().sum((2, 4)).to(torch.bfloat16).view(n_img * H * W, cin)
+            dA = dA.view(n_img, H, 2, W, 2, cin).float().sum((2, 4)).to(dA.dtype).view(n_img * H * W, cin)
     if need_dW:
         # one kernel: dW (scaled by s_acc) and, riding along in the workgroups that stream dY anyway, the bias gradient.
         # Linear weights are written in place; conv weights in the packed tap-major order and permuted afterwards
@@ -479,7 +502,7 @@ class _GegluCell:
         if self.done:
             return
         two_i = self.w.shape[0]
-        wp, bp = _packed(self.w, "fwd_geglu", lambda w: _pack_fwd(w, 0, geglu=True)), _geglu_bias32(self.b)
+        wp, bp = _packed_geglu(self.w, _el(self.x)), _geglu_bias32(self.b)
         M = self.x.shape[0]
         self.u, self.raw = _rows(M, two_i // 2, self.x), _rows(M, two_i, self.x)
         ops.gemm(self.x, wp, self.u, N=two_i, cin=wp.shape[1], bias=bp, geglu=1, raw_out=self.raw)
@@ -546,7 +569,7 @@ class GegluProj(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias):
         two_i, cin = weight.shape
-        wp, bp = _packed(weight, "fwd_geglu", lambda w: _pack_fwd(w, 0, geglu=True)), _geglu_bias32(bias)
+        wp, bp = _packed_geglu(weight, _el(x)), _geglu_bias32(bias)
         u = _rows(x.shape[0], two_i // 2, x)
         # (a cell only where a backward will run: under torch.no_grad() / with no input requiring grad -- an evaluation pass
         #  inside a checkpointed training context -- Function.forward still executes, but no consumer ever saves u, so a cell
@@ -575,7 +598,8 @@ class GegluProj(torch.autograd.Function):
             raw = ctx.cell.take("raw")                                 # (recomputed together with u: one launch)
             ctx.cell = None
         elif not ctx.has_raw:
-            wp, bp = packing.pack_geglu(weight, bias)
+            with packing.element_dtype(_el(x)):
+                wp, bp = packing.pack_geglu(weight, bias)
             raw = _rows(x.shape[0], two_i, x)
             ops.gemm(x, wp, raw, N=two_i, cin=wp.shape[1], bias=bp)    # activation recompute (no GEGLU epilogue)
         draw = torch.empty_like(raw)
@@ -819,9 +843,9 @@ def vae_res_block_train_forward(block, x, n_clips, F, H, W):
     return BlendGemm.apply(hn, t.conv2.weight, t.conv2.bias, xs, None, block.time_mixer.mix_factor, GemmSpec(**g3d), True)
 
 
-def _rows16(weight):
+def _rows16(weight, el=torch.bfloat16):
     """element-type copy of a [N, K] parameter in its own layout (the A operand of a role-swapped GEMM)"""
-    return _packed(weight, "rows16", lambda w: w.detach().to(torch.bfloat16).contiguous())
+    return _packed(weight, ("rows16", el), lambda w: w.detach().to(el).contiguous())
 
 
 class VaeAttentionCore(torch.autograd.Function):
@@ -839,9 +863,10 @@ class VaeAttentionCore(torch.autograd.Function):
         C, dev = q.shape[1], q.device
         o = _rows(n * S, C, q)
         scores = torch.empty(S, S, dtype=torch.float32, device=dev)
-        probs = torch.empty(S, S, dtype=torch.bfloat16, device=dev)
-        vt = torch.empty(C, S, dtype=torch.bfloat16, device=dev)
-        wv_rows = _rows16(wv)
+        el = _el(q)
+        probs = torch.empty(S, S, dtype=el, device=dev)
+        vt = torch.empty(C, S, dtype=el, device=dev)
+        wv_rows = _rows16(wv, el)
         for f in range(n):
             r0, r1 = f * S, (f + 1) * S
             ops.gemm(q[r0:r1], k[r0:r1], scores, N=S, cin=C, s_acc=C ** -0.5, out_f32=True)
@@ -860,15 +885,16 @@ class VaeAttentionCore(torch.autograd.Function):
         scale = C ** -0.5
         do = do.contiguous()
         v = _rows(M, C, q)                                                          # V rows of every frame: one GEMM
-        ops.gemm(t, _packed(wv, ("fwd", 0), lambda w: _pack_fwd(w, 0)), v, N=C, cin=C)
+        el = _el(q)
+        ops.gemm(t, _packed_fwd(wv, 0, el), v, N=C, cin=C)
         new = torch.empty if ops.DETERMINISTIC else torch.zeros
         dq = _rows(M, C, q)
         dk32 = new(M, C, dtype=torch.float32, device=dev)
         dv32 = new(M, C, dtype=torch.float32, device=dev)
         scores = torch.empty(S, S, dtype=torch.float32, device=dev)
         dp = torch.empty(S, S, dtype=torch.float32, device=dev)
-        probs = torch.empty(S, S, dtype=torch.bfloat16, device=dev)
-        ds = torch.empty(S, S, dtype=torch.bfloat16, device=dev)
+        probs = torch.empty(S, S, dtype=el, device=dev)
+        ds = torch.empty(S, S, dtype=el, device=dev)
         flat = dict(N=S, cin=C, torch_layout=True, assign=ops.DETERMINISTIC)
         for f in range(n):
             r0, r1 = f * S, (f + 1) * S
@@ -880,8 +906,8 @@ class VaeAttentionCore(torch.autograd.Function):
             ops.gemm_wgrad(q[r0:r1], ds, dk32[r0:r1], **flat)                       # dK = dS^T Q
             ops.gemm_wgrad(do[r0:r1], probs, dv32[r0:r1], **flat)                   # dV = P^T dO
         need = ctx.needs_input_grad
-        dt, dwv, _ = gemm_grads(t, wv, dv32.to(torch.bfloat16), dict(mode=0), 1.0, need[2], need[3], False)
-        return dq, dk32.to(torch.bfloat16), dt, dwv, None, None
+        dt, dwv, _ = gemm_grads(t, wv, dv32.to(el), dict(mode=0), 1.0, need[2], need[3], False)
+        return dq, dk32.to(el), dt, dwv, None, None
 
 
 class _ExactZeroGrad(torch.autograd.Function):

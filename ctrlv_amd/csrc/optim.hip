@@ -137,11 +137,10 @@ __global__ __launch_bounds__(kThreads) void ema_kernel(float* __restrict__ ema, 
 // the record was written by an earlier launch and nobody writes it during this one).  A skipped step leaves p, m and v alone and
 // reads neither g, m nor v; the shadow still moves towards the unchanged p, as ema_kernel would move it.
 template <bool EMA>
-__global__ __launch_bounds__(kThreads) void adamw_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                             float* __restrict__ v, float* __restrict__ ema, size_t n, adamw_consts c,
-                                                             const ctrlv_grad_state* __restrict__ state) {
-  const float coef = state->coef;
-  if (state->skip) {
+__device__ __forceinline__ void adamw_dev_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                               float* __restrict__ v, float* __restrict__ ema, size_t n, const adamw_consts& c,
+                                               float coef, int skip) {
+  if (skip) {
     if (EMA) ema_block(ema, p, n, c.ema_omd);
     return;
   }
@@ -183,6 +182,24 @@ __global__ __launch_bounds__(kThreads) void adamw_dev_kernel(float* __restrict__
     p[t] = pk, m[t] = mk, v[t] = vk;
     if (EMA) ema[t] = ema_one(ema[t], pk, c.ema_omd);
   }
+}
+
+template <bool EMA>
+__global__ __launch_bounds__(kThreads) void adamw_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                             float* __restrict__ v, float* __restrict__ ema, size_t n, adamw_consts c,
+                                                             const ctrlv_grad_state* __restrict__ state) {
+  adamw_dev_body<EMA>(p, g, m, v, ema, n, c, state->coef, state->skip);
+}
+
+// ctrlv_adamw_step_scaled: the same with the unscale multiplier read from the loss-scale record (written by grad_finish_scaled_kernel in
+// an earlier launch) in the place of the host's grad_scale: (g * ls->unscale) * state->coef.  g is only read.
+template <bool EMA>
+__global__ __launch_bounds__(kThreads) void adamw_scaled_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                                float* __restrict__ v, float* __restrict__ ema, size_t n, adamw_consts c,
+                                                                const ctrlv_loss_scale_state* __restrict__ ls,
+                                                                const ctrlv_grad_state* __restrict__ state) {
+  c.grad_scale = ls->unscale;
+  adamw_dev_body<EMA>(p, g, m, v, ema, n, c, state->coef, state->skip);
 }
 
 // ---- global gradient norm: stage 1, one fp64 partial per block of kBlockElems elements
@@ -234,24 +251,65 @@ __global__ __launch_bounds__(kThreads) void grad_sumsq_kernel(const float* __res
 
 // ---- stage 2, ONE workgroup: S, then the record.  Lane l adds slots l, l + 1024, ... in index order.
 constexpr int kFinishThreads = 1024;
+// the record from S and the multiplier of the gradients (thread 0 only); returns the skip flag
+__device__ __forceinline__ int finish_record(double s, float grad_scale, float max_norm, int force_skip,
+                                             ctrlv_grad_state* __restrict__ state) {
+  const float norm = (float)(fabs((double)grad_scale) * sqrt(s));          // rounded once
+  float coef = 1.0f;
+  if (max_norm < INFINITY) {
+    coef = max_norm / (norm + 1e-6f);                                       // torch: max_norm / (total_norm + 1e-6) ...
+    coef = coef > 1.0f ? 1.0f : coef;                                       // ... clamp(max=1.0): a NaN stays a NaN
+  }
+  const int skip = (isfinite(norm) && !force_skip) ? 0 : 1;
+  state->norm = norm;
+  state->coef = coef;
+  state->skip = skip;
+  state->skipped_total = state->skipped_total + skip;
+  return skip;
+}
+
 __global__ __launch_bounds__(kFinishThreads) void grad_finish_kernel(const double* __restrict__ partials, size_t count, float grad_scale,
                                                                      float max_norm, ctrlv_grad_state* __restrict__ state) {
   double s = 0.0;
 #pragma unroll 8
   for (size_t i = threadIdx.x; i < count; i += kFinishThreads) s += partials[i];
   s = block_sum_f64<kFinishThreads>(s);
+  if (threadIdx.x == 0) finish_record(s, grad_scale, max_norm, 0, state);
+}
+
+// ctrlv_grad_finish_scaled: the same sum in the same order; the multiplier is formed from the loss-scale record, and the thread that
+// wrote the grad record then updates the scale as torch's _amp_update_scale_ does (amp_update_scale_cuda_kernel: the products
+// are taken in double there, from factors that are doubles; a product of two fp32 numbers rounded once is the fp32 product).
+__global__ __launch_bounds__(kFinishThreads) void grad_finish_scaled_kernel(const double* __restrict__ partials, size_t count,
+                                                                            float grad_scale, float max_norm,
+                                                                            ctrlv_loss_scale_state* __restrict__ ls,
+                                                                            ctrlv_grad_state* __restrict__ state) {
+  double s = 0.0;
+#pragma unroll 8
+  for (size_t i = threadIdx.x; i < count; i += kFinishThreads) s += partials[i];
+  s = block_sum_f64<kFinishThreads>(s);
   if (threadIdx.x == 0) {
-    const float norm = (float)(fabs((double)grad_scale) * sqrt(s));        // rounded once
-    float coef = 1.0f;
-    if (max_norm < INFINITY) {
-      coef = max_norm / (norm + 1e-6f);                                     // torch: max_norm / (total_norm + 1e-6) ...
-      coef = coef > 1.0f ? 1.0f : coef;                                     // ... clamp(max=1.0): a NaN stays a NaN
+    const float scale = ls->scale;
+    const bool valid = scale > 0.f && isfinite(scale);                      // false for NaN
+    // torch: _scale.double().reciprocal().float(), then the host's multiplier in fp32.  An unusable scale: NaN, and a skip
+    const float unscale = valid ? grad_scale * (float)(1.0 / (double)scale) : NAN;
+    ls->unscale = unscale;
+    const int skip = finish_record(s, unscale, max_norm, valid ? 0 : 1, state);
+    if (valid) {
+      if (skip) {
+        ls->scale = scale * ls->backoff_factor;
+        ls->growth_tracker = 0;
+      } else {
+        const int32_t successful = ls->growth_tracker + 1;
+        if (successful == ls->growth_interval) {
+          const float grown = scale * ls->growth_factor;
+          if (isfinite(grown)) ls->scale = grown;
+          ls->growth_tracker = 0;
+        } else {
+          ls->growth_tracker = successful;
+        }
+      }
     }
-    const int skip = isfinite(norm) ? 0 : 1;
-    state->norm = norm;
-    state->coef = coef;
-    state->skip = skip;
-    state->skipped_total = state->skipped_total + skip;
   }
 }
 
@@ -385,6 +443,42 @@ extern "C" int ctrlv_adamw_step_dev(float* p, const float* g, float* m, float* v
     else
       hipLaunchKernelGGL(adamw_dev_kernel<false>, dim3(blocks_for(cnt)), dim3(kThreads), 0, (hipStream_t)stream, p + off, g + off,
                          m + off, v + off, (float*)nullptr, cnt, c, state);
+    CTRLV_LAUNCH_CHECK();
+  }
+  return CTRLV_OK;
+}
+
+// ---- dynamic loss scaling on the device: the finish that unscales by the record's scale and updates it, the step that reads both records
+extern "C" int ctrlv_grad_finish_scaled(const double* partials, size_t count, float grad_scale, float max_norm,
+                                        ctrlv_loss_scale_state* ls, ctrlv_grad_state* state, ctrlv_stream_t stream) {
+  CTRLV_CHECK_ARG(partials && state, "grad_finish_scaled: partials and state must be non-null");
+  CTRLV_CHECK_SHAPE(count > 0, "grad_finish_scaled: count must be positive");
+  CTRLV_CHECK_ARG(((uintptr_t)partials & 7) == 0, "grad_finish_scaled: partials must be 8-byte aligned");
+  CTRLV_CHECK_ARG(aligned16(state), "grad_finish_scaled: state must be 16-byte aligned");
+  CTRLV_CHECK_ARG(ls && aligned16(ls), "grad_finish_scaled: ls (the loss-scale record) must be non-null and 16-byte aligned");
+  CTRLV_CHECK_ARG(isfinite(grad_scale), "grad_finish_scaled: grad_scale must be finite");
+  CTRLV_CHECK_ARG(max_norm > 0.f, "grad_finish_scaled: max_norm must be positive (+inf: the norm without clipping)");
+  hipLaunchKernelGGL(grad_finish_scaled_kernel, dim3(1), dim3(kFinishThreads), 0, (hipStream_t)stream, partials, count, grad_scale,
+                     max_norm, ls, state);
+  CTRLV_LAUNCH_CHECK();
+  return CTRLV_OK;
+}
+
+extern "C" int ctrlv_adamw_step_scaled(float* p, const float* g, float* m, float* v, float* ema, size_t n, float lr, float beta1,
+                                       float beta2, float eps, float weight_decay, float bias1, float bias2, float ema_decay,
+                                       const ctrlv_loss_scale_state* ls, const ctrlv_grad_state* state, ctrlv_stream_t stream) {
+  adamw_consts c;
+  CTRLV_TRY(adamw_host(p, g, m, v, ema, n, lr, beta1, beta2, eps, weight_decay, bias1, bias2, 1.0f, ema_decay, c));
+  CTRLV_CHECK_ARG(ls && aligned16(ls), "adamw_step_scaled: ls (the loss-scale record) must be non-null and 16-byte aligned");
+  CTRLV_CHECK_ARG(state && aligned16(state), "adamw_step_scaled: state must be non-null and 16-byte aligned");
+  for (size_t off = 0; off < n; off += kMaxLaunchElems) {
+    const size_t cnt = n - off < kMaxLaunchElems ? n - off : kMaxLaunchElems;
+    if (ema)
+      hipLaunchKernelGGL(adamw_scaled_kernel<true>, dim3(blocks_for(cnt)), dim3(kThreads), 0, (hipStream_t)stream, p + off, g + off,
+                         m + off, v + off, ema + off, cnt, c, ls, state);
+    else
+      hipLaunchKernelGGL(adamw_scaled_kernel<false>, dim3(blocks_for(cnt)), dim3(kThreads), 0, (hipStream_t)stream, p + off, g + off,
+                         m + off, v + off, (float*)nullptr, cnt, c, ls, state);
     CTRLV_LAUNCH_CHECK();
   }
   return CTRLV_OK;

@@ -10,6 +10,7 @@ import ctypes
 import json
 import math
 import os
+import struct
 import weakref
 
 import torch
@@ -121,7 +122,18 @@ class AdamW(torch.optim.Optimizer):
     are not written and nothing is read back; `grad_state()` hands out the record.  A norm that is not finite (an inf or NaN
     gradient) leaves parameters and moments untouched; an attached EMA still averages the unchanged parameters, as
     `ema.step()` after a skipped `optimizer.step()` would.  `max_grad_norm=math.inf` computes norm and flag without clipping;
-    None (the default) is the plain step, with no norm at all."""
+    None (the default) is the plain step, with no norm at all.
+
+    `step(scaler=loss_scaler)` (a `ctrlv_amd.optim.LossScaler`; what `LossScaler.step(optimizer)` calls) is the step of a
+    loss-scaled backward: always the three stages, with the last two in their scaled forms (`ctrlv_grad_finish_scaled`,
+    `ctrlv_adamw_step_scaled`).  The finish launch forms the unscale multiplier from the scale on the device, takes norm,
+    coefficient and skip flag of the UNSCALED gradients, and updates the scale (backoff on a skip, growth after
+    `growth_interval` good steps); the AdamW pass multiplies each gradient by multiplier and coefficient as it reads it.  Without
+    `max_grad_norm` the norm is taken without clipping (max_norm = +inf): a loss-scaled step costs the one extra read of the
+    gradients that clipping costs, and clipping on top of it costs nothing more.  `grad_scale` stays a host multiplier folded into
+    the unscale (the 1 / steps of gradient accumulation); `grad_state()` works as for a clipped step.  The gradient buffers are NOT
+    written: `.grad` stays SCALED after the step, unlike after torch's `unscale_`.  Step counts stay ATTEMPTED steps:
+    `torch.amp.GradScaler` does not count a skipped step, so after k skips the bias corrections here are those of step t + k."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
         if not math.isfinite(lr) or lr < 0.0:
@@ -260,7 +272,12 @@ class AdamW(torch.optim.Optimizer):
         return runs
 
     @torch.no_grad()
-    def step(self, closure=None, ema=None, grad_scale=1.0, max_grad_norm=None):
+    def step(self, closure=None, ema=None, grad_scale=1.0, max_grad_norm=None, scaler=None):
+        if scaler is not None and not isinstance(scaler, LossScaler):
+            raise TypeError(f"ctrlv_amd.optim.AdamW.step: scaler must be a ctrlv_amd.optim.LossScaler, not {type(scaler).__name__} "
+                            "(the scale is read and updated on the device; there is no host-read route)")
+        if scaler is not None and not scaler.is_enabled():
+            scaler = None
         if max_grad_norm is None:
             max_grad_norm = self._max_grad_norm                                      # (None unless clip_grad_norm() set one)
         if max_grad_norm is not None and not _f32(max_grad_norm) > 0.0:             # (false for NaN too) before any device work
@@ -272,8 +289,8 @@ class AdamW(torch.optim.Optimizer):
         if ema is None:
             ema = self._ema
         ema_decay = ema._begin_fused_step(self) if ema is not None else 0.0
-        if max_grad_norm is not None:
-            self._step_clipped(ema, ema_decay, float(grad_scale), float(max_grad_norm))
+        if max_grad_norm is not None or scaler is not None:
+            self._step_clipped(ema, ema_decay, float(grad_scale), math.inf if max_grad_norm is None else float(max_grad_norm), scaler)
             if ema is not None:
                 ema._end_fused_step(self)
             return loss
@@ -305,9 +322,10 @@ class AdamW(torch.optim.Optimizer):
             ema._end_fused_step(self)
         return loss
 
-    def _step_clipped(self, ema, ema_decay, grad_scale, max_grad_norm):
+    def _step_clipped(self, ema, ema_decay, grad_scale, max_grad_norm, scaler=None):
         """`step(max_grad_norm=...)`: the sum of squares of every run of every group into one partials array, one finish, then
-        `ctrlv_adamw_step_dev` per run, all on the current stream and without a host read."""
+        `ctrlv_adamw_step_dev` per run, all on the current stream and without a host read.  With a scaler: the scaled finish and
+        `ctrlv_adamw_step_scaled`, which read the unscale multiplier from the scaler's device record."""
         plan, dev, lib = [], None, None
         for gi, group in enumerate(self.param_groups):
             params = group["params"]
@@ -340,8 +358,13 @@ class AdamW(torch.optim.Optimizer):
                 _lib.check(lib.ctrlv_grad_sumsq(_ptr(flat.g, off), n, ctypes.c_void_p(partials.data_ptr()), partials.numel(), slot,
                                                 _stream()), "ctrlv_grad_sumsq", lib)
                 slot += lib.ctrlv_grad_sumsq_partials(n)
-        _lib.check(lib.ctrlv_grad_finish(ctypes.c_void_p(partials.data_ptr()), slot, grad_scale, max_grad_norm, state, _stream()),
-                   "ctrlv_grad_finish", lib)
+        if scaler is not None:
+            ls = ctypes.c_void_p(scaler._record_on(dev).data_ptr())
+            _lib.check(lib.ctrlv_grad_finish_scaled(ctypes.c_void_p(partials.data_ptr()), slot, grad_scale, max_grad_norm, ls, state,
+                                                    _stream()), "ctrlv_grad_finish_scaled", lib)
+        else:
+            _lib.check(lib.ctrlv_grad_finish(ctypes.c_void_p(partials.data_ptr()), slot, grad_scale, max_grad_norm, state, _stream()),
+                       "ctrlv_grad_finish", lib)
         for gi, group, flat, runs in plan:
             params = group["params"]
             lr, wd, eps = float(group["lr"]), float(group["weight_decay"]), float(group["eps"])
@@ -349,17 +372,21 @@ class AdamW(torch.optim.Optimizer):
             shadow = ema._shadow_flat(self, gi) if ema is not None else None
             for off, n, first, last, t in runs:
                 bias1, bias2 = 1.0 - b1 ** (t + 1), 1.0 - b2 ** (t + 1)
-                _lib.check(lib.ctrlv_adamw_step_dev(_ptr(flat.p, off), _ptr(flat.g, off), _ptr(flat.m, off), _ptr(flat.v, off),
-                                                    _ptr(shadow, off) if shadow is not None else None, n, lr, b1, b2, eps, wd,
-                                                    bias1, bias2, grad_scale, ema_decay, state, _stream()),
-                           "ctrlv_adamw_step_dev", lib)
+                bufs = (_ptr(flat.p, off), _ptr(flat.g, off), _ptr(flat.m, off), _ptr(flat.v, off),
+                        _ptr(shadow, off) if shadow is not None else None)
+                if scaler is not None:
+                    _lib.check(lib.ctrlv_adamw_step_scaled(*bufs, n, lr, b1, b2, eps, wd, bias1, bias2, ema_decay, ls, state, _stream()),
+                               "ctrlv_adamw_step_scaled", lib)
+                else:
+                    _lib.check(lib.ctrlv_adamw_step_dev(*bufs, n, lr, b1, b2, eps, wd, bias1, bias2, grad_scale, ema_decay, state,
+                                                        _stream()), "ctrlv_adamw_step_dev", lib)
                 for p in params[first:last + 1]:
                     self.state[p]["step"] += 1                      # ATTEMPTED steps: the host does not know about a skip
             torch.autograd.graph.increment_version([p for p in params if p.requires_grad])
 
     def grad_state(self):
-        """The record of the last `step(max_grad_norm=...)` as 0-dim DEVICE tensors: `norm` (fp32, of the gradients times
-        grad_scale, over all groups), `coef` (fp32, what the gradients were multiplied by), `skip` (int32, 1: the norm was not
+        """The record of the last `step(max_grad_norm=...)` or `step(scaler=...)` as 0-dim DEVICE tensors: `norm` (fp32, of the
+        gradients times grad_scale -- under a scaler times the unscale multiplier --, over all groups), `coef` (fp32, what the gradients were multiplied by), `skip` (int32, 1: the norm was not
         finite and the step left parameters and moments alone) and `skipped_total` (int32, skipped steps so far).  No
         synchronisation happens here; the tensors are views of the record, which the next such step overwrites -- read or clone
         them when convenient (with the loss, at logging time)."""
@@ -384,6 +411,187 @@ class AdamW(torch.optim.Optimizer):
                         view.copy_(st[key])
                         st[key] = view
                     st["step"] = torch.tensor(float(st["step"]), dtype=torch.float32)
+
+
+# ------------------------------------------------------------------------------------------------------------ loss scale
+class LossScaler:
+    """Dynamic loss scaling with the scale ON THE DEVICE: the surface of `torch.amp.GradScaler` that a training loop uses,
+
+        scaler.scale(loss).backward();  scaler.step(optimizer);  scaler.update()
+
+    for a `ctrlv_amd.optim.AdamW`.  The scale, its reciprocal and the growth tracker live in a 32-byte device record
+    (`ctrlv_loss_scale_state`, include/ctrlv_hip.h); the optimiser's finish launch unscales, decides the skip and applies
+    torch's `_amp_update_scale_` there (skip: scale *= backoff_factor; `growth_interval` unskipped steps in a row: scale *=
+    growth_factor unless that overflows), so no step reads the device.  The two factors are held as fp32 in the record (torch
+    keeps doubles: 2 and 0.5, or any fp32 number, behave identically).
+
+      * `scale(loss)` multiplies by a 0-dim device view of the scale (the record is created on `loss.device` at first use);
+      * `step(optimizer, **kw)` is `optimizer.step(scaler=self, **kw)`; any optimiser but `ctrlv_amd.optim.AdamW` is a TypeError
+        (there is no host-read fallback).  `.grad` is NOT unscaled by it: the gradient buffers keep the scaled values;
+      * `update()` does nothing -- the update already happened in the finish launch of `step`;
+      * `get_scale()` is a HOST READ (a synchronisation): for logging.  `scale_tensor()` / `growth_tracker_tensor()` hand out
+        device views without synchronising;
+      * `state_dict()` / `load_state_dict()` use exactly torch's keys (scale, growth_factor, backoff_factor, growth_interval,
+        _growth_tracker): a checkpoint moves between this class and `torch.amp.GradScaler` in both directions;
+      * `enabled=False` makes every method the identity, as in torch.
+
+    The optimiser counts ATTEMPTED steps (see `AdamW`): GradScaler's optimisers do not count a skipped step."""
+
+    def __init__(self, init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, enabled=True):
+        if enabled:
+            if not growth_factor > 1.0:
+                raise ValueError("The growth factor must be > 1.0.")
+            if not backoff_factor < 1.0:
+                raise ValueError("The backoff factor must be < 1.0.")
+        self._enabled = bool(enabled)
+        self._init_scale, self._init_growth_tracker = float(init_scale), 0
+        self._growth_factor, self._backoff_factor = float(growth_factor), float(backoff_factor)
+        self._growth_interval = int(growth_interval)
+        self._record = None         # int32[8] on the device: ctrlv_loss_scale_state
+
+    @classmethod
+    def fixed(cls, scale):
+        """A scale that never changes (static loss scaling): a growth interval no run reaches and a backoff factor of 1.  A step
+        with non-finite gradients is still skipped on the device."""
+        self = cls(init_scale=scale, growth_interval=2 ** 31 - 1)
+        self._backoff_factor = 1.0
+        return self
+
+    # ---- the record
+    def _words(self, scale, tracker):
+        return list(struct.unpack("<8i", struct.pack("<ffiiffii", _f32(scale), 0.0, int(tracker), self._growth_interval,
+                                                     _f32(self._growth_factor), _f32(self._backoff_factor), 0, 0)))
+
+    def _record_on(self, device):
+        """The record on `device`: created from the host values at first use, moved (with its current values) if it lives
+        elsewhere."""
+        device = torch.device(device)
+        if self._record is None:
+            self._record = torch.tensor(self._words(self._init_scale, self._init_growth_tracker), dtype=torch.int32).to(device)
+        elif self._record.device != device:
+            self._record = self._record.to(device)
+        return self._record
+
+    def _rewrite(self, scale=None, tracker=None):
+        """Host values changed: write them into the record, keeping the fields not named (one host read for those)."""
+        if self._record is None:
+            return
+        cur = self._record.cpu()
+        scale = float(cur[0:1].view(torch.float32)) if scale is None else scale
+        tracker = int(cur[2]) if tracker is None else tracker
+        self._record.copy_(torch.tensor(self._words(scale, tracker), dtype=torch.int32))
+
+    def scale_tensor(self):
+        """0-dim fp32 DEVICE view of the scale (None before the record exists); no synchronisation."""
+        return None if self._record is None else self._record[0].view(torch.float32)
+
+    def growth_tracker_tensor(self):
+        """0-dim int32 DEVICE view of the growth tracker (None before the record exists); no synchronisation."""
+        return None if self._record is None else self._record[2]
+
+    # ---- GradScaler's loop surface
+    def scale(self, outputs):
+        """outputs * scale: a tensor, or a (nested) list / tuple of tensors.  No host read."""
+        if not self._enabled:
+            return outputs
+        if isinstance(outputs, torch.Tensor):
+            return outputs * self._record_on(outputs.device)[0].view(torch.float32)
+        if isinstance(outputs, (list, tuple)):
+            return type(outputs)(self.scale(o) for o in outputs)
+        raise ValueError("outputs must be a Tensor or an iterable of Tensors")
+
+    def step(self, optimizer, *args, **kwargs):
+        """`optimizer.step(scaler=self, ...)`: unscale, finite check, skip and scale update inside the optimiser's launches."""
+        if not self._enabled:
+            return optimizer.step(*args, **kwargs)
+        if not isinstance(optimizer, AdamW):
+            raise TypeError(f"ctrlv_amd.optim.LossScaler.step: {type(optimizer).__name__} is not a ctrlv_amd.optim.AdamW -- the "
+                            "scale lives on the device and only that optimiser reads it there (use torch.amp.GradScaler for others)")
+        return optimizer.step(*args, scaler=self, **kwargs)
+
+    def update(self, new_scale=None):
+        """Nothing to do: the scale was updated on the device by the step.  new_scale (a float or a 1-element tensor) sets it."""
+        if not self._enabled or new_scale is None:
+            return
+        if isinstance(new_scale, torch.Tensor):
+            new_scale = float(new_scale)
+        if self._record is None:
+            self._init_scale = float(new_scale)
+        else:
+            self._rewrite(scale=float(new_scale))
+
+    def unscale_(self, optimizer):
+        raise NotImplementedError("ctrlv_amd.optim.LossScaler: .grad is never rewritten; clip with step(optimizer, max_grad_norm=...), "
+                                  "which takes the norm of the unscaled gradients on the device")
+
+    def get_scale(self):
+        """The scale as a Python float.  A HOST READ of the device record (it synchronises): for logging."""
+        if not self._enabled:
+            return 1.0
+        return self._init_scale if self._record is None else float(self._record[0:1].cpu().view(torch.float32))
+
+    def _get_growth_tracker(self):
+        if not self._enabled:
+            return 0
+        return self._init_growth_tracker if self._record is None else int(self._record[2])
+
+    def get_growth_factor(self):
+        return self._growth_factor
+
+    def set_growth_factor(self, new_factor):
+        self._growth_factor = float(new_factor)
+        self._rewrite()
+
+    def get_backoff_factor(self):
+        return self._backoff_factor
+
+    def set_backoff_factor(self, new_factor):
+        self._backoff_factor = float(new_factor)
+        self._rewrite()
+
+    def get_growth_interval(self):
+        return self._growth_interval
+
+    def set_growth_interval(self, new_interval):
+        self._growth_interval = int(new_interval)
+        self._rewrite()
+
+    def is_enabled(self):
+        return self._enabled
+
+    def state_dict(self):
+        """torch.amp.GradScaler's state dict (a host read of scale and tracker); {} when disabled."""
+        if not self._enabled:
+            return {}
+        return {"scale": self.get_scale(), "growth_factor": self._growth_factor, "backoff_factor": self._backoff_factor,
+                "growth_interval": self._growth_interval, "_growth_tracker": self._get_growth_tracker()}
+
+    def load_state_dict(self, state_dict):
+        if not self._enabled:
+            return
+        if len(state_dict) == 0:
+            raise RuntimeError("The source state dict is empty, possibly because it was saved from a disabled instance of GradScaler.")
+        self._init_scale = float(state_dict["scale"])
+        self._growth_factor, self._backoff_factor = float(state_dict["growth_factor"]), float(state_dict["backoff_factor"])
+        self._growth_interval = int(state_dict["growth_interval"])
+        self._init_growth_tracker = int(state_dict["_growth_tracker"])
+        self._rewrite(scale=self._init_scale, tracker=self._init_growth_tracker)
+
+
+def loss_scaler_from_option(option):
+    """The --loss-scale option of the tools: "none" -> None, "dynamic" -> LossScaler() (torch's defaults), a number -> that
+    scale, fixed (`LossScaler.fixed`)."""
+    if option is None or str(option).lower() == "none":
+        return None
+    if str(option).lower() == "dynamic":
+        return LossScaler()
+    try:
+        scale = float(option)
+    except ValueError:
+        raise ValueError(f"--loss-scale must be none, dynamic or a positive number, not {option!r}") from None
+    if not (scale > 0.0 and math.isfinite(scale)):
+        raise ValueError(f"--loss-scale must be none, dynamic or a positive number, not {option!r}")
+    return LossScaler.fixed(scale)
 
 
 # ------------------------------------------------------------------------------------------------------------ EMA

@@ -7,6 +7,8 @@ same blocks with the UNet's encoder, mid block and tail trainable as well.  The 
     -> frozen UNet forward: encoder + mid on the inference executor (no gradients flow there: the residuals join the skip
        tensors AFTER the down path, unet_spatio_temporal_condition.py:119-137), decoder in training mode (dgrad only)
     -> EDM-preconditioned MSE (train_video_controlnet.py:468-478) -> backward -> AdamW (torch.optim on the fp32 masters).
+The compute type is bf16 unless a step is called with compute_dtype=torch.float16 (the reference's --mixed_precision fp16), then
+usually with a `ctrlv_amd.optim.LossScaler`, whose scale is read and updated on the device inside the optimiser's launches.
 
 Everything activation-sized runs in the kernels of libctrlv_hip.so through ctrlv_amd.autograd; the per-clip vectors (time
 and added-id embeddings, time_emb_proj, the one-key cross-attention vectors, the frame positional embedding MLP) are
@@ -101,15 +103,26 @@ def up_block_train(blk, x, emb_s, ehs, B, F, H, W, skips, order):
 
 
 # ------------------------------------------------------------------------------------------------- models
+def _element_dtype(compute_dtype):
+    """The element type of a step's activations: None is torch.bfloat16 (the default route), else bf16 or fp16."""
+    if compute_dtype is None:
+        return torch.bfloat16
+    if compute_dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"compute_dtype must be torch.bfloat16 or torch.float16 (None: bfloat16), not {compute_dtype}")
+    return compute_dtype
+
+
 def _input_cols(planes, N, h, w, cp, kp, device):
-    """NCHW planes -> channels-last rows [M, cp] -> im2col [M, kp] (the tiny-channel input convs run as ONE GEMM)."""
+    """NCHW planes -> channels-last rows [M, cp] -> im2col [M, kp] (the tiny-channel input convs run as ONE GEMM), in the
+    element type of the planes (fp32 planes: bf16)."""
     M = N * h * w
-    x16 = torch.zeros(M, cp, dtype=torch.bfloat16, device=device)
+    el = planes[0].dtype if planes[0].dtype in (torch.bfloat16, torch.float16) else torch.bfloat16
+    x16 = torch.zeros(M, cp, dtype=el, device=device)
     off = 0
     for p in planes:
         ops.nchw_to_rows(p.contiguous(), x16, off)
         off += p.shape[1]
-    col = torch.empty(M, kp, dtype=torch.bfloat16, device=device)
+    col = torch.empty(M, kp, dtype=el, device=device)
     ops.im2col3x3(x16, N, h, w, col)
     return col
 
@@ -196,7 +209,7 @@ def unet_train_forward(unet, sample, timestep, encoder_hidden_states, added_time
             plan = unet._ensure_plan(sample)
             t32, ehs_p, ids32 = unet._plan_inputs(sample, timestep, encoder_hidden_states, added_time_ids)
             shapes = [plan.residual_shape(i, B, F, h, w) for i in range(plan.n_down + 1)]
-            rows = [torch.empty(M, C, dtype=torch.bfloat16, device=dev) for M, C in shapes]
+            rows = [torch.empty(M, C, dtype=sample.dtype, device=dev) for M, C in shapes]
             plan.unet_encoder_forward(sample.contiguous(), t32, ehs_p, ids32, rows[:-1], rows[-1])
             hw = [(h, w)]
             for M, _ in shapes[1:]:
@@ -259,8 +272,13 @@ def edm_loss(pred_rows, noisy_latents, target_latents, sigmas):
 
 
 def train_step(controlnet, unet, batch, optimizer=None, conditioning_scale=1.0, world_size=1, buckets=None,
-               accumulate=False, loss_scale=1.0, max_grad_norm=None):
-    """One optimisation step.  max_grad_norm: clip the gradients to that global norm in front of the optimiser step (the
+               accumulate=False, loss_scale=1.0, max_grad_norm=None, compute_dtype=None, scaler=None):
+    """One optimisation step.  compute_dtype: the element type of the activations and activation gradients, torch.bfloat16
+    (None, the default) or torch.float16 -- the reference's --mixed_precision fp16; master parameters, parameter gradients, loss and
+    optimiser stay fp32 either way.  The frozen UNet must hold its parameters in that type (`unet.half()` for fp16).  scaler: a
+    `ctrlv_amd.optim.LossScaler` -- the loss is multiplied by `scaler.scale(...)` before the backward and the step is
+    `optimizer.step(scaler=..., max_grad_norm=...)` (unscale, finite check, skipped step and scale update on the device; the
+    optimiser must be a `ctrlv_amd.optim.AdamW`; `loss_scale` stays the accumulation factor).  max_grad_norm: clip the gradients to that global norm in front of the optimiser step (the
     reference's --max_grad_norm; see `_backward_and_step`; None: no clipping).  Data parallel: pass `buckets=GradientBuckets(params)` (all-reduce overlapped with the
     backward pass), or only `world_size > 1` for the simple reduce-after-backward path.
     Gradient accumulation (`accelerator.accumulate`, gradient_accumulation_steps of train_video_controlnet.py:376): call
@@ -269,46 +287,63 @@ def train_step(controlnet, unet, batch, optimizer=None, conditioning_scale=1.0, 
     (conditioning frame repeated), control_cond (B,F,4,h,w), encoder_hidden_states (B,1,D), added_time_ids (B,3)).
     Returns the loss as a device tensor; the one host read of the step is the batched mix-factor fetch at its start."""
     prefetch_mix_factors(controlnet, unet)          # the step's only device-to-host read (about 60 scalars, one copy)
-    lat, sig, noisy, timesteps, sample = _noised_inputs(batch)
+    el = _element_dtype(compute_dtype)
+    _check_scaler(scaler, optimizer)
+    udt = next(unet.parameters()).dtype
+    if udt != el and udt != torch.float32:
+        raise ValueError(f"train_step: compute_dtype {el} with a frozen UNet held in {udt}: cast it first (unet.to({el}))")
+    lat, sig, noisy, timesteps, sample = _noised_inputs(batch, el)
     down, mid = controlnet_train_forward(controlnet, sample, timesteps, batch["encoder_hidden_states"],
-                                         batch["added_time_ids"], batch["control_cond"].to(torch.bfloat16),
+                                         batch["added_time_ids"], batch["control_cond"].to(el),
                                          conditioning_scale)
     pred = unet_train_forward(unet, sample, timesteps, batch["encoder_hidden_states"], batch["added_time_ids"], down, mid)
     loss = edm_loss(pred, noisy, lat, sig)
-    return _backward_and_step(controlnet, loss, optimizer, world_size, buckets, accumulate, loss_scale, max_grad_norm)
+    return _backward_and_step(controlnet, loss, optimizer, world_size, buckets, accumulate, loss_scale, max_grad_norm, scaler)
 
 
-def unet_train_step(unet, batch, optimizer=None, world_size=1, buckets=None, accumulate=False, loss_scale=1.0, max_grad_norm=None):
+def unet_train_step(unet, batch, optimizer=None, world_size=1, buckets=None, accumulate=False, loss_scale=1.0, max_grad_norm=None,
+                    compute_dtype=None, scaler=None):
     """One stage-1 optimisation step: the whole UNet fine-tuned (tools/train_video_diffusion.py:515-541; UNet forward,
     EDM loss, backward, optimizer step).  Which parameters train is the caller's choice through `unet.enable_grad(...)`
     (all=True: the demo scripts; temporal_transformer_block=True: temporal-only mode) -- frozen parameters get no gradient,
     and switching modes between steps needs nothing else (packed forms are cached only for frozen parameters, keyed on
     their version).  batch: `train_step`'s keys without control_cond; image_latents (B,F,4,h,w) per frame (the
     predict-bbox layout passes unchanged), encoder_hidden_states with the caller's conditioning dropout already applied.
-    Data parallel / gradient accumulation / max_grad_norm / zero gradients for parameters without a gradient path: as in
-    `train_step`.  Returns the detached loss."""
+    Data parallel / gradient accumulation / max_grad_norm / compute_dtype / scaler / zero gradients for parameters without a
+    gradient path: as in `train_step`.  Returns the detached loss."""
+    el = _element_dtype(compute_dtype)
+    _check_scaler(scaler, optimizer)
     prefetch_mix_factors(unet)
-    lat, sig, noisy, timesteps, sample = _noised_inputs(batch)
+    lat, sig, noisy, timesteps, sample = _noised_inputs(batch, el)
     pred = unet_full_train_forward(unet, sample, timesteps, batch["encoder_hidden_states"], batch["added_time_ids"])
     loss = edm_loss(pred, noisy, lat, sig)
-    return _backward_and_step(unet, loss, optimizer, world_size, buckets, accumulate, loss_scale, max_grad_norm)
+    return _backward_and_step(unet, loss, optimizer, world_size, buckets, accumulate, loss_scale, max_grad_norm, scaler)
 
 
-def _noised_inputs(batch):
+def _check_scaler(scaler, optimizer):
+    """A loss scaler works with the project's optimiser only (the scale is read and updated on the device): refused before any
+    device work.  A disabled scaler is no scaler."""
+    if scaler is not None and not isinstance(scaler, _optim.LossScaler):
+        raise TypeError(f"scaler must be a ctrlv_amd.optim.LossScaler, not {type(scaler).__name__}")
+    if scaler is not None and scaler.is_enabled() and optimizer is not None and not isinstance(optimizer, _optim.AdamW):
+        raise TypeError(f"a LossScaler steps a ctrlv_amd.optim.AdamW only, not {type(optimizer).__name__}")
+
+
+def _noised_inputs(batch, el=torch.bfloat16):
     """EDM noising of a batch (train_video_controlnet.py:404-410, train_video_diffusion.py:519-527): (clean latents,
-    sigmas, noisy latents, continuous timesteps 0.25 ln sigma, bf16 model input = [scaled noisy | image latents]).  A batch
+    sigmas, noisy latents, continuous timesteps 0.25 ln sigma, model input = [scaled noisy | image latents] in the element type `el`).  A batch
     from `prepare_batch` carries noisy_latents / sample / timesteps already (ctrlv_train_assemble wrote them, the timesteps
     are the scheduler's table entries): they are used as they are."""
     if "noisy_latents" in batch and "sample" in batch and "timesteps" in batch:
         return (batch["latents"].float(), batch["sigmas"].float(), batch["noisy_latents"].float(), batch["timesteps"].float(),
-                batch["sample"].to(torch.bfloat16))
+                batch["sample"].to(el))
     lat, noise, sig = batch["latents"].float(), batch["noise"].float(), batch["sigmas"].float()
     B = lat.shape[0]
     s5 = sig.reshape(B, 1, 1, 1, 1)
     noisy = lat + noise * s5                                                    # EulerDiscreteScheduler.add_noise
     inp = noisy / (s5 * s5 + 1) ** 0.5                                          # :410
     timesteps = 0.25 * torch.log(sig)                                           # continuous timestep of sigma
-    sample = torch.cat([inp, batch["image_latents"].float()], dim=2).to(torch.bfloat16)
+    sample = torch.cat([inp, batch["image_latents"].float()], dim=2).to(el)
     return lat, sig, noisy, timesteps, sample
 
 
@@ -335,15 +370,22 @@ def prepare_batch(plan, clips, box_frames=None, *, mode, seed, step, num_cond_fr
     return batch
 
 
-def _backward_and_step(model, loss, optimizer, world_size, buckets, accumulate, loss_scale, max_grad_norm=None):
+def _backward_and_step(model, loss, optimizer, world_size, buckets, accumulate, loss_scale, max_grad_norm=None, scaler=None):
     """backward, gradient reduction and optimizer step of `train_step` / `unet_train_step` (model: the trained one).
     max_grad_norm: the gradients are clipped to that global L2 norm in front of the step (the reference's --max_grad_norm,
     `accelerator.clip_grad_norm_`): a `ctrlv_amd.optim.AdamW` does it inside its own pass on the device
     (`step(max_grad_norm=...)`), any other optimiser gets `torch.nn.utils.clip_grad_norm_` over its parameters.  Either way the
-    norm is taken AFTER the gradient reduction: every rank computes the same bits from the same gradients, no collective is added."""
+    norm is taken AFTER the gradient reduction: every rank computes the same bits from the same gradients, no collective is added.
+    scaler (a `ctrlv_amd.optim.LossScaler`): the backward starts from loss * scale, and the optimiser -- a `ctrlv_amd.optim.AdamW`,
+    anything else raises -- unscales, checks and steps or skips on the device (`step(scaler=...)`); the found-inf decision is taken
+    from that same post-reduction norm, so it needs no collective either.  loss_scale stays the accumulation factor."""
+    _check_scaler(scaler, optimizer)
+    if scaler is not None and not scaler.is_enabled():
+        scaler = None
     if buckets is not None:
         buckets.enabled = not accumulate
-    (loss * loss_scale if loss_scale != 1.0 else loss).backward()
+    scaled = loss * loss_scale if loss_scale != 1.0 else loss
+    (scaler.scale(scaled) if scaler is not None else scaled).backward()
     if accumulate:
         return loss.detach()
     if buckets is not None:
@@ -356,7 +398,9 @@ def _backward_and_step(model, loss, optimizer, world_size, buckets, accumulate, 
         if p.requires_grad and p.grad is None:
             p.grad = torch.zeros_like(p)
     if optimizer is not None:
-        if max_grad_norm is None:
+        if scaler is not None:
+            optimizer.step(scaler=scaler, max_grad_norm=max_grad_norm)
+        elif max_grad_norm is None:
             optimizer.step()
         elif isinstance(optimizer, _optim.AdamW):
             optimizer.step(max_grad_norm=max_grad_norm)

@@ -51,7 +51,8 @@ enum {
  * entry points (ctrlv_frame_stats, ctrlv_frame_ssim, ctrlv_frame_ssim_ws_bytes, ctrlv_resize_frames_u8,
  * ctrlv_resize_frames_ws_bytes) or the LPIPS entry points (ctrlv_lpips_*, ctrlv_relu_maxpool_rows) or the optimiser pass (ctrlv_adamw_step, ctrlv_ema_step)
  * or the gradient-norm clipping in front of it (ctrlv_grad_sumsq, ctrlv_grad_sumsq_partials, ctrlv_grad_finish,
- * ctrlv_adamw_step_dev), and a host that needs them fails at symbol lookup on a library without them.
+ * ctrlv_adamw_step_dev) or the loss-scaled forms of its last two stages (ctrlv_grad_finish_scaled, ctrlv_adamw_step_scaled),
+ * and a host that needs them fails at symbol lookup on a library without them.
  * NOT neutral, although the number did not move: ctrlv_gemm_desc.pad_br gives meaning to four bytes that were alignment
  * padding, so descriptors must now be zero-initialised (see the field). */
 int ctrlv_abi_version(void);
@@ -1466,6 +1467,40 @@ int ctrlv_grad_finish(const double* partials, size_t count, float grad_scale, fl
 int ctrlv_adamw_step_dev(float* p, const float* g, float* m, float* v, float* ema, size_t n, float lr, float beta1, float beta2,
                          float eps, float weight_decay, float bias1, float bias2, float grad_scale, float ema_decay,
                          const ctrlv_grad_state* state, ctrlv_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Dynamic loss scaling on the device (csrc/optim.hip): what accelerate's GradScaler does around the backward of a step under
+ * --mixed_precision fp16 -- unscale, found-inf check, skipped step, scale update (torch's _amp_update_scale_) -- inside the
+ * three stages above, without a host read.  The scale lives in a second device record that updates itself.
+ *
+ * The record.  32 bytes, 16-byte aligned, initialised by the host once (scale, growth_interval, the two factors; the rest 0). */
+typedef struct ctrlv_loss_scale_state {
+  float scale;            /* multiplier of the NEXT backward's loss */
+  float unscale;          /* what THIS step multiplies gradients by: fp32(host grad_scale * fp32(1.0 / (double)scale)),
+                             scale taken before the update -- torch: _scale.double().reciprocal().float() */
+  int32_t growth_tracker; /* consecutive unskipped steps since the last change of scale */
+  int32_t growth_interval;
+  float growth_factor, backoff_factor; /* fp32: torch keeps Python doubles; 2 and 0.5 (any fp32 number) behave identically */
+  int32_t reserved[2];
+} ctrlv_loss_scale_state;
+
+/* Stage 2 under a loss scale: ctrlv_grad_finish with the multiplier formed ON THE DEVICE, unscale = grad_scale * fp32(1 / (double)
+ * ls->scale) (one fp32 product; grad_scale is the host's multiplier, e.g. 1 / accumulation steps).  Writes ls->unscale, then norm,
+ * coef, skip and skipped_total of `state` exactly as ctrlv_grad_finish does with grad_scale = unscale: one workgroup, the same
+ * summation order, so the norm is bit-identical given the same multiplier.  The same thread then applies torch's
+ * _amp_update_scale_: on skip scale *= backoff_factor and growth_tracker = 0; otherwise, when growth_tracker + 1 == growth_interval,
+ * scale *= growth_factor if that product is finite, and growth_tracker = 0; otherwise growth_tracker += 1.  The record is validated
+ * on the device: a scale that is not positive and finite sets skip (unscale, and so norm, are NaN) and leaves scale and
+ * growth_tracker alone.  Refused on the host: what ctrlv_grad_finish refuses, plus a NULL or misaligned ls. */
+int ctrlv_grad_finish_scaled(const double* partials, size_t count, float grad_scale, float max_norm, ctrlv_loss_scale_state* ls,
+                             ctrlv_grad_state* state, ctrlv_stream_t stream);
+/* Stage 3 under a loss scale: ctrlv_adamw_step_dev with the gradient taken as (g * ls->unscale) * state->coef, two fp32
+ * multiplications in that order; ls->unscale == grad_scale gives ctrlv_adamw_step_dev's bits.  Skip and EMA-on-skip as there.
+ * g is NEVER written: the gradient buffer keeps the SCALED gradients (unlike after torch's unscale_).  Same refusals as
+ * ctrlv_adamw_step (without grad_scale), plus a NULL or misaligned ls or state. */
+int ctrlv_adamw_step_scaled(float* p, const float* g, float* m, float* v, float* ema, size_t n, float lr, float beta1, float beta2,
+                            float eps, float weight_decay, float bias1, float bias2, float ema_decay,
+                            const ctrlv_loss_scale_state* ls, const ctrlv_grad_state* state, ctrlv_stream_t stream);
 
 #ifdef __cplusplus
 }

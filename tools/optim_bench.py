@@ -9,7 +9,10 @@ the buffers are far larger than the 256 MiB Infinity Cache at the default sizes.
 torch.nn.utils.clip_grad_norm_ followed by the plain step (at its best here: ONE flat gradient tensor, where a model has hundreds;
 a norm pass, a read-modify-write of g, then the step: 40 / 48 bytes per element).  The variants of one n are timed `--repeats` times
 in turn, so that a drift of the machine shows as a spread of every row and not as a difference between rows.
-usage: python tools/optim_bench.py [--n 268435456,1073741825] [--iters 20] [--warmup 3] [--max-grad-norm 1.0] [--repeats 3]"""
+--loss-scale {dynamic,<number>} adds the loss-scaled step of `AdamW.step(scaler=...)` -- ctrlv_grad_sumsq, ctrlv_grad_finish_scaled,
+ctrlv_adamw_step_scaled: the same 32 / 40 bytes per element as the clipped step, with --max-grad-norm as its max_norm (+inf without).
+usage: python tools/optim_bench.py [--n 268435456,1073741825] [--iters 20] [--warmup 3] [--max-grad-norm 1.0] [--loss-scale dynamic]
+                                   [--repeats 3]"""
 import argparse
 import ctypes
 import json
@@ -27,11 +30,12 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--max-grad-norm", type=float, default=None, help="also time the clipped step and its alternatives")
+    ap.add_argument("--loss-scale", default="none", help="none | dynamic | a number: also time the loss-scaled three-stage step")
     ap.add_argument("--repeats", type=int, default=1, help="time every variant of an n this many times, in turn")
     args = ap.parse_args()
     import __graft_entry__ as ge
     ge.build()
-    from ctrlv_amd import _lib
+    from ctrlv_amd import _lib, optim
     lib = _lib.load()
     dev = torch.device("cuda:0")
     ptr = lambda t: ctypes.c_void_p(t.data_ptr())                 # noqa: E731
@@ -77,6 +81,22 @@ def main():
                          ("clip+adamw", lambda: clipped(False), 32), ("clip+adamw+ema", lambda: clipped(True), 40),
                          ("torch_clip_grad_norm+adamw", lambda: torch_clip(False), 40),
                          ("torch_clip_grad_norm+adamw+ema", lambda: torch_clip(True), 48)]
+        scaler = optim.loss_scaler_from_option(args.loss_scale)
+        if scaler is not None:
+            ls = scaler._record_on(dev)
+            ls_slots = lib.ctrlv_grad_sumsq_partials(n)
+            ls_partials = torch.zeros(ls_slots, dtype=torch.float64, device=dev)
+            ls_state = torch.zeros(4, dtype=torch.int32, device=dev)
+            ls_norm = float("inf") if args.max_grad_norm is None else args.max_grad_norm
+
+            def scaled(ema):
+                _lib.check(lib.ctrlv_grad_sumsq(ptr(g), n, ptr(ls_partials), ls_slots, 0, stream()), "ctrlv_grad_sumsq", lib)
+                _lib.check(lib.ctrlv_grad_finish_scaled(ptr(ls_partials), ls_slots, 1.0, ls_norm, ptr(ls), ptr(ls_state), stream()),
+                           "ctrlv_grad_finish_scaled", lib)
+                _lib.check(lib.ctrlv_adamw_step_scaled(ptr(p), ptr(g), ptr(m), ptr(v), ptr(e) if ema else None, n, *hyper[:7], hyper[8],
+                                                       ptr(ls), ptr(ls_state), stream()), "ctrlv_adamw_step_scaled", lib)
+
+            variants += [("scaled+adamw", lambda: scaled(False), 32), ("scaled+adamw+ema", lambda: scaled(True), 40)]
         for rep in range(args.repeats):
             for name, fn, nbytes in variants:
                 for _ in range(args.warmup):
@@ -94,6 +114,8 @@ def main():
                     row["repeat"] = rep
                 if args.max_grad_norm is not None:
                     row["max_grad_norm"] = args.max_grad_norm
+                if scaler is not None:
+                    row["loss_scale"] = args.loss_scale
                 print(json.dumps(row), flush=True)
                 if args.max_grad_norm is not None:
                     g.normal_()                 # torch's clip scales g in place: every variant starts from gradients of the same size

@@ -44,9 +44,16 @@ def main():
     ap.add_argument("--mark-steps", type=int, default=0,
                     help="1: a torch.cuda._sleep kernel in front of every step (tools/trace_last_step.py cuts a rocprofv3 "
                          "kernel trace at these marks)")
+    ap.add_argument("--dtype", choices=("bf16", "fp16"), default="bf16",
+                    help="element type of activations and activation gradients (the frozen UNet is held in it)")
+    ap.add_argument("--loss-scale", default="none",
+                    help="none | dynamic (ctrlv_amd.optim.LossScaler, torch's defaults) | a number (a fixed scale: no growth, no "
+                         "backoff); needs --optimizer hip: the scale is read and updated on the device")
     ap.add_argument("--gpus", type=int, default=0,
                     help="N > 1 without a torchrun environment: start N rank processes (one per GPU) from this GPU-free parent")
     args = ap.parse_args()
+    if args.loss_scale != "none" and args.optimizer != "hip":
+        raise SystemExit("train_bench.py: --loss-scale needs --optimizer hip")
     if args.gpus > 1 and "RANK" not in os.environ:
         from ctrlv_amd.distributed import launch_local_ranks
         launch_local_ranks(__file__, sys.argv[1:], args.gpus)
@@ -68,7 +75,8 @@ def main():
     from ctrlv_amd import training
     from ctrlv_amd.models import ControlNetModel, UNetSpatioTemporalConditionModel
     from ctrlv_amd.utils import build_on_device, random_init_
-    unet = build_on_device(UNetSpatioTemporalConditionModel, dev, num_frames=args.frames)
+    el = torch.float16 if args.dtype == "fp16" else torch.bfloat16
+    unet = build_on_device(UNetSpatioTemporalConditionModel, dev, dtype=el, num_frames=args.frames)
     random_init_(unet, seed=0)
     ctrl = build_on_device(ControlNetModel, dev, dtype=torch.float32, num_frames=args.frames)      # fp32 masters
     random_init_(ctrl, seed=1, zero_conv_std=0.02)
@@ -84,6 +92,7 @@ def main():
         opt = optim.AdamW(params, lr=args.lr, weight_decay=1e-2).attach_ema(ema)      # the shadow update rides in the AdamW pass
     else:
         opt = torch.optim.AdamW(params, lr=args.lr, weight_decay=1e-2, fused=bool(args.fused_adamw))
+    scaler = optim.loss_scaler_from_option(args.loss_scale)
     buckets = training.GradientBuckets(params) if world > 1 else None
     B, F, h, w = 1, args.frames, args.height // 8, args.width // 8
     g = torch.Generator(device=dev).manual_seed(1234 + rank)             # every rank: its own clip
@@ -105,19 +114,22 @@ def main():
         lat, noise, sig = batch["latents"], batch["noise"], batch["sigmas"]
         s5 = sig.reshape(B, 1, 1, 1, 1)
         noisy = lat + noise * s5
-        sample = torch.cat([noisy / (s5 * s5 + 1) ** 0.5, batch["image_latents"]], dim=2).to(torch.bfloat16)
+        sample = torch.cat([noisy / (s5 * s5 + 1) ** 0.5, batch["image_latents"]], dim=2).to(el)
         ts = 0.25 * torch.log(sig)
         down, mid = training.controlnet_train_forward(ctrl, sample, ts, batch["encoder_hidden_states"],
-                                                      batch["added_time_ids"], batch["control_cond"].to(torch.bfloat16))
+                                                      batch["added_time_ids"], batch["control_cond"].to(el))
         pred = training.unet_train_forward(unet, sample, ts, batch["encoder_hidden_states"], batch["added_time_ids"],
                                            down, mid)
         loss = training.edm_loss(pred, noisy, lat, sig)
         e[1].record()
-        loss.backward()
+        (scaler.scale(loss) if scaler is not None else loss).backward()
         if buckets is not None:
             buckets.finish()
         e[2].record()
-        if args.max_grad_norm is None:
+        if scaler is not None:
+            scaler.step(opt, max_grad_norm=args.max_grad_norm)    # unscale, finite check, skip and scale update on the device
+            scaler.update()
+        elif args.max_grad_norm is None:
             opt.step()
         elif args.optimizer == "hip":
             opt.step(max_grad_norm=args.max_grad_norm)            # norm, coefficient and skip flag on the device, inside the pass
@@ -151,7 +163,9 @@ def main():
                       "losses": [round(v, 5) for v in losses],
                       "gradient_checkpointing": bool(args.gradient_checkpointing), "optimizer": args.optimizer, "ema": bool(args.ema),
                       **({"max_grad_norm": args.max_grad_norm} if args.max_grad_norm is not None else {}),
-                      "dtype": "bf16 compute, fp32 master parameters + AdamW",
+                      **({"loss_scale": args.loss_scale, "final_scale": scaler.get_scale(),
+                          "skipped_steps": int(opt.grad_state()["skipped_total"])} if scaler is not None else {}),
+                      "dtype": f"{args.dtype} compute, fp32 master parameters + AdamW",
                       "data": "synthetic, random-init weights"}))
 
 

@@ -81,9 +81,15 @@ def main():
     ap.add_argument("--gradient-checkpointing", type=int, default=0,
                     help="1: unet.enable_gradient_checkpointing() (the GEGLU feed-forward intermediates are recomputed in "
                          "the backward)")
+    ap.add_argument("--dtype", choices=("bf16", "fp16"), default="bf16", help="element type of activations and activation gradients")
+    ap.add_argument("--loss-scale", default="none",
+                    help="none | dynamic (ctrlv_amd.optim.LossScaler, torch's defaults) | a number (a fixed scale: no growth, no "
+                         "backoff); needs --optimizer hip: the scale is read and updated on the device")
     ap.add_argument("--gpus", type=int, default=0,
                     help="N > 1 without a torchrun environment: start N rank processes (one per GPU) from this GPU-free parent")
     args = ap.parse_args()
+    if args.loss_scale != "none" and args.optimizer != "hip":
+        raise SystemExit("train_unet_bench.py: --loss-scale needs --optimizer hip")
     if args.gpus > 1 and "RANK" not in os.environ:
         from ctrlv_amd.distributed import launch_local_ranks
         launch_local_ranks(__file__, sys.argv[1:], args.gpus)
@@ -124,6 +130,8 @@ def main():
         opt = optim.AdamW(params, lr=args.lr, weight_decay=1e-2).attach_ema(ema)      # the shadow update rides in the AdamW pass
     else:
         opt = torch.optim.AdamW(params, lr=args.lr, weight_decay=1e-2, fused=bool(args.fused_adamw))
+    el = torch.float16 if args.dtype == "fp16" else torch.bfloat16
+    scaler = optim.loss_scaler_from_option(args.loss_scale)
     buckets = training.GradientBuckets(params) if world > 1 else None
     B, F, h, w = 1, args.frames, args.height // 8, args.width // 8
     g = torch.Generator(device=dev).manual_seed(1234 + rank)             # every rank: its own clip
@@ -142,13 +150,16 @@ def main():
         e[0].record()
         # unet_train_step, cut at its phase boundaries
         prefetch_mix_factors(unet)
-        lat, sig, noisy, ts, sample = training._noised_inputs(batch)
+        lat, sig, noisy, ts, sample = training._noised_inputs(batch, el)
         pred = training.unet_full_train_forward(unet, sample, ts, batch["encoder_hidden_states"], batch["added_time_ids"])
         loss = training.edm_loss(pred, noisy, lat, sig)
         e[1].record()
-        training._backward_and_step(unet, loss, None, world, buckets, False, 1.0)
+        training._backward_and_step(unet, loss, None, world, buckets, False, 1.0, None, scaler)
         e[2].record()
-        if args.max_grad_norm is None:
+        if scaler is not None:
+            scaler.step(opt, max_grad_norm=args.max_grad_norm)    # unscale, finite check, skip and scale update on the device
+            scaler.update()
+        elif args.max_grad_norm is None:
             opt.step()
         elif args.optimizer == "hip":
             opt.step(max_grad_norm=args.max_grad_norm)            # norm, coefficient and skip flag on the device, inside the pass
@@ -186,7 +197,9 @@ def main():
                       "gradient_checkpointing": bool(args.gradient_checkpointing), "optimizer": args.optimizer, "ema": bool(args.ema),
                       **({"rank": args.rank} if args.mode == "lora" else {}),
                       **({"max_grad_norm": args.max_grad_norm} if args.max_grad_norm is not None else {}),
-                      "dtype": "bf16 compute, fp32 master parameters + AdamW", "data": "synthetic, random-init weights"}))
+                      **({"loss_scale": args.loss_scale, "final_scale": scaler.get_scale(),
+                          "skipped_steps": int(opt.grad_state()["skipped_total"])} if scaler is not None else {}),
+                      "dtype": f"{args.dtype} compute, fp32 master parameters + AdamW", "data": "synthetic, random-init weights"}))
 
 
 if __name__ == "__main__":
