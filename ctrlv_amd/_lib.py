@@ -173,6 +173,27 @@ class BestChainRequest(ctypes.Structure):
     _fields_ = [("boxes", BestBoxesRequest), ("video", ClipRequest), ("reserved", c_int)]
 
 
+class BoxObject(ctypes.Structure):
+    """Mirror of `ctrlv_box_object` (64 bytes): one object of a box or trajectory frame."""
+    _fields_ = [("x1", c_int), ("y1", c_int), ("x2", c_int), ("y2", c_int),
+                ("fill_rgb", ctypes.c_uint8 * 3), ("pad0", ctypes.c_uint8), ("line_rgb", ctypes.c_uint8 * 3), ("pad1", ctypes.c_uint8),
+                ("corner", (ctypes.c_int16 * 2) * 8), ("flags", ctypes.c_uint32), ("reserved", c_int)]
+
+
+class BoxFrame(ctypes.Structure):
+    """Mirror of `ctrlv_box_frame` (16 bytes)."""
+    _fields_ = [("first", c_int), ("count", c_int), ("kind", c_int), ("reserved", c_int)]
+
+
+BOX_FILL, BOX_OUTLINE, BOX_WIRE = 1, 2, 4
+
+
+class BoxRenderRequest(ctypes.Structure):
+    """Mirror of `ctrlv_box_render_request`."""
+    _fields_ = [("objects", c_void_p), ("frames", c_void_p), ("n_objects", c_int), ("n_frames", c_int),
+                ("src_height", c_int), ("src_width", c_int), ("reserved", c_int * 2)]
+
+
 class TrainBatchRequest(ctypes.Structure):
     """Mirror of `ctrlv_train_batch_request` (ctypes clears it: the library requires a cleared struct)."""
     _fields_ = [
@@ -399,6 +420,17 @@ SIGNATURES = {
     "ctrlv_grad_finish_scaled": (c_int, [c_void_p, c_size_t, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "ctrlv_adamw_step_scaled": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float, c_float, c_float,
                                         c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
+    "ctrlv_render_box_frames": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ctrlv_box_frames_cond_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "ctrlv_box_frames_cond": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
+                                      c_void_p, c_size_t, c_void_p]),
+    "ctrlv_box_class_color": (c_int, [c_int, ctypes.POINTER(ctypes.c_uint8)]),
+    "ctrlv_box_track_color": (c_int, [ctypes.c_uint64, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint8)]),
+    "ctrlv_box_project_corners": (c_int, [ctypes.POINTER(ctypes.c_double), c_int, ctypes.POINTER(ctypes.c_double),
+                                          ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.POINTER(ctypes.c_int16)]),
+    "ctrlv_pipeline_from_boxes_workspace_bytes": (c_size_t, [c_void_p, ctypes.POINTER(ClipRequest), ctypes.POINTER(BoxRenderRequest)]),
+    "ctrlv_pipeline_generate_from_boxes": (c_int, [c_void_p, ctypes.POINTER(ClipRequest), ctypes.POINTER(BoxRenderRequest), c_void_p,
+                                                   c_size_t, c_void_p]),
 }
 
 _libs = {}                # element dtype code (2 bf16 / 1 fp16) -> CDLL
@@ -414,6 +446,7 @@ _NO_STATUS = {"ctrlv_abi_version", "ctrlv_elem_dtype", "ctrlv_build_id", "ctrlv_
               "ctrlv_pipeline_seeded_workspace_bytes", "ctrlv_pipeline_best_boxes_workspace_bytes",
               "ctrlv_pipeline_best_chain_workspace_bytes", "ctrlv_frame_ssim_ws_bytes", "ctrlv_resize_frames_ws_bytes",
               "ctrlv_train_batch_workspace_bytes", "ctrlv_lpips_ws_bytes",
+              "ctrlv_box_frames_cond_ws_bytes", "ctrlv_pipeline_from_boxes_workspace_bytes",
               # a count of workgroups
               "ctrlv_lpips_distance_blocks",
               # a radius, or a negative status

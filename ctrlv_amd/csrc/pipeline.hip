@@ -789,6 +789,68 @@ extern "C" int ctrlv_pipeline_generate_seeded(ctrlv_pipeline* p, const ctrlv_cli
   return run_seeded(&sd, s, ws, stream);
 }
 
+// csrc/box_render.hip: every refusal of ctrlv_box_frames_cond that depends on neither its output nor its workspace, and the bytes
+// of workspace it needs without an out_u8
+int ctrlv_box_frames_cond_check(const void* objects, int n_objects, const void* frames, int n_frames, int Hs, int Ws, int H, int W,
+                                size_t* ws_bytes);
+
+namespace {
+
+struct FromBoxes {           // ctrlv_pipeline_generate_from_boxes: the rendered condition in front, the clip behind it
+  Stage clip;
+  size_t cond, cond_ws_bytes, stage, total;      // the render's own workspace aliases the clip's: it is dead when the clip starts
+};
+
+int plan_from_boxes(ctrlv_pipeline* p, const ctrlv_clip_request* r, const ctrlv_box_render_request* b, FromBoxes* fb) {
+  CTRLV_CHECK_ARG(p != nullptr, "generate_from_boxes: null pipeline");
+  CTRLV_CHECK_ARG(r != nullptr, "generate_from_boxes: null request");
+  CTRLV_CHECK_ARG(b != nullptr, "generate_from_boxes: null box render request");
+  CTRLV_CHECK_ARG(r->cond == nullptr, "generate_from_boxes: cond is set together with boxes; the driver supplies the rendered frames");
+  CTRLV_CHECK_ARG(p->cn != nullptr, "generate_from_boxes: the pipeline has no ControlNet to take the box frames");
+  CTRLV_CHECK_ARG(b->reserved[0] == 0 && b->reserved[1] == 0, "generate_from_boxes: box render request reserved must be 0");
+  ctrlv_clip_request v = *r;
+  v.cond_channels = 3;
+  v.cond_dtype = CTRLV_ELEM_DTYPE;
+  CTRLV_TRY(validate_stage(p, &v, nullptr, kCond, &fb->clip));
+  const Geo& g = fb->clip.g;
+  CTRLV_CHECK_SHAPE(b->n_frames == g.B * g.F, "generate_from_boxes: the frame table has n_frames=%d records, the request %d clips "
+                    "of %d frames", b->n_frames, g.B, g.F);
+  CTRLV_TRY(ctrlv_box_frames_cond_check(b->objects, b->n_objects, b->frames, b->n_frames, b->src_height, b->src_width, g.H, g.W,
+                                        &fb->cond_ws_bytes));
+  CTRLV_TRY(layout_stage(&fb->clip));
+  Carver cv;
+  fb->cond = cv.take((size_t)g.B * g.F * 3 * g.H * g.W * sizeof(el_t));
+  fb->stage = cv.o;
+  fb->total = cv.o + (fb->cond_ws_bytes > fb->clip.L.total ? fb->cond_ws_bytes : fb->clip.L.total);
+  return CTRLV_OK;
+}
+
+// the two calls a host would make by hand
+int run_from_boxes(FromBoxes* fb, const ctrlv_box_render_request* b, void* ws, ctrlv_stream_t stream) {
+  char* base = (char*)ws;
+  const Geo& g = fb->clip.g;
+  fb->clip.r.cond = base + fb->cond;
+  CTRLV_TRY(ctrlv_box_frames_cond(b->objects, b->n_objects, b->frames, b->n_frames, b->src_height, b->src_width, g.H, g.W,
+                                  base + fb->cond, CTRLV_ELEM_DTYPE, nullptr, base + fb->stage, fb->cond_ws_bytes, stream));
+  return run_stage(fb->clip, base + fb->stage, stream);
+}
+
+}  // namespace
+
+extern "C" size_t ctrlv_pipeline_from_boxes_workspace_bytes(ctrlv_pipeline* p, const ctrlv_clip_request* r,
+                                                            const ctrlv_box_render_request* b) {
+  FromBoxes fb;
+  return plan_from_boxes(p, r, b, &fb) == CTRLV_OK ? fb.total : 0;
+}
+
+extern "C" int ctrlv_pipeline_generate_from_boxes(ctrlv_pipeline* p, const ctrlv_clip_request* r, const ctrlv_box_render_request* b,
+                                                  void* ws, size_t ws_bytes, ctrlv_stream_t stream) {
+  FromBoxes fb;
+  CTRLV_TRY(plan_from_boxes(p, r, b, &fb));
+  CTRLV_TRY(check_workspace("pipeline_generate_from_boxes", "ctrlv_pipeline_from_boxes_workspace_bytes", ws, ws_bytes, fb.total));
+  return run_from_boxes(&fb, b, ws, stream);
+}
+
 namespace {
 
 constexpr int kMaxCandidates = 8;

@@ -1280,6 +1280,54 @@ def resize_frames_u8(frames_u8, h, w, resample="bicubic", out=None, workspace=No
     return out
 
 
+# ---- box and trajectory frames from coordinates (csrc/box_render.hip)
+def _box_table(fn, table):
+    for name, t in (("objects", table.objects), ("frames", table.frames)):
+        _need_gpu(t, f"table.{name}")
+        _need_dense(fn, **{name: t})
+    if table.frames.device != table.objects.device:
+        raise ValueError(f"{fn}: the two tables live on {table.objects.device} and {table.frames.device}")
+    return table.n_objects, table.n_frames, (table.n_clips, table.num_frames)
+
+
+def render_box_frames(table, source_size, out=None):
+    """A `ctrlv_amd.boxes.BoxTable` on the device -> (n, F, 3, Hs, Ws) uint8 box / trajectory frames at source_size = (Hs, Ws)
+    (ctrlv_render_box_frames: the integer geometry of include/ctrlv_hip.h, not OpenCV's raster)."""
+    fn = "render_box_frames"
+    n_obj, n_fr, lead = _box_table(fn, table)
+    Hs, Ws = int(source_size[0]), int(source_size[1])
+    lib = _lib.load()
+    out = _out_arg(True if out is None else out, lead + (3, Hs, Ws), torch.uint8, table.device, fn, "out")
+    with torch.cuda.device(table.device):
+        check(lib.ctrlv_render_box_frames(_p(table.objects), n_obj, _p(table.frames), n_fr, Hs, Ws, _p(out), _stream()),
+              "ctrlv_render_box_frames")
+    return out
+
+
+def box_frames_cond(table, source_size, size, dtype=torch.bfloat16, out=None, return_u8=False, workspace=None):
+    """A `BoxTable` -> the ControlNet's condition (n, F, 3, H, W) at size = (H, W) in `dtype` (fp32, or bf16 / fp16: the library of
+    that element type): the frames rendered at source_size, PIL's BILINEAR resize, (v / 255 - 0.5) / 0.5 (ctrlv_box_frames_cond).
+    return_u8: also the rendered (n, F, 3, Hs, Ws) uint8 frames."""
+    fn = "box_frames_cond"
+    n_obj, n_fr, lead = _box_table(fn, table)
+    (Hs, Ws), (H, W) = (int(v) for v in source_size), (int(v) for v in size)
+    if dtype not in _DT:
+        raise ValueError(f"{fn}: dtype {dtype} must be fp32, fp16 or bf16")
+    lib = _lib.load(None if dtype == torch.float32 else dtype)
+    need = lib.ctrlv_box_frames_cond_ws_bytes(n_fr, Hs, Ws, H, W)
+    if need == 0:
+        check(-2, "ctrlv_box_frames_cond_ws_bytes", lib=lib)
+    dev = table.device
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if workspace is None else workspace
+    _need_dense(fn, workspace=ws)
+    out = _out_arg(True if out is None else out, lead + (3, H, W), dtype, dev, fn, "out")
+    u8 = torch.empty(lead + (3, Hs, Ws), dtype=torch.uint8, device=dev) if return_u8 else None
+    with torch.cuda.device(dev):
+        check(lib.ctrlv_box_frames_cond(_p(table.objects), n_obj, _p(table.frames), n_fr, Hs, Ws, H, W, _p(out), _DT[dtype], _p(u8),
+                                        _p(ws), ws.numel(), _stream()), "ctrlv_box_frames_cond")
+    return (out, u8) if return_u8 else out
+
+
 # ---- LPIPS (csrc/lpips.hip): the split-operand im2col, the pool on fp32 rows and the per-layer distance
 LPIPS_SRC = {torch.float32: 0, torch.uint8: 3}       # src_dtype codes of the first-layer im2col and of ctrlv_lpips_frames
 

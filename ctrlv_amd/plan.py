@@ -594,8 +594,28 @@ class PipelinePlan(_Handle):
                                                ws.data_ptr(), ws.numel(), self._stream()), "ctrlv_pipeline_prepare")
         return out, ws
 
+    def box_render_request(self, boxes, source_size):
+        """The `ctrlv_box_render_request` of a `ctrlv_amd.boxes.BoxTable` on the plan's device; keep the table alive beside it."""
+        if source_size is None:
+            raise ValueError("PipelinePlan: boxes= needs source_size=(Hs, Ws), the size the coordinates refer to")
+        for t in (boxes.objects, boxes.frames):
+            if not t.is_cuda or (t.device.index or 0) != (self.device.index or 0) or not t.is_contiguous():
+                raise ValueError(f"PipelinePlan: the box table must be dense on {self.device} (BoxTable.to(device))")
+        b = _lib.BoxRenderRequest()
+        b.objects, b.frames = boxes.objects.data_ptr(), boxes.frames.data_ptr()
+        b.n_objects, b.n_frames = boxes.n_objects, boxes.n_frames
+        b.src_height, b.src_width = int(source_size[0]), int(source_size[1])
+        return b
+
+    def _rendered(self, who, boxes, source_size, height, width):
+        """The box frames of a table at the working size in the plan's element type (ops.box_frames_cond)."""
+        from . import ops
+        if source_size is None:
+            raise ValueError(f"{who}: boxes= needs source_size=(Hs, Ws), the size the coordinates refer to")
+        return ops.box_frames_cond(boxes, source_size, (height, width), dtype=self.dtype)
+
     def generate(self, image_u8, latents=None, sigmas=None, timesteps=None, *, cond=None, aug_noise=None, frames=True,
-                 frames_u8=True, seed=None, **kw):
+                 frames_u8=True, seed=None, boxes=None, source_size=None, **kw):
         """image_u8 (n, H, W, 3) uint8 at the working size; latents fp32 (n, F, L, h, w) already multiplied by
         init_noise_sigma; sigmas [steps + 1] / timesteps [steps]: the scheduler's values (host floats); cond (n, F, 3, H, W)
         pixels or (n, F, L, h, w) latents; aug_noise fp32 (n, 3, H, W) or None; the other fields of `request` by keyword.
@@ -604,9 +624,23 @@ class PipelinePlan(_Handle):
 
         With `seed=` (ctrlv_pipeline_generate_seeded): latents, sigmas and timesteps may be omitted -- give num_steps= and
         num_frames= --, image_u8 may have any size when height= and width= are given, and what is omitted comes from the
-        library: see `_stage_request` for the other keywords (clip_index0, call, sigma_min, sigma_max)."""
+        library: see `_stage_request` for the other keywords (clip_index0, call, sigma_min, sigma_max).
+
+        With `boxes=` (a `ctrlv_amd.boxes.BoxTable` on the device; mutually exclusive with cond) and source_size=(Hs, Ws): the
+        condition is rendered from the table by the library (ctrlv_pipeline_generate_from_boxes)."""
         if seed is None and (latents is None or sigmas is None or timesteps is None):
             raise ValueError("PipelinePlan.generate: latents, sigmas and timesteps are needed without seed=")
+        if boxes is not None:
+            if cond is not None:
+                raise ValueError("PipelinePlan.generate: boxes and cond are mutually exclusive (the library renders the condition)")
+            if seed is not None:
+                raise ValueError("PipelinePlan.generate: boxes= goes with explicit latents and a schedule, not with seed=")
+            st = self._stage_request("generate", image_u8, latents=latents, sigmas=sigmas, timesteps=timesteps,
+                                     aug_noise=aug_noise, frames=frames, frames_u8=frames_u8, **kw)
+            b = self.box_render_request(boxes, source_size)
+            self._run("ctrlv_pipeline_from_boxes_workspace_bytes", "ctrlv_pipeline_generate_from_boxes", self._h,
+                      ctypes.byref(st.request), ctypes.byref(b))
+            return st.out
         st = self._stage_request("generate", image_u8, seed=seed, latents=latents, sigmas=sigmas, timesteps=timesteps, cond=cond,
                                  aug_noise=aug_noise, frames=frames, frames_u8=frames_u8, **kw)
         if seed is None:
@@ -625,12 +659,20 @@ class PipelinePlan(_Handle):
         bc.num_cond_frames = int(num_cond_frames)
         return bc
 
-    def predict_boxes(self, image_u8, latents, sigmas, timesteps, bbox_frames, num_cond_frames=3, *, aug_noise=None, frames=True,
-                      frames_u8=True, seed=None, **kw):
+    def predict_boxes(self, image_u8, latents, sigmas, timesteps, bbox_frames=None, num_cond_frames=3, *, aug_noise=None, frames=True,
+                      frames_u8=True, seed=None, boxes=None, source_size=None, **kw):
         """The box predictor (ctrlv_pipeline_predict_boxes; a plan without a ControlNet): `generate` with the conditioning
         channels of frames [0, num_cond_frames) and F - 1 overwritten by bbox_frames -- (n, F, 3, H, W) pixels in [-1, 1], VAE
         encoded, or (n, F, L, h, w) latents -- and the decoded frames clamped to [-1, 1].  Same returns as `generate`; with
-        `seed=`, latents / sigmas / timesteps may be None: ctrlv_pipeline_prepare fills them."""
+        `seed=`, latents / sigmas / timesteps may be None: ctrlv_pipeline_prepare fills them.  `boxes=` (a `BoxTable`) with
+        source_size=(Hs, Ws) instead of bbox_frames: the frames are rendered from the table first (a trajectory frame is a frame
+        record with kind 1)."""
+        if boxes is not None:
+            # the two-call composition: ctrlv_box_frames_cond, then the predictor on its output, on one stream
+            if bbox_frames is not None:
+                raise ValueError("PipelinePlan.predict_boxes: boxes and bbox_frames are mutually exclusive")
+            H, W = int(kw.get("height") or image_u8.shape[1]), int(kw.get("width") or image_u8.shape[2])
+            bbox_frames = self._rendered("PipelinePlan.predict_boxes", boxes, source_size, H, W)
         if bbox_frames is None:
             raise ValueError("PipelinePlan.predict_boxes: bbox_frames is None")
         st = self._stage_request("predict_boxes", image_u8, seed=seed, prepare=True, latents=latents, sigmas=sigmas,
@@ -841,16 +883,26 @@ class TrainBatchPlan:
         return n
 
     def prepare(self, clips, box_frames=None, *, mode, seed, step, num_cond_frames=0, dropout_prob=None, scaling_factor=0.0,
-                clip_mean=None, clip_std=None, sample_dtype=None, return_noise=False):
+                clip_mean=None, clip_std=None, sample_dtype=None, return_noise=False, boxes=None, source_size=None):
         """clips / box_frames (n, F, 3, H, W) pixels in [-1, 1] (fp32, fp16 or bf16) on the plans' device; mode "controlnet"
         (box_frames become control_cond), "unet" (no box_frames) or "boxes" (the box predictor: box_frames are the target, frames
         [0, num_cond_frames) and F - 1 condition on them); seed: a `DeviceSeed`; step: the optimisation step.  Returns a dict of
         device tensors: target_latents, noisy_latents (fp32 (n, F, L, h, w)), sample ((n, F, 2 L, h, w) of sample_dtype, default
         the plans' element type), control_cond (fp32, mode "controlnet"), encoder_hidden_states ((n, 1, D) elements), sigmas,
         timesteps, random_p (fp32 (n)), indices (int32 (n)) and, with return_noise, noise.  Clip i's values depend on (seed.seed,
-        seed.clip_index0 + i, step) only.  Enqueued on torch's current stream; no host sync."""
+        seed.clip_index0 + i, step) only.  Enqueued on torch's current stream; no host sync.  boxes= (a `ctrlv_amd.boxes.BoxTable`
+        on the device) with source_size=(Hs, Ws) instead of box_frames: the frames are rendered from the table first."""
         who = "TrainBatchPlan.prepare"
         dev = self.device
+        if boxes is not None:
+            # training from coordinates is a composition: ctrlv_box_frames_cond into the buffer box_frames points at, then the
+            # call below on the same stream
+            if box_frames is not None:
+                raise ValueError(f"{who}: boxes and box_frames are mutually exclusive")
+            if source_size is None:
+                raise ValueError(f"{who}: boxes= needs source_size=(Hs, Ws), the size the coordinates refer to")
+            from . import ops
+            box_frames = ops.box_frames_cond(boxes, source_size, tuple(clips.shape[-2:]), dtype=self.dtype)
         for name, t in (("clips", clips), ("box_frames", box_frames)):
             if t is None:
                 continue

@@ -348,16 +348,17 @@ def _noised_inputs(batch, el=torch.bfloat16):
 
 
 def prepare_batch(plan, clips, box_frames=None, *, mode, seed, step, num_cond_frames=0, dropout_prob=None, fps=7,
-                  motion_bucket_id=127, noise_aug_strength=0.02, return_noise=False):
+                  motion_bucket_id=127, noise_aug_strength=0.02, return_noise=False, boxes=None, source_size=None):
     """A data-loader batch -> the dict `train_step` (mode "controlnet") / `unet_train_step` (modes "unet" and "boxes") take,
     in one library call (plan: a `ctrlv_amd.plan.TrainBatchPlan`; tools/train_video_controlnet.py:366-449,
     tools/train_video_diffusion.py:428-514): CLIP on the clamped first frame, the VAE posterior samples, the draws into the
     scheduler's tables, the noising, both conditioning-dropout masks, the frame layout and the channel concat, all keyed on
     (seed: a `DeviceSeed`, step, clip index).  clips / box_frames: (n, F, 3, H, W) pixels in [-1, 1] on the plan's device.  The
     dict carries noisy_latents / sample / timesteps, which `_noised_inputs` then takes as they are; added_time_ids is
-    [fps - 1, motion_bucket_id, noise_aug_strength] per clip, as the reference's get_add_time_ids (the one upload of the call; nothing is read back)."""
+    [fps - 1, motion_bucket_id, noise_aug_strength] per clip, as the reference's get_add_time_ids (the one upload of the call; nothing is read back).
+    boxes= (a `ctrlv_amd.boxes.BoxTable`) with source_size= instead of box_frames: the frames are rendered from the table."""
     out = plan.prepare(clips, box_frames, mode=mode, seed=seed, step=step, num_cond_frames=num_cond_frames,
-                       dropout_prob=dropout_prob, return_noise=return_noise)
+                       dropout_prob=dropout_prob, return_noise=return_noise, boxes=boxes, source_size=source_size)
     n = clips.shape[0]
     batch = {"latents": out["target_latents"], "sigmas": out["sigmas"], "noisy_latents": out["noisy_latents"],
              "sample": out["sample"], "timesteps": out["timesteps"], "encoder_hidden_states": out["encoder_hidden_states"],

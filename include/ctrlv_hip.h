@@ -51,7 +51,8 @@ enum {
  * entry points (ctrlv_frame_stats, ctrlv_frame_ssim, ctrlv_frame_ssim_ws_bytes, ctrlv_resize_frames_u8,
  * ctrlv_resize_frames_ws_bytes) or the LPIPS entry points (ctrlv_lpips_*, ctrlv_relu_maxpool_rows) or the optimiser pass (ctrlv_adamw_step, ctrlv_ema_step)
  * or the gradient-norm clipping in front of it (ctrlv_grad_sumsq, ctrlv_grad_sumsq_partials, ctrlv_grad_finish,
- * ctrlv_adamw_step_dev) or the loss-scaled forms of its last two stages (ctrlv_grad_finish_scaled, ctrlv_adamw_step_scaled),
+ * ctrlv_adamw_step_dev) or the loss-scaled forms of its last two stages (ctrlv_grad_finish_scaled, ctrlv_adamw_step_scaled)
+ * or the box-frame rendering (ctrlv_render_box_frames, ctrlv_box_*, ctrlv_pipeline_generate_from_boxes),
  * and a host that needs them fails at symbol lookup on a library without them.
  * NOT neutral, although the number did not move: ctrlv_gemm_desc.pad_br gives meaning to four bytes that were alignment
  * padding, so descriptors must now be zero-initialised (see the field). */
@@ -1501,6 +1502,117 @@ int ctrlv_grad_finish_scaled(const double* partials, size_t count, float grad_sc
 int ctrlv_adamw_step_scaled(float* p, const float* g, float* m, float* v, float* ema, size_t n, float lr, float beta1, float beta2,
                             float eps, float weight_decay, float bias1, float bias2, float ema_decay,
                             const ctrlv_loss_scale_state* ls, const ctrlv_grad_state* state, ctrlv_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Box and trajectory frames from coordinates (csrc/box_render.hip, csrc/pipeline.hip): what the reference draws on the host with
+ * OpenCV (src/ctrlv/utils/plotting.py:33-124 plot_3d_bbox / plot_trajectory, called from datasets/kitti_abstract.py:220-241)
+ * and then takes through Resize -> ToTensor -> Normalize(0.5, 0.5) (kitti_abstract.py:92-96).  A device table of box records goes
+ * in, the conditioning frames come out.  Additive entry points: the ABI number does not change, no existing struct changes its
+ * layout, no existing entry point its bits.
+ *
+ * THE CONTRACT IS THE INTEGER GEOMETRY STATED HERE, NOT OpenCV'S BYTES.  It follows what OpenCV's drawing does as far as that can
+ * be stated without running it (an inclusive fill, a thickness-2 line as a radius-1 capsule, a saturating round-half-even
+ * write-out of the 0.75 / 0.25 blend); that agreement is UNVERIFIED, and cv2's exact line rasters are out of scope.  The
+ * reference's own frames are not reproducible either: its track colours come from an unseeded np.random (plotting.py:29).
+ * tests/box_render_ref.py restates this section in numpy.
+ *
+ * The records.  Clear before setting; little-endian; both tables live on the DEVICE. */
+typedef struct ctrlv_box_object { /* 64 bytes */
+  int32_t x1, y1, x2, y2;         /* the 2-D box in source pixels, already truncated toward zero (the reference's int(...));
+                                     either corner order */
+  uint8_t fill_rgb[3], pad0;      /* the track colour, written to channels 0, 1, 2 as it stands */
+  uint8_t line_rgb[3], pad1;      /* the class colour, same rule */
+  int16_t corner[8][2];           /* the projected 3-D corners (x, y) in the reference's loop order (i in 1, -1; j in 1, -1; k in
+                                     0, 1).  On a trajectory frame corner[0] is the centre of the discs */
+  uint32_t flags;                 /* CTRLV_BOX_FILL | CTRLV_BOX_OUTLINE | CTRLV_BOX_WIRE; the kernel tests only these bits */
+  int32_t reserved;               /* must be 0 */
+} ctrlv_box_object;
+enum { CTRLV_BOX_FILL = 1, CTRLV_BOX_OUTLINE = 2, CTRLV_BOX_WIRE = 4 };
+typedef struct ctrlv_box_frame { /* 16 bytes */
+  int32_t first, count;           /* frame j draws objects first .. first + count - 1 in that order */
+  int32_t kind;                   /* 0: a box frame; 1: a trajectory frame (any other value is drawn as a box frame) */
+  int32_t reserved;               /* must be 0 */
+} ctrlv_box_frame;
+/* The kernel is safe for ANY table content: no content makes a lane read outside the two tables or write outside its frame.
+ *   - first outside [0, n_objects): the frame's count becomes 0.  Otherwise count becomes min(count, n_objects - first, 1024), and
+ *     0 when it is negative.
+ *   - every coordinate (x1 .. y2, corner) is clamped to [-8191, 8191] before use; source sizes are at most 4096 per axis.  With
+ *     these limits every product below fits in int64 (the worst case is 4 (2 * 12287 * 16382)^2 < 2^63).
+ *
+ * The picture, in integers only, per pixel q = (x, y) and channel c.
+ *   capsule(P0, P1, R4): with d = P1 - P0, e = q - P0, L = d.d, t = d.e the pixel is covered iff
+ *       L == 0 or t <= 0:  4 e.e <= R4;      t >= L:  4 |q - P1|^2 <= R4;      otherwise:  4 (d x e)^2 <= R4 L.
+ *     R4 = 4 is a radius-1 capsule (the "thickness 2" lines), R4 = 1 radius 1/2 ("thickness 1").  The bounds are closed.
+ *   With xa = min(x1, x2), xb = max(x1, x2), ya, yb likewise:
+ *     rect(o)  xa <= x <= xb and ya <= y <= yb, both corners inclusive.
+ *     ring(o)  the union of the radius-1 capsules of the box's four edges: a 3-pixel band around the box without its four outermost
+ *              corner pixels.
+ *     wire(o)  the radius-1 capsules of corner[2i] - corner[2i+1], i = 0 .. 3, and of corner[i] - corner[(i+2) % 8], i = 0 .. 7,
+ *              and the radius-1/2 capsules of corner[2] - corner[5] and corner[3] - corner[4].
+ *   Box frame (kind 0).  Three layers U, T, W start at zero.  The objects are visited in order; a later object overwrites an earlier
+ *   one, and all three channels are written, zeros included:
+ *       OUTLINE and q in ring: U = line_rgb;      FILL and q in rect: T = fill_rgb;      WIRE and q in wire: W = line_rgb.
+ *   Then per channel, as the reference's per-element masks do (plotting.py:120-123):
+ *       out[c] = W[c] != 0 ? W[c] : (T[c] != 0 ? rhe((3 T[c] + U[c]) / 4) : U[c]),
+ *   rhe = round-half-to-even of the exact quarter (the 0.75 / 0.25 addWeighted and its saturating write-out).
+ *   Trajectory frame (kind 1).  The objects are visited in order and write directly, no blend: the closed disc
+ *   |q - corner[0]|^2 <= 400 in fill_rgb, then the closed disc <= 100 in line_rgb.
+ *
+ * out_u8 (n_frames, 3, Hs, Ws) uint8, planar: the layout ctrlv_resize_frames_u8 takes with planes = 3 n_frames.  One workgroup
+ * per 128 x 32 tile of a frame: it culls the frame's objects against the tile, compacts the survivors into LDS in table order
+ * (wave ballots plus a prefix over the waves, 256 objects per round) and its lanes walk only that list, each lane owning 4
+ * consecutive x of a row: per channel one 32-bit store where the address is aligned, two 16-bit or four single stores elsewhere
+ * and at the right edge.  No atomics; the bytes do not depend on the grid, the tile, the pointer's
+ * alignment or on how many frames share a launch.  CTRLV_E_BAD_ARG: NULL tables or output, n_objects < 0; CTRLV_E_BAD_SHAPE:
+ * n_frames < 1, Hs or Ws outside [1, 4096], more than 2^31 - 1 tiles. */
+int ctrlv_render_box_frames(const ctrlv_box_object* objects, int n_objects, const ctrlv_box_frame* frames, int n_frames, int Hs,
+                            int Ws, void* out_u8, ctrlv_stream_t stream);
+/* The conditioning frames at the working size, in order:
+ *   1. ctrlv_render_box_frames at (Hs, Ws) -- into out_u8 (n_frames, 3, Hs, Ws) when it is given, else into ws;
+ *   2. ctrlv_resize_frames_u8 with filter 2 (BILINEAR: what transforms.Resize does to a PIL image) to (H, W); skipped when
+ *      (Hs, Ws) == (H, W) -- PIL returns a copy there;
+ *   3. out = rne_el(((float) v / 255.0f - 0.5f) / 0.5f), each operation rounded in fp32 (ToTensor, then Normalize).
+ * out (n_frames, 3, H, W), 16-byte aligned, out_dtype 0 (fp32, no last rounding) or the library's element code.  ws:
+ * ctrlv_box_frames_cond_ws_bytes bytes, 16-byte aligned (the query is 0 for sizes the call would refuse).  Refused by name on the
+ * host before any launch: what ctrlv_render_box_frames and ctrlv_resize_frames_u8 refuse, a NULL or misaligned out
+ * (CTRLV_E_BAD_ARG), another out_dtype (CTRLV_E_BAD_DTYPE), ws_bytes too small (CTRLV_E_WORKSPACE). */
+size_t ctrlv_box_frames_cond_ws_bytes(int n_frames, int Hs, int Ws, int H, int W);
+int ctrlv_box_frames_cond(const ctrlv_box_object* objects, int n_objects, const ctrlv_box_frame* frames, int n_frames, int Hs,
+                          int Ws, int H, int W, void* out, int out_dtype, void* out_u8, void* ws, size_t ws_bytes,
+                          ctrlv_stream_t stream);
+/* Host-only helpers for filling the tables (no GPU needed).
+ * The reference's eleven-entry class palette (plotting.py:30 TYPE_LOOKUP) in its order, the three numbers of an entry as they
+ * stand there.  An id outside [0, 11) is CTRLV_E_BAD_ARG. */
+int ctrlv_box_class_color(int id, uint8_t* rgb);
+/* A track's colour as a function of (seed, track_id): one Philox4x32-10 block under ctrlv_randn's key rule, counter
+ * ((uint32) track_id, (uint32) (track_id >> 32), 7, 0) -> x0 .. x3; rgb[c] = 50 + (uint8) (((uint64) x_c * 205) >> 32), the
+ * reference's range [50, 254] -- and the same colour for the same track in every frame and run, which the reference does not give. */
+int ctrlv_box_track_color(uint64_t seed, int64_t track_id, uint8_t* rgb);
+/* The eight projected corners of a 3-D box, in double as plotting.py:81-95 computes them.  cam_to_img: row-major (3, cols), cols 3
+ * or 4; location (x, y, z); dimensions (h, w, l); for (i in 1, -1) (j in 1, -1) (k in 0, 1):
+ *     px = x + i w / 2 cos(-rot_y + pi / 2) + (j i) l / 2 cos(-rot_y);  pz = z + i w / 2 sin(-rot_y + pi / 2) + (j i) l / 2 sin(-rot_y);
+ *     py = y - k h;   v = cam_to_img . (px, py, pz[, 1]);   (u0, u1) = (v0, v1) / (|v2| > 1e-4 ? v2 : 1e-4),
+ * each product and sum in the order written there.  corners[8][2] = (u0, u1) truncated toward zero, then clamped to
+ * [-8191, 8191] (a NaN becomes 0).  CTRLV_E_BAD_ARG: NULL pointers; CTRLV_E_BAD_SHAPE: cols not 3 or 4. */
+int ctrlv_box_project_corners(const double* cam_to_img, int cols, const double* location, const double* dimensions, double rot_y,
+                              int16_t* corners);
+/* The tables of one ctrlv_pipeline_generate_from_boxes call.  Clear the struct before setting fields. */
+typedef struct ctrlv_box_render_request {
+  const ctrlv_box_object* objects;  /* DEVICE, n_objects records */
+  const ctrlv_box_frame* frames;    /* DEVICE, n_frames records: frame f of clip i is record i * num_frames + f */
+  int32_t n_objects, n_frames;      /* n_frames must equal n_clips * num_frames of the clip request */
+  int32_t src_height, src_width;    /* (Hs, Ws) */
+  int32_t reserved[2];              /* must be 0 */
+} ctrlv_box_render_request;
+/* 0 for a request the call would refuse (ctrlv_last_error). */
+size_t ctrlv_pipeline_from_boxes_workspace_bytes(ctrlv_pipeline* p, const ctrlv_clip_request* r, const ctrlv_box_render_request* b);
+/* ctrlv_box_frames_cond of `b` to (height, width) of `r` in the element type, into the workspace; then exactly
+ * ctrlv_pipeline_generate on `r` with that buffer as cond, cond_channels = 3: the bits of the two calls made by hand.  Refused by
+ * name before any launch: r->cond set (CTRLV_E_BAD_ARG: the driver supplies it), a pipeline without a ControlNet, reserved != 0,
+ * n_frames != n_clips * num_frames (CTRLV_E_BAD_SHAPE), and whatever the two calls refuse.  A trajectory frame is a record with
+ * kind = 1 (the reference's if_last_frame_trajectory at inference: frame num_frames - 1). */
+int ctrlv_pipeline_generate_from_boxes(ctrlv_pipeline* p, const ctrlv_clip_request* r, const ctrlv_box_render_request* b, void* ws,
+                                       size_t ws_bytes, ctrlv_stream_t stream);
 
 #ifdef __cplusplus
 }
